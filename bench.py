@@ -7,12 +7,21 @@ before the timed region.  With N > 1 every rank encodes its own GOPs (GOPs are i
 weak scaling, no data-path collective); the timed region is bracketed by barriers and the
 slowest rank's time is used.
 
-Prints ONE JSON line (see the task contract) with two extra objects:
+Prints ONE JSON line.  A plain run sets up, warms up, times --steps steps,
+writes --dump-outputs if asked and prints the line; everything else is measured only with --full,
+which adds (among others):
   roofline     achieved TFLOP/s of the dominant kernel (3x3 stride-1 fp32-MFMA convolution),
                = algorithmic conv FLOPs of its launches / their summed HIP-event durations,
                measured live on the launch stream in one extra (untimed) P picture
   cpu_baseline the CPU oracle (oracle/dcvc_ref.py, a torch-CPU port of the reference path)
                timed on this box's host cores on a bounded sample (rank 0, N=1 only)
+and the one-stream rate and PSNR, the exact-fp32 parity leg and the decode / files / training-step
+measurements of the same command.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32 / float64; rank 0 only): for the encode workload per GOP stream the payload sizes, digests,
+header q indexes and bytes and the final DPB; arrays too large for the 64 MB budget are written as a
+fixed, seeded sample of their elements (dump_outputs).  The inputs depend only on the arguments.
 """
 import argparse
 import json
@@ -43,6 +52,51 @@ def synth_sequence(dev, n, h, w, seed):
         f = (f + torch.randn(f.shape, generator=g, device=dev) / 255.0).clamp_(0, 1)
         out.append(f[None].contiguous())
     return out
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """Write [(name, value)] as dirname/<name>.npy: float64 numpy arrays as they are (the small host-side lists),
+    everything else as float32.  A value is a tensor, a numpy array, bytes, or a list of tensors taken as their
+    flattened concatenation.  Every array gets an equal share of the 64 MB budget (at most 1 M elements); a larger one
+    is written as a sample of its flattened elements at sorted positions drawn from a generator seeded by its name, so
+    that two runs of any build sample the same positions of an output of the same size."""
+    import zlib
+
+    import numpy as np
+
+    def numel(p):
+        return int(p.numel()) if torch.is_tensor(p) else int(p.size)
+
+    os.makedirs(dirname, exist_ok=True)
+    cap = min(1 << 20, (DUMP_BUDGET_BYTES - (1 << 20)) // (4 * max(1, len(arrays))))
+    total = 0
+    for name, v in arrays:
+        if isinstance(v, (bytes, bytearray)):
+            v = np.frombuffer(bytes(v), np.uint8)
+        parts = v if isinstance(v, list) else [v]
+        n = sum(numel(p) for p in parts)
+        idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).integers(0, n, cap)) if n > cap else None
+        out, lo = [], 0
+        for p in parts:
+            m = numel(p)
+            sel = None if idx is None else idx[np.searchsorted(idx, lo):np.searchsorted(idx, lo + m)] - lo
+            if torch.is_tensor(p):
+                flat = p.detach().reshape(-1)
+                a = (flat if sel is None else flat[torch.from_numpy(sel).to(flat.device)]).float().cpu().numpy()
+            else:
+                a = p.reshape(-1) if sel is None else p.reshape(-1)[sel]
+            out.append(a if a.dtype == np.float64 else a.astype(np.float32))
+            lo += m
+        a = np.concatenate(out)
+        if idx is None and len(parts) == 1:
+            a = a.reshape(tuple(parts[0].shape))
+        total += a.nbytes
+        assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs over its {DUMP_BUDGET_BYTES >> 20} MB budget at {name}"
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return total
 
 
 def host_cores():
@@ -292,6 +346,8 @@ def train_workload(args, dev, rank, world):
     g = torch.Generator().manual_seed(100 + rank)
     clip = torch.rand(batch, args.warmup + args.steps + 1, 3, size, size, generator=g).to(dev)
 
+    last = [None]
+
     def run(t0, n):
         r = None
         dpb = {"ref_frame": clip[:, t0], "ref_feature": None, "ref_y": None, "ref_mv_y": None}
@@ -301,11 +357,29 @@ def train_workload(args, dev, rank, world):
             r["loss_to_opt"].backward()
             opt.step()
             dpb = r["dpb"]
+        last[0] = r
         return float(r["loss_to_opt"].detach()) if r is not None else float("nan")
 
     run(0, 1)  # one-off initialisation (not a step): weight packing, buffers, optimiser state
     run(0, args.warmup)
     dt, loss = timed_region(lambda: run(args.warmup, args.steps), dev)
+    if rank == 0 and args.dump_outputs and last[0] is not None:
+        # what the last optimiser step hands back: its loss, the DPB it passes on, and the updated weights
+        r = last[0]
+        dump_outputs(args.dump_outputs, [("loss_to_opt", r["loss_to_opt"])]
+                     + [(f"dpb_{k}", v) for k, v in sorted(r["dpb"].items()) if torch.is_tensor(v)]
+                     + [("parameters", [p for _, p in model.named_parameters()])])
+    out = {"metric": "trainer step pictures/sec (batch 4 x 256x256 per GPU, bpp+MSE, AdamW)", "value": round(world * batch * args.steps / dt, 2),
+           "unit": "pictures/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f32" if prec == "fp32" else "f32 (fp16x3 split-MFMA convolutions; weight gradients: split-bf16 MFMA for stride-1 layers, fp32 MFMA for stride-2 layers)", "data": "synthetic",
+           "config": {"workload": "trainer.py / trainer_multi.py optimiser step (configs[2] at N=1, configs[3] at N>1): "
+                                  "forward_one_frame + backward + AdamW, single mode, uniform-random clips, random-init weights",
+                      "batch_per_gpu": batch, "global_batch": batch * world, "height": size, "width": size, "precision": prec,
+                      "parallelism": f"ddp x{world} ({args.dist_backend})" if net is not model else "single GPU", "final_loss": round(loss, 4),
+                      "launch_mode": "hipGraph replay of the picture's forward and reverse pass" if model.dmc.graph_training else "eager (Python-issued launches)"}}
+    if not args.full:
+        return out
     eng = model.dmc.engine()
     eng.profile = {}
     graphed, model.dmc.graph_training = model.dmc.graph_training, False  # (events go around Python-issued launches)
@@ -316,18 +390,9 @@ def train_workload(args, dev, rank, world):
     dom = prof.get("conv3x3s1", {"flops": 0.0, "ms": 1.0, "launches": 0})
     peak = PEAK_F32_MFMA_TFLOPS if prec == "fp32" else PEAK_F16_MFMA_TFLOPS / 3.0
     achieved = dom["flops"] / (dom["ms"] * 1e-3) / 1e12
-    out = {"metric": "trainer step pictures/sec (batch 4 x 256x256 per GPU, bpp+MSE, AdamW)", "value": round(world * batch * args.steps / dt, 2),
-           "unit": "pictures/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "f32" if prec == "fp32" else "f32 (fp16x3 split-MFMA convolutions; weight gradients: split-bf16 MFMA for stride-1 layers, fp32 MFMA for stride-2 layers)", "data": "synthetic",
-           "config": {"workload": "trainer.py / trainer_multi.py optimiser step (configs[2] at N=1, configs[3] at N>1): "
-                                  "forward_one_frame + backward + AdamW, single mode, uniform-random clips, random-init weights",
-                      "batch_per_gpu": batch, "global_batch": batch * world, "height": size, "width": size, "precision": prec,
-                      "parallelism": f"ddp x{world} ({args.dist_backend})" if net is not model else "single GPU", "final_loss": round(loss, 4),
-                      "launch_mode": "hipGraph replay of the picture's forward and reverse pass" if model.dmc.graph_training else "eager (Python-issued launches)"},
-           "roofline": {"bound": "mfma", "kernel": "conv_mfma<3,1,*> forward + data-gradient launches of one step",
-                        "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                        "traffic": None, "launches": dom["launches"]}}
+    out["roofline"] = {"bound": "mfma", "kernel": "conv_mfma<3,1,*> forward + data-gradient launches of one step",
+                       "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                       "traffic": None, "launches": dom["launches"]}
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import dcvc_ref as R  # checker timed as the CPU baseline, never on the product path
         from vcm_ts_amd.params import dmc_spec, seeded_state_dict
@@ -392,7 +457,20 @@ def main():
     ap.add_argument("--strict-parity", action="store_true",
                     help="exit 3 (after printing the JSON line) when the fast mode misses the 1e-4 tolerance against the "
                          "fp32 mode or the range check fires; the line always carries within_tolerance")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: the one-stream rate and PSNR, the dominant "
+                         "kernel's roofline, the exact-fp32 parity leg, the decode / files / training-step workloads and the "
+                         "CPU baseline (--workload train: its roofline and CPU baseline); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all; "
+                         "a larger output as a fixed, seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.strict_parity and not args.full:
+        ap.error("--strict-parity needs --full (the exact-fp32 parity leg runs only there)")
+    if args.dump_outputs and args.workload == "files":
+        ap.error("--dump-outputs: the files workload's outputs are the .bin files of its temporary folder; not supported")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: start one rank per GPU (env:// rendezvous on 127.0.0.1, as
@@ -465,11 +543,16 @@ def main():
             cenc.decode_gops(coded, args.height, args.width)
 
         def dwork():
+            recs = None
             for _ in range(args.steps):
-                cenc.decode_gops(coded, args.height, args.width)
-            return 0
+                recs = cenc.decode_gops(coded, args.height, args.width)
+            return recs
 
-        dt, _ = timed_region(dwork, dev)
+        dt, recs = timed_region(dwork, dev)
+        if rank == 0 and args.dump_outputs and recs is not None:
+            # what decode_gops hands back: the reconstructed pictures of every GOP
+            dump_outputs(args.dump_outputs, [(f"gop{k}_x_hat", r) for k, r in enumerate(recs)])
+        del recs
         bits = sum(len(p[2]) * 8 for p in coded[0])
         out = {"metric": "decoded frames/sec at 1920x1080 GOP-32", "value": round(K * args.gop * args.steps * world / dt, 3),
                "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -485,16 +568,14 @@ def main():
             dist.destroy_process_group()
         return
 
-    bits_gop0 = [0]
-    last_coded = [None]
+    last = [None]
 
     def work():
         b = 0
         for _ in range(args.steps):
             res = cenc.encode_gops(seqs, q_i, q_mv, q_y)
             b = sum(r[1] for r in res)
-            bits_gop0[0] = res[0][1]
-            last_coded[0] = res[0][0]
+            last[0] = res
         return b
 
     # what a rank costs the HOST while it codes (for sizing an 8-rank node without having one):
@@ -509,23 +590,94 @@ def main():
         host_threads = None
     import hashlib
 
-    payload_sha = hashlib.sha256(b"".join(c[2] for c in last_coded[0])).hexdigest()[:16]
+    payload_sha = hashlib.sha256(b"".join(c[2] for c in last[0][0][0])).hexdigest()[:16]
+    if rank == 0 and args.dump_outputs:
+        # what encode_gops hands back for every GOP stream of the last step: the coded pictures (payload sizes, a 48-bit
+        # digest of each payload, the header q indexes, the payload bytes themselves) with the total bits, and the DPB
+        import numpy as np
+
+        arrays = []
+        for k, (coded, gop_bits, dpb) in enumerate(last[0]):
+            arrays += [(f"gop{k}_bits", np.array([gop_bits], np.float64)),
+                       (f"gop{k}_payload_sizes", np.array([len(c[2]) for c in coded], np.float64)),
+                       (f"gop{k}_payload_digests", np.array([int.from_bytes(hashlib.sha256(c[2]).digest()[:6], "big")
+                                                             for c in coded], np.float64)),
+                       (f"gop{k}_q_indexes", np.array([(list(c[1]) + [-1])[:2] for c in coded], np.float64)),
+                       (f"gop{k}_payload_bytes", b"".join(c[2] for c in coded))]
+            arrays += [(f"gop{k}_dpb_{n}", v) for n, v in sorted(dpb.items()) if torch.is_tensor(v)]
+        dump_outputs(args.dump_outputs, arrays)
+        del arrays
+    last[0] = None
     bits = bits / K  # per GOP
     frames_total = K * args.gop * args.steps * world
     fps = frames_total / dt
-    # the same GOP alone on the GPU (one stream), untimed for `value`: the one-stream rate, then once more with the
-    # reconstructions' PSNR collected.  The range guard of the fast mode (every convolution output against the
-    # magnitude split-fp16 operands can hold) is on in every launch of this program, the timed ones included
+    # the range guard of the fast mode (every convolution output against the magnitude split-fp16 operands can hold) is
+    # on in every launch of this program, the timed ones included
     eng_i, eng_p = i_net.engine(), p_net.engine()
     assert eng_i.range_check and eng_p.range_check
+    saturation = 0
+    for e_ in cenc.encoders:
+        saturation |= e_.i_net.engine().read_status() | e_.p_net.engine().read_status()
+    out = {
+        "metric": "encoded frames/sec at 1920x1080 GOP-32", "value": round(fps, 3), "unit": "frames/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" if args.precision == "fp32" else "f32 (fp16x3 split-MFMA, fp32 accumulate)", "data": "synthetic",
+        "config": {"workload": "1920x1080 GOP-32 synthetic sequence, single-rate encode (configs[1]); padded 1088x1920; "
+                               f"a step codes {K} GOPs of 1 I + 31 P pictures per GPU, in flight together on {K} HIP "
+                               "streams; random-init name-seeded weights",
+                   "gop": args.gop, "height": args.height, "width": args.width, "precision": args.precision,
+                   "parallelism": f"gop-sharded x{world} GPUs x{K} concurrent GOP streams per GPU",
+                   "gops_per_step_per_gpu": K, "frames_per_step_per_gpu": K * args.gop,
+                   "host_cpu_s_per_frame": round(host_cpu_s / (K * args.gop * args.steps), 5),
+                   "host_cpu_cores_busy": round(host_cpu_s / dt_local, 2),
+                   "host_threads": host_threads,
+                   "hbm_bytes_reserved": int(torch.cuda.memory_reserved(dev)),
+                   "hbm_bytes_workspaces": int(sum(e_.i_net.engine().bytes_reserved() + e_.p_net.engine().bytes_reserved()
+                                                   for e_ in cenc.encoders)),
+                   "host_note": "per RANK: CPU seconds of this process per coded frame over the timed region (all threads: "
+                                "feeder, rANS coder), cores kept busy, threads alive, device memory held (caching allocator / "
+                                "the engines' named workspaces); an 8-rank node needs 8 x these",
+                   "payload_sha16_gop0": payload_sha,
+                   "device": torch.cuda.get_device_name(dev), "device_uuid": str(getattr(torch.cuda.get_device_properties(dev), "uuid", "")),
+                   "bits_per_gop": int(bits), "bpp": round(bits / (args.gop * args.height * args.width), 4),
+                   "fp16x3_range_status": int(saturation),
+                   "fp16x3_range_note": "0 = no convolution output of ANY launch of this run (timed steps included: the guard is "
+                                        "always on) exceeded |8188|, the magnitude split-fp16 operands can hold "
+                                        "(DCVC_STATUS_ACT_SATURATED otherwise)"},
+    }
+
+    def finish(out):
+        if grouped:
+            # self-verification of a multi-GPU run: how many ranks the collective backend really joined (an all-reduce
+            # of ones over the process group: RCCL when the backend is nccl) and what each rank delivered by its own clock
+            on_gpu = dist.get_backend() == "nccl"
+            one = torch.ones(1, dtype=torch.float64, device=dev if on_gpu else "cpu")
+            dist.all_reduce(one)
+            mine = torch.tensor([K * args.gop * args.steps / dt_local], dtype=torch.float64, device=dev if on_gpu else "cpu")
+            every = [torch.zeros_like(mine) for _ in range(dist.get_world_size())]
+            dist.all_gather(every, mine)
+            out["config"]["dist_backend"] = args.dist_backend
+            out["config"]["collective_ranks"] = int(round(float(one.item())))
+            if on_gpu:
+                out["config"]["rccl_ranks"] = int(round(float(one.item())))
+            out["config"]["per_rank_frames_per_s"] = [round(float(t.item()), 3) for t in every]
+        if rank == 0:
+            print(json.dumps(out))
+        if grouped:
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish(out)
+        return
+    # --full from here on: the same GOP alone on the GPU (one stream), untimed for `value`: the one-stream rate, then
+    # once more with the reconstructions' PSNR collected
     dt1, bits1 = timed_region(lambda: enc.encode_gop(seq, q_i, q_mv, q_y)[1], dev)
     one_stream = round(args.gop / dt1, 3)
     quality = GopQuality(seq, args.height, args.width)
     bits1_again = enc.encode_gop(seq, q_i, q_mv, q_y, on_recon=quality)[1]
     assert bits1_again == bits1, "the same GOP codes the same bytes"
-    saturation = eng_i.read_status() | eng_p.read_status()
-    for e_ in cenc.encoders:
-        saturation |= e_.i_net.engine().read_status() | e_.p_net.engine().read_status()
+    saturation |= eng_i.read_status() | eng_p.read_status()
     psnr_fast = quality.psnr()
 
     # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream
@@ -598,39 +750,15 @@ def main():
 
     import numpy as np
 
-    out = {
-        "metric": "encoded frames/sec at 1920x1080 GOP-32", "value": round(fps, 3), "unit": "frames/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32" if args.precision == "fp32" else "f32 (fp16x3 split-MFMA, fp32 accumulate)", "data": "synthetic",
-        "config": {"workload": "1920x1080 GOP-32 synthetic sequence, single-rate encode (configs[1]); padded 1088x1920; "
-                               f"a step codes {K} GOPs of 1 I + 31 P pictures per GPU, in flight together on {K} HIP "
-                               "streams; random-init name-seeded weights",
-                   "gop": args.gop, "height": args.height, "width": args.width, "precision": args.precision,
-                   "parallelism": f"gop-sharded x{world} GPUs x{K} concurrent GOP streams per GPU",
-                   "gops_per_step_per_gpu": K, "frames_per_step_per_gpu": K * args.gop,
-                   "one_gop_stream_frames_per_s": one_stream,
-                   "host_cpu_s_per_frame": round(host_cpu_s / (K * args.gop * args.steps), 5),
-                   "host_cpu_cores_busy": round(host_cpu_s / dt_local, 2),
-                   "host_threads": host_threads,
-                   "hbm_bytes_reserved": int(torch.cuda.memory_reserved(dev)),
-                   "hbm_bytes_workspaces": int(sum(e_.i_net.engine().bytes_reserved() + e_.p_net.engine().bytes_reserved()
-                                                   for e_ in cenc.encoders)),
-                   "host_note": "per RANK: CPU seconds of this process per coded frame over the timed region (all threads: "
-                                "feeder, rANS coder), cores kept busy, threads alive, device memory held (caching allocator / "
-                                "the engines' named workspaces); an 8-rank node needs 8 x these",
-                   "payload_sha16_gop0": payload_sha,
-                   "parity_vs_reference": parity_vs_reference(args.precision),
-                   "device": torch.cuda.get_device_name(dev), "device_uuid": str(getattr(torch.cuda.get_device_properties(dev), "uuid", "")),
-                   "bits_per_gop": int(bits), "bpp": round(bits / (args.gop * args.height * args.width), 4),
-                   "psnr_db_gop_mean": round(float(psnr_fast.mean()), 4),
-                   "psnr_note": "random-init weights: PSNR is a parity quantity here, not codec quality",
-                   "fp16x3_range_status": int(saturation),
-                   "fp16x3_range_note": "0 = no convolution output of ANY launch of this run (timed steps included: the guard is "
-                                        "always on) exceeded |8188|, the magnitude split-fp16 operands can hold "
-                                        "(DCVC_STATUS_ACT_SATURATED otherwise)"},
-        "roofline": roofline,
-    }
+    out["config"]["one_gop_stream_frames_per_s"] = one_stream
+    out["config"]["parity_vs_reference"] = parity_vs_reference(args.precision)
+    out["config"]["psnr_db_gop_mean"] = round(float(psnr_fast.mean()), 4)
+    out["config"]["psnr_note"] = "random-init weights: PSNR is a parity quantity here, not codec quality"
+    out["config"]["fp16x3_range_status"] = int(saturation)
+    out["config"]["hbm_bytes_reserved"] = int(torch.cuda.memory_reserved(dev))
+    out["config"]["hbm_bytes_workspaces"] = int(sum(e_.i_net.engine().bytes_reserved() + e_.p_net.engine().bytes_reserved()
+                                                    for e_ in cenc.encoders))
+    out["roofline"] = roofline
     parity_ok = True
     if world == 1 and args.precision != "fp32" and not args.no_parity_leg:
         # the same GOP once in exact-fp32 MFMA mode ("parity mode"): rate, bits and per-picture PSNR next to
@@ -676,7 +804,7 @@ def main():
             e_.p_net.engine().release()
         torch.cuda.empty_cache()
         targs = argparse.Namespace(**vars(args))
-        targs.steps, targs.warmup, targs.no_cpu_baseline = 5, 2, True
+        targs.steps, targs.warmup, targs.no_cpu_baseline, targs.dump_outputs = 5, 2, True, None
         tr = train_workload(targs, dev, rank, world)
         out["train"] = {"value": tr["value"], "unit": tr["unit"], "ms_per_step": tr["ms_per_step"], "steps": 5,
                         "workload": tr["config"]["workload"] + "; = bench.py --workload train", "roofline_frac": tr["roofline"]["frac"]}
@@ -700,24 +828,7 @@ def main():
                           "rans_payload_bytes": nbytes, "rans_symbols": int(sum(p[0].size for p in planes)),
                           "end_to_end_fps_all_cores": round(1.0 / (sec_all + t_enc), 5),
                           "end_to_end_fps_1_thread": round(1.0 / (sec_1 + t_enc), 6)}}
-    if grouped:
-        # self-verification of a multi-GPU run: how many ranks the collective backend really joined (an all-reduce of
-        # ones over the process group: RCCL when the backend is nccl) and what each rank delivered by its own clock
-        on_gpu = dist.get_backend() == "nccl"
-        one = torch.ones(1, dtype=torch.float64, device=dev if on_gpu else "cpu")
-        dist.all_reduce(one)
-        mine = torch.tensor([K * args.gop * args.steps / dt_local], dtype=torch.float64, device=dev if on_gpu else "cpu")
-        every = [torch.zeros_like(mine) for _ in range(dist.get_world_size())]
-        dist.all_gather(every, mine)
-        out["config"]["dist_backend"] = args.dist_backend
-        out["config"]["collective_ranks"] = int(round(float(one.item())))
-        if on_gpu:
-            out["config"]["rccl_ranks"] = int(round(float(one.item())))
-        out["config"]["per_rank_frames_per_s"] = [round(float(t.item()), 3) for t in every]
-    if rank == 0:
-        print(json.dumps(out))
-    if grouped:
-        dist.destroy_process_group()
+    finish(out)
     if not parity_ok and args.strict_parity:
         sys.stderr.write("bench.py: the fp16x3 run is outside 1e-4 of the fp32 run (see parity_mode_fp32.fast_vs_fp32)\n")
         raise SystemExit(3)

@@ -77,12 +77,45 @@ def test_two_ranks_encode_disjoint_gops(tmp_path):
 
 def test_bench_runs_with_world_size_two():
     r = _run([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--height", "128", "--width", "192",
-              "--gop", "3", "--dist-backend", "gloo", "--no-cpu-baseline"], {})
+              "--gop", "3", "--dist-backend", "gloo", "--no-cpu-baseline", "--full"], {})
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert {"roofline", "metric", "unit", "ms_per_step", "config"} <= set(d)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line of exactly --steps timed steps and nothing measured
+    besides; --dump-outputs writes what the last step returned (payload sizes / digests / bytes and the DPB of every GOP
+    stream) and the same arguments give the same outputs in a new process."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps, lines = [], []
+    for run in range(2):
+        d = str(tmp_path / f"dump{run}")
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--height", "128", "--width", "192", "--gop", "3", "--dump-outputs", d], env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+        dumps.append({n[:-4]: np.load(os.path.join(d, n)) for n in sorted(os.listdir(d))})
+    d = lines[0]
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d)
+    assert not {"roofline", "parity_mode_fp32", "decode", "files", "train", "cpu_baseline"} & set(d)
+    assert d["config"]["fp16x3_range_status"] == 0
+    one, two = dumps
+    assert sorted(one) == sorted(two) and len(one) == 2 * 9, sorted(one)  # two GOP streams, nine arrays each
+    for n in one:
+        assert one[n].dtype in (np.float32, np.float64), n
+        assert np.array_equal(one[n], two[n]), n
+    assert int((one["gop0_bits"][0] + one["gop1_bits"][0]) / 2) == d["config"]["bits_per_gop"]
+    for k in range(2):  # 1 I + 2 P pictures: payloads plus their 14- / 8-byte headers
+        sizes = one[f"gop{k}_payload_sizes"]
+        assert sizes.shape == (3,) and one[f"gop{k}_bits"][0] == 8 * (sizes.sum() + 14 + 2 * 8)
+        assert one[f"gop{k}_payload_bytes"].size == sizes.sum() and one[f"gop{k}_q_indexes"].shape == (3, 2)
+    assert one["gop0_dpb_ref_frame"].shape == (1, 3, 128, 192)
+    assert sum(a.nbytes for a in one.values()) <= 64 << 20
 
 
 def test_bench_two_ranks_two_gop_streams_match_the_one_rank_run():

@@ -115,3 +115,31 @@ def test_bench_self_launch_starts_one_rank_per_gpu_and_propagates_failure():
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"],
                          env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True, timeout=120)
     assert bad.returncode != 0 and "WORLD_SIZE=2" in bad.stderr + bad.stdout
+
+
+def test_bench_dump_outputs_samples_large_arrays_within_budget(tmp_path):
+    """bench.py --dump-outputs: small arrays are written whole (float64 host lists kept as float64, tensors and bytes as
+    float32), an array over its share of the 64 MB budget as a sample at positions seeded by its name -- the same
+    positions in every run, so two builds can be compared output for output."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    big = torch.arange(3 << 20, dtype=torch.float32).reshape(3, 1 << 20)
+    payload = bytes(range(256)) * 8
+    arrays = [("bits", np.array([12345.0])), ("small", torch.ones(2, 3, dtype=torch.float64)), ("payload", payload),
+              ("big", big), ("parts", [big[0], big[1:]])]
+    total = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert total <= bench.DUMP_BUDGET_BYTES
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n, _ in arrays}
+    assert got["bits"].dtype == np.float64 and got["bits"].tolist() == [12345.0]
+    assert got["small"].dtype == np.float32 and got["small"].shape == (2, 3)
+    assert got["payload"].dtype == np.float32 and np.array_equal(got["payload"], np.frombuffer(payload, np.uint8))
+    for n in ("big", "parts"):
+        a = got[n]
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < big.numel()
+        assert np.all(np.diff(a) >= 0) and np.array_equal(a, np.rint(a))  # elements of arange, in order
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{n}.npy"))
+    # a list of tensors is sampled as their concatenation: the same positions under the same name
+    bench.dump_outputs(str(tmp_path / "c"), [("big", [big[0], big[1:]])] + arrays[:4])
+    assert np.array_equal(got["big"], np.load(tmp_path / "c" / "big.npy"))

@@ -7,7 +7,7 @@ R=${1:-r04}
 OUT=gpurun_out/prof_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-B="bench.py --no-cpu-baseline --no-parity-leg --no-extra-workloads --steps 2 --warmup 1"
+B="bench.py --full --no-cpu-baseline --no-parity-leg --no-extra-workloads --steps 2 --warmup 1"
 rocprofv3 --kernel-trace --stats -d $OUT -o stats1 -- python3 $B --gop-streams 1 > $OUT/stats1.log 2>&1 && echo stats1 done
 rocprofv3 --kernel-trace --stats -d $OUT -o stats2 -- python3 $B > $OUT/stats2.log 2>&1 && echo stats2 done
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT -o fetch -- python3 $B --gop-streams 1 > $OUT/fetch.log 2>&1 && echo fetch done
