@@ -136,6 +136,86 @@ def resample_cases(e):
     return worst
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Per-element tolerance rule of the operator gradient tests (tests/test_gpu_backward_ops.py).  Every element is compared
+# with a float64 autograd reference (ref64); ref32 is the same autograd in float32, the reference's own arithmetic.
+#   tier A (well-conditioned by construction, and where ref32 itself reproduces ref64 to 1e-6 of the element):
+#       |got - ref64| <= 1e-5 |ref64| + 1e-7 max|ref64|
+#   tier B (edge elements):
+#       |got - ref64| <= 4 |ref32 - ref64| + 1e-3 |ref64| + 1e-7 max|ref64|
+#   zero: where a clamp / LowerBound zeroes the reference gradient, got must be exactly 0;
+#   passes: where the branch passes, got must be nonzero unless the reference underflows (|ref64| < 1e-30) or its fp32
+#       arithmetic has lost the value (ref32 == 0, or ref32 misses ref64 by half of it: e.g. a Laplace tail whose
+#       exponential autograd rebuilds as expm1(u) + 1, on the 6e-8 grid next to 1).
+def _resolved(r64, r32):
+    return (r32 != 0) & (r64.abs() >= 1e-30) & ((r32 - r64).abs() < 0.5 * r64.abs())
+
+
+def tier_check(got, ref64, ref32, tier_a, zero=None, passes=None):
+    """-> (worst ratio on tier A, worst ratio on tier B, tier-A elements demoted by ref32, list of failures)."""
+    got, r64, r32 = (t.detach().double().cpu().reshape(-1) for t in (got, ref64, ref32))
+    a = tier_a.detach().cpu().reshape(-1).bool()
+    scale = 1e-7 * float(r64.abs().max())
+    well = (r32 - r64).abs() <= 1e-6 * r64.abs()
+    demoted = int((a & ~well).sum())
+    a = a & well
+    d = (got - r64).abs()
+    d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)
+    bound = torch.where(a, 1e-5 * r64.abs() + scale, 4 * (r32 - r64).abs() + 1e-3 * r64.abs() + scale)
+    ratio = torch.where(bound > 0, d / bound.clamp_min(1e-300), torch.where(d > 0, float("inf"), 0.0))
+    wa = float(ratio[a].max()) if a.any() else 0.0
+    wb = float(ratio[~a].max()) if (~a).any() else 0.0
+    bad = []
+    for tier, m in (("A", a), ("B", ~a)):
+        idx = torch.nonzero(m & (ratio > 1)).reshape(-1)
+        if len(idx):
+            i = int(idx[ratio[idx].argmax()])
+            bad.append(f"tier {tier}: {len(idx)} elements out of bound, worst #{i} got {float(got[i]):.9g} "
+                       f"ref64 {float(r64[i]):.9g} ref32 {float(r32[i]):.9g}")
+    if zero is not None:
+        z = zero.detach().cpu().reshape(-1).bool()
+        idx = torch.nonzero(z & (got != 0)).reshape(-1)
+        if len(idx):
+            i = int(idx[0])
+            bad.append(f"{len(idx)} masked elements are not exactly 0, e.g. #{i} got {float(got[i]):.9g}")
+    if passes is not None:
+        p = passes.detach().cpu().reshape(-1).bool() & _resolved(r64, r32)
+        idx = torch.nonzero(p & (got == 0)).reshape(-1)
+        if len(idx):
+            i = int(idx[0])
+            bad.append(f"{len(idx)} passing elements are 0, e.g. #{i} ref64 {float(r64[i]):.9g}")
+    return wa, wb, demoted, bad
+
+
+def assert_tiers(name, got, ref64, ref32, tier_a, zero=None, passes=None, unmasked=None):
+    """tier_check, printed, and its teeth shown on the same data: the output scaled by (1 + 1e-4) must fail tier A, one
+    masked element set to its unmasked value (`unmasked`, else the largest |ref64|) must fail, and so must one passing
+    element set to 0."""
+    wa, wb, dem, bad = tier_check(got, ref64, ref32, tier_a, zero, passes)
+    na = int(tier_a.reshape(-1).bool().sum()) - dem
+    print(f"{name:34s} tier A worst {wa:8.3g} ({na} el, {dem} demoted)  tier B worst {wb:8.3g} "
+          f"({got.numel() - na} el)", flush=True)
+    assert not bad, f"{name}: " + "; ".join(bad)
+    g = got.detach().double().cpu().reshape(-1)
+    if na:
+        assert tier_check(g * (1 + 1e-4), ref64, ref32, tier_a)[3], f"{name}: tier A does not see a 1e-4 scaling"
+    if zero is not None and zero.reshape(-1).bool().any():
+        z = zero.detach().cpu().reshape(-1).bool()
+        i = int(torch.nonzero(z)[0])
+        alt = float(unmasked.detach().double().cpu().reshape(-1)[i]) if unmasked is not None else 0.0
+        g2 = g.clone()
+        g2[i] = alt if alt != 0 else float(ref64.detach().double().abs().max()) or 1.0
+        assert tier_check(g2, ref64, ref32, tier_a, zero, passes)[3], f"{name}: the mask check has no teeth"
+    if passes is not None:
+        p = passes.detach().cpu().reshape(-1).bool() & _resolved(ref64.detach().double().cpu().reshape(-1),
+                                                                 ref32.detach().double().cpu().reshape(-1))
+        if p.any():
+            g2 = g.clone()
+            g2[int(torch.nonzero(p)[0])] = 0.0
+            assert tier_check(g2, ref64, ref32, tier_a, zero, passes)[3], f"{name}: the pass check has no teeth"
+    return wa, wb
+
+
 _ORACLE_STEPS = {}
 
 

@@ -608,6 +608,9 @@ extern "C" int dcvc_conv2d(const dcvc_conv_args *a, void *stream) {
     if (a->stride != 1 && a->stride != 2) return DCVC_E_ARG;
     if (a->precision != DCVC_PREC_FP32 && a->precision != DCVC_PREC_FP16X3) return DCVC_E_ARG;
     if (a->Cout_pad % 32 || a->Cout > a->Cout_pad || (a->pixel_shuffle && (a->Cout & 3))) return DCVC_E_ARG;
+    if (a->out_act < 0 || a->out_act > 3) return DCVC_E_ARG;
+    // the mask epilogue reads res2 as its mask source and has no gate, channel-sum or pixel-shuffle path
+    if (a->out_act == 3 && (!a->res2 || a->res_gate || a->chan_partial || a->pixel_shuffle)) return DCVC_E_ARG;
     ConvK k;
     memset(&k, 0, sizeof(k));
     for (int s = 0; s < a->nseg; ++s) {
