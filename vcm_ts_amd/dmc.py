@@ -121,6 +121,21 @@ class CodecBase(nn.Module):
         self._fork_stream = None
 
     # -- plumbing ------------------------------------------------------------------------
+    # Opt-in quality report (the reference's commented-out "ssim" output key, video_model.py:541,580 / image_model.py:87,101,
+    # with the module its base class owns: MS_SSIM(data_range=1.0, size_average=False), common_model.py:29).  Unset, the
+    # output dicts and the launch sequence are exactly what they were.
+    report_ssim = False
+
+    def _ssim_keys(self, res, x, recon):
+        """Adds "ssim" (N,) = ms_ssim(x, recon) on the padded, unclamped tensors and "ssim_dist" = 1 - ssim, a distortion
+        for loss_dist_key.  `recon` is the node's differentiable output in training mode, so the gradient reaches the
+        picture's tape as an upstream gradient of its reconstruction."""
+        from .metrics import ms_ssim
+
+        res["ssim"] = ms_ssim(x.detach().to(torch.float32), recon, data_range=1.0, size_average=False)
+        res["ssim_dist"] = 1.0 - res["ssim"]
+        return res
+
     def P(self, name):
         return self._pmap[name]
 
@@ -503,6 +518,9 @@ class _FrameGraph:
                 self.offsets[id(p)] = total
                 total += (p.numel() + 3) // 4 * 4
         self.flat = torch.zeros(max(total, 4), dtype=torch.float32, device=dev)
+        # report_ssim: a loss on the reconstruction sends a gradient into the node through ref_frame; it is loaded from
+        # this static buffer by one more launch at the head of the reverse graph (None: the graphs are the ones they were)
+        self.g_recon = torch.zeros_like(self.x) if model.report_ssim else None
 
         def forward():
             tape = Tape(e)
@@ -511,9 +529,11 @@ class _FrameGraph:
             o, sums = model._train_frame(tape, self.x, self.dpb, self.qm, self.qy)
             return tape, o, sums
 
-        def backward(tape):
+        def backward(tape, o):
             self.flat.zero_()
             tape.up.update(self.up)
+            if self.g_recon is not None:
+                e.from_nchw(self.g_recon, tape.grad(o["recon"]))
             tape.backward()
 
         # two eager passes first: every lazily created object (packed filters incl. the transposed ones of the data
@@ -523,9 +543,9 @@ class _FrameGraph:
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.no_grad(), torch.cuda.stream(side):
             for _ in range(2):
-                tape, _, _ = forward()
-                backward(tape)
-                del tape
+                tape, o, _ = forward()
+                backward(tape, o)
+                del tape, o
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self.fwd = torch.cuda.CUDAGraph()
@@ -536,7 +556,7 @@ class _FrameGraph:
         self.dpb_out = tuple(d[k] for k in _FrameFn.DPB_KEYS)
         self.bwd = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.bwd, pool=self.fwd.pool()):
-            backward(self.tape)
+            backward(self.tape, o)
         self.dq = {k: self.tape.q[k]["dq_scale"] for k in ("mv", "y")}
 
     def load(self, x, dpb, qm, qy):
@@ -566,7 +586,12 @@ class _GraphedFrameFn(torch.autograd.Function):
         fg = ctx.fg
         if fg is None or not fg.busy:
             raise RuntimeError("this frame's graph was already consumed (retain_graph is not supported)")
-        if any(t is not None for t in g[6:]):
+        if fg.g_recon is not None:  # (report_ssim: the one DPB output a loss of this picture itself may use)
+            if g[6] is None:
+                fg.g_recon.zero_()
+            else:
+                fg.g_recon.copy_(g[6])
+        if any(t is not None for t in g[(7 if fg.g_recon is not None else 6):]):
             raise RuntimeError("graph-replayed training pictures carry no gradient through the DPB (detach it, or set "
                                "DMC.graph_training = False for the cascade modes)")
         for name, t in zip(fg.SUMS, g[:6]):
@@ -786,7 +811,7 @@ class DMC(CodecBase):
                 or torch.cuda.is_current_stream_capturing()):
             return None
         key = (tuple(x.shape), tuple(None if v is None else tuple(v.shape) for v in dpb_t), tuple(qm.shape), tuple(qy.shape),
-               tuple((id(p), p.requires_grad, p.data_ptr()) for p in params), self.engine().precision,
+               tuple((id(p), p.requires_grad, p.data_ptr()) for p in params), self.engine().precision, bool(self.report_ssim),
                None if self._noise_override is None else tuple(t.data_ptr() for t in self._noise_override.values()))
         fg = self._frame_graphs.get(key)
         if fg is None:
@@ -821,6 +846,8 @@ class DMC(CodecBase):
                "dpb": {"ref_frame": recon, "ref_feature": feature, "ref_y": y_hat, "ref_mv_y": mv_y_hat}}
         for key, v in (("bit", bpp), ("bit_y", bpp_y), ("bit_z", bpp_z), ("bit_mv_y", bpp_mv_y), ("bit_mv_z", bpp_mv_z)):
             res[key] = torch.sum(v) * pix
+        if self.report_ssim:
+            self._ssim_keys(res, x, recon)
         return res
 
     # ------------------------------------------------------------------ public API
@@ -847,6 +874,8 @@ class DMC(CodecBase):
                "me_mse": me_mse, "mse": mse, "dpb": self._dpb_out(o)}
         for key, v in (("bit", bpp), ("bit_y", bpp_y), ("bit_z", bpp_z), ("bit_mv_y", bpp_mv_y), ("bit_mv_z", bpp_mv_z)):
             res[key] = torch.sum(v) * pix
+        if self.report_ssim:
+            self._ssim_keys(res, x, res["dpb"]["ref_frame"])
         res["_views"] = o
         return res
 

@@ -169,8 +169,9 @@ class IntraNoAR(CodecBase):
         bits_y, bits_z, sq, x_hat = _IntraFn.apply(self, x, q, *params)
         pix = x.shape[2] * x.shape[3]
         bpp_y, bpp_z = bits_y / pix, bits_z / pix
-        return {"x_hat": x_hat, "mse": sq / pix, "bit": (torch.sum(bpp_y + bpp_z) * pix).item(), "bpp": bpp_y + bpp_z,
-                "bpp_y": bpp_y, "bpp_z": bpp_z}
+        res = {"x_hat": x_hat, "mse": sq / pix, "bit": (torch.sum(bpp_y + bpp_z) * pix).item(), "bpp": bpp_y + bpp_z,
+               "bpp_y": bpp_y, "bpp_z": bpp_z}
+        return self._ssim_keys(res, x, x_hat) if self.report_ssim else res
 
     def forward(self, x, q_scale=None):
         """Training mode (round 4): the differentiable forward of image_model.py:54-106 (`bit` stays a float, :102)."""
@@ -186,8 +187,9 @@ class IntraNoAR(CodecBase):
         bpp_y = e.scale_bits(o["r"]["y_q"], o["r"]["scales_hat"], o["N"], o["y"].HW * self.N, gaussian=True) / pix
         bpp_z = e.factorized_bits(o["z_hat"], self._zblock("bit_estimator_z")) / pix
         mse = e.sq_err(o["x3"], o["x_hat"]) / pix
-        return {"x_hat": o["x_hat"].nchw(), "mse": mse, "bit": (torch.sum(bpp_y + bpp_z) * pix).item(),
-                "bpp": bpp_y + bpp_z, "bpp_y": bpp_y, "bpp_z": bpp_z, "_views": o}
+        res = {"x_hat": o["x_hat"].nchw(), "mse": mse, "bit": (torch.sum(bpp_y + bpp_z) * pix).item(),
+               "bpp": bpp_y + bpp_z, "bpp_y": bpp_y, "bpp_z": bpp_z, "_views": o}
+        return self._ssim_keys(res, x, res["x_hat"]) if self.report_ssim else res
 
     @torch.no_grad()
     def compress(self, x, q_scale, defer=False, coder="host", check_range=True):

@@ -1,4 +1,4 @@
-"""ctypes bindings of the two C-ABI libraries (include/dcvc_hip.h, include/dcvc_rans.h).
+"""ctypes bindings of the two C-ABI libraries (include/dcvc_hip*.h, include/dcvc_rans.h).
 
 There is no fallback: if a library is missing the import of the product path fails loudly
 (`LibraryMissing`) -- build with ``python -c "import __graft_entry__ as g; g.build()"`` or
@@ -189,10 +189,16 @@ _SIGS = {
     "dcvc_drans_encode": [vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp, vp],
     "dcvc_drans_decode": [vp, i64, vp, vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp],
     "dcvc_drans_build_lut": [vp, i32, i32, vp, vp],
+    # include/dcvc_hip_metrics.h
+    "dcvc_ms_ssim": [vp, vp, i32, i32, i32, i32, i32, i64, i32, i64, f32, i32, vp, vp, vp, vp, vp],
+    "dcvc_ms_ssim_grad": [vp, vp, i32, i32, i32, i32, i32, i64, i32, i64, f32, i32, vp, vp, vp, vp],
 }
 
-HIP_SYMBOLS = sorted(list(_SIGS) + ["dcvc_cdf_table_cols", "dcvc_conv_pack_size", "dcvc_conv_pack_size_paired", "dcvc_conv_small_pack_bytes", "dcvc_conv_k32_pack_bytes", "dcvc_conv_tile_rows", "dcvc_conv_chan_partial_parts", "dcvc_hip_version", "dcvc_conv_wgrad_scratch_min",
-                                    "dcvc_drans_default_lanes", "dcvc_drans_scratch_words"])
+# include/dcvc_hip_metrics.h (same library; listed apart because HIP_SYMBOLS is what the three kernel headers declare)
+METRICS_SYMBOLS = ["dcvc_ms_ssim", "dcvc_ms_ssim_grad", "dcvc_ms_ssim_workspace_bytes"]
+HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS] +
+                     ["dcvc_cdf_table_cols", "dcvc_conv_pack_size", "dcvc_conv_pack_size_paired", "dcvc_conv_small_pack_bytes", "dcvc_conv_k32_pack_bytes", "dcvc_conv_tile_rows", "dcvc_conv_chan_partial_parts", "dcvc_hip_version", "dcvc_conv_wgrad_scratch_min",
+                      "dcvc_drans_default_lanes", "dcvc_drans_scratch_words"])
 RANS_SYMBOLS = [
     "dcvc_rans_encoder_create", "dcvc_rans_encoder_destroy", "dcvc_rans_encoder_reset",
     "dcvc_rans_encoder_encode_with_indexes", "dcvc_rans_encoder_flush_bound", "dcvc_rans_encoder_flush",
@@ -231,6 +237,8 @@ def hip():
         L.dcvc_drans_default_lanes.restype = i32
         L.dcvc_drans_scratch_words.argtypes = [i64, i32]
         L.dcvc_drans_scratch_words.restype = i64
+        L.dcvc_ms_ssim_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+        L.dcvc_ms_ssim_workspace_bytes.restype = i64
         _hip = L
     return _hip
 

@@ -2,7 +2,7 @@
 ``video_coder.run_dcvc`` (/root/reference/video_coder.py:80-155) and its PNG conventions
 (DCVC_HEM/src/utils/png_reader.py:10-46, stream_helper.py:148-153) on the MI355X path.
 
-    python -m vcm_ts_amd.run_codec encode --frames DIR --bins DIR [--recon DIR] [--gop 32] [--q 1.0 1.0 1.0]
+    python -m vcm_ts_amd.run_codec encode --frames DIR --bins DIR [--recon DIR] [--gop 32] [--q 1.0 1.0 1.0] [--report JSON]
     python -m vcm_ts_amd.run_codec decode --bins DIR --recon DIR --height H --width W
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
@@ -176,9 +176,71 @@ def rate_point_q_scales(i_q_scales, y_q_scales, mv_y_q_scales, rate_count, quali
     return pick(i_q_scales), pick(mv_y_q_scales), pick(y_q_scales)
 
 
+def rd_report(frame_types, bits, psnrs, msssims, frame_pixel_num):
+    """The per-sequence RD log of the reference's test harness (DCVC_HEM/src/utils/common.py:63-112, same keys): per
+    picture bpp / PSNR / MS-SSIM and their averages over the I pictures (type 0), the P pictures (type 1) and all."""
+    out = {"frame_pixel_num": frame_pixel_num}
+    kinds = {"i": [n for n, k in enumerate(frame_types) if k == 0], "p": [n for n, k in enumerate(frame_types) if k != 0],
+             "all": list(range(len(frame_types)))}
+    out["i_frame_num"], out["p_frame_num"] = len(kinds["i"]), len(kinds["p"])
+    for name, idx in kinds.items():
+        mean = lambda v: (sum(v[n] for n in idx) / len(idx)) if idx else 0
+        out[f"ave_{name}_frame_bpp"] = mean(bits) / frame_pixel_num
+        out[f"ave_{name}_frame_psnr"] = mean(psnrs)
+        out[f"ave_{name}_frame_msssim"] = mean(msssims)
+    out["frame_bpp"] = [b / frame_pixel_num for b in bits]
+    out["frame_psnr"], out["frame_msssim"], out["frame_type"] = list(psnrs), list(msssims), list(frame_types)
+    return out
+
+
+class _QualityLog:
+    """PSNR and MS-SSIM of every coded picture of one GOP stream, taken on the device (vcm_ts_amd/metrics.py: one launch
+    sequence per picture on the stream that coded it) from the reconstruction clamped to [0, 1] against the source,
+    both cropped to the unpadded size (DCVC_HEM/test_video.py:156-163).  The values of a GOP go to pinned host memory in
+    ONE asynchronous copy behind its last picture and are looked at when the folder is done: the host never waits for a
+    picture's metric."""
+
+    def __init__(self, gop):
+        self.gop, self.cur, self.idx, self.done = gop, [], [], []
+
+    def add(self, g, recon, source, size):
+        from . import metrics
+
+        h, w = size
+        ms, _, sse = metrics.measure(recon[..., :h, :w], source[..., :h, :w], 1.0, clamp01=True)
+        self.cur.append(torch.cat([ms, sse]))
+        self.idx.append(g)
+        if len(self.cur) == self.gop:
+            self.flush()
+
+    def flush(self):
+        if self.cur:
+            dev = torch.stack(self.cur)
+            host = torch.empty(dev.shape, dtype=dev.dtype).pin_memory()
+            host.copy_(dev, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev.device))
+            self.done.append((ev, host, dev, self.idx))
+            self.cur, self.idx = [], []
+
+    def collect(self, elements):
+        """{frame number: (psnr dB, ms-ssim)}"""
+        import math
+
+        out = {}
+        for ev, host, _, idx in self.done:
+            ev.synchronize()
+            for g, (ms, sse) in zip(idx, host.double().tolist()):
+                out[g] = (10.0 * math.log10(elements / sse) if sse > 0 else float("inf"), ms)
+        return out
+
+
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
-                  i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1):
-    """Returns (bits per frame list, (height, width)).  coder="device": payloads in the opt-in GPU
+                  i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
+                  report=None):
+    """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
+    as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
+    per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
     format (include/dcvc_hip_rans.h) inside the same .bin containers; decode_folder reads both.
     io_workers: host threads decoding PNGs ahead of the encoder (0: read in the encode loop as run_dcvc does).
     nets: (i_frame_net, p_frame_net) already on the device -- or a list of such pairs, one per GOP stream -- instead
@@ -206,7 +268,8 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     pairs = [nets] if (nets is not None and not isinstance(nets, list)) else list(nets or [])
     made = iter(pairs[:K] + [None] * K)
     cenc = ConcurrentGopEncoder(lambda: next(made) or _nets(dev, precision, i_ckpt, p_ckpt), gop_size=gop, streams=K, coder=coder)
-    size, bits = [None], {}
+    size, bits, source = [None], {}, [None] * K
+    quality = [_QualityLog(gop) for _ in range(K)] if report else None
     pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
 
     def global_index(k, t):  # picture t of stream k's sequence -> 0-based frame number in the folder
@@ -256,7 +319,10 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
                 size[0] = tuple(x.shape[-2:])
             assert tuple(x.shape[-2:]) == size[0], "all frames must have one size"
             n += 1
-            yield pad_frame(x)
+            x = pad_frame(x)
+            if quality is not None:
+                source[k] = x  # (the picture on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
+            yield x
 
     def sink_of(k):
         def sink(kind, qidx, payload, t):
@@ -273,9 +339,12 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     def recon_of(k):
         def on_recon(t, ref_frame):
             h, w = size[0]
-            save_torch_image(ref_frame[..., :h, :w], os.path.join(recon_dir, f"im{str(global_index(k, t) + 1).zfill(5)}.png"), savers)
+            if quality is not None:
+                quality[k].add(global_index(k, t), ref_frame, source[k], size[0])
+            if recon_dir:
+                save_torch_image(ref_frame[..., :h, :w], os.path.join(recon_dir, f"im{str(global_index(k, t) + 1).zfill(5)}.png"), savers)
 
-        return on_recon if recon_dir else None
+        return on_recon if (recon_dir or quality is not None) else None
 
     # (GopEncoder reads the split-fp16 range guard once per GOP and raises lib.KernelError: no .bin of a clamped GOP
     # is reported as a success)
@@ -286,7 +355,23 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     finally:
         if pool is not None:
             pool.shutdown(wait=True, cancel_futures=True)
-    return [bits[g] for g in sorted(bits)], size[0]
+    bit_list = [bits[g] for g in sorted(bits)]
+    if quality is None:
+        return bit_list, size[0]
+    values = {}
+    for k, log in enumerate(quality):
+        with torch.cuda.stream(cenc.streams[k]):
+            log.flush()  # a trailing partial GOP
+        values.update(log.collect(3 * size[0][0] * size[0][1]))
+    order = sorted(bits)
+    rd = rd_report([0 if g % gop == 0 else 1 for g in order], bit_list, [values[g][0] for g in order],
+                   [values[g][1] for g in order], size[0][0] * size[0][1])
+    if isinstance(report, (str, os.PathLike)):
+        import json
+
+        with open(report, "w") as f:
+            json.dump(rd, f, indent=2)
+    return bit_list, size[0], rd
 
 
 def decode_folder(bin_dir, recon_dir, height, width, gop=32, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
@@ -341,6 +426,9 @@ def main():
                    help="GOPs of the folder in flight together on the GPU (same .bin bytes; ~33 GB of workspace each at 1080p)")
     e.add_argument("--coder", default="host", choices=["host", "device"],
                    help="host: the reference's bitstream (default); device: opt-in GPU entropy coder, own format")
+    e.add_argument("--report", metavar="JSON",
+                   help="write bpp, PSNR and MS-SSIM of every picture and their I / P / all averages (the key layout of "
+                        "the reference's test harness); measured on the device, the .bin files are the same with or without")
     d = sub.add_parser("decode")
     d.add_argument("--bins", required=True)
     d.add_argument("--recon", required=True)
@@ -372,8 +460,10 @@ def main():
                 y_qs, mv_qs = sd["y_q_scale"].reshape(-1), sd["mv_y_q_scale"].reshape(-1)
             q = rate_point_q_scales(i_qs, y_qs, mv_qs, a.rate_count, a.quality)
             print(f"rate point {a.quality} of {a.rate_count}: q_i {q[0]:.4f}  q_mv_y {q[1]:.4f}  q_y {q[2]:.4f}")
-        bits, size = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
-                                   coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams)
+        bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
+                                        coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report)
+        if rd:
+            print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f} -> {a.report}")
         print(f"{len(bits)} pictures, {size[0]}x{size[1]}, {sum(bits)} bits, {sum(bits) / (len(bits) * size[0] * size[1]):.4f} bpp")
     else:
         n = decode_folder(a.bins, a.recon, a.height, a.width, a.gop, a.device, a.precision, a.i_ckpt, a.p_ckpt, io_workers=a.io_workers)
