@@ -127,6 +127,12 @@ class DualPriorBwdArgs(C.Structure):
     ]
 
 
+class ColorCoeffs(C.Structure):  # dcvc_color_coeffs_t (include/dcvc_hip_color.h)
+    _fields_ = [(n, C.c_float) for n in ("y_off", "c_off", "y_scale", "c_scale", "crr", "cgb", "cgr", "cbb", "kr", "kg", "kb",
+                                         "icb", "icr", "y_range", "c_range")] + \
+               [(n, C.c_int32) for n in ("max_code", "bit_depth", "siting", "matrix", "range")]
+
+
 PRECISIONS = {"fp32": 0, "fp16x3": 1}
 
 _hip = None
@@ -192,11 +198,16 @@ _SIGS = {
     # include/dcvc_hip_metrics.h
     "dcvc_ms_ssim": [vp, vp, i32, i32, i32, i32, i32, i64, i32, i64, f32, i32, vp, vp, vp, vp, vp],
     "dcvc_ms_ssim_grad": [vp, vp, i32, i32, i32, i32, i32, i64, i32, i64, f32, i32, vp, vp, vp, vp],
+    # include/dcvc_hip_color.h
+    "dcvc_color_coeffs": [i32, i32, i32, i32, vp],
+    "dcvc_yuv420_to_rgb": [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i64, i32, vp],
+    "dcvc_rgb_to_yuv420": [vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp],
 }
 
 # include/dcvc_hip_metrics.h (same library; listed apart because HIP_SYMBOLS is what the three kernel headers declare)
 METRICS_SYMBOLS = ["dcvc_ms_ssim", "dcvc_ms_ssim_grad", "dcvc_ms_ssim_workspace_bytes"]
-HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS] +
+COLOR_SYMBOLS = ["dcvc_color_coeffs", "dcvc_yuv420_to_rgb", "dcvc_rgb_to_yuv420"]  # include/dcvc_hip_color.h
+HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS] +
                      ["dcvc_cdf_table_cols", "dcvc_conv_pack_size", "dcvc_conv_pack_size_paired", "dcvc_conv_small_pack_bytes", "dcvc_conv_k32_pack_bytes", "dcvc_conv_tile_rows", "dcvc_conv_chan_partial_parts", "dcvc_hip_version", "dcvc_conv_wgrad_scratch_min",
                       "dcvc_drans_default_lanes", "dcvc_drans_scratch_words"])
 RANS_SYMBOLS = [

@@ -4,6 +4,13 @@
 
     python -m vcm_ts_amd.run_codec encode --frames DIR --bins DIR [--recon DIR] [--gop 32] [--q 1.0 1.0 1.0] [--report JSON]
     python -m vcm_ts_amd.run_codec decode --bins DIR --recon DIR --height H --width W
+    python -m vcm_ts_amd.run_codec encode --video FILE.y4m --bins DIR [--recon-video FILE.y4m] [--report JSON]
+    python -m vcm_ts_amd.run_codec encode --video FILE.yuv --size 1920x1080 [--bit-depth 10] [--fps 50] --bins DIR
+    python -m vcm_ts_amd.run_codec decode --bins DIR --recon-video FILE.y4m
+
+Video files are Y4M or raw I420 at 8 or 10 bits (vcm_ts_amd/yuv.py): no PNG detour, the colour conversion runs on the
+GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` beside the `.bin` files from which
+`decode --recon-video` takes size, frame rate and colour description.
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
 reference's `.bin` format (an I picture every `gop` frames).  Unlike run_dcvc the encoder does not
@@ -16,7 +23,6 @@ import os
 
 import numpy as np
 import torch
-from PIL import Image
 
 from . import stream as S
 from .pipeline import pad_frame
@@ -41,6 +47,8 @@ class PNGReader:
     @staticmethod
     def load_u8(path):
         """(H, W, 3) uint8"""
+        from PIL import Image  # (here, not at the top: the video path never touches PNGs)
+
         return np.asarray(Image.open(path).convert("RGB"))
 
     @staticmethod
@@ -94,6 +102,8 @@ def u8_to_unit_float(u8: torch.Tensor):
 
 
 def _save_array(a, path):
+    from PIL import Image
+
     Image.fromarray(np.clip(np.rint(a * 255), 0, 255).astype(np.uint8)).save(path)
 
 
@@ -409,13 +419,305 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=32, device="cuda:0", pr
     return t
 
 
-def main():
+# ------------------------------------------------------------------------------------------------- Y4M / raw YUV files
+SEQUENCE_JSON = "sequence.json"
+
+
+def write_sequence_info(bin_dir, width, height, frames, gop, fps, spec, container, chroma=None, interlace=None, aspect=None):
+    """What decode_video needs beside the .bin files (which stay what they are): size, frame count, GOP length, frame
+    rate and colour description of the source, and the container it came in."""
+    import json
+
+    info = {"width": int(width), "height": int(height), "frames": int(frames), "gop": int(gop),
+            "fps": list(fps) if fps else None, "color": spec.to_json(), "container": container, "chroma": chroma,
+            "interlace": interlace, "aspect": aspect}
+    with open(os.path.join(bin_dir, SEQUENCE_JSON), "w") as f:
+        json.dump(info, f, indent=2)
+    return info
+
+
+def read_sequence_info(bin_dir):
+    """The dictionary write_sequence_info stored (with "color" as a ColorSpec), or None without the file."""
+    import json
+
+    from .yuv import ColorSpec
+
+    path = os.path.join(bin_dir, SEQUENCE_JSON)
+    if not os.path.exists(path):
+        return None
+    with open(path) as f:
+        info = json.load(f)
+    info["color"] = ColorSpec.from_json(info["color"])
+    info["fps"] = tuple(info["fps"]) if info.get("fps") else None
+    return info
+
+
+class _VideoOut:
+    """Output stage of one stream: a reconstruction becomes 4:2:0 samples on the stream that produced it
+    (yuv.rgb_to_yuv420) and leaves the device as 1.5 bytes per pixel into a ring of pinned buffers; a buffer is written to
+    the file, at the place its frame number gives it, when the ring comes round to it (or at close), so the host never
+    waits for the picture it has just enqueued.  Several of these share one writer: frames land in display order
+    whatever order the GOP streams finish in."""
+
+    def __init__(self, writer, depth=4):
+        from collections import deque
+
+        self.writer, self.depth, self.free, self.busy = writer, depth, [], deque()
+
+    def put(self, g, samples):
+        if len(self.busy) >= self.depth:
+            self._retire()
+        host = self.free.pop() if self.free else torch.empty(self.writer.frame_bytes, dtype=torch.uint8).pin_memory()
+        host.copy_(samples.view(torch.uint8), non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(samples.device))
+        self.busy.append((ev, host, g, samples))  # (samples: kept until its copy has run)
+
+    def _retire(self):
+        ev, host, g, _ = self.busy.popleft()
+        ev.synchronize()
+        self.writer.write(g, host.numpy())
+        self.free.append(host)
+
+    def close(self):
+        while self.busy:
+            self._retire()
+
+
+class _VideoQualityLog(_QualityLog):
+    """_QualityLog plus the three integer sums of rgb_to_yuv420(..., source=) per picture.  They ride in the GOP's one
+    asynchronous transfer as raw bits (three int64 seen as six float32 lanes of the row; nothing computes on them)."""
+
+    def add_yuv(self, g, recon, source, size, sums):
+        from . import metrics
+
+        h, w = size
+        ms, _, sse = metrics.measure(recon[..., :h, :w], source[..., :h, :w], 1.0, clamp01=True)
+        self.cur.append(torch.cat([ms, sse, sums.view(torch.float32)]))
+        self.idx.append(g)
+        if len(self.cur) == self.gop:
+            self.flush()
+
+    def collect(self, elements):
+        """{frame number: (psnr dB, ms-ssim, (sum Y, sum U, sum V))}"""
+        import math
+
+        out = {}
+        for ev, host, _, idx in self.done:
+            ev.synchronize()
+            sums = host[:, 2:].contiguous().view(torch.int64).tolist()
+            for g, (ms, sse), s in zip(idx, host[:, :2].double().tolist(), sums):
+                out[g] = (10.0 * math.log10(elements / sse) if sse > 0 else float("inf"), ms, tuple(s))
+        return out
+
+
+def _open_source(video, size, bit_depth, fps):
+    from . import yuv as Y
+
+    return Y.open_video(video, size, bit_depth, fps) if isinstance(video, (str, os.PathLike)) else video
+
+
+def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantize8=False, gop=32, q=(1.0, 1.0, 1.0),
+                 device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
+                 nets=None, gop_streams=1, report=None, bit_depth=8, fps=None):
+    """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
+    files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
+    asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
+    spec: a yuv.ColorSpec overriding what the file says (default: its header, else bt709 / limited / left).
+    quantize8: round the converted picture to 8-bit RGB first, i.e. code exactly what encode_folder would read from
+    PNGs of those pixels; default off (no second quantisation of the source).
+    recon_video: write the reconstructions as `.y4m` / `.yuv` with the source's parameters.
+    report: as encode_folder (the existing keys measure against the RGB picture the codec was given), plus
+    frame_psnr_y / _u / _v / _yuv and ave_{i,p,all}_frame_psnr_yuv in the sample domain of the source file.
+    io_workers is accepted for symmetry with encode_folder: a 4:2:0 frame needs no decoding, so this path has no helper
+    threads at any value.  Writes sequence.json beside the .bin files (read_sequence_info, decode_video)."""
+    from . import yuv as Y
+    from .pipeline import ConcurrentGopEncoder
+
+    reader = _open_source(video, size, bit_depth, fps)  # (every refusal about the file happens here, before any GPU work)
+    spec = spec or reader.spec()
+    if spec.bit_depth != reader.bit_depth:
+        raise ValueError(f"the file holds {reader.bit_depth}-bit samples, the colour description says {spec.bit_depth}")
+    h, w = reader.height, reader.width
+    n_frames = reader.n_frames if max_frames is None else min(reader.n_frames, int(max_frames))
+    if n_frames < 1:
+        raise ValueError(f"{getattr(reader, 'path', video)}: no frames")
+    os.makedirs(bin_dir, exist_ok=True)
+    dev = torch.device(device)
+    n_gops = (n_frames + gop - 1) // gop
+    K = max(1, min(int(gop_streams), n_gops))
+    pairs = [nets] if (nets is not None and not isinstance(nets, list)) else list(nets or [])
+    made = iter(pairs[:K] + [None] * K)
+    cenc = ConcurrentGopEncoder(lambda: next(made) or _nets(dev, precision, i_ckpt, p_ckpt), gop_size=gop, streams=K, coder=coder)
+    bits, source = {}, [None] * K
+    quality = [_VideoQualityLog(gop) for _ in range(K)] if report else None
+    container = "y4m" if isinstance(reader, Y.Y4MReader) else "yuv"
+    extras = dict(chroma=getattr(reader, "chroma", None), interlace=getattr(reader, "interlace", None),
+                  aspect=getattr(reader, "aspect", None))
+    writer = Y.create_video(recon_video, w, h, spec, reader.fps, **extras) if recon_video else None
+    outs = [_VideoOut(writer) for _ in range(K)] if writer else None
+    sample_dtype = torch.uint8 if spec.bit_depth == 8 else torch.int16
+
+    def global_index(k, t):  # picture t of stream k's sequence -> 0-based frame number in the file
+        return ((t // gop) * K + k) * gop + t % gop
+
+    def frames(k):
+        order = [global_index(k, t) for t in range(((n_gops - k + K - 1) // K) * gop)]
+        ring = [torch.empty(reader.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(3)]
+        done, copy_stream = [None] * len(ring), torch.cuda.Stream(dev)
+        for n, g in enumerate(g for g in order if g < n_frames):
+            j = n % len(ring)
+            if done[j] is not None:
+                done[j].synchronize()  # the copy that last read this pinned buffer (three pictures ago)
+            reader.read_into(g, ring[j].numpy())
+            with torch.cuda.stream(copy_stream):
+                d = ring[j].to(dev, non_blocking=True)
+                done[j] = torch.cuda.Event()
+                done[j].record(copy_stream)
+            cur = torch.cuda.current_stream(dev)  # (this GOP stream's: ConcurrentGopEncoder pulls frames inside it)
+            cur.wait_event(done[j])
+            d.record_stream(cur)
+            samples = d.view(sample_dtype)
+            x = Y.yuv420_to_rgb(samples, h, w, spec, pad=True, quantize8=quantize8)
+            source[k] = (x, samples)  # (what on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
+            yield x
+
+    def sink_of(k):
+        def sink(kind, qidx, payload, t):
+            g = global_index(k, t)
+            path = os.path.join(bin_dir, f"im{str(g + 1).zfill(5)}.bin")
+            if kind == "I":
+                S.encode_i(h, w, qidx[0], payload, path)
+            else:
+                S.encode_p(payload, qidx[0], qidx[1], path)
+            bits[g] = S.filesize(path) * 8
+
+        return sink
+
+    def recon_of(k):
+        def on_recon(t, ref_frame):
+            g = global_index(k, t)
+            x, samples = source[k]
+            if quality is not None:
+                out, sums = Y.rgb_to_yuv420(ref_frame, h, w, spec, source=samples)
+                quality[k].add_yuv(g, ref_frame, x, (h, w), sums)
+            elif outs:
+                out = Y.rgb_to_yuv420(ref_frame, h, w, spec)
+            if outs:
+                outs[k].put(g, out)
+
+        return on_recon if (outs or quality is not None) else None
+
+    try:
+        with torch.no_grad():
+            cenc.encode_gops([frames(k) for k in range(K)], q[0], q[1], q[2], sinks=[sink_of(k) for k in range(K)],
+                             on_recons=[recon_of(k) for k in range(K)])
+            for o in outs or []:
+                o.close()
+    finally:
+        if writer:
+            writer.close()
+        if reader is not video:
+            reader.close()
+    write_sequence_info(bin_dir, w, h, n_frames, gop, reader.fps, spec, container, **extras)
+    bit_list = [bits[g] for g in sorted(bits)]
+    if quality is None:
+        return bit_list, (h, w)
+    values = {}
+    for k, log in enumerate(quality):
+        with torch.cuda.stream(cenc.streams[k]):
+            log.flush()  # a trailing partial GOP
+        values.update(log.collect(3 * h * w))
+    order = sorted(bits)
+    types = [0 if g % gop == 0 else 1 for g in order]
+    rd = rd_report(types, bit_list, [values[g][0] for g in order], [values[g][1] for g in order], h * w)
+    per = [Y.psnr_yuv(values[g][2], h, w, spec.bit_depth) for g in order]
+    for n, name in enumerate(("y", "u", "v", "yuv")):
+        rd[f"frame_psnr_{name}"] = [p[n] for p in per]
+    for name, keep in (("i", lambda k: k == 0), ("p", lambda k: k != 0), ("all", lambda k: True)):
+        sel = [p[3] for p, k in zip(per, types) if keep(k)]
+        rd[f"ave_{name}_frame_psnr_yuv"] = sum(sel) / len(sel) if sel else 0
+    if isinstance(report, (str, os.PathLike)):
+        import json
+
+        with open(report, "w") as f:
+            json.dump(rd, f, indent=2)
+    return bit_list, (h, w), rd
+
+
+def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=None, fps=None, device="cuda:0",
+                 precision=None, i_ckpt=None, p_ckpt=None):
+    """decode_folder's loop with the video output stage.  Size, GOP length, frame rate and colour description come from
+    the sequence.json encode_video left in `bin_dir`; explicit arguments override it, and without the file height and
+    width are required (gop then defaults to 32, the colour description to yuv.ColorSpec()).  Returns the picture count."""
+    from . import yuv as Y
+
+    info = read_sequence_info(bin_dir) or {}
+    height, width = height or info.get("height"), width or info.get("width")
+    if not height or not width:
+        raise ValueError(f"no {SEQUENCE_JSON} in {bin_dir}: height and width are required")
+    gop = gop or info.get("gop") or 32
+    spec = spec or info.get("color") or Y.ColorSpec()
+    Y.check_size(height, width)
+    first = os.path.join(bin_dir, "im00001.bin")
+    if os.path.exists(first) and S.decode_i(first)[:2] != (height, width):
+        raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {(height, width)}")
+    dev = torch.device(device)
+    i_net, p_net = _nets(dev, precision, i_ckpt, p_ckpt)
+    i_net.update()
+    p_net.update()
+    t, dpb = 0, None
+
+    def range_guard():  # once per GOP: raises lib.KernelError if a split-fp16 kernel clamped an activation
+        i_net.engine().check_status()
+        p_net.engine().check_status()
+
+    writer = Y.create_video(recon_video, width, height, spec, fps or info.get("fps"), chroma=info.get("chroma"),
+                            interlace=info.get("interlace"), aspect=info.get("aspect"))
+    try:
+        out = _VideoOut(writer)
+        with torch.no_grad():
+            while True:
+                path = os.path.join(bin_dir, f"im{str(t + 1).zfill(5)}.bin")
+                if not os.path.exists(path):
+                    break
+                if t % gop == 0:
+                    if t:
+                        range_guard()
+                    h, w, qi, payload = S.decode_i(path)
+                    assert (h, w) == (height, width)
+                    x_hat = i_net.decompress(payload, h, w, qi / 100, check_range=False)["x_hat"]
+                    dpb = {"ref_frame": x_hat, "ref_feature": None, "ref_y": None, "ref_mv_y": None}
+                else:
+                    qmv, qy, payload = S.decode_p(path)
+                    dpb = p_net.decompress(dpb, payload, height, width, qmv / 100, qy / 100, check_range=False)["dpb"]
+                out.put(t, Y.rgb_to_yuv420(dpb["ref_frame"], height, width, spec))
+                t += 1
+            if t:
+                range_guard()
+            out.close()
+    finally:
+        writer.close()
+    return t
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
     e = sub.add_parser("encode")
-    e.add_argument("--frames", required=True)
+    e.add_argument("--frames", help="folder of im1.png / im00001.png ... (exactly one of --frames and --video)")
+    e.add_argument("--video", metavar="FILE", help="a .y4m file, or a raw I420 .yuv file with --size")
+    e.add_argument("--size", metavar="WxH", help="picture size of a raw .yuv file")
+    e.add_argument("--bit-depth", type=int, default=8, choices=[8, 10], help="sample depth of a raw .yuv file")
+    e.add_argument("--fps", default=None, help="frame rate of a raw .yuv file, N or N:D (recorded, and written to a .y4m output)")
+    e.add_argument("--matrix", default=None, choices=["bt709", "bt601"], help="default bt709")
+    e.add_argument("--range", default=None, choices=["limited", "full"], help="default: the Y4M header's XCOLORRANGE, else limited")
+    e.add_argument("--siting", default=None, choices=["left", "center"], help="chroma siting; default: the Y4M header's, else left")
+    e.add_argument("--quantize8", action="store_true",
+                   help="with --video: round the converted picture to 8-bit RGB before coding it (what a PNG of it would hold)")
     e.add_argument("--bins", required=True)
     e.add_argument("--recon")
+    e.add_argument("--recon-video", metavar="FILE", help="with --video: reconstructions as .y4m / .yuv")
     e.add_argument("--q", type=float, nargs=3, default=None, metavar=("I", "MV_Y", "Y"),
                    help="explicit q-scales (default 1 1 1 when no rate point is selected)")
     e.add_argument("--rate-count", type=int, default=None,
@@ -431,18 +733,44 @@ def main():
                         "the reference's test harness); measured on the device, the .bin files are the same with or without")
     d = sub.add_parser("decode")
     d.add_argument("--bins", required=True)
-    d.add_argument("--recon", required=True)
-    d.add_argument("--height", type=int, required=True)
-    d.add_argument("--width", type=int, required=True)
+    d.add_argument("--recon", help="folder for PNGs (exactly one of --recon and --recon-video)")
+    d.add_argument("--recon-video", metavar="FILE", help=".y4m / .yuv output; size and colour from the bins' sequence.json")
+    d.add_argument("--height", type=int, help="required unless sequence.json lies beside the .bin files")
+    d.add_argument("--width", type=int)
+    d.add_argument("--matrix", default=None, choices=["bt709", "bt601"])
+    d.add_argument("--range", default=None, choices=["limited", "full"])
+    d.add_argument("--siting", default=None, choices=["left", "center"])
+    d.add_argument("--bit-depth", type=int, default=None, choices=[8, 10])
     for p in (e, d):
-        p.add_argument("--gop", type=int, default=32)
+        p.add_argument("--gop", type=int, default=None, help="default 32 (decode: the sequence.json's, else 32)")
         p.add_argument("--io-workers", type=int, default=8, help="host threads for PNG decoding / encoding (0: inline)")
         p.add_argument("--device", default="cuda:0")
         p.add_argument("--precision", default=None, choices=["fp32", "fp16x3"])
         p.add_argument("--i-ckpt")
         p.add_argument("--p-ckpt")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.cmd == "encode":
+        if (a.frames is None) == (a.video is None):
+            ap.error("give exactly one of --frames and --video")
+        if a.video is None and (a.recon_video or a.size or a.quantize8 or a.matrix or a.range or a.siting):
+            ap.error("--recon-video, --size, --quantize8, --matrix, --range and --siting belong to --video")
+        if a.video is not None and a.recon:
+            ap.error("--recon (a PNG folder) belongs to --frames; use --recon-video with --video")
+        size = fps = None
+        if a.video is not None:
+            from . import yuv as Y
+
+            ext = os.path.splitext(a.video)[1].lower()
+            if ext not in (".y4m", ".yuv"):
+                ap.error("--video takes a .y4m or a .yuv file")
+            if ext == ".yuv" and not a.size:
+                ap.error("a raw .yuv file needs --size WxH")
+            try:
+                size = Y.parse_size(a.size) if a.size else None
+                fps = tuple(int(v) for v in (a.fps.split(":") + ["1"])[:2]) if a.fps else None
+            except ValueError as ex:
+                ap.error(str(ex))
+        a.gop = a.gop or 32
         if (a.rate_count is None) != (a.quality is None) or (a.q is not None and a.rate_count is not None):
             ap.error("give either --q, or --rate-count together with --quality")
         q = tuple(a.q) if a.q is not None else (1.0, 1.0, 1.0)
@@ -460,13 +788,43 @@ def main():
                 y_qs, mv_qs = sd["y_q_scale"].reshape(-1), sd["mv_y_q_scale"].reshape(-1)
             q = rate_point_q_scales(i_qs, y_qs, mv_qs, a.rate_count, a.quality)
             print(f"rate point {a.quality} of {a.rate_count}: q_i {q[0]:.4f}  q_mv_y {q[1]:.4f}  q_y {q[2]:.4f}")
-        bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
-                                        coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report)
+        if a.video is not None:
+            reader = Y.open_video(a.video, size, a.bit_depth, fps)
+            spec = reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting)
+            with reader:
+                bits, size, *rd = encode_video(reader, a.bins, a.recon_video, spec=spec, quantize8=a.quantize8, gop=a.gop, q=q,
+                                               device=a.device, precision=a.precision, i_ckpt=a.i_ckpt, p_ckpt=a.p_ckpt,
+                                               coder=a.coder, gop_streams=a.gop_streams, report=a.report)
+        else:
+            bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
+                                            coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report)
         if rd:
-            print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f} -> {a.report}")
+            yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
+            print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
         print(f"{len(bits)} pictures, {size[0]}x{size[1]}, {sum(bits)} bits, {sum(bits) / (len(bits) * size[0] * size[1]):.4f} bpp")
     else:
-        n = decode_folder(a.bins, a.recon, a.height, a.width, a.gop, a.device, a.precision, a.i_ckpt, a.p_ckpt, io_workers=a.io_workers)
+        if (a.recon is None) == (a.recon_video is None):
+            ap.error("give exactly one of --recon and --recon-video")
+        info = read_sequence_info(a.bins)
+        if info is None and (a.height is None or a.width is None):
+            ap.error(f"--height and --width are required (no {SEQUENCE_JSON} beside the .bin files)")
+        if a.recon_video is not None:
+            from . import yuv as Y
+
+            if os.path.splitext(a.recon_video)[1].lower() not in (".y4m", ".yuv"):
+                ap.error("--recon-video takes a .y4m or a .yuv file")
+            spec = None
+            if a.matrix or a.range or a.siting or a.bit_depth:
+                base = info["color"] if info else Y.ColorSpec()
+                spec = Y.ColorSpec(a.matrix or base.matrix, base.full_range if a.range is None else a.range == "full",
+                                   a.siting or base.siting, a.bit_depth or base.bit_depth)
+            n = decode_video(a.bins, a.recon_video, a.height, a.width, a.gop, spec, None, a.device, a.precision, a.i_ckpt, a.p_ckpt)
+        else:
+            if a.matrix or a.range or a.siting or a.bit_depth:
+                ap.error("--matrix, --range, --siting and --bit-depth belong to --recon-video")
+            height, width = a.height or info["height"], a.width or info["width"]
+            n = decode_folder(a.bins, a.recon, height, width, a.gop or (info or {}).get("gop") or 32, a.device, a.precision,
+                              a.i_ckpt, a.p_ckpt, io_workers=a.io_workers)
         print(f"{n} pictures decoded")
 
 
