@@ -23,6 +23,7 @@ whose backward runs the gradient kernels of include/dcvc_hip_grad.h through vcm_
 """
 from __future__ import annotations
 
+import math
 import time
 
 import numpy as np
@@ -54,14 +55,56 @@ def build_param_tree(root: nn.Module, spec, init):
         m.register_parameter(parts[-1], nn.Parameter(t.clone(), requires_grad=False))
 
 
+DPB_KEYS = ("ref_frame", "ref_feature", "ref_y", "ref_mv_y")
+
+
 class PendingStream:
     """Symbol planes of one picture on their way to the host: the D2H copies were enqueued on
     the launch stream behind the kernels that produce them; finish() waits for them and runs
-    the rANS coder.  Lets the caller enqueue the next picture's kernels first (pipeline.py)."""
+    the rANS coder.  Lets the caller enqueue the next picture's kernels first (pipeline.py).
+
+    planes: list of (table name, sym int32 device tensor, idx int32 device tensor or None,
+    (N, C, H, W) for the per-channel index of factorised planes).  Their place in the pinned host
+    buffer is decided here, once (layout_of), for whoever enqueues the copies (copy_planes) and
+    for the coder that reads them back (encode_element)."""
 
     def __init__(self, owner, host, event, layout, batch=1):
         self.owner, self.host, self.event, self.layout, self.batch = owner, host, event, layout, batch
         self._streams = None
+
+    @staticmethod
+    def layout_of(planes):
+        """([(table, offset of the symbols, offset of the indexes or None, count, chan)], total int32 words)"""
+        layout, off = [], 0
+        for table, sym, idx, chan in planes:
+            n = sym.numel()
+            s_off, off = off, off + n
+            i_off = None
+            if idx is not None:
+                i_off, off = off, off + n
+            layout.append((table, s_off, i_off, n, chan))
+        return layout, off
+
+    @staticmethod
+    def copy_planes(host, layout, planes):
+        """Enqueue the asynchronous D2H copies on the current stream."""
+        for (_, s_off, i_off, n, _), (_, sym, idx, _) in zip(layout, planes):
+            host[s_off : s_off + n].copy_(sym, non_blocking=True)
+            if idx is not None:
+                host[i_off : i_off + n].copy_(idx, non_blocking=True)
+
+    def encode_element(self, b):
+        """Feed batch element b of every plane to the owner's (reset) host coder; the copies must have arrived."""
+        ec, flat = self.owner.entropy_coder, self.host.numpy()
+        for table, s_off, i_off, n, chan in self.layout:
+            per = n // self.batch
+            cdf, ln, off = self.owner._tables[table]
+            lo = s_off + b * per
+            if i_off is None:
+                idx = self.owner._chan_index(1, *chan[1:])
+            else:
+                idx = flat[i_off + b * per : i_off + (b + 1) * per]
+            ec.encode_with_indexes(flat[lo : lo + per], idx, cdf, ln, off)
 
     def finish_all(self):
         """One payload per batch element: planes are (n, c, y, x) ordered, so element b of every
@@ -70,19 +113,10 @@ class PendingStream:
         if self._streams is None:
             self.event.synchronize()
             ec = self.owner.entropy_coder
-            flat = self.host.numpy()
             out = []
             for b in range(self.batch):
                 ec.reset_encoder()
-                for table, s_off, i_off, n, chan in self.layout:
-                    per = n // self.batch
-                    cdf, ln, off = self.owner._tables[table]
-                    lo = s_off + b * per
-                    if i_off is None:
-                        idx = self.owner._chan_index(1, *chan[1:])
-                    else:
-                        idx = flat[i_off + b * per : i_off + (b + 1) * per]
-                    ec.encode_with_indexes(flat[lo : lo + per], idx, cdf, ln, off)
+                self.encode_element(b)
                 out.append(ec.flush_encoder())
             self._streams = out
         return self._streams
@@ -91,8 +125,33 @@ class PendingStream:
         return self.finish_all()[0]
 
 
+def _load_upstream(tape, named_grads):
+    """Upstream gradients of a node's per-sample sums -> the tape (None: the caller's loss does not use that sum)."""
+    for name, g in named_grads:
+        if g is not None:
+            tape.up[name] = g.detach().to(torch.float32).contiguous()
+
+
+def _param_grads(params, needs, grad_of):
+    """One entry per parameter input of an autograd node: grad_of(p) where autograd asks for a gradient (zeros when the
+    pass produced none for it), None elsewhere."""
+    grads = []
+    for p, need in zip(params, needs):
+        g = grad_of(p) if need else None
+        grads.append(torch.zeros_like(p) if (need and g is None) else g)
+    return grads
+
+
+def _qgrad(g, shape, need):
+    """Gradient of a q-scale input of `shape` from the pass's per-sample dq_scale."""
+    if not need:
+        return None
+    return (g.sum() if math.prod(shape) == 1 else g.clone()).reshape(shape)  # (a copy: g is a slice of the tape's zeroed pool)
+
+
 class CodecBase(nn.Module):
-    """What DMC and IntraNoAR share: parameter tree, engine, q-scale plumbing, tables."""
+    """What DMC and IntraNoAR share: parameter tree, engine, q-scale plumbing, tables, the rate terms of a recorded
+    forward, symbol staging and the guarded ends of compress() / decompress()."""
 
     _tag = "codec"
     # decompress() clamps the reconstruction to [0, 1] as the reference's does (video_model.py:413, image_model.py:199).
@@ -236,10 +295,9 @@ class CodecBase(nn.Module):
         return c
 
     def _stage_symbols(self, planes, batch=1) -> PendingStream:
-        """planes: list of (table name, sym int32 device tensor, idx int32 device tensor or None,
-        (N, C, H, W) for the per-channel index of factorised planes).  One pinned host buffer per
-        alternating slot; copies are asynchronous on the current stream."""
-        total = sum(p[1].numel() + (0 if p[2] is None else p[2].numel()) for p in planes)
+        """planes: see PendingStream.  One pinned host buffer per alternating slot; copies are
+        asynchronous on the current stream."""
+        layout, total = PendingStream.layout_of(planes)
         slot = self._stage_flip
         self._stage_flip ^= 1
         prev = self._stage_owner.get(slot)
@@ -250,33 +308,12 @@ class CodecBase(nn.Module):
         if host is None:
             host = torch.empty(total, dtype=torch.int32, pin_memory=True)
             self._stage_bufs[key] = host
-        layout, off = [], 0
-        for table, sym, idx, chan in planes:
-            n = sym.numel()
-            host[off : off + n].copy_(sym, non_blocking=True)
-            s_off, off = off, off + n
-            i_off = None
-            if idx is not None:
-                host[off : off + n].copy_(idx, non_blocking=True)
-                i_off, off = off, off + n
-            layout.append((table, s_off, i_off, n, chan))
+        PendingStream.copy_planes(host, layout, planes)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         pending = PendingStream(self, host, ev, layout, batch)
         self._stage_owner[slot] = pending
         return pending
-
-    @staticmethod
-    def _stage_layout(planes):
-        layout, off = [], 0
-        for table, sym, idx, chan in planes:
-            n = sym.numel()
-            s_off, off = off, off + n
-            i_off = None
-            if idx is not None:
-                i_off, off = off, off + n
-            layout.append((table, s_off, i_off, n, chan))
-        return layout, off
 
     # -- opt-in device entropy coder (include/dcvc_hip_rans.h; NOT the reference's wire format) ---
     def device_coder(self) -> "E.DeviceCoder":
@@ -335,22 +372,11 @@ class CodecBase(nn.Module):
             torch.cuda.current_stream(self.device).wait_event(self._dc_done)
             self._dc_done = None
 
-    def _encode_factorized(self, name, sym: torch.Tensor, N, C_, H, W):
-        cdf, ln, off = self._tables[name]
-        s = sym.cpu().numpy()
-        idx = np.broadcast_to(np.arange(C_, dtype=np.int32)[None, :, None, None], (N, C_, H, W)).reshape(-1)
-        self.entropy_coder.encode_with_indexes(s, idx, cdf, ln, off)
-
-    def _encode_scale(self, sym: torch.Tensor, idx: torch.Tensor):
-        cdf, ln, off = self._tables["scale"]
-        self.entropy_coder.encode_with_indexes(sym.cpu().numpy(), idx.cpu().numpy(), cdf, ln, off)
-
     def _decode_factorized(self, name, N, C_, H, W) -> torch.Tensor:
         if self._dc_active:
             return self._dcoder.decode(name, N * C_ * H * W, chan=(C_, H * W))
         cdf, ln, off = self._tables[name]
-        idx = np.broadcast_to(np.arange(C_, dtype=np.int32)[None, :, None, None], (N, C_, H, W)).reshape(-1)
-        out = self.entropy_coder.decoder.decode_stream(idx, cdf, ln, off)
+        out = self.entropy_coder.decoder.decode_stream(self._chan_index(N, C_, H, W), cdf, ln, off)
         return torch.from_numpy(out).to(self.device)
 
     def _decode_scale(self, idx: torch.Tensor) -> torch.Tensor:
@@ -359,6 +385,86 @@ class CodecBase(nn.Module):
         cdf, ln, off = self._tables["scale"]
         out = self.entropy_coder.decoder.decode_stream(idx.cpu().numpy(), cdf, ln, off)
         return torch.from_numpy(out).to(self.device)
+
+    # -- the guarded ends of compress() / decompress() ------------------------------------
+    def _stage(self, planes, batch, coder) -> PendingStream:
+        assert coder in ("host", "device")
+        return (self._stage_symbols if coder == "host" else self._stage_symbols_device)(planes, batch=batch)
+
+    def _compress_result(self, res, pending, defer, check_range):
+        """Tail of compress(): `res` (the codec's own keys) plus "pending" when deferred, else plus the payloads, after
+        the split-fp16 range guard (DMC.compress says when a caller reads it itself)."""
+        if defer:
+            return {**res, "pending": pending}
+        streams = pending.finish_all()
+        if check_range:
+            self.engine().check_status()
+        return {**res, "bit_stream": streams[0], "bit_streams": streams}
+
+    def _decompress_guarded(self, string, coder, defer_check, check_range, *args):
+        """self._decompress(*args) for both public decompress(): picks the coder (None = tell the two formats apart by the
+        device format's magic) and reads the range guard afterwards.  _dc_active / _defer_check stay instance state:
+        _decode_factorized / _decode_scale read them, and tests replace those two on the instance with the signatures
+        they have."""
+        if self.entropy_coder is None:
+            raise RuntimeError("call update() before compress()/decompress()")
+        if coder is None:
+            coder = "device" if string[:4] == E.DRANS_MAGIC else "host"
+        self._defer_check = defer_check
+        self._dc_active = coder == "device"
+        try:
+            r = self._decompress(*args)
+        finally:
+            self._dc_active = False
+        if check_range:
+            self.engine().check_status()
+        return r
+
+    def _open_stream(self, string):
+        (self.device_coder() if self._dc_active else self.entropy_coder).set_stream(string)
+
+    def _close_stream(self):
+        if self._dc_active:
+            self._dcoder.release()
+            if not self._defer_check:
+                self._dcoder.check()  # the one synchronisation of a device-coded picture
+
+    # -- rate terms of a recorded (training-mode) forward ---------------------------------
+    _noise_override = None  # tests: {"y", "mv_y", "z", "mv_z"} -> NCHW tensors replacing add_noise's draws
+
+    def _noise(self, key, N, H, W, C_):
+        """uniform(-0.5, 0.5) like CompressionModel.add_noise (common_model.py:46-49), dense NHWC."""
+        if self._noise_override is not None:
+            t = self._noise_override[key].to(device=self.device, dtype=torch.float32)
+            assert tuple(t.shape) == (N, C_, H, W), (key, t.shape)
+            return t.permute(0, 2, 3, 1).contiguous()
+        return torch.empty((N, H, W, C_), dtype=torch.float32, device=self.device).uniform_(-0.5, 0.5)
+
+    def _record_scale_bits(self, tape, sums, name, lat: View, r, noise_key):
+        """sums[name] = bits of the noisy dual-prior residual of latent `lat` (r: its _dual_prior_encode result) under
+        this codec's scale distribution, and the tape op that differentiates it."""
+        e, N = self.engine(), lat.N
+        per = lat.HW * lat.C
+        noise = self._noise(noise_key, N, lat.H, lat.W, lat.C)
+        y_bit = torch.empty_like(noise).view(-1)
+        lib.check(e.L.dcvc_add_planes(r["y_res"].data_ptr(), lat.C, noise.data_ptr(), lat.C, y_bit.data_ptr(), lat.C,
+                                      N * lat.HW, lat.C, e.stream()), "add_planes")
+        kind = int(self._distribution == "gaussian")  # (dcvc_scale_bits / dcvc_scale_bits_bwd: 0 Laplace, 1 Gaussian)
+        sums[name] = e.scale_bits(y_bit, r["scales_hat"], N, per, gaussian=bool(kind))
+        tape.ops.append(("scale_bits", name, y_bit, r["scales_hat"], r["y_res"], N, per, kind))
+
+    def _record_factorized_bits(self, tape, sums, name, z: View, est, noise_key):
+        """sums[name] = bits of the noisy hyper latent `z` under the factorised model `est`, and its tape op."""
+        e = self.engine()
+        noise = self._noise(noise_key, z.N, z.H, z.W, z.C)
+        z_bit = View(torch.empty_like(noise), z.C)
+        lib.check(e.L.dcvc_add_planes(z.ptr, z.cs, noise.data_ptr(), z.C, z_bit.ptr, z_bit.cs, z.N * z.HW, z.C,
+                                      e.stream()), "add_planes")
+        blk = self._zblock(est)
+        sums[name] = e.factorized_bits(z_bit, blk)
+        plist = [self.P(f"{est}.f{i}.{k}") for i in (1, 2, 3) for k in ("h", "b", "a")]
+        plist += [self.P(f"{est}.f4.h"), self.P(f"{est}.f4.b")]
+        tape.ops.append(("factorized_bits", name, z_bit, z, blk, plist))
 
     # -- dual prior (both directions) -----------------------------------------------------
     def _dual_prior_encode(self, tag, y: View, fusion: View, prior_name, out: View, q_basic, q_scale, want_stats,
@@ -425,8 +531,6 @@ class _FrameFn(torch.autograd.Function):
     tensors are inputs and outputs of the node, so a DPB that is not detached carries the
     gradient into the previous picture (the reference's cascade training modes)."""
 
-    DPB_KEYS = ("ref_frame", "ref_feature", "ref_y", "ref_mv_y")
-
     @staticmethod
     def forward(ctx, model, x, rf, rfeat, ry, rmv, qm, qy, *params):
         from .grad import Tape
@@ -435,14 +539,14 @@ class _FrameFn(torch.autograd.Function):
         # in backward as None instead of as zero tensors that would be transposed into gradient buffers for nothing
         ctx.set_materialize_grads(False)
         tape = Tape(model.engine())
-        dpb_in = dict(zip(_FrameFn.DPB_KEYS, (rf, rfeat, ry, rmv)))
-        tape.dpb_grad = {k for k, need in zip(_FrameFn.DPB_KEYS, ctx.needs_input_grad[2:6]) if need}
+        dpb_in = dict(zip(DPB_KEYS, (rf, rfeat, ry, rmv)))
+        tape.dpb_grad = {k for k, need in zip(DPB_KEYS, ctx.needs_input_grad[2:6]) if need}
         o, sums = model._train_frame(tape, x.detach(), {k: (None if v is None else v.detach()) for k, v in dpb_in.items()},
                                      qm.detach(), qy.detach())
         ctx.tape, ctx.model, ctx.params = tape, model, params
         ctx.q_shapes = (qm.shape, qy.shape)
         ctx.out_views = (o["recon"], o["feature"], o["y_hat"], o["mv_y_hat"])
-        ctx.in_views = tuple(o["dv"][k] for k in _FrameFn.DPB_KEYS)
+        ctx.in_views = tuple(o["dv"][k] for k in DPB_KEYS)
         d = model._dpb_out(o)
         return (sums["bits_mv_y"], sums["bits_mv_z"], sums["bits_y"], sums["bits_z"], sums["sq"], sums["me_sq"],
                 d["ref_frame"], d["ref_feature"], d["ref_y"], d["ref_mv_y"])
@@ -453,30 +557,14 @@ class _FrameFn(torch.autograd.Function):
         if tape is None:
             raise RuntimeError("this frame's tape was already consumed (retain_graph is not supported)")
         e = tape.e
-        for name, g in (("bits_mv_y", g_mv_y), ("bits_mv_z", g_mv_z), ("bits_y", g_y), ("bits_z", g_z), ("sq", g_sq),
-                        ("me_sq", g_me)):
-            if g is not None:
-                tape.up[name] = g.detach().to(torch.float32).contiguous()
+        _load_upstream(tape, zip(_FrameGraph.SUMS, (g_mv_y, g_mv_z, g_y, g_z, g_sq, g_me)))
         for v, g in zip(ctx.out_views, g_dpb):  # gradient arriving from the next picture through the DPB
             if g is not None:
                 e.from_nchw(g, tape.grad(v))
         tape.backward()
-        grads = []
-        for p, need in zip(ctx.params, ctx.needs_input_grad[8:]):
-            g = tape.pgrads.get(id(p)) if need else None
-            grads.append(torch.zeros_like(p) if (need and g is None) else g)
-
-        def qgrad(key, shape, need):
-            if not need:
-                return None
-            g = tape.q[key]["dq_scale"]
-            n = 1
-            for s_ in shape:
-                n *= s_
-            return (g.sum() if n == 1 else g.clone()).reshape(shape)  # (a copy: g is a slice of the tape's zeroed pool)
-
-        gqm = qgrad("mv", ctx.q_shapes[0], ctx.needs_input_grad[6])
-        gqy = qgrad("y", ctx.q_shapes[1], ctx.needs_input_grad[7])
+        grads = _param_grads(ctx.params, ctx.needs_input_grad[8:], lambda p: tape.pgrads.get(id(p)))
+        gqm = _qgrad(tape.q["mv"]["dq_scale"], ctx.q_shapes[0], ctx.needs_input_grad[6])
+        gqy = _qgrad(tape.q["y"]["dq_scale"], ctx.q_shapes[1], ctx.needs_input_grad[7])
         g_in = []
         for v, need in zip(ctx.in_views, ctx.needs_input_grad[2:6]):
             gv = tape.grad(v, create=False) if (need and v is not None) else None
@@ -553,7 +641,7 @@ class _FrameGraph:
             self.tape, o, sums = forward()
         self.sums = tuple(sums[k] for k in self.SUMS)
         d = model._dpb_out(o)
-        self.dpb_out = tuple(d[k] for k in _FrameFn.DPB_KEYS)
+        self.dpb_out = tuple(d[k] for k in DPB_KEYS)
         self.bwd = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.bwd, pool=self.fwd.pool()):
             backward(self.tape, o)
@@ -574,7 +662,7 @@ class _GraphedFrameFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, fg, x, rf, rfeat, ry, rmv, qm, qy, *params):
         ctx.set_materialize_grads(False)
-        fg.load(x, dict(zip(_FrameFn.DPB_KEYS, (rf, rfeat, ry, rmv))), qm, qy)
+        fg.load(x, dict(zip(DPB_KEYS, (rf, rfeat, ry, rmv))), qm, qy)
         fg.fwd.replay()
         fg.busy = True
         ctx.fg, ctx.q_shapes = fg, (qm.shape, qy.shape)
@@ -602,20 +690,11 @@ class _GraphedFrameFn(torch.autograd.Function):
         fg.bwd.replay()
         fg.busy, ctx.fg = False, None
         out = fg.flat.clone()  # one copy out; the per-parameter gradients are views of it
-        grads = [out[fg.offsets[id(p)] : fg.offsets[id(p)] + p.numel()].view(p.shape) if (need and id(p) in fg.offsets) else None
-                 for p, need in zip(fg.params, ctx.needs_input_grad[8:])]
-
-        def qgrad(key, shape, need):
-            if not need:
-                return None
-            n = 1
-            for s_ in shape:
-                n *= s_
-            t = fg.dq[key]
-            return (t.sum() if n == 1 else t.clone()).reshape(shape)
-
-        return (None, None, None, None, None, None, qgrad("mv", ctx.q_shapes[0], ctx.needs_input_grad[6]),
-                qgrad("y", ctx.q_shapes[1], ctx.needs_input_grad[7]), *grads)
+        # (a parameter autograd asks about has a slice: the graph is keyed by every parameter's requires_grad)
+        grads = _param_grads(fg.params, ctx.needs_input_grad[8:],
+                             lambda p: out[fg.offsets[id(p)] : fg.offsets[id(p)] + p.numel()].view(p.shape))
+        return (None, None, None, None, None, None, _qgrad(fg.dq["mv"], ctx.q_shapes[0], ctx.needs_input_grad[6]),
+                _qgrad(fg.dq["y"], ctx.q_shapes[1], ctx.needs_input_grad[7]), *grads)
 
 
 class DMC(CodecBase):
@@ -672,7 +751,7 @@ class DMC(CodecBase):
         return net.three_convs("y_prior_fusion", [temporal, hier, ref_y])
 
     def _views_of_dpb(self, dpb):
-        return {k: self._dpb_in(k, dpb.get(k)) for k in ("ref_frame", "ref_feature", "ref_y", "ref_mv_y")}
+        return {k: self._dpb_in(k, dpb.get(k)) for k in DPB_KEYS}
 
     def _run(self, x, dpb, mv_y_q_scale, y_q_scale, mode, tape=None):
         """mode 'estimate' (forward_one_frame, unclamped recon as video_model.py:535) or
@@ -743,20 +822,9 @@ class DMC(CodecBase):
 
     @staticmethod
     def _dpb_out(o):
-        return {"ref_frame": o["recon"].nchw(), "ref_feature": o["feature"].nchw(), "ref_y": o["y_hat"].nchw(),
-                "ref_mv_y": o["mv_y_hat"].nchw()}
+        return {k: o[v].nchw() for k, v in zip(DPB_KEYS, ("recon", "feature", "y_hat", "mv_y_hat"))}
 
     # ------------------------------------------------------------------ training-mode forward
-    _noise_override = None  # tests: {"y", "mv_y", "z", "mv_z"} -> NCHW tensors replacing add_noise's draws
-
-    def _noise(self, key, N, H, W, C_):
-        """uniform(-0.5, 0.5) like CompressionModel.add_noise (common_model.py:46-49), dense NHWC."""
-        if self._noise_override is not None:
-            t = self._noise_override[key].to(device=self.device, dtype=torch.float32)
-            assert tuple(t.shape) == (N, C_, H, W), (key, t.shape)
-            return t.permute(0, 2, 3, 1).contiguous()
-        return torch.empty((N, H, W, C_), dtype=torch.float32, device=self.device).uniform_(-0.5, 0.5)
-
     def _train_frame(self, tape, x, dpb, mv_y_q_scale, y_q_scale):
         """Recorded forward: everything forward_one_frame computes in training mode
         (video_model.py:470-596 with self.training: straight-through rounding, noisy latents for
@@ -769,31 +837,15 @@ class DMC(CodecBase):
             tape.qstate("mv", self.P("mv_y_q_basic"), self._qvec(mv_y_q_scale, N, "mv_y_q_scale"), N, 64)
             tape.qstate("y", self.P("y_q_basic"), self._qvec(y_q_scale, N, "y_q_scale"), N, 96)
             o = self._run(x, dpb, tape.q["mv"]["q_scale"], tape.q["y"]["q_scale"], "train", tape=tape)
-            L = e.L
             sums = {}
             sums["sq"] = e.sq_err(o["recon"], o["x3"])
             tape.ops.append(("sq_err", "sq", o["recon"], o["x3"]))
             sums["me_sq"] = e.sq_err(o["warp_frame"], o["x3"])
             tape.ops.append(("sq_err", "me_sq", o["warp_frame"], o["x3"]))
-            for name, r, lat, nkey in (("bits_y", o["r_y"], o["y"], "y"), ("bits_mv_y", o["r_mv"], o["mv_y"], "mv_y")):
-                per = lat.HW * lat.C
-                noise = self._noise(nkey, N, lat.H, lat.W, lat.C)
-                y_bit = torch.empty_like(noise).view(-1)
-                lib.check(L.dcvc_add_planes(r["y_res"].data_ptr(), lat.C, noise.data_ptr(), lat.C, y_bit.data_ptr(), lat.C,
-                                            N * lat.HW, lat.C, e.stream()), "add_planes")
-                sums[name] = e.scale_bits(y_bit, r["scales_hat"], N, per)
-                tape.ops.append(("scale_bits", name, y_bit, r["scales_hat"], r["y_res"], N, per))
-            for name, z, est, nkey in (("bits_z", o["z"], "bit_estimator_z", "z"),
-                                       ("bits_mv_z", o["mv_z"], "bit_estimator_z_mv", "mv_z")):
-                noise = self._noise(nkey, N, z.H, z.W, z.C)
-                z_bit = View(torch.empty_like(noise), z.C)
-                lib.check(L.dcvc_add_planes(z.ptr, z.cs, noise.data_ptr(), z.C, z_bit.ptr, z_bit.cs, N * z.HW, z.C,
-                                            e.stream()), "add_planes")
-                blk = self._zblock(est)
-                sums[name] = e.factorized_bits(z_bit, blk)
-                plist = [self.P(f"{est}.f{i}.{k}") for i in (1, 2, 3) for k in ("h", "b", "a")]
-                plist += [self.P(f"{est}.f4.h"), self.P(f"{est}.f4.b")]
-                tape.ops.append(("factorized_bits", name, z_bit, z, blk, plist))
+            self._record_scale_bits(tape, sums, "bits_y", o["y"], o["r_y"], "y")
+            self._record_scale_bits(tape, sums, "bits_mv_y", o["mv_y"], o["r_mv"], "mv_y")
+            self._record_factorized_bits(tape, sums, "bits_z", o["z"], "bit_estimator_z", "z")
+            self._record_factorized_bits(tape, sums, "bits_mv_z", o["mv_z"], "bit_estimator_z_mv", "mv_z")
             return o, sums
         finally:
             e.tape = None
@@ -817,7 +869,7 @@ class DMC(CodecBase):
         if fg is None:
             if len(self._frame_graphs) >= 4:
                 self._frame_graphs.pop(next(iter(self._frame_graphs)))
-            fg = _FrameGraph(self, x, dict(zip(_FrameFn.DPB_KEYS, dpb_t)), qm, qy, params)
+            fg = _FrameGraph(self, x, dict(zip(DPB_KEYS, dpb_t)), qm, qy, params)
             self._frame_graphs[key] = fg
         return None if fg.busy else fg
 
@@ -831,23 +883,26 @@ class DMC(CodecBase):
         # only when it is the one passed in)
         skip = ("feature_adaptor_P." if dpb.get("ref_feature") is None else "feature_adaptor_I.")
         params = [p for n, p in self._pmap.items() if not n.startswith(skip) and n not in ("mv_y_q_scale", "y_q_scale")]
-        dpb_t = tuple(dpb.get(k) for k in _FrameFn.DPB_KEYS)
+        dpb_t = tuple(dpb.get(k) for k in DPB_KEYS)
         fg = self._frame_graph(x, dpb_t, qm, qy, params) if self.graph_training else None
         if fg is not None:
             outs = _GraphedFrameFn.apply(fg, x, *dpb_t, qm, qy, *params)
         else:
             outs = _FrameFn.apply(self, x, *dpb_t, qm, qy, *params)
-        bits_mv_y, bits_mv_z, bits_y, bits_z, sq, me_sq, recon, feature, y_hat, mv_y_hat = outs
+        bits_mv_y, bits_mv_z, bits_y, bits_z, sq, me_sq = outs[:6]
         pix = x.shape[2] * x.shape[3]
-        bpp_y, bpp_z, bpp_mv_y, bpp_mv_z = bits_y / pix, bits_z / pix, bits_mv_y / pix, bits_mv_z / pix
+        return self._result(x, pix, bits_y / pix, bits_z / pix, bits_mv_y / pix, bits_mv_z / pix, me_sq / pix, sq / pix,
+                            dict(zip(DPB_KEYS, outs[6:])))
+
+    def _result(self, x, pix, bpp_y, bpp_z, bpp_mv_y, bpp_mv_z, me_mse, mse, dpb):
+        """The result dictionary of forward_one_frame (video_model.py:575-596) from its per-sample terms."""
         bpp = bpp_y + bpp_z + bpp_mv_y + bpp_mv_z
         res = {"bpp_mv_y": bpp_mv_y, "bpp_mv_z": bpp_mv_z, "bpp_y": bpp_y, "bpp_z": bpp_z, "bpp": bpp,
-               "me_mse": me_sq / pix, "mse": sq / pix,
-               "dpb": {"ref_frame": recon, "ref_feature": feature, "ref_y": y_hat, "ref_mv_y": mv_y_hat}}
+               "me_mse": me_mse, "mse": mse, "dpb": dpb}
         for key, v in (("bit", bpp), ("bit_y", bpp_y), ("bit_z", bpp_z), ("bit_mv_y", bpp_mv_y), ("bit_mv_z", bpp_mv_z)):
             res[key] = torch.sum(v) * pix
         if self.report_ssim:
-            self._ssim_keys(res, x, recon)
+            self._ssim_keys(res, x, dpb["ref_frame"])
         return res
 
     # ------------------------------------------------------------------ public API
@@ -869,13 +924,7 @@ class DMC(CodecBase):
         bpp_mv_y = e.scale_bits(o["r_mv"]["y_q"], o["r_mv"]["scales_hat"], N, per_mv) / pix
         bpp_z = e.factorized_bits(o["z_hat"], self._zblock("bit_estimator_z")) / pix
         bpp_mv_z = e.factorized_bits(o["mv_z_hat"], self._zblock("bit_estimator_z_mv")) / pix
-        bpp = bpp_y + bpp_z + bpp_mv_y + bpp_mv_z
-        res = {"bpp_mv_y": bpp_mv_y, "bpp_mv_z": bpp_mv_z, "bpp_y": bpp_y, "bpp_z": bpp_z, "bpp": bpp,
-               "me_mse": me_mse, "mse": mse, "dpb": self._dpb_out(o)}
-        for key, v in (("bit", bpp), ("bit_y", bpp_y), ("bit_z", bpp_z), ("bit_mv_y", bpp_mv_y), ("bit_mv_z", bpp_mv_z)):
-            res[key] = torch.sum(v) * pix
-        if self.report_ssim:
-            self._ssim_keys(res, x, res["dpb"]["ref_frame"])
+        res = self._result(x, pix, bpp_y, bpp_z, bpp_mv_y, bpp_mv_z, me_mse, mse, self._dpb_out(o))
         res["_views"] = o
         return res
 
@@ -894,7 +943,7 @@ class DMC(CodecBase):
         if x.shape[0] != 1:
             raise NotImplementedError("graph replay codes one picture per call")
         ptrs = tuple(None if dpb.get(k) is None else (dpb[k].data_ptr(), tuple(dpb[k].shape), tuple(dpb[k].stride()))
-                     for k in ("ref_frame", "ref_feature", "ref_y", "ref_mv_y"))
+                     for k in DPB_KEYS)
         key = (tuple(x.shape), ptrs, self._flip, float(mv_y_q_scale), float(y_q_scale))
         g = self._graphs.get(key)
         if g is None:
@@ -906,24 +955,14 @@ class DMC(CodecBase):
             # eager warm-up with the same state: packs weights, allocates every buffer (nothing may be
             # allocated while capturing); its results are overwritten by the identical captured run
             o = self._run(xs, dpb, mv_y_q_scale, y_q_scale, "compress")
-            zm, zz = o["mv_z_hat"], o["z_hat"]
-            planes = lambda o: [("bit_estimator_z_mv", o["sym_mv_z"], None, (1, 64, zm.H, zm.W)),
-                                ("scale", o["r_mv"]["sym"][0], o["r_mv"]["idx"][0], None),
-                                ("scale", o["r_mv"]["sym"][1], o["r_mv"]["idx"][1], None),
-                                ("bit_estimator_z", o["sym_z"], None, (1, 64, zz.H, zz.W)),
-                                ("scale", o["r_y"]["sym"][0], o["r_y"]["idx"][0], None),
-                                ("scale", o["r_y"]["sym"][1], o["r_y"]["idx"][1], None)]
-            layout, total = self._stage_layout(planes(o))
+            layout, total = PendingStream.layout_of(self._planes(o))
             host = torch.empty(total, dtype=torch.int32, pin_memory=True)
             torch.cuda.synchronize(self.device)
             self._flip = flip0
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 o = self._run(xs, dpb, mv_y_q_scale, y_q_scale, "compress")
-                for (table, s_off, i_off, n, chan), (_, sym, idx, _) in zip(layout, planes(o)):
-                    host[s_off : s_off + n].copy_(sym, non_blocking=True)
-                    if idx is not None:
-                        host[i_off : i_off + n].copy_(idx, non_blocking=True)
+                PendingStream.copy_planes(host, layout, self._planes(o))
             g = dict(graph=graph, xs=xs, host=host, layout=layout, out=self._dpb_out(o), views=o, flip_after=self._flip,
                      pending=None)
             self._graphs[key] = g
@@ -937,6 +976,18 @@ class DMC(CodecBase):
         ev.record(torch.cuda.current_stream(self.device))
         g["pending"] = PendingStream(self, g["host"], ev, g["layout"], 1)
         return g
+
+    @staticmethod
+    def _planes(o):
+        """The six symbol planes of a picture in bitstream order: mv_z, mv_y step 0, mv_y step 1, z, y step 0, y step 1
+        (video_model.py:333-340)."""
+        N, zm, zz = o["N"], o["mv_z_hat"], o["z_hat"]
+        return [("bit_estimator_z_mv", o["sym_mv_z"], None, (N, 64, zm.H, zm.W)),
+                ("scale", o["r_mv"]["sym"][0], o["r_mv"]["idx"][0], None),
+                ("scale", o["r_mv"]["sym"][1], o["r_mv"]["idx"][1], None),
+                ("bit_estimator_z", o["sym_z"], None, (N, 64, zz.H, zz.W)),
+                ("scale", o["r_y"]["sym"][0], o["r_y"]["idx"][0], None),
+                ("scale", o["r_y"]["sym"][1], o["r_y"]["idx"][1], None)]
 
     @torch.no_grad()
     def compress(self, x, dpb, mv_y_q_scale, y_q_scale, defer=False, coder="host", graph=False, check_range=True):
@@ -953,33 +1004,13 @@ class DMC(CodecBase):
             if coder != "host":
                 raise NotImplementedError("graph replay is wired to the host coder")
             g = self._compress_graph(x, dpb, mv_y_q_scale, y_q_scale)
-            d = g["out"]
-            if defer:
-                return {"dbp": d, "dpb": d, "pending": g["pending"], "_views": g["views"]}
-            streams = g["pending"].finish_all()
-            if check_range:
-                self.engine().check_status()
-            return {"dbp": d, "dpb": d, "bit_stream": streams[0], "bit_streams": streams, "_views": g["views"]}
-        o = self._run(x, dpb, mv_y_q_scale, y_q_scale, "compress")
-        N = o["N"]  # N > 1: a batch of rate points, one independent stream per element ("bit_streams")
-        zm, zz = o["mv_z_hat"], o["z_hat"]
-        # bitstream order: mv_z, mv_y step 0, mv_y step 1, z, y step 0, y step 1 (video_model.py:333-340)
-        assert coder in ("host", "device")
-        pending = (self._stage_symbols if coder == "host" else self._stage_symbols_device)([
-            ("bit_estimator_z_mv", o["sym_mv_z"], None, (N, 64, zm.H, zm.W)),
-            ("scale", o["r_mv"]["sym"][0], o["r_mv"]["idx"][0], None),
-            ("scale", o["r_mv"]["sym"][1], o["r_mv"]["idx"][1], None),
-            ("bit_estimator_z", o["sym_z"], None, (N, 64, zz.H, zz.W)),
-            ("scale", o["r_y"]["sym"][0], o["r_y"]["idx"][0], None),
-            ("scale", o["r_y"]["sym"][1], o["r_y"]["idx"][1], None),
-        ], batch=N)
-        d = self._dpb_out(o)
-        if defer:
-            return {"dbp": d, "dpb": d, "pending": pending, "_views": o}
-        streams = pending.finish_all()
-        if check_range:
-            self.engine().check_status()
-        return {"dbp": d, "dpb": d, "bit_stream": streams[0], "bit_streams": streams, "_views": o}
+            d, o, pending = g["out"], g["views"], g["pending"]
+        else:
+            o = self._run(x, dpb, mv_y_q_scale, y_q_scale, "compress")
+            # N > 1: a batch of rate points, one independent stream per element ("bit_streams")
+            pending = self._stage(self._planes(o), o["N"], coder)
+            d = self._dpb_out(o)
+        return self._compress_result({"dbp": d, "dpb": d, "_views": o}, pending, defer, check_range)
 
     @torch.no_grad()
     def decompress(self, dpb, string, height, width, mv_y_q_scale, y_q_scale, coder=None, defer_check=False,
@@ -987,19 +1018,8 @@ class DMC(CodecBase):
         """coder: "host" (reference format), "device" (payloads of compress(coder="device")) or None =
         tell them apart by the device format's magic.  defer_check (device format only): do not
         synchronise to read the kernels' status word; the caller calls device_coder().check() later."""
-        self._defer_check = defer_check
-        if self.entropy_coder is None:
-            raise RuntimeError("call update() before compress()/decompress()")
-        if coder is None:
-            coder = "device" if string[:4] == E.DRANS_MAGIC else "host"
-        self._dc_active = coder == "device"
-        try:
-            r = self._decompress(dpb, string, height, width, mv_y_q_scale, y_q_scale)
-        finally:
-            self._dc_active = False
-        if check_range:  # (see compress)
-            self.engine().check_status()
-        return r
+        return self._decompress_guarded(string, coder, defer_check, check_range,
+                                        dpb, string, height, width, mv_y_q_scale, y_q_scale)
 
     def _decompress(self, dpb, string, height, width, mv_y_q_scale, y_q_scale):
         e = self.engine()
@@ -1009,10 +1029,7 @@ class DMC(CodecBase):
         q_y = self._qvec(y_q_scale, N, "y_q_scale")
         dv = self._views_of_dpb(dpb)
         k = self._out_set(*dv.values())
-        if self._dc_active:
-            self.device_coder().set_stream(string)
-        else:
-            self.entropy_coder.set_stream(string)
+        self._open_stream(string)
         pyr, pyr_done = self._fork_pyramid(net, dv, None)
         zh, zw = S.get_downsampled_shape(height, width, 64)
         H, W = zh * 64, zw * 64
@@ -1034,10 +1051,7 @@ class DMC(CodecBase):
         feature = net.buf(f"dpb{k}.ref_feature", N=N, H=H, W=W, C=64)
         recon = net.buf(f"dpb{k}.ref_frame", N=N, H=H, W=W, C=3)
         net.recon_generation(dec_feature, c1, feature, recon, clamp=self._clamp_decoded)  # recon.clamp(0, 1), :413
-        if self._dc_active:
-            self._dcoder.release()
-            if not self._defer_check:
-                self._dcoder.check()  # the one synchronisation of a device-coded picture
+        self._close_stream()
         o = dict(recon=recon, feature=feature, y_hat=y_hat, mv_y_hat=mv_y_hat)
         return {"dpb": self._dpb_out(o)}
 

@@ -160,8 +160,11 @@ class Engine:
 
     def check_status(self):
         """Raise if a split-fp16 kernel clamped (or would clamp) an activation since the last call."""
-        v = self.read_status()
+        self._raise_if_clamped(0 if self._status is None else int(self._status.item()))
+
+    def _raise_if_clamped(self, v):
         if v:
+            self._status.zero_()
             raise lib.KernelError(f"split-fp16 activation range exceeded (status {v}): |x| > 8188; use precision='fp32'")
 
     def status_snapshot(self):
@@ -177,10 +180,7 @@ class Engine:
 
         def check():
             ev.synchronize()
-            v = int(host[0])
-            if v:
-                self._status.zero_()
-                raise lib.KernelError(f"split-fp16 activation range exceeded (status {v}): |x| > 8188; use precision='fp32'")
+            self._raise_if_clamped(int(host[0]))
 
         return check
 
@@ -237,10 +237,9 @@ class Engine:
         x = x.detach()
         if x.device != self.device or x.dtype != torch.float32:
             x = x.to(device=self.device, dtype=torch.float32)
-        cs = x.stride(3) if x.dim() == 4 else 0
-        if x.stride(1) == 1 and cs >= C_ and cs % 4 == 0 and x.stride(2) == W * cs and x.stride(0) == H * W * cs \
-                and x.data_ptr() % 16 == 0:
-            lib.check(self.L.dcvc_copy_channels(x.data_ptr(), cs, out.ptr, out.cs, N * H * W, C_, self.stream()),
+        v = View.alias(x)
+        if v is not None:
+            lib.check(self.L.dcvc_copy_channels(v.ptr, v.cs, out.ptr, out.cs, N * H * W, C_, self.stream()),
                       "copy_channels")
         else:
             x = x.contiguous()
@@ -337,14 +336,20 @@ class Engine:
         for pk, ver in zip(packs, vers):
             pk.version = ver
 
-    def pack(self, key, weight: torch.Tensor, bias, seg_C, ps, cin_slice=None) -> PackedConv:
-        if self.tape is not None:
-            return self.pack_dev(key, weight, bias, seg_C, ps, cin_slice)
-        ver = (weight._version, None if bias is None else bias._version, weight.data_ptr())
-        key = (key, self.precision)
-        pk = self.packs.get(key)
-        if pk is not None and pk.version == ver:
-            return pk
+    # The host packings of one layer, one per convolution kernel:
+    #   name -> (size function, bytes per unit of its result, pack function, extra arguments of the pack function,
+    #            padded output channels where the size function does not report them)
+    # Both functions take the layer as (Cout, ks, nseg, segs) -- the tap-paired 7x7 layout, which has ONE segment of <= 8
+    # input channels, as (Cout, Cin) -- and a packing keeps the pixel shuffle exactly when its pack function is told of it.
+    _HOST_PACKINGS = {
+        "mfma": ("dcvc_conv_pack_size", 4, "dcvc_conv_pack_weights", ("ps", "precision"), None),
+        "small": ("dcvc_conv_small_pack_bytes", 1, "dcvc_conv_small_pack_weights", (), 16),   # <= 16 output channels
+        "paired": ("dcvc_conv_pack_size_paired", 4, "dcvc_conv_pack_weights_paired", (), None),
+        "k32": ("dcvc_conv_k32_pack_bytes", 1, "dcvc_conv_k32_pack_weights", ("ps",), None),  # 32-channel chunks
+    }
+
+    def _pack_host(self, variant, key, weight, bias, seg_C, ps, cin_slice, ver) -> PackedConv:
+        size_fn, unit, pack_fn, extra, cpad_fixed = self._HOST_PACKINGS[variant]
         w = weight.detach().float().cpu()
         if cin_slice is not None:
             w = w[:, cin_slice[0] : cin_slice[1]]
@@ -353,74 +358,42 @@ class Engine:
         assert sum(seg_C) == Cin, (key, seg_C, Cin)
         b = None if bias is None else bias.detach().float().cpu().contiguous().numpy()
         segs = (C.c_int32 * len(seg_C))(*seg_C)
-        cpad = C.c_int32()
-        n = self.L.dcvc_conv_pack_size(Cout, ks, len(seg_C), segs, C.byref(cpad))
+        layer = (Cout, Cin) if variant == "paired" else (Cout, ks, len(seg_C), segs)
+        cpad = C.c_int32(cpad_fixed or 0)
+        n = getattr(self.L, size_fn)(*layer, *(() if cpad_fixed else (C.byref(cpad),)))
         if n < 0:
-            raise lib.KernelError(f"conv_pack_size({key})")
-        wp = np.empty(n, np.float32)
+            raise lib.KernelError(f"{size_fn[5:]}({key})")
+        wp = np.empty(n * unit // 4, np.float32)
         bp = np.empty(cpad.value, np.float32)
-        lib.check(self.L.dcvc_conv_pack_weights(w.ctypes.data, None if b is None else b.ctypes.data, Cout, ks,
-                                                len(seg_C), segs, int(ps), lib.PRECISIONS[self.precision],
-                                                wp.ctypes.data, bp.ctypes.data),
-                  f"conv_pack_weights({key})")
+        opts = {"ps": int(ps), "precision": lib.PRECISIONS[self.precision]}
+        lib.check(getattr(self.L, pack_fn)(w.ctypes.data, None if b is None else b.ctypes.data, *layer,
+                                           *(opts[k] for k in extra), wp.ctypes.data, bp.ctypes.data),
+                  f"{pack_fn[5:]}({key}) [status -3: a |weight| >= 1023.5 does not fit split fp16, use precision='fp32']")
         pk = PackedConv()
-        pk.w = torch.from_numpy(wp).to(self.device)
-        pk.b = torch.from_numpy(bp).to(self.device)
-        pk.ks, pk.Cout, pk.Cout_pad, pk.seg_C, pk.ps, pk.version = ks, Cout, cpad.value, tuple(seg_C), bool(ps), ver
-        pk.precision = lib.PRECISIONS[self.precision]
+        pk.w, pk.b = torch.from_numpy(wp).to(self.device), torch.from_numpy(bp).to(self.device)
+        pk.ks, pk.Cout, pk.Cout_pad, pk.seg_C, pk.ps, pk.version = ks, Cout, cpad.value, tuple(seg_C), bool(ps) and "ps" in extra, ver
+        pk.precision = opts["precision"]
         pk.weight, pk.bias, pk.cin_slice, pk.key = weight, bias, cin_slice, key
-        pk.host = True  # packed from the module's own weight: the alternative kernels may re-pack it their way
-        self.packs[key] = pk
         return pk
 
-    def pack_small(self, pk: PackedConv) -> PackedConv:
-        """The same layer packed for dcvc_conv2d_small (<= 16 output channels), cached beside the other packing."""
-        q = getattr(pk, "small", None)
-        if q is not None and q.version == pk.version:
-            return q
-        w = pk.weight.detach().float().cpu()
-        if pk.cin_slice is not None:
-            w = w[:, pk.cin_slice[0] : pk.cin_slice[1]]
-        w = w.contiguous().numpy()
-        b = None if pk.bias is None else pk.bias.detach().float().cpu().contiguous().numpy()
-        segs = (C.c_int32 * len(pk.seg_C))(*pk.seg_C)
-        n = self.L.dcvc_conv_small_pack_bytes(pk.Cout, pk.ks, len(pk.seg_C), segs)
-        if n < 0:
-            raise lib.KernelError(f"conv_small_pack_bytes({pk.key})")
-        wp = np.empty(n // 4, np.float32)
-        bp = np.empty(16, np.float32)
-        lib.check(self.L.dcvc_conv_small_pack_weights(w.ctypes.data, None if b is None else b.ctypes.data, pk.Cout, pk.ks,
-                                                      len(pk.seg_C), segs, wp.ctypes.data, bp.ctypes.data),
-                  f"conv_small_pack_weights({pk.key}) [status -3: a |weight| >= 1023.5 does not fit split fp16, use precision='fp32']")
-        q = PackedConv()
-        q.w, q.b = torch.from_numpy(wp).to(self.device), torch.from_numpy(bp).to(self.device)
-        q.ks, q.Cout, q.Cout_pad, q.seg_C, q.ps, q.version, q.key = pk.ks, pk.Cout, 16, pk.seg_C, False, pk.version, pk.key
-        pk.small = q
-        return q
+    def pack(self, key, weight: torch.Tensor, bias, seg_C, ps, cin_slice=None) -> PackedConv:
+        if self.tape is not None:
+            return self.pack_dev(key, weight, bias, seg_C, ps, cin_slice)
+        ver = (weight._version, None if bias is None else bias._version, weight.data_ptr())
+        key = (key, self.precision)
+        pk = self.packs.get(key)
+        if pk is None or pk.version != ver:
+            pk = self.packs[key] = self._pack_host("mfma", key, weight, bias, seg_C, ps, cin_slice, ver)
+            pk.host = True  # packed from the module's own weight: the alternative kernels may re-pack it their way
+        return pk
 
-    def pack_paired(self, pk: PackedConv) -> PackedConv:
-        """The same 7x7 layer (one segment of <= 8 input channels) packed in tap pairs for dcvc_conv2d with pair_taps."""
-        q = getattr(pk, "paired", None)
-        if q is not None and q.version == pk.version:
-            return q
-        w = pk.weight.detach().float().cpu()
-        if pk.cin_slice is not None:
-            w = w[:, pk.cin_slice[0] : pk.cin_slice[1]]
-        w = w.contiguous().numpy()
-        b = None if pk.bias is None else pk.bias.detach().float().cpu().contiguous().numpy()
-        cpad = C.c_int32()
-        n = self.L.dcvc_conv_pack_size_paired(pk.Cout, pk.seg_C[0], C.byref(cpad))
-        if n < 0:
-            raise lib.KernelError(f"conv_pack_size_paired({pk.key})")
-        wp = np.empty(n, np.float32)
-        bp = np.empty(cpad.value, np.float32)
-        lib.check(self.L.dcvc_conv_pack_weights_paired(w.ctypes.data, None if b is None else b.ctypes.data, pk.Cout, pk.seg_C[0],
-                                                       wp.ctypes.data, bp.ctypes.data),
-                  f"conv_pack_weights_paired({pk.key}) [status -3: a |weight| >= 1023.5 does not fit split fp16, use precision='fp32']")
-        q = PackedConv()
-        q.w, q.b = torch.from_numpy(wp).to(self.device), torch.from_numpy(bp).to(self.device)
-        q.ks, q.Cout, q.Cout_pad, q.seg_C, q.ps, q.version, q.key = pk.ks, pk.Cout, cpad.value, pk.seg_C, False, pk.version, pk.key
-        pk.paired = q
+    def _repacked(self, pk: PackedConv, variant) -> PackedConv:
+        """The same layer packed for dcvc_conv2d_small ("small"), dcvc_conv2d_k32 ("k32") or dcvc_conv2d with pair_taps
+        ("paired"), cached beside the other packing."""
+        q = getattr(pk, variant, None)
+        if q is None or q.version != pk.version:
+            q = self._pack_host(variant, pk.key, pk.weight, pk.bias, pk.seg_C, pk.ps, pk.cin_slice, pk.version)
+            setattr(pk, variant, q)
         return q
 
     def pair_capable(self, pk: PackedConv, stride) -> bool:
@@ -429,32 +402,6 @@ class Engine:
         encoder and the decoder side.  Host-packed weights only (a training step packs on the device, plain layout)."""
         return (self.precision == "fp16x3" and self.tape is None and self.use_pairs and getattr(pk, "host", False)
                 and pk.ks == 7 and stride == 1 and len(pk.seg_C) == 1 and pk.seg_C[0] <= 8 and not pk.ps and pk.Cout > 16)
-
-    def pack_k32(self, pk: PackedConv) -> PackedConv:
-        """The same layer packed for dcvc_conv2d_k32 (32-channel chunks), cached beside the other packing."""
-        q = getattr(pk, "k32", None)
-        if q is not None and q.version == pk.version:
-            return q
-        w = pk.weight.detach().float().cpu()
-        if pk.cin_slice is not None:
-            w = w[:, pk.cin_slice[0] : pk.cin_slice[1]]
-        w = w.contiguous().numpy()
-        b = None if pk.bias is None else pk.bias.detach().float().cpu().contiguous().numpy()
-        segs = (C.c_int32 * len(pk.seg_C))(*pk.seg_C)
-        cpad = C.c_int32()
-        n = self.L.dcvc_conv_k32_pack_bytes(pk.Cout, pk.ks, len(pk.seg_C), segs, C.byref(cpad))
-        if n < 0:
-            raise lib.KernelError(f"conv_k32_pack_bytes({pk.key})")
-        wp = np.empty(n // 4, np.float32)
-        bp = np.empty(cpad.value, np.float32)
-        lib.check(self.L.dcvc_conv_k32_pack_weights(w.ctypes.data, None if b is None else b.ctypes.data, pk.Cout, pk.ks,
-                                                    len(pk.seg_C), segs, int(pk.ps), wp.ctypes.data, bp.ctypes.data),
-                  f"conv_k32_pack_weights({pk.key}) [status -3: a |weight| >= 1023.5 does not fit split fp16, use precision='fp32']")
-        q = PackedConv()
-        q.w, q.b = torch.from_numpy(wp).to(self.device), torch.from_numpy(bp).to(self.device)
-        q.ks, q.Cout, q.Cout_pad, q.seg_C, q.ps, q.version, q.key = pk.ks, pk.Cout, cpad.value, pk.seg_C, pk.ps, pk.version, pk.key
-        pk.k32 = q
-        return q
 
     def k32_capable(self, pk: PackedConv, stride, out: View, res, res2, gate, srcs=()) -> bool:
         """Layers routed to dcvc_conv2d_k32: fp16x3, 3x3, stride 1, every input segment a multiple of 32 channels,
@@ -499,11 +446,7 @@ class Engine:
         if self.profile is None:
             launch()
             return
-        # events go on the stream the kernel is launched on (torch's current stream)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-        launch()
-        ev1.record()
+        ev0, ev1 = self._bracket(launch)
         flops = 2.0 * s0.N * Ho * Wo * pk.Cout * sum(pk.seg_C) * pk.ks * pk.ks  # algorithmic, unpadded
         nout = s0.N * Ho * Wo * pk.Cout
         abytes = 4.0 * (s0.N * s0.H * s0.W * sum(pk.seg_C) + nout * (1 + (res is not None) + (res2 is not None))
@@ -512,6 +455,15 @@ class Engine:
         if self.profile_detail is not None:
             self.profile_detail.append((ev0, ev1, flops, f"k{pk.ks}s{stride}{tag} {pk.seg_C}->{pk.Cout}{'ps' if pk.ps else ''} "
                                                          f"{s0.H}x{s0.W}", note))
+
+    @staticmethod
+    def _bracket(launch):
+        # events go on the stream the kernel is launched on (torch's current stream)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        launch()
+        ev1.record()
+        return ev0, ev1
 
     def chan_partial_buf(self, name, pk: PackedConv, out: View, stride=1):
         """(buffer, rows per image) for the fused channel sums of a convolution writing `out`."""
@@ -535,7 +487,7 @@ class Engine:
         small = band is None and self.small_capable(pk, stride, gate, res2, chan_partial)
         k32 = not small and not isinstance(out_slope, tuple) and self.k32_capable(pk, stride, out, res, res2, gate, srcs)
         paired = not small and not k32 and self.pair_capable(pk, stride)
-        wq = self.pack_small(pk) if small else (self.pack_k32(pk) if k32 else (self.pack_paired(pk) if paired else pk))
+        wq = self._repacked(pk, "small" if small else ("k32" if k32 else "paired")) if (small or k32 or paired) else pk
         a.pair_taps = int(paired)
         a.wpack, a.bpack = wq.w.data_ptr(), wq.b.data_ptr()
         a.ks, a.stride, a.Cout, a.Cout_pad = pk.ks, stride, pk.Cout, wq.Cout_pad
@@ -588,10 +540,7 @@ class Engine:
         events on the launch stream and record its ALGORITHMIC bytes (every operand once: SURVEY 8d)."""
         if self.profile_hbm is None:
             return launch()
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-        launch()
-        ev1.record()
+        ev0, ev1 = self._bracket(launch)
         self.profile_hbm.setdefault((kernel, shape), []).append((ev0, ev1, float(abytes)))
 
     def collect_profile_hbm(self):

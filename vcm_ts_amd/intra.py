@@ -13,11 +13,8 @@ import time
 
 import torch
 
-from . import entropy as E
-from . import lib
 from . import stream as S
-from .dmc import CodecBase
-from .engine import View
+from .dmc import CodecBase, _load_upstream, _param_grads, _qgrad
 from .params import intra_spec
 
 
@@ -42,23 +39,12 @@ class _IntraFn(torch.autograd.Function):
         if tape is None:
             raise RuntimeError("this picture's tape was already consumed (retain_graph is not supported)")
         e = tape.e
-        for name, g in (("bits_y", g_y), ("bits_z", g_z), ("sq", g_sq)):
-            if g is not None:
-                tape.up[name] = g.detach().to(torch.float32).contiguous()
+        _load_upstream(tape, (("bits_y", g_y), ("bits_z", g_z), ("sq", g_sq)))
         if g_xhat is not None:  # a loss computed on the reconstruction by the caller (perceptual terms)
             e.from_nchw(g_xhat, tape.grad(ctx.out_view))
         tape.backward()
-        grads = []
-        for p, need in zip(ctx.params, ctx.needs_input_grad[3:]):
-            g = tape.pgrads.get(id(p)) if need else None
-            grads.append(torch.zeros_like(p) if (need and g is None) else g)
-        gq = None
-        if ctx.needs_input_grad[2]:
-            g = tape.q["y"]["dq_scale"]
-            n = 1
-            for s_ in ctx.q_shape:
-                n *= s_
-            gq = (g.sum() if n == 1 else g.clone()).reshape(ctx.q_shape)
+        grads = _param_grads(ctx.params, ctx.needs_input_grad[3:], lambda p: tape.pgrads.get(id(p)))
+        gq = _qgrad(tape.q["y"]["dq_scale"], ctx.q_shape, ctx.needs_input_grad[2])
         ctx.tape = None
         return (None, None, gq, *grads)
 
@@ -115,16 +101,6 @@ class IntraNoAR(CodecBase):
         return dict(N=Nb, H=H, W=W, x3=x3, y=y, z=z, z_hat=z_hat, sym_z=sym_z, r=r, x_hat=x_hat, y_hat=y_hat)
 
     # ------------------------------------------------------------------ training-mode forward (round 4)
-    _noise_override = None  # tests: {"y", "z"} -> NCHW tensors replacing add_noise's draws
-
-    def _noise(self, key, N, H, W, C_):
-        """uniform(-0.5, 0.5) like CompressionModel.add_noise (common_model.py:46-49), dense NHWC."""
-        if self._noise_override is not None:
-            t = self._noise_override[key].to(device=self.device, dtype=torch.float32)
-            assert tuple(t.shape) == (N, C_, H, W), (key, t.shape)
-            return t.permute(0, 2, 3, 1).contiguous()
-        return torch.empty((N, H, W, C_), dtype=torch.float32, device=self.device).uniform_(-0.5, 0.5)
-
     def _train_frame(self, tape, x, q_scale):
         """Recorded forward of IntraNoAR.forward in training mode (image_model.py:54-100 with self.training: straight-through
         rounding, uniform noise on the residual and on z for the bit estimates, Gaussian likelihood).  The reference's
@@ -137,27 +113,11 @@ class IntraNoAR(CodecBase):
             N = x.shape[0]
             tape.qstate("y", self.P("q_basic"), self._qvec(q_scale, N, "q_scale"), N, self.N)
             o = self._run(x, tape.q["y"]["q_scale"], "train", tape=tape)
-            L, sums = e.L, {}
+            sums = {}
             sums["sq"] = e.sq_err(o["x_hat"], o["x3"])
             tape.ops.append(("sq_err", "sq", o["x_hat"], o["x3"]))
-            lat, r = o["y"], o["r"]
-            per = lat.HW * lat.C
-            noise = self._noise("y", N, lat.H, lat.W, lat.C)
-            y_bit = torch.empty_like(noise).view(-1)
-            lib.check(L.dcvc_add_planes(r["y_res"].data_ptr(), lat.C, noise.data_ptr(), lat.C, y_bit.data_ptr(), lat.C,
-                                        N * lat.HW, lat.C, e.stream()), "add_planes")
-            sums["bits_y"] = e.scale_bits(y_bit, r["scales_hat"], N, per, gaussian=True)
-            tape.ops.append(("scale_bits", "bits_y", y_bit, r["scales_hat"], r["y_res"], N, per, 1))
-            z = o["z"]
-            noise = self._noise("z", N, z.H, z.W, z.C)
-            z_bit = View(torch.empty_like(noise), z.C)
-            lib.check(L.dcvc_add_planes(z.ptr, z.cs, noise.data_ptr(), z.C, z_bit.ptr, z_bit.cs, N * z.HW, z.C, e.stream()),
-                      "add_planes")
-            blk = self._zblock("bit_estimator_z")
-            sums["bits_z"] = e.factorized_bits(z_bit, blk)
-            plist = [self.P(f"bit_estimator_z.f{i}.{k}") for i in (1, 2, 3) for k in ("h", "b", "a")]
-            plist += [self.P("bit_estimator_z.f4.h"), self.P("bit_estimator_z.f4.b")]
-            tape.ops.append(("factorized_bits", "bits_z", z_bit, z, blk, plist))
+            self._record_scale_bits(tape, sums, "bits_y", o["y"], o["r"], "y")
+            self._record_factorized_bits(tape, sums, "bits_z", o["z"], "bit_estimator_z", "z")
             return o, sums
         finally:
             e.tape = None
@@ -197,44 +157,23 @@ class IntraNoAR(CodecBase):
             raise RuntimeError("call update() before compress()/decompress()")
         o = self._run(x, q_scale, "compress")
         N = o["N"]  # N > 1: a batch of rate points (one q-scale per element), one independent stream each
-        assert coder in ("host", "device")
         zs = o["z_hat"]
-        pending = (self._stage_symbols if coder == "host" else self._stage_symbols_device)([  # image_model.py:168-171
+        pending = self._stage([  # image_model.py:168-171
             ("bit_estimator_z", o["sym_z"], None, (N, self.N, zs.H, zs.W)),
             ("scale", o["r"]["sym"][0], o["r"]["idx"][0], None),
             ("scale", o["r"]["sym"][1], o["r"]["idx"][1], None),
-        ], batch=N)
-        if defer:
-            return {"pending": pending, "x_hat": o["x_hat"].nchw(), "_views": o}
-        streams = pending.finish_all()
-        if check_range:  # split-fp16 range guard (DMC.compress says when a caller reads it itself)
-            self.engine().check_status()
-        return {"bit_stream": streams[0], "bit_streams": streams, "x_hat": o["x_hat"].nchw(), "_views": o}
+        ], N, coder)
+        return self._compress_result({"x_hat": o["x_hat"].nchw(), "_views": o}, pending, defer, check_range)
 
     @torch.no_grad()
     def decompress(self, bit_stream, height, width, q_scale, coder=None, defer_check=False, check_range=True):
-        self._defer_check = defer_check
-        if self.entropy_coder is None:
-            raise RuntimeError("call update() before compress()/decompress()")
-        if coder is None:
-            coder = "device" if bit_stream[:4] == E.DRANS_MAGIC else "host"
-        self._dc_active = coder == "device"
-        try:
-            r = self._decompress(bit_stream, height, width, q_scale)
-        finally:
-            self._dc_active = False
-        if check_range:
-            self.engine().check_status()
-        return r
+        return self._decompress_guarded(bit_stream, coder, defer_check, check_range, bit_stream, height, width, q_scale)
 
     def _decompress(self, bit_stream, height, width, q_scale):
         e = self.engine()
         net = self._net
         q = self._qvec(q_scale, 1, "q_scale")
-        if self._dc_active:
-            self.device_coder().set_stream(bit_stream)
-        else:
-            self.entropy_coder.set_stream(bit_stream)
+        self._open_stream(bit_stream)
         zh, zw = S.get_downsampled_shape(height, width, 64)
         sym = self._decode_factorized("bit_estimator_z", 1, self.N, zh, zw)
         z_hat = e.symbols_to_nhwc(sym, net.buf("z_hat", N=1, H=zh, W=zw, C=self.N))
@@ -242,10 +181,7 @@ class IntraNoAR(CodecBase):
         y_hat = net.buf("y_hat", N=1, H=zh * 4, W=zw * 4, C=self.N)
         self._dual_prior_decode("y", fusion, "y_spatial_prior", y_hat, self.P("q_basic").reshape(-1), q)
         x_hat = self._synthesis(net, y_hat, 1, zh * 64, zw * 64, clamp=self._clamp_decoded)  # .clamp_(0, 1), :199
-        if self._dc_active:
-            self._dcoder.release()
-            if not self._defer_check:
-                self._dcoder.check()
+        self._close_stream()
         return {"x_hat": x_hat.nchw()}
 
     def encode_decode(self, x, q_scale, output_path=None, pic_width=None, pic_height=None):

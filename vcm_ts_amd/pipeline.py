@@ -57,6 +57,20 @@ def timed_region(fn, device=None, with_local=False):
     return (dt, result, local) if with_local else (dt, result)
 
 
+def intra_dpb(x_hat):
+    """The DPB an I picture leaves behind: its reconstruction and nothing else (video_coder.py:122-130)."""
+    return {"ref_frame": x_hat, "ref_feature": None, "ref_y": None, "ref_mv_y": None}
+
+
+def decode_picture(i_net, p_net, kind, q, payload, dpb, height, width, defer_check=False):
+    """Decode one coded picture ("I" with q = (q index,), "P" with q = (mv_y index, y index)) against `dpb`; returns the
+    DPB it leaves.  The split-fp16 range guard is left to the caller (once per GOP, not per picture)."""
+    if kind == "I":
+        return intra_dpb(i_net.decompress(payload, height, width, q[0] / 100, defer_check=defer_check, check_range=False)["x_hat"])
+    return p_net.decompress(dpb, payload, height, width, q[0] / 100, q[1] / 100, defer_check=defer_check,
+                            check_range=False)["dpb"]
+
+
 class GopEncoder:
     def __init__(self, i_frame_net, p_frame_net, gop_size=32, coder="host", graphs=False):
         """coder="device": payloads in the opt-in GPU format of include/dcvc_hip_rans.h (symbol planes
@@ -104,7 +118,7 @@ class GopEncoder:
         for t, x in enumerate(frames):
             if t % self.gop == 0:
                 r = self.i_net.compress(x, q_i, defer=True, coder=self.coder, check_range=False)
-                dpb = {"ref_frame": r["x_hat"], "ref_feature": None, "ref_y": None, "ref_mv_y": None}
+                dpb = intra_dpb(r["x_hat"])
                 item = ("I", (qi_idx,), r["pending"], t)
             else:
                 r = self.p_net.compress(x, dpb, q_mv_y, q_y, defer=True, coder=self.coder, graph=self.graphs, check_range=False)
@@ -138,15 +152,9 @@ class GopEncoder:
         for kind, q, payload in coded:
             # device-format pictures need no host round trip: enqueue them all, read the status once
             dev_fmt = payload[:4] == DRANS_MAGIC
-            net = self.i_net if kind == "I" else self.p_net
             if dev_fmt:
-                deferred.add(net)
-            if kind == "I":
-                x_hat = net.decompress(payload, height, width, q[0] / 100, defer_check=dev_fmt, check_range=False)["x_hat"]
-                dpb = {"ref_frame": x_hat, "ref_feature": None, "ref_y": None, "ref_mv_y": None}
-            else:
-                dpb = net.decompress(dpb, payload, height, width, q[0] / 100, q[1] / 100, defer_check=dev_fmt,
-                                     check_range=False)["dpb"]
+                deferred.add(self.i_net if kind == "I" else self.p_net)
+            dpb = decode_picture(self.i_net, self.p_net, kind, q, payload, dpb, height, width, defer_check=dev_fmt)
             recs.append(dpb["ref_frame"].clone())
         for net in deferred:
             net.device_coder().check()

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import stream as S
-from .pipeline import pad_frame
+from .pipeline import ConcurrentGopEncoder, decode_picture, pad_frame
 
 
 class PNGReader:
@@ -245,6 +245,110 @@ class _QualityLog:
         return out
 
 
+class _PinnedRing:
+    """Pictures go to the device through a ring of pinned buffers on a copy stream of their own: a pageable
+    `.to(device)` would be a synchronous copy queued BEHIND the previous picture's kernels, i.e. the host could
+    never run ahead of the GPU (measured: 26 ms of every picture's 66 spent blocked in that call)."""
+
+    def __init__(self, dev, shape, slots=3):
+        self.dev, self.n, self.copy_stream = dev, 0, torch.cuda.Stream(dev)
+        self.ring = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(slots)]
+        self.done = [None] * slots
+
+    def host(self):
+        """The next buffer to fill, as a numpy array."""
+        j = self.n % len(self.ring)
+        if self.done[j] is not None:
+            self.done[j].synchronize()  # the copy that last read this pinned buffer (three pictures ago)
+        return self.ring[j].numpy()
+
+    def upload(self):
+        """The buffer host() handed out, as a device tensor the current stream may read."""
+        j = self.n % len(self.ring)
+        self.n += 1
+        with torch.cuda.stream(self.copy_stream):
+            d = self.ring[j].to(self.dev, non_blocking=True)
+            self.done[j] = torch.cuda.Event()
+            self.done[j].record(self.copy_stream)
+        cur = torch.cuda.current_stream(self.dev)  # (this GOP stream's: ConcurrentGopEncoder pulls frames inside it)
+        cur.wait_event(self.done[j])
+        d.record_stream(cur)
+        return d
+
+
+class _EncodeRun:
+    """What encoding a sequence of `n_frames` pictures of `size` = (height, width) into `bin_dir` is, whatever the
+    pictures come from: the GOP streams and their codecs, which frame numbers each stream codes, the .bin sink and
+    the bits / quality report.  encode_folder and encode_video supply the pictures and take the reconstructions."""
+
+    def __init__(self, bin_dir, n_frames, size, gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams, log_cls):
+        """nets, gop_streams: see encode_folder.  log_cls: the _QualityLog to keep per stream, or None for no report."""
+        os.makedirs(bin_dir, exist_ok=True)
+        self.bin_dir, self.n_frames, self.size, self.gop, self.dev = bin_dir, n_frames, size, gop, torch.device(device)
+        self.n_gops = (n_frames + gop - 1) // gop
+        self.K = K = max(1, min(int(gop_streams), self.n_gops))
+        pairs = [nets] if (nets is not None and not isinstance(nets, list)) else list(nets or [])
+        made = iter(pairs[:K] + [None] * K)
+        self.cenc = ConcurrentGopEncoder(lambda: next(made) or _nets(self.dev, precision, i_ckpt, p_ckpt), gop_size=gop,
+                                         streams=K, coder=coder)
+        self.bits = {}
+        self.quality = [log_cls(gop) for _ in range(K)] if log_cls else None
+
+    def global_index(self, k, t):  # picture t of stream k's sequence -> 0-based frame number in the sequence
+        return ((t // self.gop) * self.K + k) * self.gop + t % self.gop
+
+    def order(self, k):
+        """The frame numbers stream k codes, in its coding order."""
+        order = [self.global_index(k, t) for t in range(((self.n_gops - k + self.K - 1) // self.K) * self.gop)]
+        return [g for g in order if g < self.n_frames]
+
+    def _sink(self, k):
+        def sink(kind, qidx, payload, t):
+            g = self.global_index(k, t)
+            path = os.path.join(self.bin_dir, f"im{str(g + 1).zfill(5)}.bin")
+            if kind == "I":
+                S.encode_i(self.size[0], self.size[1], qidx[0], payload, path)
+            else:
+                S.encode_p(payload, qidx[0], qidx[1], path)
+            self.bits[g] = S.filesize(path) * 8
+
+        return sink
+
+    def encode(self, frames, q, on_recon=None):
+        """frames(k): generator of stream k's padded pictures, those of order(k).  on_recon(k, g, ref_frame): sees the
+        reconstruction of frame g while it is valid (and before stream k's next picture is pulled from frames(k))."""
+        recon_of = lambda k: (lambda t, ref_frame: on_recon(k, self.global_index(k, t), ref_frame)) if on_recon else None
+        # (GopEncoder reads the split-fp16 range guard once per GOP and raises lib.KernelError: no .bin of a clamped GOP
+        # is reported as a success)
+        with torch.no_grad():
+            self.cenc.encode_gops([frames(k) for k in range(self.K)], q[0], q[1], q[2], sinks=[self._sink(k) for k in range(self.K)],
+                                  on_recons=[recon_of(k) for k in range(self.K)])
+
+    def results(self, report, extras=None):
+        """(bits per frame list, size) -- with a report also the rd_report() dictionary, which extras(rd, frame types,
+        [the logs' value per frame]) may extend before it is written to `report` (if that is a path)."""
+        order = sorted(self.bits)
+        bit_list = [self.bits[g] for g in order]
+        if self.quality is None:
+            return bit_list, self.size
+        h, w = self.size
+        values = {}
+        for k, log in enumerate(self.quality):
+            with torch.cuda.stream(self.cenc.streams[k]):
+                log.flush()  # a trailing partial GOP
+            values.update(log.collect(3 * h * w))
+        types = [0 if g % self.gop == 0 else 1 for g in order]
+        rd = rd_report(types, bit_list, [values[g][0] for g in order], [values[g][1] for g in order], h * w)
+        if extras:
+            extras(rd, types, [values[g] for g in order])
+        if isinstance(report, (str, os.PathLike)):
+            import json
+
+            with open(report, "w") as f:
+                json.dump(rd, f, indent=2)
+        return bit_list, self.size, rd
+
+
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
                   report=None):
@@ -263,37 +367,29 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
-    from .pipeline import ConcurrentGopEncoder
+    from PIL import Image
 
-    os.makedirs(bin_dir, exist_ok=True)
     if recon_dir:
         os.makedirs(recon_dir, exist_ok=True)
-    dev = torch.device(device)
     reader = PNGReader(frames_dir)
     n_frames = 0
     while os.path.exists(reader.path_of(n_frames + 1)) and (max_frames is None or n_frames < max_frames):
         n_frames += 1
-    n_gops = (n_frames + gop - 1) // gop
-    K = max(1, min(int(gop_streams), n_gops))
-    pairs = [nets] if (nets is not None and not isinstance(nets, list)) else list(nets or [])
-    made = iter(pairs[:K] + [None] * K)
-    cenc = ConcurrentGopEncoder(lambda: next(made) or _nets(dev, precision, i_ckpt, p_ckpt), gop_size=gop, streams=K, coder=coder)
-    size, bits, source = [None], {}, [None] * K
-    quality = [_QualityLog(gop) for _ in range(K)] if report else None
+    with Image.open(reader.path_of(1)) as first:  # (the header only)
+        w, h = first.size
+    run = _EncodeRun(bin_dir, n_frames, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
+                     _QualityLog if report else None)
+    source = {}
     pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
-
-    def global_index(k, t):  # picture t of stream k's sequence -> 0-based frame number in the folder
-        return ((t // gop) * K + k) * gop + t % gop
 
     def raw_frames(k):
         """Stream k's pictures in its coding order as (H, W, 3) uint8 arrays, decoded up to `depth` ahead by the shared pool."""
-        order = [global_index(k, t) for t in range(((n_gops - k + K - 1) // K) * gop)]
-        order = [g for g in order if g < n_frames]
+        order = run.order(k)
         if pool is None:
             for g in order:
                 yield reader.load_u8(reader.path_of(g + 1))
             return
-        depth, pending, nxt = max(2, 2 * io_workers // K), deque(), 0
+        depth, pending, nxt = max(2, 2 * io_workers // run.K), deque(), 0
         while nxt < len(order) or pending:
             while nxt < len(order) and len(pending) < depth:
                 pending.append(pool.submit(reader.load_u8, reader.path_of(order[nxt] + 1)))
@@ -301,94 +397,34 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
             yield pending.popleft().result()
 
     def frames(k):
-        # uint8 pixels go to the device through a ring of pinned buffers on a copy stream of their own: a pageable
-        # `.to(device)` would be a synchronous copy queued BEHIND the previous picture's kernels, i.e. the host could
-        # never run ahead of the GPU (measured: 26 ms of every picture's 66 spent blocked in that call)
-        n, ring, done, copy_stream = 0, [], [], torch.cuda.Stream(dev) if dev.type == "cuda" else None
+        ring = _PinnedRing(run.dev, (h, w, 3))
         for rgb in raw_frames(k):
-            if copy_stream is not None:
-                if not ring:
-                    ring = [torch.empty(rgb.shape, dtype=torch.uint8).pin_memory() for _ in range(3)]
-                    done = [None] * len(ring)
-                assert tuple(rgb.shape) == tuple(ring[0].shape), "all frames must have one size"
-                j = n % len(ring)
-                if done[j] is not None:
-                    done[j].synchronize()  # the copy that last read this pinned buffer (three pictures ago)
-                ring[j].numpy()[...] = rgb
-                with torch.cuda.stream(copy_stream):
-                    d = ring[j].to(dev, non_blocking=True)
-                    done[j] = torch.cuda.Event()
-                    done[j].record(copy_stream)
-                cur = torch.cuda.current_stream(dev)  # (this GOP stream's: ConcurrentGopEncoder pulls frames inside it)
-                cur.wait_event(done[j])
-                d.record_stream(cur)
-                x = u8_to_unit_float(d)
-            else:
-                x = u8_to_unit_float(torch.from_numpy(np.array(rgb)).to(dev))
-            if size[0] is None:
-                size[0] = tuple(x.shape[-2:])
-            assert tuple(x.shape[-2:]) == size[0], "all frames must have one size"
-            n += 1
-            x = pad_frame(x)
-            if quality is not None:
+            assert tuple(rgb.shape) == (h, w, 3), "all frames must have one size"
+            ring.host()[...] = rgb
+            x = pad_frame(u8_to_unit_float(ring.upload()))
+            if report:
                 source[k] = x  # (the picture on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
             yield x
 
-    def sink_of(k):
-        def sink(kind, qidx, payload, t):
-            g = global_index(k, t)
-            path = os.path.join(bin_dir, f"im{str(g + 1).zfill(5)}.bin")
-            if kind == "I":
-                S.encode_i(size[0][0], size[0][1], qidx[0], payload, path)
-            else:
-                S.encode_p(payload, qidx[0], qidx[1], path)
-            bits[g] = S.filesize(path) * 8
+    def on_recon(k, g, ref_frame):
+        if report:
+            run.quality[k].add(g, ref_frame, source[k], (h, w))
+        if recon_dir:
+            save_torch_image(ref_frame[..., :h, :w], os.path.join(recon_dir, f"im{str(g + 1).zfill(5)}.png"), savers)
 
-        return sink
-
-    def recon_of(k):
-        def on_recon(t, ref_frame):
-            h, w = size[0]
-            if quality is not None:
-                quality[k].add(global_index(k, t), ref_frame, source[k], size[0])
-            if recon_dir:
-                save_torch_image(ref_frame[..., :h, :w], os.path.join(recon_dir, f"im{str(global_index(k, t) + 1).zfill(5)}.png"), savers)
-
-        return on_recon if (recon_dir or quality is not None) else None
-
-    # (GopEncoder reads the split-fp16 range guard once per GOP and raises lib.KernelError: no .bin of a clamped GOP
-    # is reported as a success)
     try:
-        with PNGWriters(io_workers) as savers, torch.no_grad():
-            cenc.encode_gops([frames(k) for k in range(K)], q[0], q[1], q[2], sinks=[sink_of(k) for k in range(K)],
-                             on_recons=[recon_of(k) for k in range(K)])
+        with PNGWriters(io_workers) as savers:
+            run.encode(frames, q, on_recon if (recon_dir or report) else None)
     finally:
         if pool is not None:
             pool.shutdown(wait=True, cancel_futures=True)
-    bit_list = [bits[g] for g in sorted(bits)]
-    if quality is None:
-        return bit_list, size[0]
-    values = {}
-    for k, log in enumerate(quality):
-        with torch.cuda.stream(cenc.streams[k]):
-            log.flush()  # a trailing partial GOP
-        values.update(log.collect(3 * size[0][0] * size[0][1]))
-    order = sorted(bits)
-    rd = rd_report([0 if g % gop == 0 else 1 for g in order], bit_list, [values[g][0] for g in order],
-                   [values[g][1] for g in order], size[0][0] * size[0][1])
-    if isinstance(report, (str, os.PathLike)):
-        import json
-
-        with open(report, "w") as f:
-            json.dump(rd, f, indent=2)
-    return bit_list, size[0], rd
+    return run.results(report)
 
 
-def decode_folder(bin_dir, recon_dir, height, width, gop=32, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
-                  io_workers=8):
-    os.makedirs(recon_dir, exist_ok=True)
-    dev = torch.device(device)
-    i_net, p_net = _nets(dev, precision, i_ckpt, p_ckpt)
+def _decode_bins(nets, bin_dir, height, width, gop, emit):
+    """Decode im00001.bin ... of `bin_dir` (an I picture every `gop`) in order, handing every reconstruction to
+    emit(t, ref_frame) while it is valid.  Returns the picture count."""
+    i_net, p_net = nets
     i_net.update()
     p_net.update()
     t, dpb = 0, None
@@ -397,7 +433,7 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=32, device="cuda:0", pr
         i_net.engine().check_status()
         p_net.engine().check_status()
 
-    with PNGWriters(io_workers) as savers, torch.no_grad():
+    with torch.no_grad():
         while True:
             path = os.path.join(bin_dir, f"im{str(t + 1).zfill(5)}.bin")
             if not os.path.exists(path):
@@ -407,16 +443,25 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=32, device="cuda:0", pr
                     range_guard()
                 h, w, qi, payload = S.decode_i(path)
                 assert (h, w) == (height, width)
-                x_hat = i_net.decompress(payload, h, w, qi / 100, check_range=False)["x_hat"]
-                dpb = {"ref_frame": x_hat, "ref_feature": None, "ref_y": None, "ref_mv_y": None}
+                kind, q = "I", (qi,)
             else:
                 qmv, qy, payload = S.decode_p(path)
-                dpb = p_net.decompress(dpb, payload, height, width, qmv / 100, qy / 100, check_range=False)["dpb"]
-            save_torch_image(dpb["ref_frame"][..., :height, :width], os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"), savers)
+                kind, q = "P", (qmv, qy)
+            dpb = decode_picture(i_net, p_net, kind, q, payload, dpb, height, width)
+            emit(t, dpb["ref_frame"])
             t += 1
         if t:
             range_guard()
     return t
+
+
+def decode_folder(bin_dir, recon_dir, height, width, gop=32, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
+                  io_workers=8):
+    os.makedirs(recon_dir, exist_ok=True)
+    nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
+    with PNGWriters(io_workers) as savers:
+        return _decode_bins(nets, bin_dir, height, width, gop, lambda t, ref_frame: save_torch_image(
+            ref_frame[..., :height, :width], os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"), savers))
 
 
 # ------------------------------------------------------------------------------------------------- Y4M / raw YUV files
@@ -532,7 +577,6 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     io_workers is accepted for symmetry with encode_folder: a 4:2:0 frame needs no decoding, so this path has no helper
     threads at any value.  Writes sequence.json beside the .bin files (read_sequence_info, decode_video)."""
     from . import yuv as Y
-    from .pipeline import ConcurrentGopEncoder
 
     reader = _open_source(video, size, bit_depth, fps)  # (every refusal about the file happens here, before any GPU work)
     spec = spec or reader.spec()
@@ -542,107 +586,55 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     n_frames = reader.n_frames if max_frames is None else min(reader.n_frames, int(max_frames))
     if n_frames < 1:
         raise ValueError(f"{getattr(reader, 'path', video)}: no frames")
-    os.makedirs(bin_dir, exist_ok=True)
-    dev = torch.device(device)
-    n_gops = (n_frames + gop - 1) // gop
-    K = max(1, min(int(gop_streams), n_gops))
-    pairs = [nets] if (nets is not None and not isinstance(nets, list)) else list(nets or [])
-    made = iter(pairs[:K] + [None] * K)
-    cenc = ConcurrentGopEncoder(lambda: next(made) or _nets(dev, precision, i_ckpt, p_ckpt), gop_size=gop, streams=K, coder=coder)
-    bits, source = {}, [None] * K
-    quality = [_VideoQualityLog(gop) for _ in range(K)] if report else None
+    run = _EncodeRun(bin_dir, n_frames, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
+                     _VideoQualityLog if report else None)
+    source = {}
     container = "y4m" if isinstance(reader, Y.Y4MReader) else "yuv"
     extras = dict(chroma=getattr(reader, "chroma", None), interlace=getattr(reader, "interlace", None),
                   aspect=getattr(reader, "aspect", None))
     writer = Y.create_video(recon_video, w, h, spec, reader.fps, **extras) if recon_video else None
-    outs = [_VideoOut(writer) for _ in range(K)] if writer else None
+    outs = [_VideoOut(writer) for _ in range(run.K)] if writer else None
     sample_dtype = torch.uint8 if spec.bit_depth == 8 else torch.int16
 
-    def global_index(k, t):  # picture t of stream k's sequence -> 0-based frame number in the file
-        return ((t // gop) * K + k) * gop + t % gop
-
     def frames(k):
-        order = [global_index(k, t) for t in range(((n_gops - k + K - 1) // K) * gop)]
-        ring = [torch.empty(reader.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(3)]
-        done, copy_stream = [None] * len(ring), torch.cuda.Stream(dev)
-        for n, g in enumerate(g for g in order if g < n_frames):
-            j = n % len(ring)
-            if done[j] is not None:
-                done[j].synchronize()  # the copy that last read this pinned buffer (three pictures ago)
-            reader.read_into(g, ring[j].numpy())
-            with torch.cuda.stream(copy_stream):
-                d = ring[j].to(dev, non_blocking=True)
-                done[j] = torch.cuda.Event()
-                done[j].record(copy_stream)
-            cur = torch.cuda.current_stream(dev)  # (this GOP stream's: ConcurrentGopEncoder pulls frames inside it)
-            cur.wait_event(done[j])
-            d.record_stream(cur)
-            samples = d.view(sample_dtype)
+        ring = _PinnedRing(run.dev, reader.frame_bytes)
+        for g in run.order(k):
+            reader.read_into(g, ring.host())
+            samples = ring.upload().view(sample_dtype)
             x = Y.yuv420_to_rgb(samples, h, w, spec, pad=True, quantize8=quantize8)
             source[k] = (x, samples)  # (what on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
             yield x
 
-    def sink_of(k):
-        def sink(kind, qidx, payload, t):
-            g = global_index(k, t)
-            path = os.path.join(bin_dir, f"im{str(g + 1).zfill(5)}.bin")
-            if kind == "I":
-                S.encode_i(h, w, qidx[0], payload, path)
-            else:
-                S.encode_p(payload, qidx[0], qidx[1], path)
-            bits[g] = S.filesize(path) * 8
-
-        return sink
-
-    def recon_of(k):
-        def on_recon(t, ref_frame):
-            g = global_index(k, t)
-            x, samples = source[k]
-            if quality is not None:
-                out, sums = Y.rgb_to_yuv420(ref_frame, h, w, spec, source=samples)
-                quality[k].add_yuv(g, ref_frame, x, (h, w), sums)
-            elif outs:
-                out = Y.rgb_to_yuv420(ref_frame, h, w, spec)
-            if outs:
-                outs[k].put(g, out)
-
-        return on_recon if (outs or quality is not None) else None
+    def on_recon(k, g, ref_frame):
+        x, samples = source[k]
+        if report:
+            out, sums = Y.rgb_to_yuv420(ref_frame, h, w, spec, source=samples)
+            run.quality[k].add_yuv(g, ref_frame, x, (h, w), sums)
+        elif outs:
+            out = Y.rgb_to_yuv420(ref_frame, h, w, spec)
+        if outs:
+            outs[k].put(g, out)
 
     try:
-        with torch.no_grad():
-            cenc.encode_gops([frames(k) for k in range(K)], q[0], q[1], q[2], sinks=[sink_of(k) for k in range(K)],
-                             on_recons=[recon_of(k) for k in range(K)])
-            for o in outs or []:
-                o.close()
+        run.encode(frames, q, on_recon if (outs or report) else None)
+        for o in outs or []:
+            o.close()
     finally:
         if writer:
             writer.close()
         if reader is not video:
             reader.close()
     write_sequence_info(bin_dir, w, h, n_frames, gop, reader.fps, spec, container, **extras)
-    bit_list = [bits[g] for g in sorted(bits)]
-    if quality is None:
-        return bit_list, (h, w)
-    values = {}
-    for k, log in enumerate(quality):
-        with torch.cuda.stream(cenc.streams[k]):
-            log.flush()  # a trailing partial GOP
-        values.update(log.collect(3 * h * w))
-    order = sorted(bits)
-    types = [0 if g % gop == 0 else 1 for g in order]
-    rd = rd_report(types, bit_list, [values[g][0] for g in order], [values[g][1] for g in order], h * w)
-    per = [Y.psnr_yuv(values[g][2], h, w, spec.bit_depth) for g in order]
-    for n, name in enumerate(("y", "u", "v", "yuv")):
-        rd[f"frame_psnr_{name}"] = [p[n] for p in per]
-    for name, keep in (("i", lambda k: k == 0), ("p", lambda k: k != 0), ("all", lambda k: True)):
-        sel = [p[3] for p, k in zip(per, types) if keep(k)]
-        rd[f"ave_{name}_frame_psnr_yuv"] = sum(sel) / len(sel) if sel else 0
-    if isinstance(report, (str, os.PathLike)):
-        import json
 
-        with open(report, "w") as f:
-            json.dump(rd, f, indent=2)
-    return bit_list, (h, w), rd
+    def yuv_keys(rd, types, values):
+        per = [Y.psnr_yuv(v[2], h, w, spec.bit_depth) for v in values]
+        for n, name in enumerate(("y", "u", "v", "yuv")):
+            rd[f"frame_psnr_{name}"] = [p[n] for p in per]
+        for name, keep in (("i", lambda k: k == 0), ("p", lambda k: k != 0), ("all", lambda k: True)):
+            sel = [p[3] for p, k in zip(per, types) if keep(k)]
+            rd[f"ave_{name}_frame_psnr_yuv"] = sum(sel) / len(sel) if sel else 0
+
+    return run.results(report, yuv_keys)
 
 
 def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=None, fps=None, device="cuda:0",
@@ -662,40 +654,14 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     first = os.path.join(bin_dir, "im00001.bin")
     if os.path.exists(first) and S.decode_i(first)[:2] != (height, width):
         raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {(height, width)}")
-    dev = torch.device(device)
-    i_net, p_net = _nets(dev, precision, i_ckpt, p_ckpt)
-    i_net.update()
-    p_net.update()
-    t, dpb = 0, None
-
-    def range_guard():  # once per GOP: raises lib.KernelError if a split-fp16 kernel clamped an activation
-        i_net.engine().check_status()
-        p_net.engine().check_status()
-
+    nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
     writer = Y.create_video(recon_video, width, height, spec, fps or info.get("fps"), chroma=info.get("chroma"),
                             interlace=info.get("interlace"), aspect=info.get("aspect"))
     try:
         out = _VideoOut(writer)
-        with torch.no_grad():
-            while True:
-                path = os.path.join(bin_dir, f"im{str(t + 1).zfill(5)}.bin")
-                if not os.path.exists(path):
-                    break
-                if t % gop == 0:
-                    if t:
-                        range_guard()
-                    h, w, qi, payload = S.decode_i(path)
-                    assert (h, w) == (height, width)
-                    x_hat = i_net.decompress(payload, h, w, qi / 100, check_range=False)["x_hat"]
-                    dpb = {"ref_frame": x_hat, "ref_feature": None, "ref_y": None, "ref_mv_y": None}
-                else:
-                    qmv, qy, payload = S.decode_p(path)
-                    dpb = p_net.decompress(dpb, payload, height, width, qmv / 100, qy / 100, check_range=False)["dpb"]
-                out.put(t, Y.rgb_to_yuv420(dpb["ref_frame"], height, width, spec))
-                t += 1
-            if t:
-                range_guard()
-            out.close()
+        t = _decode_bins(nets, bin_dir, height, width, gop,
+                         lambda t, ref_frame: out.put(t, Y.rgb_to_yuv420(ref_frame, height, width, spec)))
+        out.close()
     finally:
         writer.close()
     return t
