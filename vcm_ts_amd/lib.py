@@ -133,6 +133,14 @@ class ColorCoeffs(C.Structure):  # dcvc_color_coeffs_t (include/dcvc_hip_color.h
                [(n, C.c_int32) for n in ("max_code", "bit_depth", "siting", "matrix", "range")]
 
 
+class RoiBox(C.Structure):  # dcvc_roi_box_t (include/dcvc_hip_roi.h)
+    _fields_ = [(n, C.c_int32) for n in ("x1", "y1", "x2", "y2", "cls")]
+
+
+class RoiClassRec(C.Structure):  # dcvc_roi_class_t
+    _fields_ = [("border", C.c_int32), ("shrink", C.c_int32), ("feather", C.c_float * 64)]
+
+
 PRECISIONS = {"fp32": 0, "fp16x3": 1}
 
 _hip = None
@@ -202,12 +210,17 @@ _SIGS = {
     "dcvc_color_coeffs": [i32, i32, i32, i32, vp],
     "dcvc_yuv420_to_rgb": [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i64, i32, vp],
     "dcvc_rgb_to_yuv420": [vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp],
+    # include/dcvc_hip_roi.h
+    "dcvc_roi_residual": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, vp, i64, i64, i32, i32, i32, i32, vp],
+    "dcvc_roi_fuse": [vp, i32, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i64, vp],
+    "dcvc_roi_sse": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, vp, i32, vp, vp],
 }
 
 # include/dcvc_hip_metrics.h (same library; listed apart because HIP_SYMBOLS is what the three kernel headers declare)
 METRICS_SYMBOLS = ["dcvc_ms_ssim", "dcvc_ms_ssim_grad", "dcvc_ms_ssim_workspace_bytes"]
 COLOR_SYMBOLS = ["dcvc_color_coeffs", "dcvc_yuv420_to_rgb", "dcvc_rgb_to_yuv420"]  # include/dcvc_hip_color.h
-HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS] +
+ROI_SYMBOLS = ["dcvc_roi_residual", "dcvc_roi_fuse", "dcvc_roi_sse"]  # include/dcvc_hip_roi.h
+HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS + ROI_SYMBOLS] +
                      ["dcvc_cdf_table_cols", "dcvc_conv_pack_size", "dcvc_conv_pack_size_paired", "dcvc_conv_small_pack_bytes", "dcvc_conv_k32_pack_bytes", "dcvc_conv_tile_rows", "dcvc_conv_chan_partial_parts", "dcvc_hip_version", "dcvc_conv_wgrad_scratch_min",
                       "dcvc_drans_default_lanes", "dcvc_drans_scratch_words"])
 RANS_SYMBOLS = [

@@ -7,10 +7,16 @@
     python -m vcm_ts_amd.run_codec encode --video FILE.y4m --bins DIR [--recon-video FILE.y4m] [--report JSON]
     python -m vcm_ts_amd.run_codec encode --video FILE.yuv --size 1920x1080 [--bit-depth 10] [--fps 50] --bins DIR
     python -m vcm_ts_amd.run_codec decode --bins DIR --recon-video FILE.y4m
+    python -m vcm_ts_amd.run_codec encode ... --roi-root DIR [--plate-border N] [--face-border N] [--residuals FILE.gbrp | DIR]
+    python -m vcm_ts_amd.run_codec decode ... --roi-root DIR --residuals FILE.gbrp | DIR
 
 Video files are Y4M or raw I420 at 8 or 10 bits (vcm_ts_amd/yuv.py): no PNG detour, the colour conversion runs on the
 GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` beside the `.bin` files from which
 `decode --recon-video` takes size, frame rate and colour description.
+
+With a ROI (vcm_ts_amd/roi.py: the reference's box files under --roi-root) `encode` also writes the residual layer of
+``video_coder.compute_residuals`` -- raw gbrp planes for an external encoder, or PNGs -- and `decode` fuses a decoded
+residual layer into its output as ``fuse_layers`` does; the .bin files are the same with or without.
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
 reference's `.bin` format (an I picture every `gop` frames).  Unlike run_dcvc the encoder does not
@@ -107,6 +113,12 @@ def _save_array(a, path):
     Image.fromarray(np.clip(np.rint(a * 255), 0, 255).astype(np.uint8)).save(path)
 
 
+def _save_u8(a, path):
+    from PIL import Image
+
+    Image.fromarray(a).save(path)
+
+
 class PNGWriters:
     """A bounded pool of PNG-encoding threads: at most 2 x workers pictures (25 MB of float32 each at 1080p) wait in
     host memory, and a failed write (disk full, bad path) surfaces in the caller -- at the next save or at close() --
@@ -119,12 +131,12 @@ class PNGWriters:
         self.pool = ThreadPoolExecutor(max_workers=workers) if workers > 0 else None
         self.pending, self.limit = deque(), 2 * max(workers, 1)
 
-    def submit(self, a, path):
+    def submit(self, a, path, save=_save_array):
         if self.pool is None:
-            return _save_array(a, path)
+            return save(a, path)
         while len(self.pending) >= self.limit:
             self.pending.popleft().result()  # re-raises a writer's exception
-        self.pending.append(self.pool.submit(_save_array, a, path))
+        self.pending.append(self.pool.submit(save, a, path))
 
     def close(self):
         try:
@@ -351,7 +363,7 @@ class _EncodeRun:
 
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
-                  report=None):
+                  report=None, roi=None, residuals=None):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -363,7 +375,13 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     instances, DPB and HIP stream each; stream k codes GOPs k, k + K, k + 2K, ...), fed by ONE pool of PNG-decoding
     threads.  GOPs are independent (every GOP starts from an I picture, video_coder.py:122-130), so the .bin files are
     byte-identical to the one-stream loop's (tests/test_gpu_codec.py); each stream holds its own workspace (~33 GB at
-    1088x1920)."""
+    1088x1920).
+    roi: a roi.Roi, or (box source, classes) -- roi.PickleBoxes or any callable frame_index -> roi.FrameBoxes.
+    residuals (with roi): where the residual layer of video_coder.compute_residuals goes, taken on the stream that coded
+    the picture from the source and the reconstruction there: a `.gbrp` path (raw G, B, R planes, what
+    `ffmpeg -f rawvideo -pix_fmt gbrp` reads) or a folder for im%05d.png.  With report and roi every picture gains
+    frame_psnr_roi / frame_psnr_bg (base layer, per sample inside and outside the boxes shrunk by their class's shrink)
+    and frame_roi_pixels.  The .bin files are the same with or without."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
@@ -377,8 +395,11 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         n_frames += 1
     with Image.open(reader.path_of(1)) as first:  # (the header only)
         w, h = first.size
+    _roi_args(roi, residuals)
+    layer = _RoiLayer(roi, n_frames, (h, w), gop, torch.device(device)) if roi is not None else None
     run = _EncodeRun(bin_dir, n_frames, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
-                     _QualityLog if report else None)
+                     (_VideoQualityLog if layer else _QualityLog) if report else None)
+    res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
     source = {}
     pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
 
@@ -402,23 +423,32 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
             assert tuple(rgb.shape) == (h, w, 3), "all frames must have one size"
             ring.host()[...] = rgb
             x = pad_frame(u8_to_unit_float(ring.upload()))
-            if report:
+            if report or res_out:
                 source[k] = x  # (the picture on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
             yield x
 
     def on_recon(k, g, ref_frame):
-        if report:
+        if res_out:
+            res_out.put(k, g, source[k][..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
+        if report and layer:
+            sums = layer.X.region_sse(ref_frame[..., :h, :w], source[k][..., :h, :w], layer.boxes(g), layer.classes)
+            run.quality[k].add_yuv(g, ref_frame, source[k], (h, w), sums)
+        elif report:
             run.quality[k].add(g, ref_frame, source[k], (h, w))
         if recon_dir:
             save_torch_image(ref_frame[..., :h, :w], os.path.join(recon_dir, f"im{str(g + 1).zfill(5)}.png"), savers)
 
+    failed = True
     try:
         with PNGWriters(io_workers) as savers:
-            run.encode(frames, q, on_recon if (recon_dir or report) else None)
+            run.encode(frames, q, on_recon if (recon_dir or report or res_out) else None)
+        failed = False
     finally:
         if pool is not None:
             pool.shutdown(wait=True, cancel_futures=True)
-    return run.results(report)
+        if res_out:
+            res_out.close(failed)
+    return run.results(report, _roi_report_keys(h, w) if layer else None)
 
 
 def _decode_bins(nets, bin_dir, height, width, gop, emit):
@@ -456,19 +486,28 @@ def _decode_bins(nets, bin_dir, height, width, gop, emit):
 
 
 def decode_folder(bin_dir, recon_dir, height, width, gop=32, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
-                  io_workers=8):
+                  io_workers=8, roi=None, residuals=None):
+    """roi, residuals: write video_coder.fuse_layers' picture instead of the reconstruction -- `residuals` is the decoded
+    residual layer (a `.gbrp` file or a folder of im%05d.png, as encode_folder writes them) and `roi` the boxes and
+    classes it was taken with.  Display side only: the decoder's reference pictures are not touched."""
+    _roi_args(roi, residuals)
     os.makedirs(recon_dir, exist_ok=True)
-    nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
-    with PNGWriters(io_workers) as savers:
-        return _decode_bins(nets, bin_dir, height, width, gop, lambda t, ref_frame: save_torch_image(
-            ref_frame[..., :height, :width], os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"), savers))
+    picture, close = _fused_emit(roi, residuals, bin_dir, (height, width), gop, torch.device(device))
+    try:
+        nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
+        with PNGWriters(io_workers) as savers:
+            return _decode_bins(nets, bin_dir, height, width, gop, lambda t, ref_frame: save_torch_image(
+                picture(t, ref_frame), os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"), savers))
+    finally:
+        close()
 
 
 # ------------------------------------------------------------------------------------------------- Y4M / raw YUV files
 SEQUENCE_JSON = "sequence.json"
 
 
-def write_sequence_info(bin_dir, width, height, frames, gop, fps, spec, container, chroma=None, interlace=None, aspect=None):
+def write_sequence_info(bin_dir, width, height, frames, gop, fps, spec, container, chroma=None, interlace=None, aspect=None,
+                        roi=None):
     """What decode_video needs beside the .bin files (which stay what they are): size, frame count, GOP length, frame
     rate and colour description of the source, and the container it came in."""
     import json
@@ -476,6 +515,8 @@ def write_sequence_info(bin_dir, width, height, frames, gop, fps, spec, containe
     info = {"width": int(width), "height": int(height), "frames": int(frames), "gop": int(gop),
             "fps": list(fps) if fps else None, "color": spec.to_json(), "container": container, "chroma": chroma,
             "interlace": interlace, "aspect": aspect}
+    if roi is not None:  # class order and borders of the enhancement layer (the boxes themselves stay where they are)
+        info["roi"] = roi.to_json()
     with open(os.path.join(bin_dir, SEQUENCE_JSON), "w") as f:
         json.dump(info, f, indent=2)
     return info
@@ -530,8 +571,9 @@ class _VideoOut:
 
 
 class _VideoQualityLog(_QualityLog):
-    """_QualityLog plus the three integer sums of rgb_to_yuv420(..., source=) per picture.  They ride in the GOP's one
-    asynchronous transfer as raw bits (three int64 seen as six float32 lanes of the row; nothing computes on them)."""
+    """_QualityLog plus integer sums per picture: the three of rgb_to_yuv420(..., source=), the three of
+    roi.region_sse, or the six of both.  They ride in the GOP's one asynchronous transfer as raw bits (an int64 seen as
+    two float32 lanes of the row; nothing computes on them)."""
 
     def add_yuv(self, g, recon, source, size, sums):
         from . import metrics
@@ -544,7 +586,7 @@ class _VideoQualityLog(_QualityLog):
             self.flush()
 
     def collect(self, elements):
-        """{frame number: (psnr dB, ms-ssim, (sum Y, sum U, sum V))}"""
+        """{frame number: (psnr dB, ms-ssim, the integer sums as a tuple)}"""
         import math
 
         out = {}
@@ -556,6 +598,148 @@ class _VideoQualityLog(_QualityLog):
         return out
 
 
+class _RoiLayer:
+    """The boxes of a file loop.  Every frame's list is read and validated when the loop starts (each refusal happens
+    by name before any GPU work); the lists of one GOP go to the device in ONE pinned asynchronous copy, on the stream
+    that codes the GOP, when its first picture asks."""
+
+    def __init__(self, roi, n_frames, size, gop, dev):
+        from . import roi as X
+
+        if dev.index is None:
+            dev = torch.device(dev.type, torch.cuda.current_device())
+        self.X, self.roi, self.gop, self.dev, self.size = X, X.as_roi(roi), gop, dev, size
+        self.classes = self.roi.classes
+        self.frames = [self.roi.frame(g, size[0], size[1]) for g in range(n_frames)]
+
+    def boxes(self, g):
+        fb = self.frames[g]
+        if len(fb) and not fb.attached(self.dev):
+            g0 = g - g % self.gop
+            group = [f for f in self.frames[g0:g0 + self.gop] if len(f)]
+            pin = torch.from_numpy(np.concatenate([f.array.reshape(-1) for f in group])).pin_memory()
+            dev, at = pin.to(self.dev, non_blocking=True), 0
+            for f in group:
+                f.attach(pin, dev[at:at + 5 * len(f)])
+                at += 5 * len(f)
+        return fb
+
+
+RESIDUAL_RAW_EXT = ".gbrp"
+
+
+class _ResidualOut:
+    """Where an encode loop's residual layer goes: a `.gbrp` file (raw G, B, R planes in display order whatever order
+    the GOP streams finish in: roi.RawPlanarWriter behind one _VideoOut per stream) or a folder of im%05d.png."""
+
+    def __init__(self, path, size, streams, io_workers):
+        from . import roi as X
+
+        self.X, self.path, (h, w) = X, path, size
+        self.writer = self.savers = None
+        if os.path.splitext(path)[1].lower() == RESIDUAL_RAW_EXT:
+            self.writer = X.RawPlanarWriter(path, w, h)
+            self.outs = [_VideoOut(self.writer) for _ in range(streams)]
+        else:
+            os.makedirs(path, exist_ok=True)
+            self.savers = PNGWriters(io_workers)
+
+    def put(self, k, g, source, recon, boxes):
+        if self.writer:
+            self.outs[k].put(g, self.X.residual_layer(source, recon, boxes, layout="planar", order="gbr").view(-1))
+        else:
+            a = self.X.residual_layer(source, recon, boxes, layout="hwc", order="rgb").cpu().numpy()
+            self.savers.submit(a, os.path.join(self.path, f"im{str(g + 1).zfill(5)}.png"), _save_u8)
+
+    def close(self, failed=False):
+        try:
+            if self.writer and not failed:
+                for o in self.outs:
+                    o.close()
+        finally:
+            if self.writer:
+                self.writer.close()
+            if self.savers:
+                self.savers.__exit__(RuntimeError if failed else None, None, None)
+
+
+class _ResidualIn:
+    """A decoded residual layer, per frame on the device: a `.gbrp` file (roi.RawPlanarReader) or a folder of
+    im%05d.png, through a ring of pinned buffers.  Everything about the files is checked when the loop starts."""
+
+    def __init__(self, path, size, n_frames, dev):
+        from . import roi as X
+
+        (h, w), self.path, self.size = size, path, size
+        self.reader = None
+        if os.path.isdir(path):
+            missing = [t + 1 for t in range(n_frames) if not os.path.exists(self.png(t))]
+            if missing:
+                raise ValueError(f"{path}: no residual picture im{str(missing[0]).zfill(5)}.png")
+            self.layout, self.order, shape = "hwc", "rgb", (h, w, 3)
+        else:
+            self.reader = X.RawPlanarReader(path, w, h)
+            if self.reader.n_frames < n_frames:
+                self.reader.close()
+                raise ValueError(f"{path}: {self.reader.n_frames} residual frames for {n_frames} pictures")
+            self.layout, self.order, shape = "planar", "gbr", (3, h, w)
+        self.ring = _PinnedRing(dev, shape)
+
+    def png(self, t):
+        return os.path.join(self.path, f"im{str(t + 1).zfill(5)}.png")
+
+    def frame(self, t):
+        host = self.ring.host()
+        if self.reader:
+            self.reader.read_into(t, host)
+        else:
+            a = PNGReader.load_u8(self.png(t))
+            if a.shape != host.shape:
+                raise ValueError(f"{self.png(t)}: a {a.shape[1]}x{a.shape[0]} picture, not {self.size[1]}x{self.size[0]}")
+            host[...] = a
+        return self.ring.upload()
+
+    def close(self):
+        if self.reader:
+            self.reader.close()
+
+
+def _roi_args(roi, residuals):
+    if residuals is not None and roi is None:
+        raise ValueError("residuals= needs roi= (the boxes the residual layer is taken in)")
+
+
+def _roi_report_keys(h, w):
+    def keys(rd, types, values):
+        from . import roi as X
+
+        per = [X.region_psnr(v[2][-3:], h, w, "samples") for v in values]
+        rd["frame_psnr_roi"], rd["frame_psnr_bg"] = [p[2] for p in per], [p[1] for p in per]
+        rd["frame_roi_pixels"] = [int(v[2][-1]) for v in values]
+
+    return keys
+
+
+def _fused_emit(roi, residuals, bin_dir, size, gop, dev):
+    """(picture(t, ref_frame) -> the fused unpadded picture, close()) of a decode loop; without a ROI the crop itself."""
+    h, w = size
+    if roi is None:
+        return (lambda t, ref_frame: ref_frame[..., :h, :w]), (lambda: None)
+    if residuals is None:
+        raise ValueError("decoding with roi= needs residuals= (the decoded residual layer to fuse)")
+    n = 0
+    while os.path.exists(os.path.join(bin_dir, f"im{str(n + 1).zfill(5)}.bin")):
+        n += 1
+    layer = _RoiLayer(roi, n, size, gop, dev)
+    source = _ResidualIn(residuals, size, n, dev)
+
+    def picture(t, ref_frame):  # display side only: the DPB keeps the base-layer reconstruction
+        return layer.X.fuse(ref_frame[..., :h, :w], source.frame(t), layer.boxes(t), layer.classes, layout=source.layout,
+                            order=source.order)
+
+    return picture, source.close
+
+
 def _open_source(video, size, bit_depth, fps):
     from . import yuv as Y
 
@@ -564,7 +748,7 @@ def _open_source(video, size, bit_depth, fps):
 
 def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantize8=False, gop=32, q=(1.0, 1.0, 1.0),
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
-                 nets=None, gop_streams=1, report=None, bit_depth=8, fps=None):
+                 nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -575,9 +759,12 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     report: as encode_folder (the existing keys measure against the RGB picture the codec was given), plus
     frame_psnr_y / _u / _v / _yuv and ave_{i,p,all}_frame_psnr_yuv in the sample domain of the source file.
     io_workers is accepted for symmetry with encode_folder: a 4:2:0 frame needs no decoding, so this path has no helper
-    threads at any value.  Writes sequence.json beside the .bin files (read_sequence_info, decode_video)."""
+    threads at any value.  Writes sequence.json beside the .bin files (read_sequence_info, decode_video).
+    roi, residuals: as encode_folder (the residual is taken against the RGB picture the codec was given); sequence.json
+    then also records the classes' names and borders."""
     from . import yuv as Y
 
+    _roi_args(roi, residuals)
     reader = _open_source(video, size, bit_depth, fps)  # (every refusal about the file happens here, before any GPU work)
     spec = spec or reader.spec()
     if spec.bit_depth != reader.bit_depth:
@@ -586,8 +773,10 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     n_frames = reader.n_frames if max_frames is None else min(reader.n_frames, int(max_frames))
     if n_frames < 1:
         raise ValueError(f"{getattr(reader, 'path', video)}: no frames")
+    layer = _RoiLayer(roi, n_frames, (h, w), gop, torch.device(device)) if roi is not None else None
     run = _EncodeRun(bin_dir, n_frames, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
                      _VideoQualityLog if report else None)
+    res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
     source = {}
     container = "y4m" if isinstance(reader, Y.Y4MReader) else "yuv"
     extras = dict(chroma=getattr(reader, "chroma", None), interlace=getattr(reader, "interlace", None),
@@ -607,27 +796,38 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
 
     def on_recon(k, g, ref_frame):
         x, samples = source[k]
+        if res_out:
+            res_out.put(k, g, x[..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
         if report:
             out, sums = Y.rgb_to_yuv420(ref_frame, h, w, spec, source=samples)
+            if layer:
+                sums = torch.cat([sums, layer.X.region_sse(ref_frame[..., :h, :w], x[..., :h, :w], layer.boxes(g), layer.classes)])
             run.quality[k].add_yuv(g, ref_frame, x, (h, w), sums)
         elif outs:
             out = Y.rgb_to_yuv420(ref_frame, h, w, spec)
         if outs:
             outs[k].put(g, out)
 
+    failed = True
     try:
-        run.encode(frames, q, on_recon if (outs or report) else None)
+        run.encode(frames, q, on_recon if (outs or report or res_out) else None)
         for o in outs or []:
             o.close()
+        failed = False
     finally:
         if writer:
             writer.close()
         if reader is not video:
             reader.close()
-    write_sequence_info(bin_dir, w, h, n_frames, gop, reader.fps, spec, container, **extras)
+        if res_out:
+            res_out.close(failed)
+    write_sequence_info(bin_dir, w, h, n_frames, gop, reader.fps, spec, container, **extras,
+                        roi=layer.roi if layer else None)
 
     def yuv_keys(rd, types, values):
-        per = [Y.psnr_yuv(v[2], h, w, spec.bit_depth) for v in values]
+        per = [Y.psnr_yuv(v[2][:3], h, w, spec.bit_depth) for v in values]
+        if layer:
+            _roi_report_keys(h, w)(rd, types, values)
         for n, name in enumerate(("y", "u", "v", "yuv")):
             rd[f"frame_psnr_{name}"] = [p[n] for p in per]
         for name, keep in (("i", lambda k: k == 0), ("p", lambda k: k != 0), ("all", lambda k: True)):
@@ -638,12 +838,14 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
 
 
 def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=None, fps=None, device="cuda:0",
-                 precision=None, i_ckpt=None, p_ckpt=None):
+                 precision=None, i_ckpt=None, p_ckpt=None, roi=None, residuals=None):
     """decode_folder's loop with the video output stage.  Size, GOP length, frame rate and colour description come from
     the sequence.json encode_video left in `bin_dir`; explicit arguments override it, and without the file height and
-    width are required (gop then defaults to 32, the colour description to yuv.ColorSpec()).  Returns the picture count."""
+    width are required (gop then defaults to 32, the colour description to yuv.ColorSpec()).  Returns the picture count.
+    roi, residuals: as decode_folder -- the fused picture is what is converted and written."""
     from . import yuv as Y
 
+    _roi_args(roi, residuals)
     info = read_sequence_info(bin_dir) or {}
     height, width = height or info.get("height"), width or info.get("width")
     if not height or not width:
@@ -654,16 +856,21 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     first = os.path.join(bin_dir, "im00001.bin")
     if os.path.exists(first) and S.decode_i(first)[:2] != (height, width):
         raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {(height, width)}")
-    nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
-    writer = Y.create_video(recon_video, width, height, spec, fps or info.get("fps"), chroma=info.get("chroma"),
-                            interlace=info.get("interlace"), aspect=info.get("aspect"))
+    picture, close = _fused_emit(roi, residuals, bin_dir, (height, width), gop, torch.device(device))
     try:
-        out = _VideoOut(writer)
-        t = _decode_bins(nets, bin_dir, height, width, gop,
-                         lambda t, ref_frame: out.put(t, Y.rgb_to_yuv420(ref_frame, height, width, spec)))
-        out.close()
+        nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
+        writer = Y.create_video(recon_video, width, height, spec, fps or info.get("fps"), chroma=info.get("chroma"),
+                                interlace=info.get("interlace"), aspect=info.get("aspect"))
+        try:
+            out = _VideoOut(writer)
+            # (without a ROI the padded reconstruction itself: rgb_to_yuv420 reads its top-left corner in place)
+            t = _decode_bins(nets, bin_dir, height, width, gop, lambda t, ref_frame: out.put(t, Y.rgb_to_yuv420(
+                ref_frame if roi is None else picture(t, ref_frame), height, width, spec)))
+            out.close()
+        finally:
+            writer.close()
     finally:
-        writer.close()
+        close()
     return t
 
 
@@ -707,7 +914,18 @@ def main(argv=None):
     d.add_argument("--range", default=None, choices=["limited", "full"])
     d.add_argument("--siting", default=None, choices=["left", "center"])
     d.add_argument("--bit-depth", type=int, default=None, choices=[8, 10])
+    e.add_argument("--residuals", metavar="PATH",
+                   help="with --roi-root: write the residual layer, FILE.gbrp (raw planes for ffmpeg -f rawvideo -pix_fmt gbrp) "
+                        "or a folder for im%%05d.png")
+    d.add_argument("--residuals", metavar="PATH",
+                   help="with --roi-root: the decoded residual layer (FILE.gbrp or a folder of im%%05d.png) to fuse into the output")
     for p in (e, d):
+        p.add_argument("--roi-root", metavar="DIR",
+                       help="the reference's box files: DIR/liplates_coords/%%05d and DIR/faces_coords/%%05d (either may be absent)")
+        p.add_argument("--plate-border", type=int, default=None, metavar="N",
+                       help="the reference's LIPLATES.PADDING: feather width and metric shrink of plate boxes "
+                            "(default 0; decode: the sequence.json's)")
+        p.add_argument("--face-border", type=int, default=None, metavar="N", help="the same for face boxes")
         p.add_argument("--gop", type=int, default=None, help="default 32 (decode: the sequence.json's, else 32)")
         p.add_argument("--io-workers", type=int, default=8, help="host threads for PNG decoding / encoding (0: inline)")
         p.add_argument("--device", default="cuda:0")
@@ -715,6 +933,23 @@ def main(argv=None):
         p.add_argument("--i-ckpt")
         p.add_argument("--p-ckpt")
     a = ap.parse_args(argv)
+    roi = None
+    if a.roi_root is None and (a.residuals or a.plate_border is not None or a.face_border is not None):
+        ap.error("--residuals, --plate-border and --face-border belong to --roi-root")
+    if a.roi_root is not None:
+        from . import roi as X
+
+        if a.cmd == "decode" and not a.residuals:
+            ap.error("decode --roi-root needs --residuals (the decoded residual layer)")
+        recorded = {c["name"]: c["border"] for c in ((read_sequence_info(a.bins) or {}).get("roi") or {}).get("classes", [])} \
+            if a.cmd == "decode" else {}
+        borders = [given if given is not None else recorded.get(name, 0)
+                   for given, name in ((a.plate_border, "liplates"), (a.face_border, "faces"))]
+        try:
+            classes = tuple(X.RoiClass(b) for b in borders)
+            roi = X.Roi(X.PickleBoxes(a.roi_root, classes), classes)
+        except (ValueError, OSError) as ex:
+            ap.error(str(ex))
     if a.cmd == "encode":
         if (a.frames is None) == (a.video is None):
             ap.error("give exactly one of --frames and --video")
@@ -760,10 +995,12 @@ def main(argv=None):
             with reader:
                 bits, size, *rd = encode_video(reader, a.bins, a.recon_video, spec=spec, quantize8=a.quantize8, gop=a.gop, q=q,
                                                device=a.device, precision=a.precision, i_ckpt=a.i_ckpt, p_ckpt=a.p_ckpt,
-                                               coder=a.coder, gop_streams=a.gop_streams, report=a.report)
+                                               coder=a.coder, gop_streams=a.gop_streams, report=a.report, roi=roi,
+                                               residuals=a.residuals)
         else:
             bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
-                                            coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report)
+                                            coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
+                                            roi=roi, residuals=a.residuals)
         if rd:
             yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
             print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
@@ -784,13 +1021,14 @@ def main(argv=None):
                 base = info["color"] if info else Y.ColorSpec()
                 spec = Y.ColorSpec(a.matrix or base.matrix, base.full_range if a.range is None else a.range == "full",
                                    a.siting or base.siting, a.bit_depth or base.bit_depth)
-            n = decode_video(a.bins, a.recon_video, a.height, a.width, a.gop, spec, None, a.device, a.precision, a.i_ckpt, a.p_ckpt)
+            n = decode_video(a.bins, a.recon_video, a.height, a.width, a.gop, spec, None, a.device, a.precision, a.i_ckpt, a.p_ckpt,
+                             roi=roi, residuals=a.residuals)
         else:
             if a.matrix or a.range or a.siting or a.bit_depth:
                 ap.error("--matrix, --range, --siting and --bit-depth belong to --recon-video")
             height, width = a.height or info["height"], a.width or info["width"]
             n = decode_folder(a.bins, a.recon, height, width, a.gop or (info or {}).get("gop") or 32, a.device, a.precision,
-                              a.i_ckpt, a.p_ckpt, io_workers=a.io_workers)
+                              a.i_ckpt, a.p_ckpt, io_workers=a.io_workers, roi=roi, residuals=a.residuals)
         print(f"{n} pictures decoded")
 
 
