@@ -200,11 +200,14 @@ int dcvc_nhwc_to_nchw(const float *src, int32_t src_cs, float *out, int32_t N, i
  * two-pass; scratch >= N*2048*C floats */
 int dcvc_channel_mean(const float *src, int32_t src_cs, float *mean, float *scratch, int32_t N, int32_t HW,
                       int32_t C, void *stream);
-/* gate = sigmoid(W2 relu(W1 mean)); W1: (Cr, C), W2: (C, Cr) as nn.Linear stores them */
+/* gate = sigmoid(W2 relu(W1 mean)); W1: (Cr, C), W2: (C, Cr) as nn.Linear stores them.
+ * DCVC_E_ARG unless N >= 1, 1 <= C <= 256 and 1 <= Cr <= 64 */
 int dcvc_se_gate(const float *mean, const float *w1, const float *w2, float *gate, int32_t N, int32_t C,
                  int32_t Cr, void *stream);
 
 /* ---- quantisation / entropy-model elementwise ------------------------------------------ */
+/* The next three functions (dcvc_scale_channels, dcvc_round_symbols, dcvc_symbols_to_nhwc) answer DCVC_E_ARG, before
+ * anything is launched, for a NULL operand, for N, H, W, HW or C <= 0 and for a channel stride smaller than C. */
 /* out = src / q  (mode 0) or src * q (mode 1);  q = max(q_basic[c], 0.5) * q_scale[n] */
 int dcvc_scale_channels(const float *src, int32_t src_cs, float *out, int32_t out_cs, const float *q_basic,
                         const float *q_scale, int32_t mode, int32_t N, int32_t HW, int32_t C, void *stream);
@@ -253,7 +256,8 @@ int dcvc_dual_prior_enc(const dcvc_dual_prior_args *a, void *stream);
 int dcvc_dual_prior_dec_index(const dcvc_dual_prior_args *a, void *stream);
 int dcvc_dual_prior_dec_apply(const dcvc_dual_prior_args *a, void *stream);
 
-/* per-sample sums; out: (N) floats; scratch >= N*1024 floats.  kind: 0 laplace, 1 gaussian */
+/* per-sample sums; out: (N) floats; scratch >= N*1024 floats.  kind: 0 laplace, 1 gaussian.  The three sums below
+ * answer DCVC_E_ARG for N, per_sample, HW or C <= 0 and for a channel stride smaller than C. */
 int dcvc_scale_bits(const float *y_q, const float *scales_hat, float *out, float *scratch, int32_t kind, int32_t N,
                     int64_t per_sample, void *stream);
 /* factorised prior bits of z_hat (N,H,W,C; cs): params (11, C): h1,b1,a1,h2,b2,a2,h3,b3,a3,h4,b4 */

@@ -178,3 +178,90 @@ def test_every_entry_point_refuses_null_and_empty_arguments(sizes):
                 args.append(C.byref(keep[-1]))
         assert getattr(L, name)(*args) == -1, name
     L.dcvc_pack_plan_destroy(None)
+
+
+# argument order of the forward entry points below; pointers are aligned dummies (a refused call returns before anything is
+# launched or dereferenced), every other value is plausible unless a case overrides it
+_FWD_ABI = {
+    "dcvc_scale_channels": ("src src_cs out out_cs q_basic q_scale mode N HW C", {"src_cs": 8, "out_cs": 8, "mode": 0}),
+    "dcvc_round_symbols": ("z z_cs z_hat zh_cs sym N H W C", {"z_cs": 8, "zh_cs": 8}),
+    "dcvc_symbols_to_nhwc": ("sym out out_cs N H W C", {"out_cs": 8}),
+    "dcvc_scale_bits": ("y_q scales_hat out scratch kind N per_sample", {"kind": 0}),
+    "dcvc_factorized_bits": ("z_hat z_cs params out scratch N HW C", {"z_cs": 8}),
+    "dcvc_sq_err": ("a a_cs b b_cs out scratch N HW C", {"a_cs": 8, "b_cs": 8}),
+    "dcvc_se_gate": ("mean w1 w2 gate N C Cr", {"Cr": 2}),
+    "dcvc_down2": ("src src_cs out out_cs N H W C scale avgpool_order", {"src_cs": 8, "out_cs": 8, "scale": 1.0, "avgpool_order": 0}),
+    "dcvc_maxpool2": ("src src_cs out out_cs N H W C", {"src_cs": 8, "out_cs": 8}),
+    "dcvc_warp": ("src src_cs flow flow_cs out out_cs N H W C", {"src_cs": 8, "flow_cs": 4, "out_cs": 8}),
+    "dcvc_channel_mean": ("src src_cs mean scratch N HW C", {"src_cs": 8}),
+}
+_FWD_SIZES = {"N": 2, "H": 4, "W": 6, "HW": 24, "C": 8, "per_sample": 24}
+_FWD_POINTERS = ("src", "out", "q_basic", "q_scale", "z", "z_hat", "sym", "y_q", "scales_hat", "scratch", "params", "a", "b",
+                 "mean", "w1", "w2", "gate", "flow")
+
+
+def _fwd_call(L, name, **override):
+    from vcm_ts_amd import lib
+
+    order, fixed = _FWD_ABI[name]
+    assert len(order.split()) + 1 == len(lib._SIGS[name]), name  # the order above is the header's, plus the stream
+    vals = dict(_FWD_SIZES, **fixed)
+    vals.update({p: 0x10000 * (k + 1) for k, p in enumerate(_FWD_POINTERS)})
+    assert set(override) <= set(order.split()), (name, override)
+    vals.update(override)
+    return getattr(L, name)(*[vals[k] for k in order.split()], None)
+
+
+def test_forward_entry_points_refuse_non_positive_sizes_and_short_strides():
+    """dcvc_scale_channels, dcvc_round_symbols, dcvc_symbols_to_nhwc, dcvc_scale_bits, dcvc_factorized_bits, dcvc_sq_err and
+    dcvc_se_gate used to launch with whatever sizes they were given: N = 0 reached the runtime as a zero-sized grid
+    (DCVC_E_LAUNCH), a channel stride below C made neighbouring pixels overlap.  They answer DCVC_E_ARG now, like their
+    siblings, for every size <= 0 and every channel stride < C.  Host-only: a refused call launches nothing."""
+    from vcm_ts_amd import lib
+
+    L = lib.hip()
+    sizes = {"dcvc_scale_channels": ("N", "HW", "C"), "dcvc_round_symbols": ("N", "H", "W", "C"),
+             "dcvc_symbols_to_nhwc": ("N", "H", "W", "C"), "dcvc_scale_bits": ("N", "per_sample"),
+             "dcvc_factorized_bits": ("N", "HW", "C"), "dcvc_sq_err": ("N", "HW", "C"), "dcvc_se_gate": ("N", "C", "Cr")}
+    strides = {"dcvc_scale_channels": ("src_cs", "out_cs"), "dcvc_round_symbols": ("z_cs", "zh_cs"),
+               "dcvc_symbols_to_nhwc": ("out_cs",), "dcvc_factorized_bits": ("z_cs",), "dcvc_sq_err": ("a_cs", "b_cs")}
+    for name, keys in sizes.items():
+        for key in keys:
+            for bad in (0, -1, -(2 ** 31)):
+                assert _fwd_call(L, name, **{key: bad}) == -1, (name, key, bad)
+    for name, keys in strides.items():
+        for key in keys:
+            for bad in (7, 0, -8):
+                assert _fwd_call(L, name, **{key: bad}) == -1, (name, key, bad)
+    # a z_hat stride is only looked at when there is a z_hat -- and without z_hat AND sym there is nothing to do
+    assert _fwd_call(L, "dcvc_round_symbols", z_hat=None, sym=None) == -1
+    assert _fwd_call(L, "dcvc_se_gate", C=257) == -1 and _fwd_call(L, "dcvc_se_gate", Cr=65) == -1
+
+
+def test_resamplers_refuse_odd_and_degenerate_pictures():
+    """dcvc_down2 / dcvc_maxpool2 need even H and W (a 2x2 block per output), dcvc_warp needs H, W >= 2 (its
+    normalised grid divides by (size - 1) / 2)."""
+    from vcm_ts_amd import lib
+
+    L = lib.hip()
+    for name in ("dcvc_down2", "dcvc_maxpool2"):
+        for bad in ({"H": 5}, {"W": 7}, {"H": 1}, {"W": 1}, {"H": 0}, {"W": 0}, {"N": 0}, {"C": 0}):
+            assert _fwd_call(L, name, **bad) == -1, (name, bad)
+    for bad in ({"H": 1}, {"W": 1}, {"H": 0}, {"W": -3}, {"N": 0}, {"C": 0}):
+        assert _fwd_call(L, "dcvc_warp", **bad) == -1, bad
+
+
+def test_channel_mean_accepts_only_power_of_two_channel_counts_and_aligned_views():
+    """channel_partial gives 16 bytes (4 channels) to a lane and 256 / (C / 4) pixels to a pass: C must be one of
+    4, 8, ..., 256, the channel stride a multiple of 4 floats and the view 16-byte aligned."""
+    from vcm_ts_amd import lib
+
+    L = lib.hip()
+    for C_ in (3, 12, 96, 512, 0, -4):
+        assert _fwd_call(L, "dcvc_channel_mean", C=C_, src_cs=512) == -1, C_
+    for cs in (9, 10, 11, 66):
+        assert _fwd_call(L, "dcvc_channel_mean", src_cs=cs) == -1, cs
+    for off in (4, 8, 12, 1):
+        assert _fwd_call(L, "dcvc_channel_mean", src=0x10000 + off) == -1, off
+    for key in ("N", "HW"):
+        assert _fwd_call(L, "dcvc_channel_mean", **{key: 0}) == -1, key

@@ -483,14 +483,14 @@ extern "C" int dcvc_channel_mean_finish(const float *chan_partial, int32_t parts
 
 extern "C" int dcvc_se_gate(const float *mean, const float *w1, const float *w2, float *gate, int32_t N, int32_t C,
                             int32_t Cr, void *stream) {
-    if (!mean || !w1 || !w2 || !gate || C > 256 || Cr > 64 || Cr <= 0) return DCVC_E_ARG;
+    if (!mean || !w1 || !w2 || !gate || N <= 0 || C <= 0 || C > 256 || Cr > 64 || Cr <= 0) return DCVC_E_ARG;
     hipLaunchKernelGGL(se_gate_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, mean, w1, w2, gate, C, Cr);
     RET_LAUNCH();
 }
 
 extern "C" int dcvc_scale_channels(const float *src, int32_t src_cs, float *out, int32_t out_cs, const float *q_basic,
                                    const float *q_scale, int32_t mode, int32_t N, int32_t HW, int32_t C, void *stream) {
-    if (!src || !out || !q_basic || !q_scale) return DCVC_E_ARG;
+    if (!src || !out || !q_basic || !q_scale || N <= 0 || HW <= 0 || C <= 0 || src_cs < C || out_cs < C) return DCVC_E_ARG;
     const int64_t total = (int64_t)N * HW * C;
     hipLaunchKernelGGL(scale_channels_kernel, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)stream, src, src_cs, out,
                        out_cs, q_basic, q_scale, mode, (int64_t)HW, C, total);
@@ -499,7 +499,7 @@ extern "C" int dcvc_scale_channels(const float *src, int32_t src_cs, float *out,
 
 extern "C" int dcvc_round_symbols(const float *z, int32_t z_cs, float *z_hat, int32_t zh_cs, int32_t *sym, int32_t N,
                                   int32_t H, int32_t W, int32_t C, void *stream) {
-    if (!z || (!z_hat && !sym)) return DCVC_E_ARG;
+    if (!z || (!z_hat && !sym) || N <= 0 || H <= 0 || W <= 0 || C <= 0 || z_cs < C || (z_hat && zh_cs < C)) return DCVC_E_ARG;
     const int64_t total = (int64_t)N * H * W * C;
     hipLaunchKernelGGL(round_symbols_kernel, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)stream, z, z_cs, z_hat,
                        zh_cs, sym, H, W, C, total);
@@ -508,7 +508,7 @@ extern "C" int dcvc_round_symbols(const float *z, int32_t z_cs, float *z_hat, in
 
 extern "C" int dcvc_symbols_to_nhwc(const int32_t *sym, float *out, int32_t out_cs, int32_t N, int32_t H, int32_t W,
                                     int32_t C, void *stream) {
-    if (!sym || !out) return DCVC_E_ARG;
+    if (!sym || !out || N <= 0 || H <= 0 || W <= 0 || C <= 0 || out_cs < C) return DCVC_E_ARG;
     const int64_t total = (int64_t)N * H * W * C;
     hipLaunchKernelGGL(symbols_to_nhwc_kernel, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)stream, sym, out,
                        out_cs, H, W, C, total);
@@ -574,7 +574,7 @@ extern "C" int dcvc_build_factorized_cdfs(const float *params, int32_t C, int32_
 
 extern "C" int dcvc_scale_bits(const float *y_q, const float *scales_hat, float *out, float *scratch, int32_t kind,
                                int32_t N, int64_t per_sample, void *stream) {
-    if (!y_q || !scales_hat || !out || !scratch) return DCVC_E_ARG;
+    if (!y_q || !scales_hat || !out || !scratch || N <= 0 || per_sample <= 0) return DCVC_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(scale_bits_kernel, dim3(RB, N), dim3(256), 0, st, y_q, scales_hat, scratch, kind, per_sample);
     hipLaunchKernelGGL(finish_sum, dim3(N), dim3(256), 0, st, scratch, out, RB);
@@ -583,7 +583,7 @@ extern "C" int dcvc_scale_bits(const float *y_q, const float *scales_hat, float 
 
 extern "C" int dcvc_factorized_bits(const float *z_hat, int32_t z_cs, const float *params, float *out, float *scratch,
                                     int32_t N, int32_t HW, int32_t C, void *stream) {
-    if (!z_hat || !params || !out || !scratch) return DCVC_E_ARG;
+    if (!z_hat || !params || !out || !scratch || N <= 0 || HW <= 0 || C <= 0 || z_cs < C) return DCVC_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(factorized_bits_kernel, dim3(RB, N), dim3(256), 0, st, z_hat, z_cs, params, scratch, (int64_t)HW,
                        C);
@@ -593,7 +593,7 @@ extern "C" int dcvc_factorized_bits(const float *z_hat, int32_t z_cs, const floa
 
 extern "C" int dcvc_sq_err(const float *a, int32_t a_cs, const float *b, int32_t b_cs, float *out, float *scratch,
                            int32_t N, int32_t HW, int32_t C, void *stream) {
-    if (!a || !b || !out || !scratch) return DCVC_E_ARG;
+    if (!a || !b || !out || !scratch || N <= 0 || HW <= 0 || C <= 0 || a_cs < C || b_cs < C) return DCVC_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(sq_err_kernel, dim3(RB, N), dim3(256), 0, st, a, a_cs, b, b_cs, scratch, (int64_t)HW, C);
     hipLaunchKernelGGL(finish_sum, dim3(N), dim3(256), 0, st, scratch, out, RB);
