@@ -24,7 +24,8 @@ def pad_frame(x: torch.Tensor):
 
 
 def shard_gops(n_gops: int, rank: int, world: int):
-    """GOP g -> rank g mod world: no data-path collective is needed."""
+    """GOP g -> rank g mod world: no data-path collective is needed.  n_gops is a COUNT of GOPs, whatever
+    their lengths: with scene-cut I pictures pass scenecut.GopPlan.n_gops (and take GOP g's frames from gop_range(g))."""
     return [g for g in range(n_gops) if g % world == rank]
 
 
@@ -82,24 +83,27 @@ class GopEncoder:
         self.i_net.update()
         self.p_net.update()
 
-    def encode_gop(self, frames, q_i, q_mv_y, q_y, sink=None, on_recon=None):
+    def encode_gop(self, frames, q_i, q_mv_y, q_y, sink=None, on_recon=None, intra=None):
         """frames: iterable of padded (1, 3, H, W) device tensors, the first coded as an I
-        picture.  Returns (list of payload bytes with their headers' q indexes, total bits of
+        picture.  intra: the set of picture numbers (positions in `frames`) coded as I pictures -- 0 among them, no two
+        further apart than gop_size -- instead of every multiple of gop_size (scenecut.GopPlan).  Returns (list of payload bytes with their headers' q indexes, total bits of
         the payloads + headers, final DPB).  `sink(kind, q_indexes, payload, t)` may persist the
         coded pictures; `on_recon(t, ref_frame)` sees each reconstruction while it is still valid."""
         res = {}
-        for _ in self.encode_steps(frames, q_i, q_mv_y, q_y, res, sink=sink, on_recon=on_recon):
+        for _ in self.encode_steps(frames, q_i, q_mv_y, q_y, res, sink=sink, on_recon=on_recon, intra=intra):
             pass
         return res["coded"], res["bits"], res["dpb"]
 
-    def encode_steps(self, frames, q_i, q_mv_y, q_y, res, sink=None, on_recon=None):
+    def encode_steps(self, frames, q_i, q_mv_y, q_y, res, sink=None, on_recon=None, intra=None):
         """encode_gop as a generator that yields after every picture it has enqueued, so that several
         encoders can be interleaved by one host thread (ConcurrentGopEncoder).  Fills `res` with
         "coded", "bits", "dpb" when exhausted."""
         q_i, qi_idx = S.get_rounded_q(q_i)
         q_mv_y, qmv_idx = S.get_rounded_q(q_mv_y)
         q_y, qy_idx = S.get_rounded_q(q_y)
-        out, bits, dpb, prev = [], 0, None, None
+        out, bits, dpb, prev, last_i = [], 0, None, None, 0
+        if intra is not None and 0 not in intra:
+            raise ValueError("intra: picture 0 of a sequence is an I picture")
 
         def retire(item):  # host half of a picture: wait for its planes, rANS-code them
             nonlocal bits
@@ -116,7 +120,8 @@ class GopEncoder:
         # to pinned host memory asynchronously) BEFORE picture t-1 is entropy-coded on the host,
         # so the GPU works on t while the CPU codes t-1.  The DPB never leaves the device.
         for t, x in enumerate(frames):
-            if t % self.gop == 0:
+            if (t % self.gop == 0) if intra is None else (t in intra):
+                last_i = t
                 r = self.i_net.compress(x, q_i, defer=True, coder=self.coder, check_range=False)
                 dpb = intra_dpb(r["x_hat"])
                 item = ("I", (qi_idx,), r["pending"], t)
@@ -124,11 +129,12 @@ class GopEncoder:
                 r = self.p_net.compress(x, dpb, q_mv_y, q_y, defer=True, coder=self.coder, graph=self.graphs, check_range=False)
                 dpb = r["dpb"]
                 item = ("P", (qmv_idx, qy_idx), r["pending"], t)
-            # once per GOP (behind its last picture; a trailing partial GOP is covered after the loop): the status
+            # once per GOP (behind its last picture -- with `intra` the one before the next I picture, or the one that
+            # fills the GOP's maximum length; a trailing partial GOP is covered after the loop): the status
             # word of both engines, read asynchronously -- the copy rides behind the picture's kernels and is looked
             # at when that picture is retired, so the host never drains the GPU for it
             guards = ()
-            if t % self.gop == self.gop - 1:
+            if (t % self.gop == self.gop - 1) if intra is None else (t + 1 in intra or t + 1 - last_i >= self.gop):
                 guards = tuple(c for c in (self.i_net.engine().status_snapshot(), self.p_net.engine().status_snapshot()) if c)
             item = item + (guards,)
             if on_recon is not None:  # reconstruction == what the decoder will produce (clamped)
@@ -180,10 +186,11 @@ class ConcurrentGopEncoder:
         self.device = dev
         self.streams = [torch.cuda.Stream(dev) for _ in self.encoders]
 
-    def encode_gops(self, sequences, q_i, q_mv_y, q_y, sinks=None, on_recons=None):
+    def encode_gops(self, sequences, q_i, q_mv_y, q_y, sinks=None, on_recons=None, intra=None):
         """sequences: up to `streams` iterables of padded pictures (one sequence of whole GOPs each; an iterable is
         pulled INSIDE its stream, so a generator may upload its pictures there).  Returns a list of
-        (coded, bits, dpb) in the same order.  sinks / on_recons: per-sequence callbacks of GopEncoder.encode_gop."""
+        (coded, bits, dpb) in the same order.  sinks / on_recons: per-sequence callbacks of GopEncoder.encode_gop; intra:
+        per-sequence sets of the picture numbers coded as I (GopEncoder.encode_gop), None for every multiple of gop_size."""
         assert len(sequences) <= len(self.encoders)
         cur = torch.cuda.current_stream(self.device)
         results = [{} for _ in sequences]
@@ -191,7 +198,8 @@ class ConcurrentGopEncoder:
         for k, seq in enumerate(sequences):
             self.streams[k].wait_stream(cur)  # the pictures were produced on the caller's stream
             gens.append(self.encoders[k].encode_steps(seq, q_i, q_mv_y, q_y, results[k], sink=sinks[k] if sinks else None,
-                                                      on_recon=on_recons[k] if on_recons else None))
+                                                      on_recon=on_recons[k] if on_recons else None,
+                                                      intra=intra[k] if intra else None))
         live = list(range(len(gens)))
         while live:
             for k in list(live):

@@ -9,6 +9,7 @@
     python -m vcm_ts_amd.run_codec decode --bins DIR --recon-video FILE.y4m
     python -m vcm_ts_amd.run_codec encode ... --roi-root DIR [--plate-border N] [--face-border N] [--residuals FILE.gbrp | DIR]
     python -m vcm_ts_amd.run_codec decode ... --roi-root DIR --residuals FILE.gbrp | DIR
+    python -m vcm_ts_amd.run_codec encode ... --scenecut T [--min-gop N]
 
 Video files are Y4M or raw I420 at 8 or 10 bits (vcm_ts_amd/yuv.py): no PNG detour, the colour conversion runs on the
 GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` beside the `.bin` files from which
@@ -17,6 +18,11 @@ GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` be
 With a ROI (vcm_ts_amd/roi.py: the reference's box files under --roi-root) `encode` also writes the residual layer of
 ``video_coder.compute_residuals`` -- raw gbrp planes for an external encoder, or PNGs -- and `decode` fuses a decoded
 residual layer into its output as ``fuse_layers`` does; the .bin files are the same with or without.
+
+With --scenecut T an I picture also opens a new GOP wherever consecutive pictures differ by more than T
+(vcm_ts_amd/scenecut.py: a scan pass over the source first, then the coding pass); --gop becomes the longest GOP, and the
+I pictures are listed in a `gops.json` beside the `.bin` files, which `decode` follows when it is there.  There is no
+default T.
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
 reference's `.bin` format (an I picture every `gop` frames).  Unlike run_dcvc the encoder does not
@@ -31,6 +37,7 @@ import numpy as np
 import torch
 
 from . import stream as S
+from .scenecut import GopPlan
 from .pipeline import ConcurrentGopEncoder, decode_picture, pad_frame
 
 
@@ -222,8 +229,8 @@ class _QualityLog:
     ONE asynchronous copy behind its last picture and are looked at when the folder is done: the host never waits for a
     picture's metric."""
 
-    def __init__(self, gop):
-        self.gop, self.cur, self.idx, self.done = gop, [], [], []
+    def __init__(self, plan):
+        self.plan, self.cur, self.idx, self.done = plan, [], [], []
 
     def add(self, g, recon, source, size):
         from . import metrics
@@ -232,7 +239,7 @@ class _QualityLog:
         ms, _, sse = metrics.measure(recon[..., :h, :w], source[..., :h, :w], 1.0, clamp01=True)
         self.cur.append(torch.cat([ms, sse]))
         self.idx.append(g)
-        if len(self.cur) == self.gop:
+        if self.plan.is_gop_end(g):
             self.flush()
 
     def flush(self):
@@ -293,26 +300,32 @@ class _EncodeRun:
     pictures come from: the GOP streams and their codecs, which frame numbers each stream codes, the .bin sink and
     the bits / quality report.  encode_folder and encode_video supply the pictures and take the reconstructions."""
 
-    def __init__(self, bin_dir, n_frames, size, gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams, log_cls):
-        """nets, gop_streams: see encode_folder.  log_cls: the _QualityLog to keep per stream, or None for no report."""
+    def __init__(self, bin_dir, plan, size, gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams, log_cls):
+        """plan: the GopPlan of the sequence (`gop` is its longest GOP).  nets, gop_streams: see encode_folder.
+        log_cls: the _QualityLog to keep per stream, or None for no report."""
         os.makedirs(bin_dir, exist_ok=True)
-        self.bin_dir, self.n_frames, self.size, self.gop, self.dev = bin_dir, n_frames, size, gop, torch.device(device)
-        self.n_gops = (n_frames + gop - 1) // gop
+        self.bin_dir, self.plan, self.n_frames, self.size, self.gop = bin_dir, plan, plan.n_frames, size, gop
+        self.dev = torch.device(device)
+        self.n_gops = plan.n_gops
         self.K = K = max(1, min(int(gop_streams), self.n_gops))
         pairs = [nets] if (nets is not None and not isinstance(nets, list)) else list(nets or [])
         made = iter(pairs[:K] + [None] * K)
         self.cenc = ConcurrentGopEncoder(lambda: next(made) or _nets(self.dev, precision, i_ckpt, p_ckpt), gop_size=gop,
                                          streams=K, coder=coder)
         self.bits = {}
-        self.quality = [log_cls(gop) for _ in range(K)] if log_cls else None
+        self.quality = [log_cls(plan) for _ in range(K)] if log_cls else None
+        self.orders = [plan.order(k, K) for k in range(K)]
 
     def global_index(self, k, t):  # picture t of stream k's sequence -> 0-based frame number in the sequence
-        return ((t // self.gop) * self.K + k) * self.gop + t % self.gop
+        return self.orders[k][t]
 
     def order(self, k):
-        """The frame numbers stream k codes, in its coding order."""
-        order = [self.global_index(k, t) for t in range(((self.n_gops - k + self.K - 1) // self.K) * self.gop)]
-        return [g for g in order if g < self.n_frames]
+        """The frame numbers stream k codes, in its coding order: GOPs k, k + K, ... of the plan."""
+        return self.orders[k]
+
+    def intra(self, k):
+        """The picture numbers of stream k's sequence that are coded as I pictures."""
+        return {t for t, g in enumerate(self.orders[k]) if self.plan.is_intra(g)}
 
     def _sink(self, k):
         def sink(kind, qidx, payload, t):
@@ -334,7 +347,7 @@ class _EncodeRun:
         # is reported as a success)
         with torch.no_grad():
             self.cenc.encode_gops([frames(k) for k in range(self.K)], q[0], q[1], q[2], sinks=[self._sink(k) for k in range(self.K)],
-                                  on_recons=[recon_of(k) for k in range(self.K)])
+                                  on_recons=[recon_of(k) for k in range(self.K)], intra=[self.intra(k) for k in range(self.K)])
 
     def results(self, report, extras=None):
         """(bits per frame list, size) -- with a report also the rd_report() dictionary, which extras(rd, frame types,
@@ -349,7 +362,7 @@ class _EncodeRun:
             with torch.cuda.stream(self.cenc.streams[k]):
                 log.flush()  # a trailing partial GOP
             values.update(log.collect(3 * h * w))
-        types = [0 if g % self.gop == 0 else 1 for g in order]
+        types = [0 if self.plan.is_intra(g) else 1 for g in order]
         rd = rd_report(types, bit_list, [values[g][0] for g in order], [values[g][1] for g in order], h * w)
         if extras:
             extras(rd, types, [values[g] for g in order])
@@ -361,9 +374,75 @@ class _EncodeRun:
         return bit_list, self.size, rd
 
 
+GOPS_JSON = "gops.json"
+
+
+def _scene_plan(n_frames, size, gop, scenecut, min_gop, device, pictures):
+    """The GopPlan of an encode loop.  Without `scenecut` the fixed one, and `pictures` is not touched.  With it the scan
+    pass: pictures() yields every picture of the sequence once, in order, as the coding pass will see it (same reader,
+    same conversion); each is summarised on the device (scenecut.SceneScan: one kernel per picture, nothing
+    synchronised) and the distances are read back in one copy at the end."""
+    from . import scenecut as SC
+
+    SC.check_options(gop, scenecut, min_gop)
+    if scenecut is None:
+        return GopPlan.fixed(n_frames, gop)
+    scan = SC.SceneScan(device, size[0], size[1], n_frames)
+    with torch.no_grad():
+        for x in pictures():
+            scan.add(x)
+    if scan.n != n_frames:
+        raise ValueError(f"the scan pass saw {scan.n} pictures of {n_frames}")
+    return GopPlan(n_frames, SC.plan(scan.distances(), gop, scenecut, min_gop))
+
+
+def write_gop_plan(bin_dir, plan, gop, scenecut, min_gop):
+    """gops.json beside the .bin files -- only for a plan that came from a scan: a fixed plan needs none (and a stale
+    file of an earlier encode into the same folder must not describe these .bin files)."""
+    import json
+
+    path = os.path.join(bin_dir, GOPS_JSON)
+    if scenecut is None:
+        if os.path.exists(path):
+            os.remove(path)
+        return
+    with open(path, "w") as f:
+        json.dump(dict(plan.to_json(), gop=int(gop), min_gop=int(min_gop), scenecut=float(scenecut)), f, indent=2)
+
+
+def _count_bins(bin_dir):
+    n = 0
+    while os.path.exists(os.path.join(bin_dir, f"im{str(n + 1).zfill(5)}.bin")):
+        n += 1
+    return n
+
+
+def read_gop_plan(bin_dir, gop=None):
+    """(GopPlan of the .bin files in `bin_dir`, its longest GOP): from gops.json when encode left one, else an I picture
+    every `gop` (default 32) pictures.  Refused by name: a plan whose frame count is not the number of .bin files, and an
+    explicit `gop` that is not the plan's."""
+    import json
+
+    n, path = _count_bins(bin_dir), os.path.join(bin_dir, GOPS_JSON)
+    if not os.path.exists(path):
+        return GopPlan.fixed(n, gop or 32), gop or 32
+    with open(path) as f:
+        info = json.load(f)
+    try:
+        plan = GopPlan.from_json(info)
+    except ValueError as ex:
+        raise ValueError(f"{path}: {ex}") from None
+    if plan.n_frames != n:
+        raise ValueError(f"{path}: a plan of {plan.n_frames} frames beside {n} .bin files")
+    if gop is not None and info.get("gop") is not None and int(gop) != int(info["gop"]):
+        raise ValueError(f"{path}: the plan was made with gop {info['gop']}, not {gop}")
+    longest = max((len(plan.gop_range(j)) for j in range(plan.n_gops)), default=1)
+    return plan, int(info.get("gop") or longest)
+
+
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
-                  report=None, roi=None, residuals=None):
+                  report=None, roi=None, residuals=None, scenecut=None, min_gop=1):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -381,7 +460,12 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     the picture from the source and the reconstruction there: a `.gbrp` path (raw G, B, R planes, what
     `ffmpeg -f rawvideo -pix_fmt gbrp` reads) or a folder for im%05d.png.  With report and roi every picture gains
     frame_psnr_roi / frame_psnr_bg (base layer, per sample inside and outside the boxes shrunk by their class's shrink)
-    and frame_roi_pixels.  The .bin files are the same with or without."""
+    and frame_roi_pixels.  The .bin files are the same with or without.
+    scenecut: a threshold in (0, 1] on the distance of consecutive pictures (vcm_ts_amd/scenecut.py; no default value
+    exists).  A scan pass then reads every picture once, through the same pool and upload path as the coding pass, before
+    anything is coded; an I picture opens a new GOP wherever the distance exceeds the threshold and the GOP is at least
+    min_gop pictures old, `gop` becomes the longest GOP, and the plan is written to gops.json beside the .bin files
+    (decode_folder follows it).  Without scenecut nothing changes and no such file is written."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
@@ -396,33 +480,46 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     with Image.open(reader.path_of(1)) as first:  # (the header only)
         w, h = first.size
     _roi_args(roi, residuals)
-    layer = _RoiLayer(roi, n_frames, (h, w), gop, torch.device(device)) if roi is not None else None
-    run = _EncodeRun(bin_dir, n_frames, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
-                     (_VideoQualityLog if layer else _QualityLog) if report else None)
-    res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
-    source = {}
+    dev = torch.device(device)
     pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
 
-    def raw_frames(k):
-        """Stream k's pictures in its coding order as (H, W, 3) uint8 arrays, decoded up to `depth` ahead by the shared pool."""
-        order = run.order(k)
+    def raw_frames(order, sharers):
+        """The pictures `order` names as (H, W, 3) uint8 arrays, decoded up to `depth` ahead by the shared pool (which
+        `sharers` such generators draw on together)."""
         if pool is None:
             for g in order:
                 yield reader.load_u8(reader.path_of(g + 1))
             return
-        depth, pending, nxt = max(2, 2 * io_workers // run.K), deque(), 0
+        depth, pending, nxt = max(2, 2 * io_workers // sharers), deque(), 0
         while nxt < len(order) or pending:
             while nxt < len(order) and len(pending) < depth:
                 pending.append(pool.submit(reader.load_u8, reader.path_of(order[nxt] + 1)))
                 nxt += 1
             yield pending.popleft().result()
 
-    def frames(k):
-        ring = _PinnedRing(run.dev, (h, w, 3))
-        for rgb in raw_frames(k):
+    def uploaded(order, sharers):
+        """raw_frames on the device, as the padded float32 pictures the codec takes."""
+        ring = _PinnedRing(dev, (h, w, 3))
+        for rgb in raw_frames(order, sharers):
             assert tuple(rgb.shape) == (h, w, 3), "all frames must have one size"
             ring.host()[...] = rgb
-            x = pad_frame(u8_to_unit_float(ring.upload()))
+            yield pad_frame(u8_to_unit_float(ring.upload()))
+
+    try:
+        plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: uploaded(range(n_frames), 1))
+        layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
+        run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
+                         (_VideoQualityLog if layer else _QualityLog) if report else None)
+        write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
+        res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
+    except BaseException:
+        if pool is not None:
+            pool.shutdown(wait=True, cancel_futures=True)
+        raise
+    source = {}
+
+    def frames(k):
+        for x in uploaded(run.order(k), run.K):
             if report or res_out:
                 source[k] = x  # (the picture on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
             yield x
@@ -451,24 +548,22 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     return run.results(report, _roi_report_keys(h, w) if layer else None)
 
 
-def _decode_bins(nets, bin_dir, height, width, gop, emit):
-    """Decode im00001.bin ... of `bin_dir` (an I picture every `gop`) in order, handing every reconstruction to
-    emit(t, ref_frame) while it is valid.  Returns the picture count."""
+def _decode_bins(nets, bin_dir, height, width, plan, emit):
+    """Decode im00001.bin ... of `bin_dir` (I pictures where `plan`, read_gop_plan's, has them) in order, handing every
+    reconstruction to emit(t, ref_frame) while it is valid.  Returns the picture count."""
     i_net, p_net = nets
     i_net.update()
     p_net.update()
-    t, dpb = 0, None
+    dpb = None
 
     def range_guard():  # once per GOP: raises lib.KernelError if a split-fp16 kernel clamped an activation
         i_net.engine().check_status()
         p_net.engine().check_status()
 
     with torch.no_grad():
-        while True:
+        for t in range(plan.n_frames):
             path = os.path.join(bin_dir, f"im{str(t + 1).zfill(5)}.bin")
-            if not os.path.exists(path):
-                break
-            if t % gop == 0:
+            if plan.is_intra(t):
                 if t:
                     range_guard()
                 h, w, qi, payload = S.decode_i(path)
@@ -479,24 +574,26 @@ def _decode_bins(nets, bin_dir, height, width, gop, emit):
                 kind, q = "P", (qmv, qy)
             dpb = decode_picture(i_net, p_net, kind, q, payload, dpb, height, width)
             emit(t, dpb["ref_frame"])
-            t += 1
-        if t:
+        if plan.n_frames:
             range_guard()
-    return t
+    return plan.n_frames
 
 
-def decode_folder(bin_dir, recon_dir, height, width, gop=32, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
+def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
                   io_workers=8, roi=None, residuals=None):
     """roi, residuals: write video_coder.fuse_layers' picture instead of the reconstruction -- `residuals` is the decoded
     residual layer (a `.gbrp` file or a folder of im%05d.png, as encode_folder writes them) and `roi` the boxes and
-    classes it was taken with.  Display side only: the decoder's reference pictures are not touched."""
+    classes it was taken with.  Display side only: the decoder's reference pictures are not touched.
+    gop: an I picture every `gop` pictures (default 32) -- unless encode left a gops.json beside the .bin files, which then
+    says where the I pictures are; a `gop` given against it is refused (read_gop_plan)."""
     _roi_args(roi, residuals)
+    plan, _ = read_gop_plan(bin_dir, gop)
     os.makedirs(recon_dir, exist_ok=True)
-    picture, close = _fused_emit(roi, residuals, bin_dir, (height, width), gop, torch.device(device))
+    picture, close = _fused_emit(roi, residuals, plan, (height, width), torch.device(device))
     try:
         nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
         with PNGWriters(io_workers) as savers:
-            return _decode_bins(nets, bin_dir, height, width, gop, lambda t, ref_frame: save_torch_image(
+            return _decode_bins(nets, bin_dir, height, width, plan, lambda t, ref_frame: save_torch_image(
                 picture(t, ref_frame), os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"), savers))
     finally:
         close()
@@ -582,7 +679,7 @@ class _VideoQualityLog(_QualityLog):
         ms, _, sse = metrics.measure(recon[..., :h, :w], source[..., :h, :w], 1.0, clamp01=True)
         self.cur.append(torch.cat([ms, sse, sums.view(torch.float32)]))
         self.idx.append(g)
-        if len(self.cur) == self.gop:
+        if self.plan.is_gop_end(g):
             self.flush()
 
     def collect(self, elements):
@@ -603,20 +700,20 @@ class _RoiLayer:
     by name before any GPU work); the lists of one GOP go to the device in ONE pinned asynchronous copy, on the stream
     that codes the GOP, when its first picture asks."""
 
-    def __init__(self, roi, n_frames, size, gop, dev):
+    def __init__(self, roi, plan, size, dev):
         from . import roi as X
 
         if dev.index is None:
             dev = torch.device(dev.type, torch.cuda.current_device())
-        self.X, self.roi, self.gop, self.dev, self.size = X, X.as_roi(roi), gop, dev, size
+        self.X, self.roi, self.plan, self.dev, self.size = X, X.as_roi(roi), plan, dev, size
         self.classes = self.roi.classes
-        self.frames = [self.roi.frame(g, size[0], size[1]) for g in range(n_frames)]
+        self.frames = [self.roi.frame(g, size[0], size[1]) for g in range(plan.n_frames)]
 
     def boxes(self, g):
         fb = self.frames[g]
         if len(fb) and not fb.attached(self.dev):
-            g0 = g - g % self.gop
-            group = [f for f in self.frames[g0:g0 + self.gop] if len(f)]
+            frames = self.plan.gop_range(self.plan.gop_of(g))  # (never beyond the GOP: the next one may belong to another stream)
+            group = [f for f in self.frames[frames.start:frames.stop] if len(f)]
             pin = torch.from_numpy(np.concatenate([f.array.reshape(-1) for f in group])).pin_memory()
             dev, at = pin.to(self.dev, non_blocking=True), 0
             for f in group:
@@ -720,18 +817,15 @@ def _roi_report_keys(h, w):
     return keys
 
 
-def _fused_emit(roi, residuals, bin_dir, size, gop, dev):
+def _fused_emit(roi, residuals, plan, size, dev):
     """(picture(t, ref_frame) -> the fused unpadded picture, close()) of a decode loop; without a ROI the crop itself."""
     h, w = size
     if roi is None:
         return (lambda t, ref_frame: ref_frame[..., :h, :w]), (lambda: None)
     if residuals is None:
         raise ValueError("decoding with roi= needs residuals= (the decoded residual layer to fuse)")
-    n = 0
-    while os.path.exists(os.path.join(bin_dir, f"im{str(n + 1).zfill(5)}.bin")):
-        n += 1
-    layer = _RoiLayer(roi, n, size, gop, dev)
-    source = _ResidualIn(residuals, size, n, dev)
+    layer = _RoiLayer(roi, plan, size, dev)
+    source = _ResidualIn(residuals, size, plan.n_frames, dev)
 
     def picture(t, ref_frame):  # display side only: the DPB keeps the base-layer reconstruction
         return layer.X.fuse(ref_frame[..., :h, :w], source.frame(t), layer.boxes(t), layer.classes, layout=source.layout,
@@ -748,7 +842,8 @@ def _open_source(video, size, bit_depth, fps):
 
 def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantize8=False, gop=32, q=(1.0, 1.0, 1.0),
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
-                 nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None):
+                 nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
+                 min_gop=1):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -761,7 +856,9 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     io_workers is accepted for symmetry with encode_folder: a 4:2:0 frame needs no decoding, so this path has no helper
     threads at any value.  Writes sequence.json beside the .bin files (read_sequence_info, decode_video).
     roi, residuals: as encode_folder (the residual is taken against the RGB picture the codec was given); sequence.json
-    then also records the classes' names and borders."""
+    then also records the classes' names and borders.
+    scenecut, min_gop: as encode_folder; the scan pass reads the file once through the same ring, copy and colour
+    conversion (spec, quantize8) as the coding pass.  sequence.json is the same with or without."""
     from . import yuv as Y
 
     _roi_args(roi, residuals)
@@ -773,9 +870,22 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     n_frames = reader.n_frames if max_frames is None else min(reader.n_frames, int(max_frames))
     if n_frames < 1:
         raise ValueError(f"{getattr(reader, 'path', video)}: no frames")
-    layer = _RoiLayer(roi, n_frames, (h, w), gop, torch.device(device)) if roi is not None else None
-    run = _EncodeRun(bin_dir, n_frames, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
+    dev = torch.device(device)
+    sample_dtype = torch.uint8 if spec.bit_depth == 8 else torch.int16
+
+    def converted(order):
+        """(the padded RGB picture the codec takes, the file's samples on the device) of every frame `order` names"""
+        ring = _PinnedRing(dev, reader.frame_bytes)
+        for g in order:
+            reader.read_into(g, ring.host())
+            samples = ring.upload().view(sample_dtype)
+            yield Y.yuv420_to_rgb(samples, h, w, spec, pad=True, quantize8=quantize8), samples
+
+    plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: (x for x, _ in converted(range(n_frames))))
+    layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
+    run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
                      _VideoQualityLog if report else None)
+    write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
     res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
     source = {}
     container = "y4m" if isinstance(reader, Y.Y4MReader) else "yuv"
@@ -783,14 +893,9 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
                   aspect=getattr(reader, "aspect", None))
     writer = Y.create_video(recon_video, w, h, spec, reader.fps, **extras) if recon_video else None
     outs = [_VideoOut(writer) for _ in range(run.K)] if writer else None
-    sample_dtype = torch.uint8 if spec.bit_depth == 8 else torch.int16
 
     def frames(k):
-        ring = _PinnedRing(run.dev, reader.frame_bytes)
-        for g in run.order(k):
-            reader.read_into(g, ring.host())
-            samples = ring.upload().view(sample_dtype)
-            x = Y.yuv420_to_rgb(samples, h, w, spec, pad=True, quantize8=quantize8)
+        for x, samples in converted(run.order(k)):
             source[k] = (x, samples)  # (what on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
             yield x
 
@@ -850,13 +955,13 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     height, width = height or info.get("height"), width or info.get("width")
     if not height or not width:
         raise ValueError(f"no {SEQUENCE_JSON} in {bin_dir}: height and width are required")
-    gop = gop or info.get("gop") or 32
+    plan, _ = read_gop_plan(bin_dir, gop or info.get("gop"))  # (gops.json, when encode left one, says where the I pictures are)
     spec = spec or info.get("color") or Y.ColorSpec()
     Y.check_size(height, width)
     first = os.path.join(bin_dir, "im00001.bin")
     if os.path.exists(first) and S.decode_i(first)[:2] != (height, width):
         raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {(height, width)}")
-    picture, close = _fused_emit(roi, residuals, bin_dir, (height, width), gop, torch.device(device))
+    picture, close = _fused_emit(roi, residuals, plan, (height, width), torch.device(device))
     try:
         nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
         writer = Y.create_video(recon_video, width, height, spec, fps or info.get("fps"), chroma=info.get("chroma"),
@@ -864,7 +969,7 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
         try:
             out = _VideoOut(writer)
             # (without a ROI the padded reconstruction itself: rgb_to_yuv420 reads its top-left corner in place)
-            t = _decode_bins(nets, bin_dir, height, width, gop, lambda t, ref_frame: out.put(t, Y.rgb_to_yuv420(
+            t = _decode_bins(nets, bin_dir, height, width, plan, lambda t, ref_frame: out.put(t, Y.rgb_to_yuv420(
                 ref_frame if roi is None else picture(t, ref_frame), height, width, spec)))
             out.close()
         finally:
@@ -904,6 +1009,14 @@ def main(argv=None):
     e.add_argument("--report", metavar="JSON",
                    help="write bpp, PSNR and MS-SSIM of every picture and their I / P / all averages (the key layout of "
                         "the reference's test harness); measured on the device, the .bin files are the same with or without")
+    e.add_argument("--scenecut", type=float, default=None, metavar="T",
+                   help="also open a GOP with an I picture where consecutive pictures differ by more than T, 0 < T <= 1 (0: "
+                        "identical regional luma histograms, 1: disjoint; no default exists -- the right value depends on "
+                        "the content).  A scan pass reads the source once before coding; --gop becomes the longest GOP; the "
+                        "I pictures are listed in gops.json beside the .bin files, which decode follows")
+    e.add_argument("--min-gop", type=int, default=None, metavar="N",
+                   help="with --scenecut: no I picture closer than N pictures behind the last one (default 1, at most --gop); "
+                        "a cut that falls inside stays a P picture")
     d = sub.add_parser("decode")
     d.add_argument("--bins", required=True)
     d.add_argument("--recon", help="folder for PNGs (exactly one of --recon and --recon-video)")
@@ -926,7 +1039,8 @@ def main(argv=None):
                        help="the reference's LIPLATES.PADDING: feather width and metric shrink of plate boxes "
                             "(default 0; decode: the sequence.json's)")
         p.add_argument("--face-border", type=int, default=None, metavar="N", help="the same for face boxes")
-        p.add_argument("--gop", type=int, default=None, help="default 32 (decode: the sequence.json's, else 32)")
+        p.add_argument("--gop", type=int, default=None,
+                       help="default 32 (decode: the sequence.json's, else 32; refused if a gops.json beside the .bin files says otherwise)")
         p.add_argument("--io-workers", type=int, default=8, help="host threads for PNG decoding / encoding (0: inline)")
         p.add_argument("--device", default="cuda:0")
         p.add_argument("--precision", default=None, choices=["fp32", "fp16x3"])
@@ -972,6 +1086,15 @@ def main(argv=None):
             except ValueError as ex:
                 ap.error(str(ex))
         a.gop = a.gop or 32
+        if a.min_gop is not None and a.scenecut is None:
+            ap.error("--min-gop belongs to --scenecut")
+        a.min_gop = 1 if a.min_gop is None else a.min_gop
+        try:
+            from .scenecut import check_options
+
+            check_options(a.gop, a.scenecut, a.min_gop)
+        except ValueError as ex:
+            ap.error(str(ex))
         if (a.rate_count is None) != (a.quality is None) or (a.q is not None and a.rate_count is not None):
             ap.error("give either --q, or --rate-count together with --quality")
         q = tuple(a.q) if a.q is not None else (1.0, 1.0, 1.0)
@@ -996,11 +1119,11 @@ def main(argv=None):
                 bits, size, *rd = encode_video(reader, a.bins, a.recon_video, spec=spec, quantize8=a.quantize8, gop=a.gop, q=q,
                                                device=a.device, precision=a.precision, i_ckpt=a.i_ckpt, p_ckpt=a.p_ckpt,
                                                coder=a.coder, gop_streams=a.gop_streams, report=a.report, roi=roi,
-                                               residuals=a.residuals)
+                                               residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop)
         else:
             bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
                                             coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
-                                            roi=roi, residuals=a.residuals)
+                                            roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop)
         if rd:
             yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
             print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
@@ -1027,7 +1150,7 @@ def main(argv=None):
             if a.matrix or a.range or a.siting or a.bit_depth:
                 ap.error("--matrix, --range, --siting and --bit-depth belong to --recon-video")
             height, width = a.height or info["height"], a.width or info["width"]
-            n = decode_folder(a.bins, a.recon, height, width, a.gop or (info or {}).get("gop") or 32, a.device, a.precision,
+            n = decode_folder(a.bins, a.recon, height, width, a.gop or (info or {}).get("gop"), a.device, a.precision,
                               a.i_ckpt, a.p_ckpt, io_workers=a.io_workers, roi=roi, residuals=a.residuals)
         print(f"{n} pictures decoded")
 
