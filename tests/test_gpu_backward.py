@@ -516,3 +516,42 @@ def test_batch_pack_plan_equals_per_layer_packing():
     assert calls == n_before
     e.repack_all()  # nothing changed since: no launch, plan kept
     assert e._plan[1] == n_before
+
+
+@pytest.mark.parametrize("precision", [0, 1], ids=["fp32", "fp16x3"])
+@pytest.mark.parametrize("Cout,ps", [(33, 0), (8, 1)], ids=["cout33", "cout8_ps"])
+def test_device_packer_writes_the_host_packers_bytes(Cout, ps, precision):
+    """dcvc_conv_pack_weights_dev (transposed = 0) and the host's dcvc_conv_pack_weights are two writers of ONE layout
+    (vcm_ts_amd/csrc/kernel_common.h), which dcvc_conv2d reads: the same weights must give the same bytes, padding
+    included -- three segments with chunk tails, PixelShuffle order, both precisions; zeros of both signs and magnitudes
+    whose lo part is an fp16 subnormal."""
+    import ctypes as C
+
+    from vcm_ts_amd import lib
+
+    L = lib.hip()
+    seg_C, ks = (17, 5, 32), 3
+    Cin = sum(seg_C)
+    g = torch.Generator().manual_seed(11 + Cout)
+    w = torch.randn(Cout, Cin, ks, ks, generator=g) * 0.1
+    w.view(-1)[:6] = torch.tensor([0.0, -0.0, 1e-6, -1e-6, 3e-6, -7e-7])
+    b = torch.randn(Cout, generator=g) * 0.1
+    segs = (C.c_int32 * 3)(*seg_C)
+    cp = C.c_int32(0)
+    total = L.dcvc_conv_pack_size(Cout, ks, 3, segs, C.byref(cp))
+    assert total > 0
+    w_host, b_host = torch.full((total,), float("nan")), torch.full((cp.value,), float("nan"))
+    lib.check(L.dcvc_conv_pack_weights(w.data_ptr(), b.data_ptr(), Cout, ks, 3, segs, ps, precision, w_host.data_ptr(),
+                                       b_host.data_ptr()), "host pack")
+    dev = torch.device("cuda:0")
+    wd, bd = w.to(dev), b.to(dev)
+    w_dev, b_dev = torch.full((total,), float("nan"), device=dev), torch.full((cp.value,), float("nan"), device=dev)
+    torch.cuda.synchronize()
+    lib.check(L.dcvc_conv_pack_weights_dev(wd.data_ptr(), bd.data_ptr(), Cout, Cin, ks, 3, segs, 0, ps, precision, 0,
+                                           w_dev.data_ptr(), b_dev.data_ptr(), None), "device pack")
+    torch.cuda.synchronize()
+    assert torch.equal(b_dev.cpu().view(torch.int32), b_host.view(torch.int32))
+    got, want = w_dev.cpu().view(torch.int16), w_host.view(torch.int16)
+    bad = torch.nonzero(got != want).flatten()
+    assert bad.numel() == 0, f"{bad.numel()} of {want.numel()} halfwords differ, first at {bad[:8].tolist()}: " \
+                             f"device {got[bad[:8]].tolist()} host {want[bad[:8]].tolist()}"

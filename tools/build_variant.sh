@@ -9,7 +9,7 @@ SRC=$C/$unit
 if [ "$unit" = "conv_k32.hip" ]; then  # the developer switches live in a patch, not in the product source
   make -s -C tools/probes conv_k32_dev.hip && cp tools/probes/conv_k32_dev.hip $O/obj/conv_k32.hip && SRC=$O/obj/conv_k32.hip
 fi
-F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude"
+F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Ivcm_ts_amd/csrc"
 /opt/rocm/bin/hipcc $F -cuid=dcvc_${unit%.hip} --offload-device-only -Xclang -target-feature -Xclang -packed-fp32-ops "$@" -c $SRC -o $O/obj/$name.hipfb
 /opt/rocm/bin/hipcc $F -cuid=dcvc_${unit%.hip} --offload-host-only -Xclang -fcuda-include-gpubinary -Xclang $O/obj/$name.hipfb "$@" -c $SRC -o $O/obj/$name.o
 objs=""; for f in $C/build/*.o; do [ "$(basename $f)" = "${unit%.hip}.o" ] || objs="$objs $f"; done

@@ -19,19 +19,9 @@
 #include <vector>
 
 #include "dcvc_hip_grad.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_common.h"
 
 namespace {
-
-#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? DCVC_OK : DCVC_E_LAUNCH
-inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-constexpr int KC = 16;               // must match conv_mfma.hip
-constexpr float WGT_SCALE = 64.f;    // must match conv_mfma.hip
-constexpr float F16_MAX = 65504.f;
 
 __device__ __forceinline__ float block_sum(float v, float *sm) {
     const int t = threadIdx.x;
@@ -46,7 +36,7 @@ __device__ __forceinline__ float block_sum(float v, float *sm) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// device-side weight packing
+// device-side weight packing: the conv_mfma layout of kernel_common.h, one thread per packed fp32 element
 struct PackK {
     const float *w;
     const float *b;
@@ -69,7 +59,7 @@ __device__ __forceinline__ void pack_body(const PackK &a, const int64_t gid) {
         if (!a.transposed && a.b && gid < a.Npk) {
             const int np = (int)gid;
             const int Cq = a.Npk >> 2;
-            const int n = a.ps ? (np % Cq) * 4 + np / Cq : np;
+            const int n = a.ps ? ps_source_channel(np, Cq) : np;
             bv = a.b[n];
         }
         a.bpack[gid] = bv;
@@ -83,11 +73,11 @@ __device__ __forceinline__ void pack_body(const PackK &a, const int64_t gid) {
     int s = 0;
     for (int i = 1; i < a.nseg; ++i)
         if (cg >= a.seg_chunk0[i]) s = i;
-    const int c = (cg - a.seg_chunk0[s]) * KC + kq * 4 + j;
+    const int c = (cg - a.seg_chunk0[s]) * MFMA_KC + kq * 4 + j;
     float v = 0.f;
     if (c < a.seg_C[s] && np < a.Npk) {
         const int Cq = a.Npk >> 2;
-        const int n = a.ps ? (np % Cq) * 4 + np / Cq : np;
+        const int n = a.ps ? ps_source_channel(np, Cq) : np;
         if (!a.transposed)
             v = a.w[((size_t)n * a.CinT + a.cin_offset + a.seg_cin0[s] + c) * a.T + t];
         else  // packed input channel c = forward output channel, packed output n = forward input channel
@@ -96,13 +86,12 @@ __device__ __forceinline__ void pack_body(const PackK &a, const int64_t gid) {
     if (a.precision == DCVC_PREC_FP32) {
         a.wpack[gid] = v;
     } else {
-        const int cc = kq * 4 + j, h = cc >> 3, jj = cc & 7;
         float sv = v * WGT_SCALE;
-        sv = fminf(fmaxf(sv, -F16_MAX), F16_MAX);
-        const _Float16 hi = (_Float16)sv, lo = (_Float16)(sv - (float)hi);
+        sv = fminf(fmaxf(sv, -F16_MAX), F16_MAX);  // no status to report from a kernel (kernel_common.h)
+        const SplitF16 p = split_f16(sv);
         _Float16 *base = (_Float16 *)a.wpack;
-        base[((((size_t)cg * a.T + t) * 4 + h) * a.cp + np) * 8 + jj] = hi;
-        base[((((size_t)cg * a.T + t) * 4 + 2 + h) * a.cp + np) * 8 + jj] = lo;
+        base[mfma_wpack_f16(cg, a.T, t, kq * 4 + j, a.cp, np, 0)] = p.hi;
+        base[mfma_wpack_f16(cg, a.T, t, kq * 4 + j, a.cp, np, 1)] = p.lo;
     }
 }
 
@@ -1146,7 +1135,7 @@ static int make_pack(PackK &k, const float *w, const float *b, int32_t Cout, int
             k.seg_C[s] = seg_C[s];
             k.seg_chunk0[s] = chunks;
             k.seg_cin0[s] = cin0;
-            chunks += (seg_C[s] + KC - 1) / KC;
+            chunks += (seg_C[s] + MFMA_KC - 1) / MFMA_KC;
             cin0 += seg_C[s];
         }
         if (cin_offset < 0 || cin_offset + cin0 > Cin_total) return DCVC_E_ARG;
@@ -1155,7 +1144,7 @@ static int make_pack(PackK &k, const float *w, const float *b, int32_t Cout, int
         k.Npk = seg_C[0];
         k.nseg = 1;
         k.seg_C[0] = Cout;
-        chunks = (Cout + KC - 1) / KC;
+        chunks = (Cout + MFMA_KC - 1) / MFMA_KC;
     }
     if (pixel_shuffle && (k.Npk & 3)) return DCVC_E_ARG;
     k.cp = round_up(k.Npk, 32);

@@ -13,12 +13,11 @@
 
 #include "dcvc_hip.h"
 #include "dcvc_hip_color.h"
+#include "kernel_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? DCVC_OK : DCVC_E_LAUNCH
 
 #include "unit8_table.h"
 

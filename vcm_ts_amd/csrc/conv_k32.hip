@@ -32,10 +32,7 @@
 #include <string.h>
 
 #include "dcvc_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+#include "kernel_common.h"
 
 // (Developer builds -- s_memtime stamps at the phase boundaries, ablation variants without MFMAs / fragment reads /
 // stores, the staging and epilogue alternatives measured in round 3 -- are produced by applying
@@ -45,10 +42,6 @@ namespace {
 
 constexpr int KC = 32;   // channels per K chunk
 constexpr int REC = 40;  // floats per pixel record of the LDS patch (160 B)
-constexpr float ACT_SCALE = 8.f;
-constexpr float WGT_SCALE = 64.f;
-constexpr float F16_MAX = 65504.f;
-constexpr float ACT_LIMIT = F16_MAX / ACT_SCALE;
 
 struct K32 {
     const float *seg_ptr[DCVC_MAX_SEG];
@@ -76,8 +69,6 @@ struct K32 {
     int ntx;
     int ty0, nty, band_rows;  // band of tile rows this launch computes (dcvc_conv_args.tile_row0 / tile_rows)
 };
-
-__device__ __forceinline__ float act(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 template <int KS, int NTW, int NWAVE>
 __global__ __launch_bounds__(64 * NWAVE, NWAVE / 2) void conv_k32(const K32 a) {
@@ -418,13 +409,10 @@ int launch(K32 &k, int N, hipStream_t st) {
     const int rows = k.band_rows > 0 ? (k.band_rows < k.nty - k.ty0 ? k.band_rows : k.nty - k.ty0) : k.nty;
     dim3 grid((unsigned)(k.ntx * (k.Cout_pad / BN)), (unsigned)rows, (unsigned)N);
     hipLaunchKernelGGL((conv_k32<KS, NTW, NWAVE>), grid, dim3(64 * NWAVE), 0, st, k);
-    return hipGetLastError() == hipSuccess ? DCVC_OK : DCVC_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 int g_k32_waves = 8;
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-inline bool aligned16(const void *p, int cs) { return p == nullptr || ((((uintptr_t)p) & 15) == 0 && (cs & 3) == 0); }
 
 }  // namespace
 
@@ -441,7 +429,7 @@ extern "C" int64_t dcvc_conv_k32_pack_bytes(int32_t Cout, int32_t ks, int32_t ns
 }
 
 // wpack as 16-byte entries: entry[((chunk * T + tap) * 2 + hl) * 4 + kq][n'] = 8 fp16: w[n][cin = 32 chunk + 8 kq + j][tap]
-// (hl 0: hi, 1: lo of 64 w), n' = n, or with pixel shuffle n' = (n % 4) * (Cout / 4) + n / 4 (sub-pixel planes contiguous).
+// (hl 0: hi, 1: lo of 64 w), n' = n, or with pixel shuffle ps_packed_channel(n) (kernel_common.h).
 extern "C" int dcvc_conv_k32_pack_weights(const float *w, const float *b, int32_t Cout, int32_t ks, int32_t nseg,
                                           const int32_t *seg_C, int32_t pixel_shuffle, void *wpack, float *bpack) {
     int32_t cp = 0;
@@ -459,21 +447,15 @@ extern "C" int dcvc_conv_k32_pack_weights(const float *w, const float *b, int32_
         const int cg = c / KC, kq = (c % KC) >> 3, j = c & 7;
         for (int t = 0; t < T; ++t)
             for (int n = 0; n < Cout; ++n) {
-                const int np = pixel_shuffle ? (n & 3) * Cq + (n >> 2) : n;
+                const int np = pixel_shuffle ? ps_packed_channel(n, Cq) : n;
                 float sv = w[((size_t)n * Cin + c) * T + t] * WGT_SCALE;
-                if (!(fabsf(sv) <= F16_MAX)) {
-                    clamped = true;
-                    sv = sv > 0.f ? F16_MAX : -F16_MAX;
-                }
-                const _Float16 hi = (_Float16)sv, lo = (_Float16)(sv - (float)hi);
-                base[(((((size_t)cg * T + t) * 2 + 0) * 4 + kq) * cp + np) * 8 + j] = hi;
-                base[(((((size_t)cg * T + t) * 2 + 1) * 4 + kq) * cp + np) * 8 + j] = lo;
+                if (!(fabsf(sv) <= F16_MAX)) { clamped = true; sv = sv > 0.f ? F16_MAX : -F16_MAX; }  // reported; NaN -> -max
+                const SplitF16 p = split_f16(sv);
+                base[(((((size_t)cg * T + t) * 2 + 0) * 4 + kq) * cp + np) * 8 + j] = p.hi;
+                base[(((((size_t)cg * T + t) * 2 + 1) * 4 + kq) * cp + np) * 8 + j] = p.lo;
             }
     }
-    for (int n = 0; n < Cout; ++n) {
-        const int np = pixel_shuffle ? (n & 3) * Cq + (n >> 2) : n;
-        bpack[np] = b ? b[n] : 0.f;
-    }
+    for (int n = 0; n < Cout; ++n) bpack[pixel_shuffle ? ps_packed_channel(n, Cq) : n] = b ? b[n] : 0.f;
     return clamped ? DCVC_E_RANGE : DCVC_OK;
 }
 
@@ -484,20 +466,12 @@ extern "C" int dcvc_conv_k32_set_waves(int32_t waves) {
 }
 
 extern "C" int dcvc_conv2d_k32(const dcvc_conv_args *a, void *stream) {
-    if (!a || a->nseg < 1 || a->nseg > DCVC_MAX_SEG || !a->out || !a->wpack || !a->bpack) return DCVC_E_ARG;
+    if (!conv_args_ok(a)) return DCVC_E_ARG;
     if (a->stride != 1 || (a->ks != 1 && a->ks != 3) || a->precision != DCVC_PREC_FP16X3) return DCVC_E_ARG;
     if (a->Cout_pad % 32 || a->Cout > a->Cout_pad || (a->pixel_shuffle && (a->Cout & 3))) return DCVC_E_ARG;
     if (a->out_act < 0 || a->out_act > 2) return DCVC_E_ARG;  // (the mask epilogue, out_act 3, is dcvc_conv2d's)
-    K32 k;
-    memset(&k, 0, sizeof(k));
-    for (int s = 0; s < a->nseg; ++s) {
-        if (!a->seg[s].ptr || a->seg[s].C <= 0 || a->seg[s].C % KC || (a->seg[s].cs & 3) || a->seg[s].cs < a->seg[s].C ||
-            ((uintptr_t)a->seg[s].ptr & 15))
-            return DCVC_E_ARG;
-        k.seg_ptr[s] = a->seg[s].ptr;
-        k.seg_C[s] = a->seg[s].C;
-        k.seg_cs[s] = a->seg[s].cs;
-    }
+    for (int s = 0; s < a->nseg; ++s)
+        if (a->seg[s].C <= 0 || a->seg[s].C % KC) return DCVC_E_ARG;
     {  // output / residual images are addressed with 32-bit byte offsets (and as raw buffers)
         const unsigned long long opix = (unsigned long long)a->Hin * a->Win * (a->pixel_shuffle ? 4 : 1);
         // the kernel forms pixel index x channel stride with 24-bit multiplies (load_patch, out_off): both factors
@@ -515,35 +489,14 @@ extern "C" int dcvc_conv2d_k32(const dcvc_conv_args *a, void *stream) {
     if (a->in_act && !(a->in_slope >= 0.f && a->in_slope <= 1.f)) return DCVC_E_ARG;  // (store_patch's max(s, s * slope))
     for (int s = 0; s < a->nseg; ++s)  // an image of a segment is addressed with 32-bit byte offsets (and as a raw buffer)
         if ((unsigned long long)a->Hin * a->Win * a->seg[s].cs * 4ull > 0xfffffff0ull) return DCVC_E_ARG;
-    k.nseg = a->nseg;
+    // this kernel has the 16-byte epilogue only (every layer it is meant for qualifies); others stay on dcvc_conv2d
+    if (!vec_epilogue_ok(a)) return DCVC_E_ARG;
+    if (a->chan_partial && a->pixel_shuffle) return DCVC_E_ARG;
+    K32 k;
+    memset(&k, 0, sizeof(k));
+    copy_conv_args_full(k, a);
     k.H = a->Hin;
     k.W = a->Win;
-    k.in_act = a->in_act;
-    k.in_slope = a->in_slope;
-    k.wpack = a->wpack;
-    k.bpack = a->bpack;
-    k.Cout = a->Cout;
-    k.Cout_pad = a->Cout_pad;
-    k.out = a->out;
-    k.out_cs = a->out_cs;
-    k.out_act = a->out_act;
-    k.out_slope = a->out_slope;
-    k.ps = a->pixel_shuffle;
-    k.res = a->res;
-    k.res_cs = a->res_cs;
-    k.res_gate = a->res_gate;
-    k.res2 = a->res2;
-    k.res2_cs = a->res2_cs;
-    k.status = a->status;
-    k.chan_partial = a->chan_partial;
-    k.ty0 = a->tile_rows > 0 ? a->tile_row0 : 0;
-    k.band_rows = a->tile_rows > 0 ? a->tile_rows : 0;
-    const int cfin = a->pixel_shuffle ? a->Cout / 4 : a->Cout;
-    // this kernel has the 16-byte epilogue only (every layer it is meant for qualifies); others stay on dcvc_conv2d
-    if ((cfin % 4) || !aligned16(a->out, a->out_cs) || !aligned16(a->res, a->res_cs) || !aligned16(a->res2, a->res2_cs) ||
-        (a->res_gate && (((uintptr_t)a->res_gate) & 15)))
-        return DCVC_E_ARG;
-    if (a->chan_partial && a->pixel_shuffle) return DCVC_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     const bool wide = (a->Cout_pad % 64) == 0;
     // the wide 3x3 kernel runs as 8-wave workgroups (four waves per SIMD with two resident workgroups);

@@ -29,27 +29,14 @@
 #include <vector>
 
 #include "dcvc_hip.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+#include "kernel_common.h"
 
 namespace {
 
-constexpr int KC = 16;   // channels per K chunk
 constexpr int LDK = 20;  // padded channel stride of the LDS patch, in floats
 
-// Split-fp16 mode ("fp16x3"): every fp32 operand v is carried as hi = fp16(v * 2^s) and
-// lo = fp16(v * 2^s - hi); x*w ~= xh*wh + xh*wl + xl*wh on v_mfma_f32_32x32x16_f16 with fp32
-// accumulation (products of fp16 are exact in fp32; the dropped xl*wl is <= 2^-22 |x w|).
-// gfx950's MFMA honours fp16 subnormals (tools/probes/mfma_f16_subnormal.hip), so lo needs no
-// separate scale: representation error <= max(2^-22 |v|, 2^-25 / 2^s).  The power-of-two
-// pre-scales keep typical activations / weights in fp16's normal range and are undone exactly
-// in the epilogue.  3 MFMAs of 32 cycles replace 8 fp32 MFMAs of 64 cycles per 16-deep K step.
-constexpr float ACT_SCALE = 8.f;     // activations: |x| < 8188 representable
-constexpr float WGT_SCALE = 64.f;    // weights:     |w| < 1023 representable
-constexpr float F16_MAX = 65504.f;
+// Split-fp16 mode (kernel_common.h) runs on v_mfma_f32_32x32x16_f16: 3 MFMAs of 32 cycles replace 8 fp32 MFMAs of 64
+// cycles per 16-deep K step (one chunk of MFMA_KC channels).
 
 struct ConvK {
     const float *seg_ptr[DCVC_MAX_SEG];
@@ -79,10 +66,6 @@ struct ConvK {
     int ty0, nty;         // first tile row of this launch's band, tile rows of the whole picture
     int band_rows;        // tile rows of the band (0: all)
 };
-
-constexpr float ACT_LIMIT = 65504.f / 8.f;  // F16_MAX / ACT_SCALE
-
-__device__ __forceinline__ float act(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // Developer A/B switches of this file change launch geometry only (never a result bit) and are honoured only in a process
 // that declares itself a developer run with DCVC_DEV=1, like the routing switches of vcm_ts_amd/engine.py (a
@@ -146,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma(const ConvK a) {
         if (++k.st == NST) {
             k.st = 0;
             ++k.cg;
-            k.c0 += KC;
+            k.c0 += MFMA_KC;
             if (k.c0 >= a.seg_C[k.s]) {
                 ++k.s;
                 k.c0 = 0;
@@ -488,25 +471,21 @@ int launch(ConvK &k, int N, hipStream_t st, int precision) {
         hipLaunchKernelGGL((conv_mfma<KS, S, RPW, NT, true>), grid, dim3(256), 0, st, k);
     else
         hipLaunchKernelGGL((conv_mfma<KS, S, RPW, NT, false>), grid, dim3(256), 0, st, k);
-    return hipGetLastError() == hipSuccess ? DCVC_OK : DCVC_E_LAUNCH;
+    RET_LAUNCH();
 }
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 }  // namespace
 
 extern "C" int64_t dcvc_conv_pack_size(int32_t Cout, int32_t ks, int32_t nseg, const int32_t *seg_C, int32_t *cout_pad) {
     if (Cout <= 0 || nseg <= 0 || nseg > DCVC_MAX_SEG || (ks != 1 && ks != 3 && ks != 7)) return DCVC_E_ARG;
     int chunks = 0;
-    for (int s = 0; s < nseg; ++s) chunks += (seg_C[s] + KC - 1) / KC;
+    for (int s = 0; s < nseg; ++s) chunks += (seg_C[s] + MFMA_KC - 1) / MFMA_KC;
     const int cp = round_up(Cout, 32);
     if (cout_pad) *cout_pad = cp;
     return (int64_t)chunks * ks * ks * 4 * cp * 4;
 }
 
-// wpack[((chunk*T + tap)*4 + kq)*Cout_pad + n'][j] = w[n][cin(chunk, kq, j)][tap]
-// with n' = n, or for pixel shuffle n' = (n % 4) * (Cout/4) + n / 4 so that the four
-// sub-pixel planes are contiguous channel ranges.
+// the layout of kernel_common.h (mfma_wpack_f32 / mfma_wpack_f16); n' = n, or with pixel shuffle ps_packed_channel(n)
 extern "C" int dcvc_conv_pack_weights(const float *w, const float *b, int32_t Cout, int32_t ks, int32_t nseg,
                                       const int32_t *seg_C, int32_t pixel_shuffle, int32_t precision, float *wpack,
                                       float *bpack) {
@@ -520,44 +499,35 @@ extern "C" int dcvc_conv_pack_weights(const float *w, const float *b, int32_t Co
     memset(wpack, 0, (size_t)total * sizeof(float));
     memset(bpack, 0, (size_t)cp * sizeof(float));
     const int Cq = Cout / 4;
+    _Float16 *base = (_Float16 *)wpack;
     int cg = 0, cin0 = 0;
     for (int s = 0; s < nseg; ++s) {
-        for (int c0 = 0; c0 < seg_C[s]; c0 += KC, ++cg) {
+        for (int c0 = 0; c0 < seg_C[s]; c0 += MFMA_KC, ++cg) {
             for (int t = 0; t < T; ++t)
-                for (int kq = 0; kq < 4; ++kq)
-                    for (int j = 0; j < 4; ++j) {
-                        const int c = c0 + kq * 4 + j;
-                        if (c >= seg_C[s]) continue;
-                        for (int n = 0; n < Cout; ++n) {
-                            const int np = pixel_shuffle ? (n & 3) * Cq + (n >> 2) : n;
-                            const float v = w[((size_t)n * Cin + cin0 + c) * T + t];
-                            if (precision == DCVC_PREC_FP32) {
-                                wpack[((((size_t)cg * T + t) * 4 + kq) * cp + np) * 4 + j] = v;
-                            } else {
-                                // rows [hi h0, hi h1, lo h0, lo h1], 8 fp16 per (row, n): channel 4kq+j = 8h+jj
-                                const int cc = kq * 4 + j, h = cc >> 3, jj = cc & 7;
-                                float sv = v * WGT_SCALE;
-                                sv = sv > F16_MAX ? F16_MAX : (sv < -F16_MAX ? -F16_MAX : sv);
-                                const _Float16 hi = (_Float16)sv, lo = (_Float16)(sv - (float)hi);
-                                _Float16 *base = (_Float16 *)wpack;
-                                base[((((size_t)cg * T + t) * 4 + h) * cp + np) * 8 + jj] = hi;
-                                base[((((size_t)cg * T + t) * 4 + 2 + h) * cp + np) * 8 + jj] = lo;
-                            }
+                for (int cc = 0; cc < MFMA_KC && c0 + cc < seg_C[s]; ++cc)
+                    for (int n = 0; n < Cout; ++n) {
+                        const int np = pixel_shuffle ? ps_packed_channel(n, Cq) : n;
+                        const float v = w[((size_t)n * Cin + cin0 + c0 + cc) * T + t];
+                        if (precision == DCVC_PREC_FP32) {
+                            wpack[mfma_wpack_f32(cg, T, t, cc, cp, np)] = v;
+                        } else {
+                            float sv = v * WGT_SCALE;
+                            sv = sv > F16_MAX ? F16_MAX : (sv < -F16_MAX ? -F16_MAX : sv);  // silent; a NaN stays a NaN
+                            const SplitF16 p = split_f16(sv);
+                            base[mfma_wpack_f16(cg, T, t, cc, cp, np, 0)] = p.hi;
+                            base[mfma_wpack_f16(cg, T, t, cc, cp, np, 1)] = p.lo;
                         }
                     }
         }
         cin0 += seg_C[s];
     }
-    for (int n = 0; n < Cout; ++n) {
-        const int np = pixel_shuffle ? (n & 3) * Cq + (n >> 2) : n;
-        bpack[np] = b ? b[n] : 0.f;
-    }
+    for (int n = 0; n < Cout; ++n) bpack[pixel_shuffle ? ps_packed_channel(n, Cq) : n] = b ? b[n] : 0.f;
     return DCVC_OK;
 }
 
 // Tap-paired packing of a 7x7 layer with one input segment of <= 8 channels (split fp16 only; see PAIR above):
 // K step (ky, j) holds tap (ky, 2j) in channel half 0 and tap (ky, 2j + 1) in half 1 (zero for kx = 7).
-// wpack rows [(ky * 4 + j)][hi h0, hi h1, lo h0, lo h1][n][8 fp16].
+// wpack rows [(ky * 4 + j)][hi h0, hi h1, lo h0, lo h1][n][8 fp16]: the fp16 form of ONE chunk whose taps are the K steps.
 extern "C" int64_t dcvc_conv_pack_size_paired(int32_t Cout, int32_t Cin, int32_t *cout_pad) {
     if (Cout <= 0 || Cin <= 0 || Cin > 8) return DCVC_E_ARG;
     const int cp = round_up(Cout, 32);
@@ -579,13 +549,10 @@ extern "C" int dcvc_conv_pack_weights_paired(const float *w, const float *b, int
             for (int c = 0; c < Cin; ++c)
                 for (int n = 0; n < Cout; ++n) {
                     float sv = w[((size_t)n * Cin + c) * 49 + ky * 7 + kx] * WGT_SCALE;
-                    if (!(fabsf(sv) <= F16_MAX)) {
-                        clamped = true;
-                        sv = sv > 0.f ? F16_MAX : -F16_MAX;
-                    }
-                    const _Float16 hi = (_Float16)sv, lo = (_Float16)(sv - (float)hi);
-                    base[(((size_t)step * 4 + h) * cp + n) * 8 + c] = hi;
-                    base[(((size_t)step * 4 + 2 + h) * cp + n) * 8 + c] = lo;
+                    if (!(fabsf(sv) <= F16_MAX)) { clamped = true; sv = sv > 0.f ? F16_MAX : -F16_MAX; }  // reported; NaN -> -max
+                    const SplitF16 p = split_f16(sv);
+                    base[mfma_wpack_f16(0, 28, step, 8 * h + c, cp, n, 0)] = p.hi;
+                    base[mfma_wpack_f16(0, 28, step, 8 * h + c, cp, n, 1)] = p.lo;
                 }
         }
     for (int n = 0; n < Cout; ++n) bpack[n] = b ? b[n] : 0.f;
@@ -604,7 +571,7 @@ extern "C" int32_t dcvc_conv_chan_partial_parts(int32_t ks, int32_t stride, int3
 }
 
 extern "C" int dcvc_conv2d(const dcvc_conv_args *a, void *stream) {
-    if (!a || a->nseg < 1 || a->nseg > DCVC_MAX_SEG || !a->out || !a->wpack || !a->bpack) return DCVC_E_ARG;
+    if (!conv_args_ok(a)) return DCVC_E_ARG;
     if (a->stride != 1 && a->stride != 2) return DCVC_E_ARG;
     if (a->precision != DCVC_PREC_FP32 && a->precision != DCVC_PREC_FP16X3) return DCVC_E_ARG;
     if (a->Cout_pad % 32 || a->Cout > a->Cout_pad || (a->pixel_shuffle && (a->Cout & 3))) return DCVC_E_ARG;
@@ -613,46 +580,13 @@ extern "C" int dcvc_conv2d(const dcvc_conv_args *a, void *stream) {
     if (a->out_act == 3 && (!a->res2 || a->res_gate || a->chan_partial || a->pixel_shuffle)) return DCVC_E_ARG;
     ConvK k;
     memset(&k, 0, sizeof(k));
-    for (int s = 0; s < a->nseg; ++s) {
-        if (!a->seg[s].ptr || (a->seg[s].cs & 3) || a->seg[s].cs < round_up(a->seg[s].C, 4) ||
-            ((uintptr_t)a->seg[s].ptr & 15))
-            return DCVC_E_ARG;
-        k.seg_ptr[s] = a->seg[s].ptr;
-        k.seg_C[s] = a->seg[s].C;
-        k.seg_cs[s] = a->seg[s].cs;
-    }
-    k.nseg = a->nseg;
+    copy_conv_args_full(k, a);
     k.Hin = a->Hin;
     k.Win = a->Win;
     const int pad = a->ks / 2;
     k.Hout = (a->Hin + 2 * pad - a->ks) / a->stride + 1;
     k.Wout = (a->Win + 2 * pad - a->ks) / a->stride + 1;
-    k.in_act = a->in_act;
-    k.in_slope = a->in_slope;
-    k.wpack = a->wpack;
-    k.bpack = a->bpack;
-    k.Cout = a->Cout;
-    k.Cout_pad = a->Cout_pad;
-    k.out = a->out;
-    k.out_cs = a->out_cs;
-    k.out_act = a->out_act;
-    k.out_slope = a->out_slope;
-    k.ps = a->pixel_shuffle;
-    k.res = a->res;
-    k.res_cs = a->res_cs;
-    k.res_gate = a->res_gate;
-    k.res2 = a->res2;
-    k.res2_cs = a->res2_cs;
-    k.status = a->status;
-    k.chan_partial = a->chan_partial;
-    k.ty0 = a->tile_rows > 0 ? a->tile_row0 : 0;
-    k.band_rows = a->tile_rows > 0 ? a->tile_rows : 0;
-    {
-        const int cfin = a->pixel_shuffle ? a->Cout / 4 : a->Cout;
-        auto al = [](const void *p, int cs) { return p == nullptr || ((((uintptr_t)p) & 15) == 0 && (cs & 3) == 0); };
-        k.vec_epi = (cfin % 4 == 0) && al(a->out, a->out_cs) && al(a->res, a->res_cs) && al(a->res2, a->res2_cs) &&
-                    (a->res_gate == nullptr || (((uintptr_t)a->res_gate) & 15) == 0);
-    }
+    k.vec_epi = vec_epilogue_ok(a);
     if (a->chan_partial && (!k.vec_epi || a->pixel_shuffle)) return DCVC_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     const bool wide = (a->Cout_pad % 64) == 0;

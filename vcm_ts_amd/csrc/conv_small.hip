@@ -21,16 +21,11 @@
 #include <string.h>
 
 #include "dcvc_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+#include "kernel_common.h"
 
 namespace {
 
-constexpr int KC = 16;
-constexpr float ACT_SCALE = 8.f, WGT_SCALE = 64.f, F16_MAX = 65504.f;
-constexpr float ACT_LIMIT = F16_MAX / ACT_SCALE;
+constexpr int KC = 16;  // channels per K chunk: the 32-deep K of the instruction carries hi and lo of 16 channels
 
 struct SmallK {
     const float *seg_ptr[DCVC_MAX_SEG];
@@ -50,8 +45,6 @@ struct SmallK {
     int res_cs;
     int *status;
 };
-
-__device__ __forceinline__ float act(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 template <int KS>
 __global__ __launch_bounds__(256, 3) void conv_small(const SmallK a) {
@@ -255,14 +248,11 @@ extern "C" int dcvc_conv_small_pack_weights(const float *w, const float *b, int3
                 for (int cc = 0; cc < KC && c0 + cc < seg_C[s]; ++cc)
                     for (int n = 0; n < Cout; ++n) {
                         float sv = w[((size_t)n * Cin + cin0 + c0 + cc) * T + t] * WGT_SCALE;
-                        if (!(sv <= F16_MAX && sv >= -F16_MAX)) {
-                            status = DCVC_E_RANGE;
-                            sv = sv > 0 ? F16_MAX : -F16_MAX;
-                        }
-                        const _Float16 hi = (_Float16)sv, lo = (_Float16)(sv - (float)hi);
+                        if (!(fabsf(sv) <= F16_MAX)) { status = DCVC_E_RANGE; sv = sv > 0.f ? F16_MAX : -F16_MAX; }  // reported; NaN -> -max
+                        const SplitF16 p = split_f16(sv);
                         const size_t blk = ((size_t)cg * T + t) * 4;
-                        base[((blk + (cc >> 3)) * 16 + n) * 8 + (cc & 7)] = hi;
-                        base[((blk + 2 + (cc >> 3)) * 16 + n) * 8 + (cc & 7)] = lo;
+                        base[((blk + (cc >> 3)) * 16 + n) * 8 + (cc & 7)] = p.hi;
+                        base[((blk + 2 + (cc >> 3)) * 16 + n) * 8 + (cc & 7)] = p.lo;
                     }
         cin0 += seg_C[s];
     }
@@ -272,33 +262,20 @@ extern "C" int dcvc_conv_small_pack_weights(const float *w, const float *b, int3
 // dcvc_conv_args as for dcvc_conv2d, restricted to: Cout <= 16, ks 3 or 7, stride 1, no pixel shuffle, no gate,
 // no second residual, no chan_partial; wpack / bpack from dcvc_conv_small_pack_weights; DCVC_PREC_FP16X3.
 extern "C" int dcvc_conv2d_small(const dcvc_conv_args *a, void *stream) {
-    if (a && (a->out_act < 0 || a->out_act > 2)) return DCVC_E_ARG;  // (the mask epilogue, out_act 3, is dcvc_conv2d's)
-    if (!a || a->nseg < 1 || a->nseg > DCVC_MAX_SEG || !a->out || !a->wpack || !a->bpack) return DCVC_E_ARG;
+    if (!conv_args_ok(a)) return DCVC_E_ARG;
+    if (a->out_act < 0 || a->out_act > 2) return DCVC_E_ARG;  // (the mask epilogue, out_act 3, is dcvc_conv2d's)
     if (a->tile_rows > 0) return DCVC_E_ARG;  // no banded launches for this kernel
     if (a->Cout <= 0 || a->Cout > 16 || (a->ks != 3 && a->ks != 7) || a->stride != 1 || a->pixel_shuffle || a->res_gate ||
         a->res2 || a->chan_partial || a->precision != DCVC_PREC_FP16X3 || a->N <= 0)
         return DCVC_E_ARG;
     SmallK k;
     memset(&k, 0, sizeof(k));
-    for (int s = 0; s < a->nseg; ++s) {
-        if (!a->seg[s].ptr || (a->seg[s].cs & 3) || a->seg[s].cs < ((a->seg[s].C + 3) & ~3) || ((uintptr_t)a->seg[s].ptr & 15))
-            return DCVC_E_ARG;
-        k.seg_ptr[s] = a->seg[s].ptr;
-        k.seg_C[s] = a->seg[s].C;
-        k.seg_cs[s] = a->seg[s].cs;
-    }
-    k.nseg = a->nseg;
+    copy_conv_args(k, a);
     k.H = a->Hin, k.W = a->Win;
-    k.in_act = a->in_act, k.in_slope = a->in_slope;
-    k.wpack = (const char *)a->wpack, k.bpack = a->bpack;
-    k.Cout = a->Cout;
-    k.out = a->out, k.out_cs = a->out_cs, k.out_act = a->out_act, k.out_slope = a->out_slope;
-    k.res = a->res, k.res_cs = a->res_cs;
-    k.status = a->status;
     dim3 grid((unsigned)((a->Win + 31) / 32), (unsigned)((a->Hin + 7) / 8), (unsigned)a->N);
     if (a->ks == 7)
         hipLaunchKernelGGL(conv_small<7>, grid, dim3(256), 0, (hipStream_t)stream, k);
     else
         hipLaunchKernelGGL(conv_small<3>, grid, dim3(256), 0, (hipStream_t)stream, k);
-    return hipGetLastError() == hipSuccess ? DCVC_OK : DCVC_E_LAUNCH;
+    RET_LAUNCH();
 }

@@ -15,13 +15,9 @@
 #include <stdint.h>
 
 #include "dcvc_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_common.h"
 
 namespace {
-
-#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? DCVC_OK : DCVC_E_LAUNCH
-inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 constexpr int RB = 1024;  // partial-sum blocks per sample for scalar reductions
 constexpr int MB = 2048;  // partial-sum blocks per sample for channel means

@@ -22,12 +22,11 @@
 
 #include "dcvc_hip.h"
 #include "dcvc_hip_metrics.h"
+#include "kernel_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? DCVC_OK : DCVC_E_LAUNCH
 
 constexpr int TAPS = 11, HALO = TAPS - 1, TILE = 32, IN = TILE + HALO, LEVELS = DCVC_MS_SSIM_LEVELS, THREADS = 256;
 constexpr int MAX_SIDE = 32768, MAX_PLANES = 65535;

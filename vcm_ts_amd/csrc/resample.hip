@@ -13,14 +13,9 @@
 #include <stdint.h>
 
 #include "dcvc_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_common.h"
 
 namespace {
-
-#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? DCVC_OK : DCVC_E_LAUNCH
-
-inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 // torch.linspace(-1, 1, n)[i] in fp32 (symmetric form used by ATen's CPU kernel)
 __device__ __forceinline__ float lin11(int i, int n) {

@@ -23,12 +23,11 @@
 
 #include "dcvc_hip.h"
 #include "dcvc_hip_scene.h"
+#include "kernel_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? DCVC_OK : DCVC_E_LAUNCH
 
 constexpr int TILE_W = 256, TILE_H = 8, GRID = DCVC_SCENE_GRID, BINS = DCVC_SCENE_BINS;
 
