@@ -211,6 +211,15 @@ int dcvc_se_gate(const float *mean, const float *w1, const float *w2, float *gat
 /* out = src / q  (mode 0) or src * q (mode 1);  q = max(q_basic[c], 0.5) * q_scale[n] */
 int dcvc_scale_channels(const float *src, int32_t src_cs, float *out, int32_t out_cs, const float *q_basic,
                         const float *q_scale, int32_t mode, int32_t N, int32_t HW, int32_t C, void *stream);
+/* The same with a per-cell factor on the step (ROI-weighted quantisation, include/dcvc_hip_roi.h "Q-scale map"): H x W is
+ * the latent grid, H * W == HW, and q_map holds N * HW floats, one per latent cell in (n, y, x) order.
+ *   q = (max(q_basic[c], 0.5) * q_scale[n]) * q_map[(n * H + y) * W + x]
+ * -- one more correctly rounded fp32 multiply, in that order.  q_map == NULL is dcvc_scale_channels itself: the same
+ * kernel, the expression above it, no multiply (so a map of 1.0f gives the bits of no map).  Also refused: H or W <= 0,
+ * H * W != HW. */
+int dcvc_scale_channels_map(const float *src, int32_t src_cs, float *out, int32_t out_cs, const float *q_basic,
+                            const float *q_scale, int32_t mode, int32_t N, int32_t HW, int32_t C, const float *q_map,
+                            int32_t H, int32_t W, void *stream);
 /* z_hat = rint(z) (half to even); sym (optional): int32 in (n, c, y, x) order */
 int dcvc_round_symbols(const float *z, int32_t z_cs, float *z_hat, int32_t zh_cs, int32_t *sym, int32_t N,
                        int32_t H, int32_t W, int32_t C, void *stream);
@@ -246,6 +255,10 @@ typedef struct {
                               round(y / q_step - mean) at the positions of this step -- "teacher forcing" with symbol
                               planes recorded from the reference, so that a parity test is not derailed by a value
                               that sits on a rounding tie (tests/test_gpu_backward.py, forced-symbol replay) */
+    const float *q_map;    /* NULL (every caller that does not know it), or (N,H,W) floats, one per latent cell: the step
+                              of `out` becomes (max(q_basic[c], 0.5) * q_scale[n]) * q_map[(n * H + y) * W + x], one more
+                              correctly rounded fp32 multiply in that order (dcvc_scale_channels_map).  Read only where
+                              step == 1 writes `out`, by enc and dec_apply; NULL is the expression without the multiply */
 } dcvc_dual_prior_args;
 
 /* GaussianEncoder.build_indexes (entropy_models.py:264-268) on a flat array, bit-exact through idx_edges. */

@@ -1,5 +1,6 @@
 /* dcvc_hip_roi.h -- the region-of-interest enhancement layer around the codec: residual picture inside boxes, fusion of
- * a decoded residual through a feathered mask, squared error inside and outside the boxes.
+ * a decoded residual through a feathered mask, squared error inside and outside the boxes -- and the per-cell q-scale
+ * map that lets the base layer itself quantise finer inside the boxes (ROI-weighted quantisation).
  *
  * Conventions of dcvc_hip_color.h: raw device pointers, a hipStream_t passed as void*, 0 or a negative DCVC_E_* code,
  * nothing launched (and nothing dereferenced) on a bad argument.  Float pictures are PLANAR fp32 with explicit strides
@@ -50,6 +51,23 @@
  *   shrinks to nothing is empty.  ADDS three unsigned 64-bit integers to sums[0..2]: the sum over the 3 channels of
  *   (code(a) - code(b))^2 inside the mask, the same outside, and the number of PIXELS inside (a pixel in several
  *   boxes counts once).  The caller zeroes them.  Integer sums: exact and order-independent.
+ *
+ * Q-scale map  (ROI-weighted quantisation of the latent y; used by dcvc_scale_channels_map and by the q_map member of
+ *   dcvc_dual_prior_args, include/dcvc_hip.h)
+ *   Latent grid: DCVC_ROI_CELL = 16.  For a picture of H x W pixels, Hp x Wp is the size padded to multiples of 64 (as
+ *   the codec pads pictures); the grid is hc = Hp / 16 rows by wc = Wp / 16 columns, and cell (i, j) covers pixel rows
+ *   [16 i, 16 i + 16) and columns [16 j, 16 j + 16).
+ *   Factors: an integer k of hundredths, 10 <= k <= 1000, stands for f = (float) k / 100.0f as the HOST's IEEE division
+ *   gives it; the device never computes a factor.  factors[0] is the background's, factors[1 + c] class c's.
+ *   Map: a non-empty box is grown by `grow` pixels, 0 <= grow <= 255, and clipped to the picture:
+ *     x1' = max(x1 - grow, 0), x2' = min(x2 + grow, W), y1' = max(y1 - grow, 0), y2' = min(y2 + grow, H).
+ *   The grown box TOUCHES cell (i, j) iff  x1' < 16 j + 16 && x2' > 16 j && y1' < 16 i + 16 && y2' > 16 i.
+ *   map[i * wc + j] = the minimum of factors[1 + cls] over the boxes that touch the cell, factors[0] where none does:
+ *   independent of list order.  Cells that lie wholly in the padding get factors[0] (a clipped box ends at W, H).
+ *   Use: wherever the codec forms the step of the latent y, cq = max(q_basic[c], 0.5) * q_scale[n], the step becomes
+ *   cq * map[cell] -- one more correctly rounded fp32 multiply, in that order.  It applies to the y of an I picture and
+ *   to the y of a P picture; mv_y keeps its scalar.  No map means exactly the expression without the multiply, so a
+ *   map of 1.0f gives the same bits as no map.
  */
 #ifndef DCVC_HIP_ROI_H
 #define DCVC_HIP_ROI_H
@@ -64,6 +82,8 @@ extern "C" {
 #define DCVC_ROI_MAX_BOXES 1024
 #define DCVC_ROI_MAX_CLASSES 4
 #define DCVC_ROI_MAX_BORDER 64
+#define DCVC_ROI_CELL 16
+#define DCVC_ROI_MAX_GROW 255
 
 typedef struct {
     int32_t x1, y1, x2, y2, cls;
@@ -98,6 +118,14 @@ int dcvc_roi_sse(const float *a, int32_t a_row_stride, int64_t a_plane_stride, c
                  int64_t b_plane_stride, int32_t H, int32_t W, const dcvc_roi_box_t *boxes_host,
                  const dcvc_roi_box_t *boxes_dev, int32_t n, const dcvc_roi_class_t *classes, int32_t n_classes,
                  uint64_t *sums, void *stream);
+
+/* The q-scale map above: writes exactly hc * wc floats to `map` (DEVICE), hc = 4 * ceil(H / 64), wc = 4 * ceil(W / 64).
+ * One launch on `stream`, nothing synchronised.  factors: HOST pointer to 1 + n_classes floats, read before the launch.
+ * Refused: NULL factors or map; H or W not in 1 .. DCVC_ROI_MAX_SIDE; grow outside 0 .. DCVC_ROI_MAX_GROW; n_classes
+ * outside 0 .. DCVC_ROI_MAX_CLASSES; a factor that is not finite or not in [0.1, 10]; and what dcvc_roi_residual refuses
+ * about boxes (n, NULL lists with n > 0, coordinates), with cls outside 0 .. n_classes - 1. */
+int dcvc_roi_qmap(int32_t H, int32_t W, const dcvc_roi_box_t *boxes_host, const dcvc_roi_box_t *boxes_dev, int32_t n,
+                  int32_t grow, const float *factors, int32_t n_classes, float *map, void *stream);
 
 #ifdef __cplusplus
 }

@@ -131,14 +131,15 @@ __global__ void se_gate_kernel(const float *__restrict__ mean, const float *__re
 
 // ---- quantisation --------------------------------------------------------------------------
 __global__ void scale_channels_kernel(const float *__restrict__ src, int src_cs, float *__restrict__ out, int out_cs,
-                                      const float *__restrict__ q_basic, const float *__restrict__ q_scale, int mode,
-                                      int64_t HW, int C, int64_t total) {
+                                      const float *__restrict__ q_basic, const float *__restrict__ q_scale,
+                                      const float *__restrict__ q_map, int mode, int64_t HW, int C, int64_t total) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= total) return;
     const int c = (int)(gid % C);
-    const int64_t pix = gid / C;
+    const int64_t pix = gid / C;  // (n * H + y) * W + x: the cell of q_map
     const int n = (int)(pix / HW);
-    const float q = fmaxf(q_basic[c], 0.5f) * q_scale[n];
+    float q = fmaxf(q_basic[c], 0.5f) * q_scale[n];
+    if (q_map) q = q * q_map[pix];
     const float v = src[pix * src_cs + c];
     out[pix * out_cs + c] = mode ? v * q : v / q;
 }
@@ -262,7 +263,8 @@ __global__ void dual_prior_kernel(const dcvc_dual_prior_args a, int64_t total) {
             pr[3 * C + c] = qs;
         }
     } else {
-        const float cq = fmaxf(a.q_basic[c], 0.5f) * a.q_scale[n];
+        float cq = fmaxf(a.q_basic[c], 0.5f) * a.q_scale[n];
+        if (a.q_map) cq = cq * a.q_map[pix];  // pix == (n * H + y) * W + x
         a.out[pix * a.out_cs + c] = (hat * qs) * cq;
     }
 }
@@ -489,7 +491,18 @@ extern "C" int dcvc_scale_channels(const float *src, int32_t src_cs, float *out,
     if (!src || !out || !q_basic || !q_scale || N <= 0 || HW <= 0 || C <= 0 || src_cs < C || out_cs < C) return DCVC_E_ARG;
     const int64_t total = (int64_t)N * HW * C;
     hipLaunchKernelGGL(scale_channels_kernel, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)stream, src, src_cs, out,
-                       out_cs, q_basic, q_scale, mode, (int64_t)HW, C, total);
+                       out_cs, q_basic, q_scale, (const float *)nullptr, mode, (int64_t)HW, C, total);
+    RET_LAUNCH();
+}
+
+extern "C" int dcvc_scale_channels_map(const float *src, int32_t src_cs, float *out, int32_t out_cs, const float *q_basic,
+                                       const float *q_scale, int32_t mode, int32_t N, int32_t HW, int32_t C,
+                                       const float *q_map, int32_t H, int32_t W, void *stream) {
+    if (!src || !out || !q_basic || !q_scale || N <= 0 || HW <= 0 || C <= 0 || src_cs < C || out_cs < C) return DCVC_E_ARG;
+    if (H <= 0 || W <= 0 || (int64_t)H * W != HW) return DCVC_E_ARG;
+    const int64_t total = (int64_t)N * HW * C;
+    hipLaunchKernelGGL(scale_channels_kernel, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)stream, src, src_cs, out,
+                       out_cs, q_basic, q_scale, q_map, mode, (int64_t)HW, C, total);
     RET_LAUNCH();
 }
 

@@ -264,6 +264,46 @@ __global__ __launch_bounds__(256) void roi_kernel(const RoiArgs p) {
     }
 }
 
+// The q-scale map (header: "Q-scale map").  One lane per cell of the latent grid; a workgroup first puts the whole list
+// into LDS as grown, clipped boxes with their class factor (empty boxes become boxes that touch nothing), then every cell
+// walks it.  At 1080p that is 8160 cells in 32 workgroups against at most 1024 boxes.  Like the kernels above it
+// addresses nothing through a box.
+struct QmapArgs {
+    const dcvc_roi_box_t *boxes;
+    float *map;
+    int32_t H, W, hc, wc, n, grow;
+    float f[1 + DCVC_ROI_MAX_CLASSES];
+};
+
+__global__ __launch_bounds__(256) void roi_qmap_kernel(const QmapArgs p) {
+    __shared__ int4 box[DCVC_ROI_MAX_BOXES];
+    __shared__ float fac[DCVC_ROI_MAX_BOXES];
+    const int n = min(p.n, DCVC_ROI_MAX_BOXES);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const dcvc_roi_box_t rec = p.boxes[i];
+        int4 bx = make_int4(0, 0, 0, 0);  // touches no cell
+        if (rec.x2 > rec.x1 && rec.y2 > rec.y1)  // (max / min before the sum: no overflow whatever the record holds)
+            bx = make_int4(max(rec.x1, p.grow) - p.grow, max(rec.y1, p.grow) - p.grow, min(rec.x2, p.W - p.grow) + p.grow,
+                           min(rec.y2, p.H - p.grow) + p.grow);
+        box[i] = bx;
+        fac[i] = p.f[1 + (rec.cls & (DCVC_ROI_MAX_CLASSES - 1))];
+    }
+    __syncthreads();
+    const int cell = blockIdx.x * blockDim.x + threadIdx.x;
+    if (cell >= p.hc * p.wc) return;
+    const int x0 = (cell % p.wc) * DCVC_ROI_CELL, y0 = (cell / p.wc) * DCVC_ROI_CELL;
+    float v = p.f[0];
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        const int4 bx = box[i];
+        if (bx.x < x0 + DCVC_ROI_CELL && bx.z > x0 && bx.y < y0 + DCVC_ROI_CELL && bx.w > y0) {
+            v = any ? fminf(v, fac[i]) : fac[i];
+            any = true;
+        }
+    }
+    p.map[cell] = v;
+}
+
 bool aligned(const void *p, size_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
 
 bool size_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && H <= DCVC_ROI_MAX_SIDE && W <= DCVC_ROI_MAX_SIDE; }
@@ -366,4 +406,22 @@ extern "C" int dcvc_roi_sse(const float *pa, int32_t a_row_stride, int64_t a_pla
     a.boxes = boxes_dev, a.n = n, a.H = H, a.W = W;
     set_classes(&a, classes, n_classes);
     return launch<SSE>(a, stream);
+}
+
+extern "C" int dcvc_roi_qmap(int32_t H, int32_t W, const dcvc_roi_box_t *boxes_host, const dcvc_roi_box_t *boxes_dev, int32_t n,
+                             int32_t grow, const float *factors, int32_t n_classes, float *map, void *stream) {
+    if (!size_ok(H, W) || !factors || !map || grow < 0 || grow > DCVC_ROI_MAX_GROW || n_classes < 0 ||
+        n_classes > DCVC_ROI_MAX_CLASSES || !boxes_ok(boxes_host, boxes_dev, n, H, W, n_classes))
+        return DCVC_E_ARG;
+    QmapArgs a{};
+    for (int32_t c = 0; c <= DCVC_ROI_MAX_CLASSES; ++c) {
+        const float f = factors[c <= n_classes ? c : 0];  // (a class no validated box names: the background's)
+        if (!(f >= 0.1f && f <= 10.0f)) return DCVC_E_ARG;  // (false for a NaN too)
+        a.f[c] = f;
+    }
+    a.boxes = boxes_dev, a.map = map, a.H = H, a.W = W, a.n = n, a.grow = grow;
+    a.hc = 4 * ((H + 63) / 64), a.wc = 4 * ((W + 63) / 64);
+    const int cells = a.hc * a.wc;  // (at most 2048 * 2048)
+    roi_qmap_kernel<<<dim3((cells + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(a);
+    RET_LAUNCH();
 }

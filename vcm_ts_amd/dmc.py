@@ -228,6 +228,28 @@ class CodecBase(nn.Module):
             return q.contiguous()
         return torch.full((N,), float(q), dtype=torch.float32, device=self.device)
 
+    def _qmap(self, q_map, N, H, W, graph=False):
+        """The q_map argument of compress() / decompress() -- ROI-weighted quantisation of the latent y (roi.q_map,
+        include/dcvc_hip_roi.h): None, or a float32 tensor on this codec's device of one factor per 16x16 cell of the padded
+        H x W picture, shaped (hc, wc), (1, 1, hc, wc) or (N, 1, hc, wc) -> the contiguous (N * hc * wc) tensor the kernels
+        read.  Refused by name: anything else, a map with graph replay, a map in .train() mode."""
+        if q_map is None:
+            return None
+        if graph:
+            raise NotImplementedError("q_map: graph replay with a q-scale map is not supported (pass graph=False)")
+        if self.training:
+            raise ValueError("q_map: a q-scale map is for .eval() mode (training with a map is not supported)")
+        hc, wc = H // 16, W // 16
+        if not torch.is_tensor(q_map) or q_map.dtype != torch.float32:
+            raise ValueError(f"q_map: expected a float32 tensor, got {getattr(q_map, 'dtype', type(q_map).__name__)}")
+        if q_map.device != self.device:
+            raise ValueError(f"q_map: on {q_map.device}, the codec is on {self.device}")
+        if tuple(q_map.shape) not in ((hc, wc), (1, 1, hc, wc), (N, 1, hc, wc)):
+            raise ValueError(f"q_map: expected shape ({hc}, {wc}), (1, 1, {hc}, {wc}) or ({N}, 1, {hc}, {wc}) for a padded "
+                             f"{W}x{H} picture, got {tuple(q_map.shape)}")
+        m = q_map.detach().reshape(-1, hc * wc)
+        return (m.expand(N, -1) if m.shape[0] != N else m).contiguous().view(-1)
+
     def _frame_in(self, name, x, cs=None) -> View:
         e = self.engine()
         N, C_, H, W = x.shape
@@ -468,7 +490,7 @@ class CodecBase(nn.Module):
 
     # -- dual prior (both directions) -----------------------------------------------------
     def _dual_prior_encode(self, tag, y: View, fusion: View, prior_name, out: View, q_basic, q_scale, want_stats,
-                           want_symbols, want_res=False, qkey=None):
+                           want_symbols, want_res=False, qkey=None, q_map=None):
         """forward_dual_prior (common_model.py:104-177): returns dict with y_q / scales_hat
         (dense NHWC planes for the bit estimate) and the two (sym, idx) int32 pairs."""
         e, net = self.engine(), self._net
@@ -497,12 +519,12 @@ class CodecBase(nn.Module):
         e.dual_prior("enc", 0, sym=sym[0], idx=idx[0], **common)
         spatial = net.three_convs(prior_name, params)
         e.dual_prior("enc", 1, spatial=spatial, sym=sym[1], idx=idx[1], out=out, q_basic=q_basic, q_scale=q_scale,
-                     **common)
+                     q_map=q_map, **common)
         r["sym"], r["idx"] = sym, idx
         r["params"], r["spatial"] = params, spatial  # (views, for gradient diagnostics)
         return r
 
-    def _dual_prior_decode(self, tag, fusion: View, prior_name, out: View, q_basic, q_scale):
+    def _dual_prior_decode(self, tag, fusion: View, prior_name, out: View, q_basic, q_scale, q_map=None):
         """decompress_dual_prior (common_model.py:182-217): two rANS decodes with the spatial
         prior in between; everything else stays on the device."""
         e, net = self.engine(), self._net
@@ -519,7 +541,8 @@ class CodecBase(nn.Module):
         spatial = net.three_convs(prior_name, params)
         e.dual_prior("dec_index", 1, spatial=spatial, idx=idx, **common)
         sym = self._decode_scale(idx)
-        e.dual_prior("dec_apply", 1, spatial=spatial, sym=sym, out=out, q_basic=q_basic, q_scale=q_scale, **common)
+        e.dual_prior("dec_apply", 1, spatial=spatial, sym=sym, out=out, q_basic=q_basic, q_scale=q_scale, q_map=q_map,
+                     **common)
         return out
 
 
@@ -753,14 +776,16 @@ class DMC(CodecBase):
     def _views_of_dpb(self, dpb):
         return {k: self._dpb_in(k, dpb.get(k)) for k in DPB_KEYS}
 
-    def _run(self, x, dpb, mv_y_q_scale, y_q_scale, mode, tape=None):
+    def _run(self, x, dpb, mv_y_q_scale, y_q_scale, mode, tape=None, q_map=None):
         """mode 'estimate' (forward_one_frame, unclamped recon as video_model.py:535) or
         'compress' (recon clamped to [0, 1] exactly as the decoder will, :413, so that the
-        encoder's own DPB is bit-identical to the decoder's and no decode pass is needed)."""
+        encoder's own DPB is bit-identical to the decoder's and no decode pass is needed).
+        q_map: see compress() -- the step of y only, mv_y keeps its scalar."""
         e = self.engine()
         net = self._net
         N, _, H, W = x.shape
         assert H % 64 == 0 and W % 64 == 0, "pad to a multiple of 64 first (stream.get_padding_size)"
+        q_map = self._qmap(q_map, N, H, W)
         q_mv = self._qvec(mv_y_q_scale, N, "mv_y_q_scale")
         q_y = self._qvec(y_q_scale, N, "y_q_scale")
         dv = self._views_of_dpb(dpb)
@@ -796,7 +821,8 @@ class DMC(CodecBase):
         c1, c2, c3, warp_frame = net.motion_compensation(dv["ref_frame"], dv["ref_feature"], mv_hat, enc_cat2, enc_cat3,
                                                          want_warp_frame=(mode != "compress"), pyramid=pyr)
         y_raw = net.contextual_encoder(x3, c1, enc_cat2, enc_cat3)
-        y = e.scale_channels(y_raw, net.buf("y", like=y_raw, C=96), self.P("y_q_basic").reshape(-1), q_y, qkey="y")
+        y = e.scale_channels(y_raw, net.buf("y", like=y_raw, C=96), self.P("y_q_basic").reshape(-1), q_y, qkey="y",
+                             q_map=q_map)
         n_ = "contextual_hyper_prior_encoder"
         t = net.conv(f"{n_}.0", y, out_slope=0.01)
         t = net.conv(f"{n_}.2", t, stride=2, out_slope=0.01)
@@ -810,7 +836,7 @@ class DMC(CodecBase):
         y_hat = net.buf(f"dpb{k}.ref_y", like=y, C=96)
         r_y = self._dual_prior_encode("y", y, fusion, "y_spatial_prior", y_hat, self.P("y_q_basic").reshape(-1), q_y,
                                       want_stats=(mode != "compress"), want_symbols=(mode == "compress"),
-                                      want_res=(mode == "train"), qkey="y")
+                                      want_res=(mode == "train"), qkey="y", q_map=q_map)
         dec_feature = net.contextual_decoder(y_hat, c2, c3)
         feature = net.buf(f"dpb{k}.ref_feature", N=N, H=H, W=W, C=64)
         recon = net.buf(f"dpb{k}.ref_frame", N=N, H=H, W=W, C=3)
@@ -990,23 +1016,27 @@ class DMC(CodecBase):
                 ("scale", o["r_y"]["sym"][1], o["r_y"]["idx"][1], None)]
 
     @torch.no_grad()
-    def compress(self, x, dpb, mv_y_q_scale, y_q_scale, defer=False, coder="host", graph=False, check_range=True):
+    def compress(self, x, dpb, mv_y_q_scale, y_q_scale, defer=False, coder="host", graph=False, check_range=True,
+                 q_map=None):
         """defer=True returns {"dpb", "pending"}: call pending.finish() later for the bytes.
         check_range: a call that returns bytes (defer=False) raises lib.KernelError if a split-fp16 kernel met an
         activation beyond +-8188 (one status read after the picture is done); pipelined callers (defer=True, or
         check_range=False) read Engine.check_status() / status_snapshot() themselves, as GopEncoder does per GOP.
         coder="device": opt-in lane-interleaved GPU coder (include/dcvc_hip_rans.h, its own format).
         graph=True: replay the picture's launches as a captured hipGraph (host coder, batch 1, float
-        q-scales): pays when the picture is small enough for the host enqueue to be the bottleneck."""
+        q-scales): pays when the picture is small enough for the host enqueue to be the bottleneck.
+        q_map: ROI-weighted quantisation (roi.q_map; CodecBase._qmap says what is taken): one factor per 16x16 cell on the
+        quantisation step of y.  decompress() needs the same map.  None: exactly the launches and bytes without it."""
         if self.entropy_coder is None:
             raise RuntimeError("call update() before compress()/decompress()")
+        self._qmap(q_map, x.shape[0], x.shape[2], x.shape[3], graph=graph)  # (every refusal, before any GPU work)
         if graph:
             if coder != "host":
                 raise NotImplementedError("graph replay is wired to the host coder")
             g = self._compress_graph(x, dpb, mv_y_q_scale, y_q_scale)
             d, o, pending = g["out"], g["views"], g["pending"]
         else:
-            o = self._run(x, dpb, mv_y_q_scale, y_q_scale, "compress")
+            o = self._run(x, dpb, mv_y_q_scale, y_q_scale, "compress", q_map=q_map)
             # N > 1: a batch of rate points, one independent stream per element ("bit_streams")
             pending = self._stage(self._planes(o), o["N"], coder)
             d = self._dpb_out(o)
@@ -1014,25 +1044,27 @@ class DMC(CodecBase):
 
     @torch.no_grad()
     def decompress(self, dpb, string, height, width, mv_y_q_scale, y_q_scale, coder=None, defer_check=False,
-                   check_range=True):
+                   check_range=True, q_map=None):
         """coder: "host" (reference format), "device" (payloads of compress(coder="device")) or None =
         tell them apart by the device format's magic.  defer_check (device format only): do not
-        synchronise to read the kernels' status word; the caller calls device_coder().check() later."""
+        synchronise to read the kernels' status word; the caller calls device_coder().check() later.
+        q_map: the map compress() was given (the stream does not carry it)."""
         return self._decompress_guarded(string, coder, defer_check, check_range,
-                                        dpb, string, height, width, mv_y_q_scale, y_q_scale)
+                                        dpb, string, height, width, mv_y_q_scale, y_q_scale, q_map)
 
-    def _decompress(self, dpb, string, height, width, mv_y_q_scale, y_q_scale):
+    def _decompress(self, dpb, string, height, width, mv_y_q_scale, y_q_scale, q_map=None):
         e = self.engine()
         net = self._net
         N = 1
         q_mv = self._qvec(mv_y_q_scale, N, "mv_y_q_scale")
         q_y = self._qvec(y_q_scale, N, "y_q_scale")
+        zh, zw = S.get_downsampled_shape(height, width, 64)
+        H, W = zh * 64, zw * 64
+        q_map = self._qmap(q_map, N, H, W)
         dv = self._views_of_dpb(dpb)
         k = self._out_set(*dv.values())
         self._open_stream(string)
         pyr, pyr_done = self._fork_pyramid(net, dv, None)
-        zh, zw = S.get_downsampled_shape(height, width, 64)
-        H, W = zh * 64, zw * 64
         sym = self._decode_factorized("bit_estimator_z_mv", N, 64, zh, zw)
         mv_z_hat = e.symbols_to_nhwc(sym, net.buf("mv_z_hat", N=N, H=zh, W=zw, C=64))
         mv_y_hat, _ = self._mv_side(net, dv, None, mv_z_hat, N, q_mv, k, "decode", decode=True)
@@ -1046,7 +1078,7 @@ class DMC(CodecBase):
         z_hat = e.symbols_to_nhwc(sym, net.buf("z_hat", N=N, H=zh, W=zw, C=64))
         fusion = self._y_prior(net, dv, c3, z_hat)
         y_hat = net.buf(f"dpb{k}.ref_y", N=N, H=H // 16, W=W // 16, C=96)
-        self._dual_prior_decode("y", fusion, "y_spatial_prior", y_hat, self.P("y_q_basic").reshape(-1), q_y)
+        self._dual_prior_decode("y", fusion, "y_spatial_prior", y_hat, self.P("y_q_basic").reshape(-1), q_y, q_map=q_map)
         dec_feature = net.contextual_decoder(y_hat, c2, c3)
         feature = net.buf(f"dpb{k}.ref_feature", N=N, H=H, W=W, C=64)
         recon = net.buf(f"dpb{k}.ref_frame", N=N, H=H, W=W, C=3)

@@ -624,9 +624,16 @@ class Engine:
         return gate
 
     # ------------------------------------------------------------------ entropy-model elementwise
-    def scale_channels(self, src: View, out: View, q_basic, q_scale, multiply=False, qkey=None):
-        lib.check(self.L.dcvc_scale_channels(src.ptr, src.cs, out.ptr, out.cs, q_basic.data_ptr(), q_scale.data_ptr(),
-                                             int(multiply), src.N, src.HW, src.C, self.stream()), "scale_channels")
+    def scale_channels(self, src: View, out: View, q_basic, q_scale, multiply=False, qkey=None, q_map=None):
+        """q_map: None, or the (N * H * W) per-cell factors of ROI-weighted quantisation (include/dcvc_hip_roi.h)."""
+        if q_map is None:
+            lib.check(self.L.dcvc_scale_channels(src.ptr, src.cs, out.ptr, out.cs, q_basic.data_ptr(), q_scale.data_ptr(),
+                                                 int(multiply), src.N, src.HW, src.C, self.stream()), "scale_channels")
+        else:
+            assert q_map.numel() == src.N * src.HW and self.tape is None
+            lib.check(self.L.dcvc_scale_channels_map(src.ptr, src.cs, out.ptr, out.cs, q_basic.data_ptr(), q_scale.data_ptr(),
+                                                     int(multiply), src.N, src.HW, src.C, q_map.data_ptr(), src.H, src.W,
+                                                     self.stream()), "scale_channels_map")
         self.calls += 1
         self._rec("scale_channels", src, out, q_basic, q_scale, multiply, qkey)
         return out
@@ -647,7 +654,7 @@ class Engine:
 
     def dual_prior(self, mode, step, *, y: View = None, fusion: View, spatial: View = None, params: View,
                    y_hat: torch.Tensor, y_q=None, y_res=None, scales_hat=None, sym=None, idx=None, out: View = None,
-                   q_basic=None, q_scale=None, distribution="laplace", qkey=None, forced_q=None):
+                   q_basic=None, q_scale=None, distribution="laplace", qkey=None, forced_q=None, q_map=None):
         a = lib.DualPriorArgs()
         Cc = fusion.C // 3
         if y is not None:
@@ -658,7 +665,7 @@ class Engine:
         a.params, a.params_cs = params.ptr, params.cs
         a.y_hat = y_hat.data_ptr()
         for nm, t in (("y_q", y_q), ("y_res", y_res), ("scales_hat", scales_hat), ("sym", sym), ("idx", idx),
-                      ("q_basic", q_basic), ("q_scale", q_scale), ("forced_q", forced_q)):
+                      ("q_basic", q_basic), ("q_scale", q_scale), ("forced_q", forced_q), ("q_map", q_map)):
             if t is not None:
                 setattr(a, nm, t.data_ptr())
         if out is not None:

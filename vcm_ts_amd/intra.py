@@ -75,19 +75,21 @@ class IntraNoAR(CodecBase):
         """image_model.py:50-52: max(q_basic, 0.5) * q_scale."""
         return torch.clamp_min(self.P("q_basic"), 0.5) * q_scale
 
-    def _run(self, x, q_scale, mode, tape=None):
-        """mode 'estimate' / 'compress' / 'train' (a recorded forward: straight-through rounding, y_res kept)."""
+    def _run(self, x, q_scale, mode, tape=None, q_map=None):
+        """mode 'estimate' / 'compress' / 'train' (a recorded forward: straight-through rounding, y_res kept).
+        q_map: see compress()."""
         e = self.engine()
         net = self._net
         Nb, _, H, W = x.shape
         assert H % 64 == 0 and W % 64 == 0, "pad to a multiple of 64 first (stream.get_padding_size)"
+        q_map = self._qmap(q_map, Nb, H, W)
         q = self._qvec(q_scale, Nb, "q_scale")
         qb = self.P("q_basic").reshape(-1)
         x3 = self._frame_in("x", x)
         if tape is not None:
             tape.mark_const(x3)  # the picture carries no gradient
         y_raw = net.encoder_stack("enc", x3)
-        y = e.scale_channels(y_raw, net.buf("y", like=y_raw, C=self.N), qb, q, qkey="y")
+        y = e.scale_channels(y_raw, net.buf("y", like=y_raw, C=self.N), qb, q, qkey="y", q_map=q_map)
         z = net.hyper_enc5("hyper_enc", y)
         z_hat = net.buf("z_hat", like=z, C=self.N)
         sym_z = e.ibuf("intra/sym_z", Nb * self.N * z.HW) if mode == "compress" else None
@@ -96,7 +98,8 @@ class IntraNoAR(CodecBase):
         fusion = net.three_convs("y_prior_fusion", net.hyper_dec("hyper_dec", z_hat))
         y_hat = net.buf("y_hat", like=y, C=self.N)
         r = self._dual_prior_encode("y", y, fusion, "y_spatial_prior", y_hat, qb, q, want_stats=(mode != "compress"),
-                                    want_symbols=(mode == "compress"), want_res=(mode == "train"), qkey="y")
+                                    want_symbols=(mode == "compress"), want_res=(mode == "train"), qkey="y",
+                                    q_map=q_map)
         x_hat = self._synthesis(net, y_hat, Nb, H, W, clamp=(mode == "compress"))  # compress == decoder output
         return dict(N=Nb, H=H, W=W, x3=x3, y=y, z=z, z_hat=z_hat, sym_z=sym_z, r=r, x_hat=x_hat, y_hat=y_hat)
 
@@ -152,10 +155,12 @@ class IntraNoAR(CodecBase):
         return self._ssim_keys(res, x, res["x_hat"]) if self.report_ssim else res
 
     @torch.no_grad()
-    def compress(self, x, q_scale, defer=False, coder="host", check_range=True):
+    def compress(self, x, q_scale, defer=False, coder="host", check_range=True, q_map=None):
+        """q_map: ROI-weighted quantisation (roi.q_map; CodecBase._qmap says what is taken): one factor per 16x16 cell on the
+        quantisation step of y.  decompress() needs the same map.  None: exactly the launches and bytes without it."""
         if self.entropy_coder is None:
             raise RuntimeError("call update() before compress()/decompress()")
-        o = self._run(x, q_scale, "compress")
+        o = self._run(x, q_scale, "compress", q_map=q_map)
         N = o["N"]  # N > 1: a batch of rate points (one q-scale per element), one independent stream each
         zs = o["z_hat"]
         pending = self._stage([  # image_model.py:168-171
@@ -166,20 +171,23 @@ class IntraNoAR(CodecBase):
         return self._compress_result({"x_hat": o["x_hat"].nchw(), "_views": o}, pending, defer, check_range)
 
     @torch.no_grad()
-    def decompress(self, bit_stream, height, width, q_scale, coder=None, defer_check=False, check_range=True):
-        return self._decompress_guarded(bit_stream, coder, defer_check, check_range, bit_stream, height, width, q_scale)
+    def decompress(self, bit_stream, height, width, q_scale, coder=None, defer_check=False, check_range=True, q_map=None):
+        """q_map: the map compress() was given (the stream does not carry it)."""
+        return self._decompress_guarded(bit_stream, coder, defer_check, check_range, bit_stream, height, width, q_scale,
+                                        q_map)
 
-    def _decompress(self, bit_stream, height, width, q_scale):
+    def _decompress(self, bit_stream, height, width, q_scale, q_map=None):
         e = self.engine()
         net = self._net
         q = self._qvec(q_scale, 1, "q_scale")
-        self._open_stream(bit_stream)
         zh, zw = S.get_downsampled_shape(height, width, 64)
+        q_map = self._qmap(q_map, 1, zh * 64, zw * 64)
+        self._open_stream(bit_stream)
         sym = self._decode_factorized("bit_estimator_z", 1, self.N, zh, zw)
         z_hat = e.symbols_to_nhwc(sym, net.buf("z_hat", N=1, H=zh, W=zw, C=self.N))
         fusion = net.three_convs("y_prior_fusion", net.hyper_dec("hyper_dec", z_hat))
         y_hat = net.buf("y_hat", N=1, H=zh * 4, W=zw * 4, C=self.N)
-        self._dual_prior_decode("y", fusion, "y_spatial_prior", y_hat, self.P("q_basic").reshape(-1), q)
+        self._dual_prior_decode("y", fusion, "y_spatial_prior", y_hat, self.P("q_basic").reshape(-1), q, q_map=q_map)
         x_hat = self._synthesis(net, y_hat, 1, zh * 64, zw * 64, clamp=self._clamp_decoded)  # .clamp_(0, 1), :199
         self._close_stream()
         return {"x_hat": x_hat.nchw()}

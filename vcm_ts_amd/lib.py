@@ -82,6 +82,7 @@ class DualPriorArgs(C.Structure):
         ("sym", C.c_void_p), ("idx", C.c_void_p), ("out", C.c_void_p), ("out_cs", C.c_int32),
         ("q_basic", C.c_void_p), ("q_scale", C.c_void_p), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
         ("C", C.c_int32), ("step", C.c_int32), ("idx_edges", C.c_void_p), ("forced_q", C.c_void_p),
+        ("q_map", C.c_void_p),
     ]
 
 
@@ -166,6 +167,7 @@ _SIGS = {
     "dcvc_se_gate": [vp, vp, vp, vp, i32, i32, i32, vp],
     "dcvc_channel_mean_finish": [vp, i32, i32, vp, i32, i32, i32, vp],
     "dcvc_scale_channels": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp],
+    "dcvc_scale_channels_map": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp],
     "dcvc_round_symbols": [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp],
     "dcvc_symbols_to_nhwc": [vp, vp, i32, i32, i32, i32, i32, vp],
     "dcvc_scale_indexes": [vp, vp, i64, vp, vp],
@@ -214,6 +216,7 @@ _SIGS = {
     "dcvc_roi_residual": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, vp, i64, i64, i32, i32, i32, i32, vp],
     "dcvc_roi_fuse": [vp, i32, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i64, vp],
     "dcvc_roi_sse": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, vp, i32, vp, vp],
+    "dcvc_roi_qmap": [i32, i32, vp, vp, i32, i32, vp, i32, vp, vp],
     # include/dcvc_hip_scene.h
     "dcvc_scene_hist": [vp, i32, i64, i32, i32, vp, vp],
 }
@@ -221,7 +224,7 @@ _SIGS = {
 # include/dcvc_hip_metrics.h (same library; listed apart because HIP_SYMBOLS is what the three kernel headers declare)
 METRICS_SYMBOLS = ["dcvc_ms_ssim", "dcvc_ms_ssim_grad", "dcvc_ms_ssim_workspace_bytes"]
 COLOR_SYMBOLS = ["dcvc_color_coeffs", "dcvc_yuv420_to_rgb", "dcvc_rgb_to_yuv420"]  # include/dcvc_hip_color.h
-ROI_SYMBOLS = ["dcvc_roi_residual", "dcvc_roi_fuse", "dcvc_roi_sse"]  # include/dcvc_hip_roi.h
+ROI_SYMBOLS = ["dcvc_roi_residual", "dcvc_roi_fuse", "dcvc_roi_sse", "dcvc_roi_qmap"]  # include/dcvc_hip_roi.h
 SCENE_SYMBOLS = ["dcvc_scene_hist"]  # include/dcvc_hip_scene.h
 HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS + ROI_SYMBOLS + SCENE_SYMBOLS] +
                      ["dcvc_cdf_table_cols", "dcvc_conv_pack_size", "dcvc_conv_pack_size_paired", "dcvc_conv_small_pack_bytes", "dcvc_conv_k32_pack_bytes", "dcvc_conv_tile_rows", "dcvc_conv_chan_partial_parts", "dcvc_hip_version", "dcvc_conv_wgrad_scratch_min",

@@ -63,13 +63,15 @@ def intra_dpb(x_hat):
     return {"ref_frame": x_hat, "ref_feature": None, "ref_y": None, "ref_mv_y": None}
 
 
-def decode_picture(i_net, p_net, kind, q, payload, dpb, height, width, defer_check=False):
+def decode_picture(i_net, p_net, kind, q, payload, dpb, height, width, defer_check=False, q_map=None):
     """Decode one coded picture ("I" with q = (q index,), "P" with q = (mv_y index, y index)) against `dpb`; returns the
-    DPB it leaves.  The split-fp16 range guard is left to the caller (once per GOP, not per picture)."""
+    DPB it leaves.  The split-fp16 range guard is left to the caller (once per GOP, not per picture).
+    q_map: the q-scale map the picture was coded with (roi.q_map), None for none."""
     if kind == "I":
-        return intra_dpb(i_net.decompress(payload, height, width, q[0] / 100, defer_check=defer_check, check_range=False)["x_hat"])
+        return intra_dpb(i_net.decompress(payload, height, width, q[0] / 100, defer_check=defer_check, check_range=False,
+                                          q_map=q_map)["x_hat"])
     return p_net.decompress(dpb, payload, height, width, q[0] / 100, q[1] / 100, defer_check=defer_check,
-                            check_range=False)["dpb"]
+                            check_range=False, q_map=q_map)["dpb"]
 
 
 class GopEncoder:
@@ -83,18 +85,21 @@ class GopEncoder:
         self.i_net.update()
         self.p_net.update()
 
-    def encode_gop(self, frames, q_i, q_mv_y, q_y, sink=None, on_recon=None, intra=None):
+    def encode_gop(self, frames, q_i, q_mv_y, q_y, sink=None, on_recon=None, intra=None, q_maps=None):
         """frames: iterable of padded (1, 3, H, W) device tensors, the first coded as an I
         picture.  intra: the set of picture numbers (positions in `frames`) coded as I pictures -- 0 among them, no two
         further apart than gop_size -- instead of every multiple of gop_size (scenecut.GopPlan).  Returns (list of payload bytes with their headers' q indexes, total bits of
         the payloads + headers, final DPB).  `sink(kind, q_indexes, payload, t)` may persist the
-        coded pictures; `on_recon(t, ref_frame)` sees each reconstruction while it is still valid."""
+        coded pictures; `on_recon(t, ref_frame)` sees each reconstruction while it is still valid.
+        q_maps: a callable, picture number (position in `frames`) -> the q-scale map that picture is coded with (roi.q_map;
+        made on the current stream when the picture is about to be coded) or None for none.  The payloads do not carry
+        the maps: decode_picture needs the same ones."""
         res = {}
-        for _ in self.encode_steps(frames, q_i, q_mv_y, q_y, res, sink=sink, on_recon=on_recon, intra=intra):
+        for _ in self.encode_steps(frames, q_i, q_mv_y, q_y, res, sink=sink, on_recon=on_recon, intra=intra, q_maps=q_maps):
             pass
         return res["coded"], res["bits"], res["dpb"]
 
-    def encode_steps(self, frames, q_i, q_mv_y, q_y, res, sink=None, on_recon=None, intra=None):
+    def encode_steps(self, frames, q_i, q_mv_y, q_y, res, sink=None, on_recon=None, intra=None, q_maps=None):
         """encode_gop as a generator that yields after every picture it has enqueued, so that several
         encoders can be interleaved by one host thread (ConcurrentGopEncoder).  Fills `res` with
         "coded", "bits", "dpb" when exhausted."""
@@ -120,13 +125,15 @@ class GopEncoder:
         # to pinned host memory asynchronously) BEFORE picture t-1 is entropy-coded on the host,
         # so the GPU works on t while the CPU codes t-1.  The DPB never leaves the device.
         for t, x in enumerate(frames):
+            qm = q_maps(t) if q_maps is not None else None
             if (t % self.gop == 0) if intra is None else (t in intra):
                 last_i = t
-                r = self.i_net.compress(x, q_i, defer=True, coder=self.coder, check_range=False)
+                r = self.i_net.compress(x, q_i, defer=True, coder=self.coder, check_range=False, q_map=qm)
                 dpb = intra_dpb(r["x_hat"])
                 item = ("I", (qi_idx,), r["pending"], t)
             else:
-                r = self.p_net.compress(x, dpb, q_mv_y, q_y, defer=True, coder=self.coder, graph=self.graphs, check_range=False)
+                r = self.p_net.compress(x, dpb, q_mv_y, q_y, defer=True, coder=self.coder, graph=self.graphs, check_range=False,
+                                        q_map=qm)
                 dpb = r["dpb"]
                 item = ("P", (qmv_idx, qy_idx), r["pending"], t)
             # once per GOP (behind its last picture -- with `intra` the one before the next I picture, or the one that
@@ -186,11 +193,12 @@ class ConcurrentGopEncoder:
         self.device = dev
         self.streams = [torch.cuda.Stream(dev) for _ in self.encoders]
 
-    def encode_gops(self, sequences, q_i, q_mv_y, q_y, sinks=None, on_recons=None, intra=None):
+    def encode_gops(self, sequences, q_i, q_mv_y, q_y, sinks=None, on_recons=None, intra=None, q_maps=None):
         """sequences: up to `streams` iterables of padded pictures (one sequence of whole GOPs each; an iterable is
         pulled INSIDE its stream, so a generator may upload its pictures there).  Returns a list of
         (coded, bits, dpb) in the same order.  sinks / on_recons: per-sequence callbacks of GopEncoder.encode_gop; intra:
-        per-sequence sets of the picture numbers coded as I (GopEncoder.encode_gop), None for every multiple of gop_size."""
+        per-sequence sets of the picture numbers coded as I (GopEncoder.encode_gop), None for every multiple of gop_size.
+        q_maps: per-sequence callables of GopEncoder.encode_gop (each is called inside its sequence's stream)."""
         assert len(sequences) <= len(self.encoders)
         cur = torch.cuda.current_stream(self.device)
         results = [{} for _ in sequences]
@@ -199,7 +207,8 @@ class ConcurrentGopEncoder:
             self.streams[k].wait_stream(cur)  # the pictures were produced on the caller's stream
             gens.append(self.encoders[k].encode_steps(seq, q_i, q_mv_y, q_y, results[k], sink=sinks[k] if sinks else None,
                                                       on_recon=on_recons[k] if on_recons else None,
-                                                      intra=intra[k] if intra else None))
+                                                      intra=intra[k] if intra else None,
+                                                      q_maps=q_maps[k] if q_maps else None))
         live = list(range(len(gens)))
         while live:
             for k in list(live):

@@ -24,6 +24,7 @@ from . import lib
 from .yuv import _Indexed, _readinto, _writefrom
 
 MAX_BOXES, MAX_CLASSES, MAX_BORDER, MAX_SIDE = 1024, 4, 64, 32768
+CELL, MAX_GROW, MIN_Q, MAX_Q = 16, 255, 10, 1000  # the q-scale map: cell side in pixels, factors in hundredths
 ORDERS = {"rgb": (0, 1, 2), "gbr": (1, 2, 0)}  # slot j of the 8-bit picture holds channel ORDERS[..][j]
 LAYOUTS = ("planar", "hwc")
 
@@ -148,6 +149,109 @@ class Roi:
 
     def to_json(self):
         return {"classes": [{"name": n, "border": c.border, "shrink": c.shrink} for n, c in zip(self.names, self.classes)]}
+
+
+@dataclass(frozen=True)
+class RoiQ:
+    """ROI-weighted quantisation (include/dcvc_hip_roi.h, "Q-scale map"): a factor on the quantisation step of the latent
+    y per 16x16-pixel cell -- `background` where no box touches the cell, else the smallest of classes[cls] over the boxes
+    (grown by `grow` pixels) that do.  Factors are integers in HUNDREDTHS, 10..1000; the value used is
+    float32(k) / float32(100).  Below 100 quantises finer (more bits), above 100 coarser.  There are no tuned values:
+    every default is 100, which codes exactly what no map codes."""
+    background: int = 100
+    classes: tuple = ()
+    grow: int = 0
+
+    def __post_init__(self):
+        try:
+            classes = tuple(self.classes)
+        except TypeError:
+            raise ValueError(f"classes: expected a sequence of factors in hundredths, got {self.classes!r}") from None
+        if len(classes) > MAX_CLASSES:
+            raise ValueError(f"classes: at most {MAX_CLASSES} factors, got {len(classes)}")
+
+        def whole(name, v, lo, hi, unit):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError(f"{name} must be an integer within {lo}..{hi} ({unit}), got {v!r}")
+            return int(v)
+
+        object.__setattr__(self, "background", whole("background", self.background, MIN_Q, MAX_Q, "hundredths"))
+        object.__setattr__(self, "classes", tuple(whole(f"classes[{i}]", v, MIN_Q, MAX_Q, "hundredths")
+                                                  for i, v in enumerate(classes)))
+        object.__setattr__(self, "grow", whole("grow", self.grow, 0, MAX_GROW, "pixels"))
+
+    @staticmethod
+    def hundredths(value, name="factor"):
+        """A float factor snapped to hundredths (the command line's --plate-q 0.6 -> 60)."""
+        if not math.isfinite(value):
+            raise ValueError(f"{name} must be a finite number, got {value!r}")
+        return int(round(float(value) * 100.0))
+
+    def factors(self):
+        """[background, class 0, ...] as the float32 values the kernels multiply with (the HOST's IEEE division)."""
+        return np.array((self.background,) + self.classes, dtype=np.float32) / np.float32(100)
+
+    def is_neutral(self):
+        return self.background == 100 and all(k == 100 for k in self.classes)
+
+    def to_json(self, names):
+        names = tuple(names)
+        if len(names) != len(self.classes) or len(set(names)) != len(names):
+            raise ValueError(f"classes: {len(self.classes)} factors for the class names {list(names)}")
+        return {"cell": CELL, "background": self.background, "classes": dict(zip(names, self.classes)), "grow": self.grow}
+
+    @classmethod
+    def from_json(cls, info, names=None):
+        """names: the class names the factors must belong to, in order (a Roi's); None takes the file's order."""
+        if not isinstance(info, dict) or set(info) != {"cell", "background", "classes", "grow"} or \
+                not isinstance(info["classes"], dict):
+            raise ValueError("expected the keys cell, background, classes (a name -> factor table) and grow")
+        if info["cell"] != CELL:
+            raise ValueError(f"cell must be {CELL}, got {info['cell']!r}")
+        have = tuple(info["classes"])
+        if names is not None and tuple(names) != have:
+            raise ValueError(f"the class names {list(have)} are not the boxes' {list(names)}")
+        return cls(info["background"], tuple(info["classes"][n] for n in have), info["grow"])
+
+
+def grid_of(height, width):
+    """(hc, wc): the latent grid of a height x width picture padded to multiples of 64."""
+    return 4 * ((int(height) + 63) // 64), 4 * ((int(width) + 63) // 64)
+
+
+def q_map(boxes, height, width, roiq, out=None, device=None):
+    """The (1, 1, hc, wc) float32 q-scale map of one picture's boxes on the device, made by one kernel on the current
+    stream (nothing synchronised): what IntraNoAR / DMC .compress and .decompress take as q_map=.  height, width: the
+    UNPADDED picture the boxes live in.  device: where, unless `out` (a contiguous float32 tensor of hc * wc elements) or
+    boxes already on a device say so; default the current one."""
+    torch = _torch()
+    if not isinstance(roiq, RoiQ):
+        raise ValueError(f"roiq: expected a RoiQ, got {type(roiq).__name__}")
+    H, W = int(height), int(width)
+    if not (0 < H <= MAX_SIDE and 0 < W <= MAX_SIDE):
+        raise ValueError(f"picture sides must be within 1..{MAX_SIDE}, got {W}x{H}")
+    hc, wc = grid_of(H, W)
+    boxes = as_boxes(boxes)
+    if out is not None:
+        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.numel() == hc * wc and out.is_contiguous()):
+            raise ValueError(f"out: expected a contiguous float32 tensor of {hc} x {wc} elements on the GPU")
+        dev = out.device
+    elif device is not None:
+        dev = torch.device(device)
+    else:
+        dev = boxes._dev.device if boxes._dev is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise ValueError("q_map: the map is made on the GPU (no CPU fallback exists)")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    f = np.ascontiguousarray(roiq.factors())
+    with torch.cuda.device(dev):
+        keep, host, devp, n = _box_args(boxes, H, W, len(roiq.classes), dev)
+        if out is None:
+            out = torch.empty((1, 1, hc, wc), dtype=torch.float32, device=dev)
+        lib.check(lib.hip().dcvc_roi_qmap(H, W, host, devp, n, roiq.grow, f.ctypes.data, len(roiq.classes), out.data_ptr(),
+                                          _stream(dev)), "roi_qmap")
+    return out.view(1, 1, hc, wc)
 
 
 def as_roi(roi):

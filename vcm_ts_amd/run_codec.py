@@ -10,6 +10,7 @@
     python -m vcm_ts_amd.run_codec encode ... --roi-root DIR [--plate-border N] [--face-border N] [--residuals FILE.gbrp | DIR]
     python -m vcm_ts_amd.run_codec decode ... --roi-root DIR --residuals FILE.gbrp | DIR
     python -m vcm_ts_amd.run_codec encode ... --scenecut T [--min-gop N]
+    python -m vcm_ts_amd.run_codec encode ... --roi-root DIR [--plate-q F] [--face-q F] [--background-q F] [--roi-q-grow N]
 
 Video files are Y4M or raw I420 at 8 or 10 bits (vcm_ts_amd/yuv.py): no PNG detour, the colour conversion runs on the
 GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` beside the `.bin` files from which
@@ -23,6 +24,11 @@ With --scenecut T an I picture also opens a new GOP wherever consecutive picture
 (vcm_ts_amd/scenecut.py: a scan pass over the source first, then the coding pass); --gop becomes the longest GOP, and the
 I pictures are listed in a `gops.json` beside the `.bin` files, which `decode` follows when it is there.  There is no
 default T.
+
+With --plate-q / --face-q / --background-q F (and a ROI) the base layer itself quantises its latent y with a step that
+varies per 16x16-pixel cell: F times the picture's step in the cells a plate / face box touches, the background's factor
+elsewhere (vcm_ts_amd/roi.py RoiQ, q_map).  The .bin format is unchanged; the factors go to a `roiq.json` beside the .bin
+files, and `decode` then needs the same boxes (--roi-root) to rebuild the maps.  There are no defaults other than 1.00.
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
 reference's `.bin` format (an I picture every `gop` frames).  Unlike run_dcvc the encoder does not
@@ -339,15 +345,18 @@ class _EncodeRun:
 
         return sink
 
-    def encode(self, frames, q, on_recon=None):
+    def encode(self, frames, q, on_recon=None, q_map=None):
         """frames(k): generator of stream k's padded pictures, those of order(k).  on_recon(k, g, ref_frame): sees the
-        reconstruction of frame g while it is valid (and before stream k's next picture is pulled from frames(k))."""
+        reconstruction of frame g while it is valid (and before stream k's next picture is pulled from frames(k)).
+        q_map(g): the q-scale map frame g is coded with, made on the stream that codes it (None: no maps, no launch)."""
+        maps_of = lambda k: (lambda t: q_map(self.global_index(k, t))) if q_map else None
         recon_of = lambda k: (lambda t, ref_frame: on_recon(k, self.global_index(k, t), ref_frame)) if on_recon else None
         # (GopEncoder reads the split-fp16 range guard once per GOP and raises lib.KernelError: no .bin of a clamped GOP
         # is reported as a success)
         with torch.no_grad():
             self.cenc.encode_gops([frames(k) for k in range(self.K)], q[0], q[1], q[2], sinks=[self._sink(k) for k in range(self.K)],
-                                  on_recons=[recon_of(k) for k in range(self.K)], intra=[self.intra(k) for k in range(self.K)])
+                                  on_recons=[recon_of(k) for k in range(self.K)], intra=[self.intra(k) for k in range(self.K)],
+                                  q_maps=[maps_of(k) for k in range(self.K)] if q_map else None)
 
     def results(self, report, extras=None):
         """(bits per frame list, size) -- with a report also the rd_report() dictionary, which extras(rd, frame types,
@@ -410,6 +419,60 @@ def write_gop_plan(bin_dir, plan, gop, scenecut, min_gop):
         json.dump(dict(plan.to_json(), gop=int(gop), min_gop=int(min_gop), scenecut=float(scenecut)), f, indent=2)
 
 
+ROIQ_JSON = "roiq.json"
+
+
+def _roiq_args(roi, roi_q):
+    """roi_q= of an encode loop against its roi=, refused by name before any GPU work."""
+    if roi_q is None:
+        return
+    from . import roi as X
+
+    if roi is None:
+        raise ValueError("roi_q= needs roi= (the boxes the q-scale maps are made from)")
+    if not isinstance(roi_q, X.RoiQ):
+        raise ValueError(f"roi_q: expected a roi.RoiQ, got {type(roi_q).__name__}")
+    names = X.as_roi(roi).names
+    if len(roi_q.classes) != len(names):
+        raise ValueError(f"roi_q: {len(roi_q.classes)} class factors for the roi's classes {list(names)}")
+
+
+def write_roiq(bin_dir, roi_q, names=()):
+    """roiq.json beside the .bin files -- only for an encode with q-scale maps: without them none is needed (and a stale
+    file of an earlier encode into the same folder must not describe these .bin files)."""
+    import json
+
+    path = os.path.join(bin_dir, ROIQ_JSON)
+    if roi_q is None:
+        if os.path.exists(path):
+            os.remove(path)
+        return
+    info = roi_q.to_json(names)
+    with open(path, "w") as f:
+        json.dump(info, f, indent=2)
+
+
+def read_roiq(bin_dir, roi=None):
+    """The roi.RoiQ the .bin files of `bin_dir` were coded with, or None without a roiq.json.  Refused by name: the file
+    without `roi` (the maps are rebuilt from the boxes), class names that are not the roi's, values out of range."""
+    import json
+
+    from . import roi as X
+
+    path = os.path.join(bin_dir, ROIQ_JSON)
+    if not os.path.exists(path):
+        return None
+    if roi is None:
+        raise ValueError(f"{path}: these pictures were coded with q-scale maps made from ROI boxes; decoding them needs the "
+                         f"same boxes (roi=, --roi-root)")
+    with open(path) as f:
+        info = json.load(f)
+    try:
+        return X.RoiQ.from_json(info, X.as_roi(roi).names)
+    except ValueError as ex:
+        raise ValueError(f"{path}: {ex}") from None
+
+
 def _count_bins(bin_dir):
     n = 0
     while os.path.exists(os.path.join(bin_dir, f"im{str(n + 1).zfill(5)}.bin")):
@@ -442,7 +505,7 @@ def read_gop_plan(bin_dir, gop=None):
 
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
-                  report=None, roi=None, residuals=None, scenecut=None, min_gop=1):
+                  report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -465,7 +528,12 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     exists).  A scan pass then reads every picture once, through the same pool and upload path as the coding pass, before
     anything is coded; an I picture opens a new GOP wherever the distance exceeds the threshold and the GOP is at least
     min_gop pictures old, `gop` becomes the longest GOP, and the plan is written to gops.json beside the .bin files
-    (decode_folder follows it).  Without scenecut nothing changes and no such file is written."""
+    (decode_folder follows it).  Without scenecut nothing changes and no such file is written.
+    roi_q (with roi): a roi.RoiQ -- ROI-weighted quantisation.  The map of picture g is made from the roi's boxes of g on
+    the stream that codes it (one small launch per picture) and multiplies the quantisation step of the latent y cell by
+    cell; the factors are written to roiq.json beside the .bin files, and decode_folder / decode_video then need the same
+    roi.  The .bin format is unchanged.  Without roi_q nothing changes, no kernel is launched and no such file is written
+    (a stale one is removed)."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
@@ -480,6 +548,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     with Image.open(reader.path_of(1)) as first:  # (the header only)
         w, h = first.size
     _roi_args(roi, residuals)
+    _roiq_args(roi, roi_q)
     dev = torch.device(device)
     pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
 
@@ -511,6 +580,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
                          (_VideoQualityLog if layer else _QualityLog) if report else None)
         write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
+        write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
     except BaseException:
         if pool is not None:
@@ -538,7 +608,8 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     failed = True
     try:
         with PNGWriters(io_workers) as savers:
-            run.encode(frames, q, on_recon if (recon_dir or report or res_out) else None)
+            run.encode(frames, q, on_recon if (recon_dir or report or res_out) else None,
+                       (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None)
         failed = False
     finally:
         if pool is not None:
@@ -548,9 +619,10 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     return run.results(report, _roi_report_keys(h, w) if layer else None)
 
 
-def _decode_bins(nets, bin_dir, height, width, plan, emit):
+def _decode_bins(nets, bin_dir, height, width, plan, emit, q_map=None):
     """Decode im00001.bin ... of `bin_dir` (I pictures where `plan`, read_gop_plan's, has them) in order, handing every
-    reconstruction to emit(t, ref_frame) while it is valid.  Returns the picture count."""
+    reconstruction to emit(t, ref_frame) while it is valid.  q_map(t): the q-scale map picture t was coded with (None: no
+    maps).  Returns the picture count."""
     i_net, p_net = nets
     i_net.update()
     p_net.update()
@@ -572,7 +644,7 @@ def _decode_bins(nets, bin_dir, height, width, plan, emit):
             else:
                 qmv, qy, payload = S.decode_p(path)
                 kind, q = "P", (qmv, qy)
-            dpb = decode_picture(i_net, p_net, kind, q, payload, dpb, height, width)
+            dpb = decode_picture(i_net, p_net, kind, q, payload, dpb, height, width, q_map=q_map(t) if q_map else None)
             emit(t, dpb["ref_frame"])
         if plan.n_frames:
             range_guard()
@@ -585,16 +657,21 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", 
     residual layer (a `.gbrp` file or a folder of im%05d.png, as encode_folder writes them) and `roi` the boxes and
     classes it was taken with.  Display side only: the decoder's reference pictures are not touched.
     gop: an I picture every `gop` pictures (default 32) -- unless encode left a gops.json beside the .bin files, which then
-    says where the I pictures are; a `gop` given against it is refused (read_gop_plan)."""
+    says where the I pictures are; a `gop` given against it is refused (read_gop_plan).
+    A roiq.json beside the .bin files (encode_folder's roi_q=) is followed: the q-scale maps are rebuilt from `roi`, which
+    is then required -- with or without residuals."""
     _roi_args(roi, residuals)
     plan, _ = read_gop_plan(bin_dir, gop)
+    roi_q = read_roiq(bin_dir, roi)
     os.makedirs(recon_dir, exist_ok=True)
-    picture, close = _fused_emit(roi, residuals, plan, (height, width), torch.device(device))
+    dev = torch.device(device)
+    picture, close = _fused_emit(_fuse_roi(roi, residuals, roi_q), residuals, plan, (height, width), dev)
     try:
-        nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
+        maps = _decode_maps(roi, roi_q, plan, (height, width), dev)
+        nets = _nets(dev, precision, i_ckpt, p_ckpt)
         with PNGWriters(io_workers) as savers:
             return _decode_bins(nets, bin_dir, height, width, plan, lambda t, ref_frame: save_torch_image(
-                picture(t, ref_frame), os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"), savers))
+                picture(t, ref_frame), os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"), savers), maps)
     finally:
         close()
 
@@ -709,6 +786,10 @@ class _RoiLayer:
         self.classes = self.roi.classes
         self.frames = [self.roi.frame(g, size[0], size[1]) for g in range(plan.n_frames)]
 
+    def q_map(self, g, roi_q):
+        """The q-scale map of frame g on the current stream (roi.q_map: one launch, nothing synchronised)."""
+        return self.X.q_map(self.boxes(g), self.size[0], self.size[1], roi_q, device=self.dev)
+
     def boxes(self, g):
         fb = self.frames[g]
         if len(fb) and not fb.attached(self.dev):
@@ -806,6 +887,19 @@ def _roi_args(roi, residuals):
         raise ValueError("residuals= needs roi= (the boxes the residual layer is taken in)")
 
 
+def _fuse_roi(roi, residuals, roi_q):
+    """The roi a decode loop fuses a residual layer with: none when the roi is only there for the q-scale maps."""
+    return None if (residuals is None and roi_q is not None) else roi
+
+
+def _decode_maps(roi, roi_q, plan, size, dev):
+    """q_map(t) of a decode loop that follows a roiq.json, or None without one."""
+    if roi_q is None:
+        return None
+    layer = _RoiLayer(roi, plan, size, dev)
+    return lambda t: layer.q_map(t, roi_q)
+
+
 def _roi_report_keys(h, w):
     def keys(rd, types, values):
         from . import roi as X
@@ -843,7 +937,7 @@ def _open_source(video, size, bit_depth, fps):
 def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantize8=False, gop=32, q=(1.0, 1.0, 1.0),
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
-                 min_gop=1):
+                 min_gop=1, roi_q=None):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -858,10 +952,12 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     roi, residuals: as encode_folder (the residual is taken against the RGB picture the codec was given); sequence.json
     then also records the classes' names and borders.
     scenecut, min_gop: as encode_folder; the scan pass reads the file once through the same ring, copy and colour
-    conversion (spec, quantize8) as the coding pass.  sequence.json is the same with or without."""
+    conversion (spec, quantize8) as the coding pass.  sequence.json is the same with or without.
+    roi_q: as encode_folder (roiq.json beside the .bin files; sequence.json is the same with or without)."""
     from . import yuv as Y
 
     _roi_args(roi, residuals)
+    _roiq_args(roi, roi_q)
     reader = _open_source(video, size, bit_depth, fps)  # (every refusal about the file happens here, before any GPU work)
     spec = spec or reader.spec()
     if spec.bit_depth != reader.bit_depth:
@@ -886,6 +982,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
                      _VideoQualityLog if report else None)
     write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
+    write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
     res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
     source = {}
     container = "y4m" if isinstance(reader, Y.Y4MReader) else "yuv"
@@ -915,7 +1012,8 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
 
     failed = True
     try:
-        run.encode(frames, q, on_recon if (outs or report or res_out) else None)
+        run.encode(frames, q, on_recon if (outs or report or res_out) else None,
+                   (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None)
         for o in outs or []:
             o.close()
         failed = False
@@ -947,7 +1045,8 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     """decode_folder's loop with the video output stage.  Size, GOP length, frame rate and colour description come from
     the sequence.json encode_video left in `bin_dir`; explicit arguments override it, and without the file height and
     width are required (gop then defaults to 32, the colour description to yuv.ColorSpec()).  Returns the picture count.
-    roi, residuals: as decode_folder -- the fused picture is what is converted and written."""
+    roi, residuals: as decode_folder -- the fused picture is what is converted and written.  A roiq.json beside the .bin
+    files is followed as decode_folder does."""
     from . import yuv as Y
 
     _roi_args(roi, residuals)
@@ -961,8 +1060,11 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     first = os.path.join(bin_dir, "im00001.bin")
     if os.path.exists(first) and S.decode_i(first)[:2] != (height, width):
         raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {(height, width)}")
-    picture, close = _fused_emit(roi, residuals, plan, (height, width), torch.device(device))
+    roi_q = read_roiq(bin_dir, roi)
+    fuse_roi = _fuse_roi(roi, residuals, roi_q)
+    picture, close = _fused_emit(fuse_roi, residuals, plan, (height, width), torch.device(device))
     try:
+        maps = _decode_maps(roi, roi_q, plan, (height, width), torch.device(device))
         nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
         writer = Y.create_video(recon_video, width, height, spec, fps or info.get("fps"), chroma=info.get("chroma"),
                                 interlace=info.get("interlace"), aspect=info.get("aspect"))
@@ -970,7 +1072,7 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
             out = _VideoOut(writer)
             # (without a ROI the padded reconstruction itself: rgb_to_yuv420 reads its top-left corner in place)
             t = _decode_bins(nets, bin_dir, height, width, plan, lambda t, ref_frame: out.put(t, Y.rgb_to_yuv420(
-                ref_frame if roi is None else picture(t, ref_frame), height, width, spec)))
+                ref_frame if fuse_roi is None else picture(t, ref_frame), height, width, spec)), maps)
             out.close()
         finally:
             writer.close()
@@ -1017,6 +1119,15 @@ def main(argv=None):
     e.add_argument("--min-gop", type=int, default=None, metavar="N",
                    help="with --scenecut: no I picture closer than N pictures behind the last one (default 1, at most --gop); "
                         "a cut that falls inside stays a P picture")
+    e.add_argument("--plate-q", type=float, default=None, metavar="F",
+                   help="with --roi-root: ROI-weighted quantisation -- multiply the quantisation step of the latent y by F "
+                        "(0.1 .. 10, snapped to hundredths; below 1 is finer) in every 16x16 cell a plate box touches.  Any of "
+                        "--plate-q, --face-q, --background-q switches it on, the others default to 1.00 (no tuned values "
+                        "exist); the factors go to roiq.json beside the .bin files and decode then needs --roi-root")
+    e.add_argument("--face-q", type=float, default=None, metavar="F", help="the same for face boxes")
+    e.add_argument("--background-q", type=float, default=None, metavar="F", help="the factor of the cells no box touches")
+    e.add_argument("--roi-q-grow", type=int, default=None, metavar="N",
+                   help="with one of the three above: grow every box by N pixels (0 .. 255, default 0) before it is laid on the cells")
     d = sub.add_parser("decode")
     d.add_argument("--bins", required=True)
     d.add_argument("--recon", help="folder for PNGs (exactly one of --recon and --recon-video)")
@@ -1047,13 +1158,31 @@ def main(argv=None):
         p.add_argument("--i-ckpt")
         p.add_argument("--p-ckpt")
     a = ap.parse_args(argv)
-    roi = None
+    roi = roi_q = None
+    factors = [getattr(a, n, None) for n in ("plate_q", "face_q", "background_q")]
+    if a.cmd == "encode":
+        if a.roi_root is None and (any(f is not None for f in factors) or a.roi_q_grow is not None):
+            ap.error("--plate-q, --face-q, --background-q and --roi-q-grow belong to --roi-root")
+        if a.roi_q_grow is not None and all(f is None for f in factors):
+            ap.error("--roi-q-grow belongs to --plate-q, --face-q or --background-q")
+        if any(f is not None for f in factors):
+            from . import roi as X
+
+            try:
+                plate, face, ground = (100 if f is None else X.RoiQ.hundredths(f, n) for f, n in
+                                       zip(factors, ("--plate-q", "--face-q", "--background-q")))
+                roi_q = X.RoiQ(ground, (plate, face), 0 if a.roi_q_grow is None else a.roi_q_grow)
+            except ValueError as ex:
+                ap.error(f"ROI-weighted quantisation: {ex}")
+    elif a.roi_root is None and os.path.exists(os.path.join(a.bins, ROIQ_JSON)):
+        ap.error(f"{os.path.join(a.bins, ROIQ_JSON)}: these pictures were coded with q-scale maps made from ROI boxes; "
+                 f"decode needs --roi-root")
     if a.roi_root is None and (a.residuals or a.plate_border is not None or a.face_border is not None):
         ap.error("--residuals, --plate-border and --face-border belong to --roi-root")
     if a.roi_root is not None:
         from . import roi as X
 
-        if a.cmd == "decode" and not a.residuals:
+        if a.cmd == "decode" and not a.residuals and not os.path.exists(os.path.join(a.bins, ROIQ_JSON)):
             ap.error("decode --roi-root needs --residuals (the decoded residual layer)")
         recorded = {c["name"]: c["border"] for c in ((read_sequence_info(a.bins) or {}).get("roi") or {}).get("classes", [])} \
             if a.cmd == "decode" else {}
@@ -1119,11 +1248,11 @@ def main(argv=None):
                 bits, size, *rd = encode_video(reader, a.bins, a.recon_video, spec=spec, quantize8=a.quantize8, gop=a.gop, q=q,
                                                device=a.device, precision=a.precision, i_ckpt=a.i_ckpt, p_ckpt=a.p_ckpt,
                                                coder=a.coder, gop_streams=a.gop_streams, report=a.report, roi=roi,
-                                               residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop)
+                                               residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q)
         else:
             bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
                                             coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
-                                            roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop)
+                                            roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q)
         if rd:
             yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
             print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
