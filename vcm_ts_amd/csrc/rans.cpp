@@ -72,7 +72,10 @@ extern "C" int dcvc_rans_encoder_encode_with_indexes(dcvc_rans_encoder *e, const
             escape = true;
         }
         if (escape) v = sentinel;
-        e->rec.push_back(pack((uint32_t)cdf[v] & 0xFFFFu, (uint32_t)(cdf[v + 1] - cdf[v]) & 0xFFFFu));
+        // a frequency of 2^16 (a row that holds nothing but its sentinel) leaves the state as it is and emits nothing:
+        // no record -- its low 16 bits are 0, which would read as a bypass nibble
+        if ((uint32_t)(cdf[v + 1] - cdf[v]) != (1u << kProbBits))
+            e->rec.push_back(pack((uint32_t)cdf[v] & 0xFFFFu, (uint32_t)(cdf[v + 1] - cdf[v]) & 0xFFFFu));
         if (escape) {
             int32_t nib = 0;
             while (nib < 8 && (raw >> (nib * kNibbleBits)) != 0) ++nib;

@@ -172,6 +172,7 @@ class CodecBase(nn.Module):
         self._net = None
         self.entropy_coder = None
         self._tables = None
+        self._cost = None  # (tables, bitmap.CostTables made from them): see _cost_tables()
         self._flip = 0
         self._chan_cache, self._stage_bufs, self._stage_flip, self._stage_owner = {}, {}, 0, {}
         self._dcoder, self._dc_active, self._dc_stream, self._dc_done = None, False, None, None
@@ -413,9 +414,37 @@ class CodecBase(nn.Module):
         assert coder in ("host", "device")
         return (self._stage_symbols if coder == "host" else self._stage_symbols_device)(planes, batch=batch)
 
-    def _compress_result(self, res, pending, defer, check_range):
+    def _cost_tables(self):
+        """bitmap.CostTables of this model's tables on its device: built on first use (a model that never asks for a bit
+        map builds and uploads nothing), rebuilt when update() has made new tables."""
+        from .bitmap import CostTables
+
+        if self._tables is None:
+            raise RuntimeError("call update() before compress()/decompress()")
+        c = self._cost
+        if c is None or c[0] is not self._tables:
+            c = self._cost = (self._tables, CostTables(self._tables))
+        return c[1].on(self.device)
+
+    def _bit_map(self, bit_map, planes, N, graph=False):
+        """The bit_map argument of compress() (include/dcvc_hip_bits.h, bitmap.BitMap): the code length of every symbol of
+        `planes`, summed per latent position, by kernels enqueued on the launch stream right behind the kernels that
+        wrote the planes -- the next picture rewrites those buffers, and stream order is what protects them.  Works with
+        either coder, with q_map, defer and batches of rate points; refused with graph replay."""
+        if not bit_map:
+            return None
+        if graph:
+            raise NotImplementedError("bit_map: graph replay with a bit map is not supported (pass graph=False)")
+        from .bitmap import BitMap
+
+        return BitMap.from_planes(self._cost_tables(), planes, N)
+
+    def _compress_result(self, res, pending, defer, check_range, bits=None):
         """Tail of compress(): `res` (the codec's own keys) plus "pending" when deferred, else plus the payloads, after
-        the split-fp16 range guard (DMC.compress says when a caller reads it itself)."""
+        the split-fp16 range guard (DMC.compress says when a caller reads it itself).  bits: the picture's BitMap, added
+        as "bit_map" when there is one."""
+        if bits is not None:
+            res = {**res, "bit_map": bits}
         if defer:
             return {**res, "pending": pending}
         streams = pending.finish_all()
@@ -1017,7 +1046,7 @@ class DMC(CodecBase):
 
     @torch.no_grad()
     def compress(self, x, dpb, mv_y_q_scale, y_q_scale, defer=False, coder="host", graph=False, check_range=True,
-                 q_map=None):
+                 q_map=None, bit_map=False):
         """defer=True returns {"dpb", "pending"}: call pending.finish() later for the bytes.
         check_range: a call that returns bytes (defer=False) raises lib.KernelError if a split-fp16 kernel met an
         activation beyond +-8188 (one status read after the picture is done); pipelined callers (defer=True, or
@@ -1026,11 +1055,15 @@ class DMC(CodecBase):
         graph=True: replay the picture's launches as a captured hipGraph (host coder, batch 1, float
         q-scales): pays when the picture is small enough for the host enqueue to be the bottleneck.
         q_map: ROI-weighted quantisation (roi.q_map; CodecBase._qmap says what is taken): one factor per 16x16 cell on the
-        quantisation step of y.  decompress() needs the same map.  None: exactly the launches and bytes without it."""
+        quantisation step of y.  decompress() needs the same map.  None: exactly the launches and bytes without it.
+        bit_map=True: the result also carries "bit_map", a bitmap.BitMap of the picture's six planes (CodecBase._bit_map).
+        False: exactly the launches, bytes and result keys without it."""
         if self.entropy_coder is None:
             raise RuntimeError("call update() before compress()/decompress()")
         self._qmap(q_map, x.shape[0], x.shape[2], x.shape[3], graph=graph)  # (every refusal, before any GPU work)
+        bits = None
         if graph:
+            self._bit_map(bit_map, None, 0, graph=True)  # (refused, before any GPU work)
             if coder != "host":
                 raise NotImplementedError("graph replay is wired to the host coder")
             g = self._compress_graph(x, dpb, mv_y_q_scale, y_q_scale)
@@ -1038,9 +1071,11 @@ class DMC(CodecBase):
         else:
             o = self._run(x, dpb, mv_y_q_scale, y_q_scale, "compress", q_map=q_map)
             # N > 1: a batch of rate points, one independent stream per element ("bit_streams")
-            pending = self._stage(self._planes(o), o["N"], coder)
+            planes = self._planes(o)
+            bits = self._bit_map(bit_map, planes, o["N"])
+            pending = self._stage(planes, o["N"], coder)
             d = self._dpb_out(o)
-        return self._compress_result({"dbp": d, "dpb": d, "_views": o}, pending, defer, check_range)
+        return self._compress_result({"dbp": d, "dpb": d, "_views": o}, pending, defer, check_range, bits)
 
     @torch.no_grad()
     def decompress(self, dpb, string, height, width, mv_y_q_scale, y_q_scale, coder=None, defer_check=False,

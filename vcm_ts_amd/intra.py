@@ -155,20 +155,24 @@ class IntraNoAR(CodecBase):
         return self._ssim_keys(res, x, res["x_hat"]) if self.report_ssim else res
 
     @torch.no_grad()
-    def compress(self, x, q_scale, defer=False, coder="host", check_range=True, q_map=None):
+    def compress(self, x, q_scale, defer=False, coder="host", check_range=True, q_map=None, bit_map=False):
         """q_map: ROI-weighted quantisation (roi.q_map; CodecBase._qmap says what is taken): one factor per 16x16 cell on the
-        quantisation step of y.  decompress() needs the same map.  None: exactly the launches and bytes without it."""
+        quantisation step of y.  decompress() needs the same map.  None: exactly the launches and bytes without it.
+        bit_map=True: the result also carries "bit_map", a bitmap.BitMap of the picture's z and y planes
+        (CodecBase._bit_map).  False: exactly the launches, bytes and result keys without it."""
         if self.entropy_coder is None:
             raise RuntimeError("call update() before compress()/decompress()")
         o = self._run(x, q_scale, "compress", q_map=q_map)
         N = o["N"]  # N > 1: a batch of rate points (one q-scale per element), one independent stream each
         zs = o["z_hat"]
-        pending = self._stage([  # image_model.py:168-171
+        planes = [  # image_model.py:168-171
             ("bit_estimator_z", o["sym_z"], None, (N, self.N, zs.H, zs.W)),
             ("scale", o["r"]["sym"][0], o["r"]["idx"][0], None),
             ("scale", o["r"]["sym"][1], o["r"]["idx"][1], None),
-        ], N, coder)
-        return self._compress_result({"x_hat": o["x_hat"].nchw(), "_views": o}, pending, defer, check_range)
+        ]
+        bits = self._bit_map(bit_map, planes, N)
+        pending = self._stage(planes, N, coder)
+        return self._compress_result({"x_hat": o["x_hat"].nchw(), "_views": o}, pending, defer, check_range, bits)
 
     @torch.no_grad()
     def decompress(self, bit_stream, height, width, q_scale, coder=None, defer_check=False, check_range=True, q_map=None):

@@ -85,7 +85,7 @@ class GopEncoder:
         self.i_net.update()
         self.p_net.update()
 
-    def encode_gop(self, frames, q_i, q_mv_y, q_y, sink=None, on_recon=None, intra=None, q_maps=None):
+    def encode_gop(self, frames, q_i, q_mv_y, q_y, sink=None, on_recon=None, intra=None, q_maps=None, bit_maps=None):
         """frames: iterable of padded (1, 3, H, W) device tensors, the first coded as an I
         picture.  intra: the set of picture numbers (positions in `frames`) coded as I pictures -- 0 among them, no two
         further apart than gop_size -- instead of every multiple of gop_size (scenecut.GopPlan).  Returns (list of payload bytes with their headers' q indexes, total bits of
@@ -93,13 +93,16 @@ class GopEncoder:
         coded pictures; `on_recon(t, ref_frame)` sees each reconstruction while it is still valid.
         q_maps: a callable, picture number (position in `frames`) -> the q-scale map that picture is coded with (roi.q_map;
         made on the current stream when the picture is about to be coded) or None for none.  The payloads do not carry
-        the maps: decode_picture needs the same ones."""
+        the maps: decode_picture needs the same ones.
+        bit_maps: a callable (picture number, bitmap.BitMap) -> None.  Every picture is then coded with bit_map=True and its
+        map handed over as soon as its kernels are enqueued (nothing is read back here); payloads are unchanged."""
         res = {}
-        for _ in self.encode_steps(frames, q_i, q_mv_y, q_y, res, sink=sink, on_recon=on_recon, intra=intra, q_maps=q_maps):
+        for _ in self.encode_steps(frames, q_i, q_mv_y, q_y, res, sink=sink, on_recon=on_recon, intra=intra, q_maps=q_maps,
+                                   bit_maps=bit_maps):
             pass
         return res["coded"], res["bits"], res["dpb"]
 
-    def encode_steps(self, frames, q_i, q_mv_y, q_y, res, sink=None, on_recon=None, intra=None, q_maps=None):
+    def encode_steps(self, frames, q_i, q_mv_y, q_y, res, sink=None, on_recon=None, intra=None, q_maps=None, bit_maps=None):
         """encode_gop as a generator that yields after every picture it has enqueued, so that several
         encoders can be interleaved by one host thread (ConcurrentGopEncoder).  Fills `res` with
         "coded", "bits", "dpb" when exhausted."""
@@ -109,6 +112,9 @@ class GopEncoder:
         out, bits, dpb, prev, last_i = [], 0, None, None, 0
         if intra is not None and 0 not in intra:
             raise ValueError("intra: picture 0 of a sequence is an I picture")
+        if bit_maps is not None and self.graphs:
+            raise NotImplementedError("bit_maps: graph replay with a bit map is not supported")
+        want_bits = bit_maps is not None
 
         def retire(item):  # host half of a picture: wait for its planes, rANS-code them
             nonlocal bits
@@ -128,14 +134,16 @@ class GopEncoder:
             qm = q_maps(t) if q_maps is not None else None
             if (t % self.gop == 0) if intra is None else (t in intra):
                 last_i = t
-                r = self.i_net.compress(x, q_i, defer=True, coder=self.coder, check_range=False, q_map=qm)
+                r = self.i_net.compress(x, q_i, defer=True, coder=self.coder, check_range=False, q_map=qm, bit_map=want_bits)
                 dpb = intra_dpb(r["x_hat"])
                 item = ("I", (qi_idx,), r["pending"], t)
             else:
                 r = self.p_net.compress(x, dpb, q_mv_y, q_y, defer=True, coder=self.coder, graph=self.graphs, check_range=False,
-                                        q_map=qm)
+                                        q_map=qm, bit_map=want_bits)
                 dpb = r["dpb"]
                 item = ("P", (qmv_idx, qy_idx), r["pending"], t)
+            if want_bits:
+                bit_maps(t, r["bit_map"])
             # once per GOP (behind its last picture -- with `intra` the one before the next I picture, or the one that
             # fills the GOP's maximum length; a trailing partial GOP is covered after the loop): the status
             # word of both engines, read asynchronously -- the copy rides behind the picture's kernels and is looked
@@ -193,12 +201,12 @@ class ConcurrentGopEncoder:
         self.device = dev
         self.streams = [torch.cuda.Stream(dev) for _ in self.encoders]
 
-    def encode_gops(self, sequences, q_i, q_mv_y, q_y, sinks=None, on_recons=None, intra=None, q_maps=None):
+    def encode_gops(self, sequences, q_i, q_mv_y, q_y, sinks=None, on_recons=None, intra=None, q_maps=None, bit_maps=None):
         """sequences: up to `streams` iterables of padded pictures (one sequence of whole GOPs each; an iterable is
         pulled INSIDE its stream, so a generator may upload its pictures there).  Returns a list of
         (coded, bits, dpb) in the same order.  sinks / on_recons: per-sequence callbacks of GopEncoder.encode_gop; intra:
         per-sequence sets of the picture numbers coded as I (GopEncoder.encode_gop), None for every multiple of gop_size.
-        q_maps: per-sequence callables of GopEncoder.encode_gop (each is called inside its sequence's stream)."""
+        q_maps, bit_maps: per-sequence callables of GopEncoder.encode_gop (each is called inside its sequence's stream)."""
         assert len(sequences) <= len(self.encoders)
         cur = torch.cuda.current_stream(self.device)
         results = [{} for _ in sequences]
@@ -208,7 +216,8 @@ class ConcurrentGopEncoder:
             gens.append(self.encoders[k].encode_steps(seq, q_i, q_mv_y, q_y, results[k], sink=sinks[k] if sinks else None,
                                                       on_recon=on_recons[k] if on_recons else None,
                                                       intra=intra[k] if intra else None,
-                                                      q_maps=q_maps[k] if q_maps else None))
+                                                      q_maps=q_maps[k] if q_maps else None,
+                                                      bit_maps=bit_maps[k] if bit_maps else None))
         live = list(range(len(gens)))
         while live:
             for k in list(live):

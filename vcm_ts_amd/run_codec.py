@@ -11,6 +11,7 @@
     python -m vcm_ts_amd.run_codec decode ... --roi-root DIR --residuals FILE.gbrp | DIR
     python -m vcm_ts_amd.run_codec encode ... --scenecut T [--min-gop N]
     python -m vcm_ts_amd.run_codec encode ... --roi-root DIR [--plate-q F] [--face-q F] [--background-q F] [--roi-q-grow N]
+    python -m vcm_ts_amd.run_codec encode ... --report JSON --bit-map [DIR]
 
 Video files are Y4M or raw I420 at 8 or 10 bits (vcm_ts_amd/yuv.py): no PNG detour, the colour conversion runs on the
 GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` beside the `.bin` files from which
@@ -29,6 +30,10 @@ With --plate-q / --face-q / --background-q F (and a ROI) the base layer itself q
 varies per 16x16-pixel cell: F times the picture's step in the cells a plate / face box touches, the background's factor
 elsewhere (vcm_ts_amd/roi.py RoiQ, q_map).  The .bin format is unchanged; the factors go to a `roiq.json` beside the .bin
 files, and `decode` then needs the same boxes (--roi-root) to rebuild the maps.  There are no defaults other than 1.00.
+
+With --bit-map the report also says where the bits of every picture went (vcm_ts_amd/bitmap.py: the code lengths of the
+coder's own symbols, summed per 16x16-pixel cell on the GPU): per component, and with a ROI inside and outside the
+boxes; with a DIR the per-cell maps are written there as im%05d.npy.  The .bin files are the same with or without.
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
 reference's `.bin` format (an I picture every `gop` frames).  Unlike run_dcvc the encoder does not
@@ -270,6 +275,77 @@ class _QualityLog:
         return out
 
 
+def _bitmap_args(bit_map, report):
+    """bit_map= of an encode loop (None | True | a folder for im%05d.npy) -> the folder or None, refused by name before any
+    GPU work."""
+    if bit_map is None or bit_map is False:
+        return None
+    if bit_map is True:
+        if not report:
+            raise ValueError("bit_map=True needs report= (where the regional bit counts go), or give a folder for the maps")
+        return None
+    if not isinstance(bit_map, (str, os.PathLike)):
+        raise ValueError(f"bit_map: expected None, True or a folder, got {type(bit_map).__name__}")
+    return os.fspath(bit_map)
+
+
+BIT_KEYS = ("frame_bits_mv_z", "frame_bits_mv_y", "frame_bits_z", "frame_bits_y")  # (bitmap.COMPONENTS' order)
+
+
+class _BitLog:
+    """The bit maps (vcm_ts_amd/bitmap.py) of every coded picture of one GOP stream.  The region sums of a picture are
+    enqueued on the stream that coded it, behind its map kernels (labels 0 / 1 from labels_of(g), or one label without a
+    ROI); the rows of a GOP -- and, with a folder, its per-cell maps -- go to pinned host memory in ONE asynchronous copy
+    behind its last picture and are looked at when the sequence is done, like the _QualityLog's values."""
+
+    def __init__(self, plan, labels_of, keep_cells):
+        self.plan, self.labels_of, self.keep_cells = plan, labels_of, keep_cells
+        self.K = 2 if labels_of else 1
+        self.cur, self.cells, self.idx, self.done, self._one = [], [], [], [], None
+
+    def add(self, g, bits):
+        if self.labels_of:
+            labels = self.labels_of(g)
+        else:
+            if self._one is None or tuple(self._one.shape[1:]) != (bits.hc, bits.wc):
+                self._one = torch.zeros((1, bits.hc, bits.wc), dtype=torch.uint8, device=bits.status.device)
+            labels = self._one
+        row = bits.regions_enqueue(labels, self.K)
+        self.cur.append(torch.cat([row, labels.sum(dtype=torch.int64).reshape(1)]))
+        if self.keep_cells:
+            self.cells.append(bits.cells_device())
+        self.idx.append(g)
+        if self.plan.is_gop_end(g):
+            self.flush()
+
+    def flush(self):
+        if self.cur:
+            pair = []
+            for dev in (torch.stack(self.cur), torch.stack(self.cells) if self.cells else None):
+                if dev is None:
+                    pair.append((None, None))
+                    continue
+                host = torch.empty(dev.shape, dtype=dev.dtype).pin_memory()
+                host.copy_(dev, non_blocking=True)
+                pair.append((host, dev))
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(pair[0][1].device))
+            self.done.append((ev, pair, self.idx))
+            self.cur, self.cells, self.idx = [], [], []
+
+    def collect(self):
+        """{frame number: ((K, 4) int64 sums in 2^-20 bit, cells of label 1, the (1, hc, wc) float64 cell map or None)}"""
+        from .bitmap import BitMap
+
+        out = {}
+        for ev, ((rows, _), (cells, _)), idx in self.done:
+            ev.synchronize()
+            for n, g in enumerate(idx):
+                row = rows[n].numpy()
+                out[g] = (BitMap.decode(row[:-1], 1, self.K)[0], int(row[-1]), None if cells is None else cells[n].numpy())
+        return out
+
+
 class _PinnedRing:
     """Pictures go to the device through a ring of pinned buffers on a copy stream of their own: a pageable
     `.to(device)` would be a synchronous copy queued BEHIND the previous picture's kernels, i.e. the host could
@@ -306,9 +382,11 @@ class _EncodeRun:
     pictures come from: the GOP streams and their codecs, which frame numbers each stream codes, the .bin sink and
     the bits / quality report.  encode_folder and encode_video supply the pictures and take the reconstructions."""
 
-    def __init__(self, bin_dir, plan, size, gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams, log_cls):
+    def __init__(self, bin_dir, plan, size, gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams, log_cls,
+                 bit_log=None):
         """plan: the GopPlan of the sequence (`gop` is its longest GOP).  nets, gop_streams: see encode_folder.
-        log_cls: the _QualityLog to keep per stream, or None for no report."""
+        log_cls: the _QualityLog to keep per stream, or None for no report.
+        bit_log: None, or (labels_of or None, folder or None) -- keep a _BitLog per stream (encode_folder's bit_map=)."""
         os.makedirs(bin_dir, exist_ok=True)
         self.bin_dir, self.plan, self.n_frames, self.size, self.gop = bin_dir, plan, plan.n_frames, size, gop
         self.dev = torch.device(device)
@@ -320,6 +398,10 @@ class _EncodeRun:
                                          streams=K, coder=coder)
         self.bits = {}
         self.quality = [log_cls(plan) for _ in range(K)] if log_cls else None
+        self.bit_dir = bit_log[1] if bit_log else None
+        self.bit_logs = [_BitLog(plan, bit_log[0], self.bit_dir is not None) for _ in range(K)] if bit_log else None
+        if self.bit_dir:
+            os.makedirs(self.bit_dir, exist_ok=True)
         self.orders = [plan.order(k, K) for k in range(K)]
 
     def global_index(self, k, t):  # picture t of stream k's sequence -> 0-based frame number in the sequence
@@ -351,18 +433,40 @@ class _EncodeRun:
         q_map(g): the q-scale map frame g is coded with, made on the stream that codes it (None: no maps, no launch)."""
         maps_of = lambda k: (lambda t: q_map(self.global_index(k, t))) if q_map else None
         recon_of = lambda k: (lambda t, ref_frame: on_recon(k, self.global_index(k, t), ref_frame)) if on_recon else None
+        bits_of = lambda k: (lambda t, bits: self.bit_logs[k].add(self.global_index(k, t), bits))
         # (GopEncoder reads the split-fp16 range guard once per GOP and raises lib.KernelError: no .bin of a clamped GOP
         # is reported as a success)
         with torch.no_grad():
             self.cenc.encode_gops([frames(k) for k in range(self.K)], q[0], q[1], q[2], sinks=[self._sink(k) for k in range(self.K)],
                                   on_recons=[recon_of(k) for k in range(self.K)], intra=[self.intra(k) for k in range(self.K)],
-                                  q_maps=[maps_of(k) for k in range(self.K)] if q_map else None)
+                                  q_maps=[maps_of(k) for k in range(self.K)] if q_map else None,
+                                  bit_maps=[bits_of(k) for k in range(self.K)] if self.bit_logs else None)
+
+    def _bit_results(self, order):
+        """Collects the bit logs: writes im%05d.npy when a folder was given, returns the report's keys."""
+        values = {}
+        for k, log in enumerate(self.bit_logs):
+            with torch.cuda.stream(self.cenc.streams[k]):
+                log.flush()  # a trailing partial GOP
+            values.update(log.collect())
+        if self.bit_dir:
+            for g in order:
+                np.save(os.path.join(self.bit_dir, f"im{str(g + 1).zfill(5)}.npy"), values[g][2])
+        from .bitmap import REGION_UNIT
+
+        keys = {name: [float(values[g][0][:, c].sum()) / REGION_UNIT for g in order] for c, name in enumerate(BIT_KEYS)}
+        if self.bit_logs[0].K == 2:
+            keys["frame_bits_roi"] = [float(values[g][0][1].sum()) / REGION_UNIT for g in order]
+            keys["frame_bits_bg"] = [float(values[g][0][0].sum()) / REGION_UNIT for g in order]
+            keys["frame_roi_cells"] = [values[g][1] for g in order]
+        return keys
 
     def results(self, report, extras=None):
         """(bits per frame list, size) -- with a report also the rd_report() dictionary, which extras(rd, frame types,
         [the logs' value per frame]) may extend before it is written to `report` (if that is a path)."""
         order = sorted(self.bits)
         bit_list = [self.bits[g] for g in order]
+        bit_keys = self._bit_results(order) if self.bit_logs else None
         if self.quality is None:
             return bit_list, self.size
         h, w = self.size
@@ -375,6 +479,8 @@ class _EncodeRun:
         rd = rd_report(types, bit_list, [values[g][0] for g in order], [values[g][1] for g in order], h * w)
         if extras:
             extras(rd, types, [values[g] for g in order])
+        if bit_keys:
+            rd.update(bit_keys)
         if isinstance(report, (str, os.PathLike)):
             import json
 
@@ -505,7 +611,7 @@ def read_gop_plan(bin_dir, gop=None):
 
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
-                  report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None):
+                  report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -533,7 +639,13 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     the stream that codes it (one small launch per picture) and multiplies the quantisation step of the latent y cell by
     cell; the factors are written to roiq.json beside the .bin files, and decode_folder / decode_video then need the same
     roi.  The .bin format is unchanged.  Without roi_q nothing changes, no kernel is launched and no such file is written
-    (a stale one is removed)."""
+    (a stale one is removed).
+    bit_map: True (needs report), or a folder -- where the bits of every picture went (vcm_ts_amd/bitmap.py: the code lengths
+    of the coder's own symbols, summed per 16x16 cell on the stream that coded the picture).  The report gains
+    frame_bits_mv_z / _mv_y / _z / _y (floats in bits; the mv entries of an I picture are 0) and, with roi,
+    frame_bits_roi / frame_bits_bg / frame_roi_cells: the bits and the number of the cells a box touches -- boxes grown by
+    roi_q.grow when roi_q is on, by 0 otherwise.  A folder also receives im%05d.npy, the (1, hc, wc) float64 bits per cell of
+    each picture.  One more host read per GOP; the .bin files are the same with or without.  None: nothing changes."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
@@ -549,6 +661,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         w, h = first.size
     _roi_args(roi, residuals)
     _roiq_args(roi, roi_q)
+    bit_dir = _bitmap_args(bit_map, report)
     dev = torch.device(device)
     pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
 
@@ -578,7 +691,8 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: uploaded(range(n_frames), 1))
         layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
         run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
-                         (_VideoQualityLog if layer else _QualityLog) if report else None)
+                         (_VideoQualityLog if layer else _QualityLog) if report else None,
+                         _bit_log(bit_map, bit_dir, layer, roi_q))
         write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
         write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
@@ -900,6 +1014,19 @@ def _decode_maps(roi, roi_q, plan, size, dev):
     return lambda t: layer.q_map(t, roi_q)
 
 
+def _bit_log(bit_map, bit_dir, layer, roi_q):
+    """_EncodeRun's bit_log of an encode loop: (labels of frame g or None without a ROI, the folder or None); None without
+    bit_map."""
+    if not bit_map:
+        return None
+    if layer is None:
+        return None, bit_dir
+    from .bitmap import labels_from_boxes
+
+    grow = roi_q.grow if roi_q is not None else 0
+    return (lambda g: labels_from_boxes(layer.boxes(g), layer.size[0], layer.size[1], grow, device=layer.dev)), bit_dir
+
+
 def _roi_report_keys(h, w):
     def keys(rd, types, values):
         from . import roi as X
@@ -937,7 +1064,7 @@ def _open_source(video, size, bit_depth, fps):
 def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantize8=False, gop=32, q=(1.0, 1.0, 1.0),
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
-                 min_gop=1, roi_q=None):
+                 min_gop=1, roi_q=None, bit_map=None):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -953,11 +1080,13 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     then also records the classes' names and borders.
     scenecut, min_gop: as encode_folder; the scan pass reads the file once through the same ring, copy and colour
     conversion (spec, quantize8) as the coding pass.  sequence.json is the same with or without.
-    roi_q: as encode_folder (roiq.json beside the .bin files; sequence.json is the same with or without)."""
+    roi_q: as encode_folder (roiq.json beside the .bin files; sequence.json is the same with or without).
+    bit_map: as encode_folder."""
     from . import yuv as Y
 
     _roi_args(roi, residuals)
     _roiq_args(roi, roi_q)
+    bit_dir = _bitmap_args(bit_map, report)
     reader = _open_source(video, size, bit_depth, fps)  # (every refusal about the file happens here, before any GPU work)
     spec = spec or reader.spec()
     if spec.bit_depth != reader.bit_depth:
@@ -980,7 +1109,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: (x for x, _ in converted(range(n_frames))))
     layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
     run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
-                     _VideoQualityLog if report else None)
+                     _VideoQualityLog if report else None, _bit_log(bit_map, bit_dir, layer, roi_q))
     write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
     write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
     res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
@@ -1111,6 +1240,10 @@ def main(argv=None):
     e.add_argument("--report", metavar="JSON",
                    help="write bpp, PSNR and MS-SSIM of every picture and their I / P / all averages (the key layout of "
                         "the reference's test harness); measured on the device, the .bin files are the same with or without")
+    e.add_argument("--bit-map", nargs="?", const=True, default=None, metavar="DIR",
+                   help="where the bits of every picture went: --report gains frame_bits_mv_z / _mv_y / _z / _y and, with "
+                        "--roi-root, frame_bits_roi / frame_bits_bg / frame_roi_cells; with DIR also im%%05d.npy, the bits per "
+                        "16x16 cell of each picture.  Needs --report or DIR; the .bin files are the same with or without")
     e.add_argument("--scenecut", type=float, default=None, metavar="T",
                    help="also open a GOP with an I picture where consecutive pictures differ by more than T, 0 < T <= 1 (0: "
                         "identical regional luma histograms, 1: disjoint; no default exists -- the right value depends on "
@@ -1196,6 +1329,8 @@ def main(argv=None):
     if a.cmd == "encode":
         if (a.frames is None) == (a.video is None):
             ap.error("give exactly one of --frames and --video")
+        if a.bit_map is True and not a.report:
+            ap.error("--bit-map needs --report (where the regional bit counts go) or a DIR for the per-cell maps")
         if a.video is None and (a.recon_video or a.size or a.quantize8 or a.matrix or a.range or a.siting):
             ap.error("--recon-video, --size, --quantize8, --matrix, --range and --siting belong to --video")
         if a.video is not None and a.recon:
@@ -1248,11 +1383,13 @@ def main(argv=None):
                 bits, size, *rd = encode_video(reader, a.bins, a.recon_video, spec=spec, quantize8=a.quantize8, gop=a.gop, q=q,
                                                device=a.device, precision=a.precision, i_ckpt=a.i_ckpt, p_ckpt=a.p_ckpt,
                                                coder=a.coder, gop_streams=a.gop_streams, report=a.report, roi=roi,
-                                               residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q)
+                                               residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
+                                               bit_map=a.bit_map)
         else:
             bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
                                             coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
-                                            roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q)
+                                            roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
+                                            bit_map=a.bit_map)
         if rd:
             yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
             print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
