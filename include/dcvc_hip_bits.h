@@ -38,6 +38,22 @@
  *     map[n][i / 4][j / 4] of the z-type maps to its label, so that a z-type element is split evenly and exactly over the
  *     4 x 4 cells it covers.  A label map of zeros gives the picture's totals (times 16).
  *   A label >= K adds nothing and ORs DCVC_BITS_BAD_LABEL into *status.
+ *
+ * Ladder sweep:  what the two-step scale-coded latent of one picture would cost by the coder's tables if
+ *   its quantisation step were f times as large and the prior rescaled with it, for K factors f_0 .. f_{K-1} at once.
+ *   y_res and scales_hat are the dense NHWC planes (N, H, W, C), fp32, that dcvc_dual_prior_enc writes (the residual
+ *   before rounding, the predicted scale); after both steps every element has been written once.  Per element and k:
+ *     s   = (int32) rintf(res / f_k)                         (round half to even)
+ *     row = the number of idx_edges[0 .. 254] <= sc / f_k     (the function the dual-prior kernel uses; 256 edges)
+ *     the cost of (row, s) by the rule above;  est[n][k], int64 in 2^-16 bit, is the sum over sample n.
+ *   f_k is whatever float the HOST passes; callers form it as float32(h_k) / float32(100) from integer hundredths h_k,
+ *   the device never forms a factor.  The two divisions are IEEE correctly rounded fp32 divisions: the library is built
+ *   without fast-math and with the compiler's default of correctly rounded division, and it has to stay so -- a
+ *   reciprocal-multiply would move symbols across .5 and scales across an edge.  Everything after the two divisions is
+ *   an integer, so est is defined bit for bit.  With f_k = 1 the candidate is the coded symbol and the coded row:
+ *   est[n][k] equals the sum of dcvc_bits_map_scale's map of sample n.
+ *   A res or sc that is not finite, or a quotient res / f_k at or beyond +-2^31 for any k, makes the element cost 0 for
+ *   EVERY k and ORs DCVC_BITS_BAD_VALUE into *status.  Rows as above (DCVC_BITS_BAD_INDEX).
  */
 #ifndef DCVC_HIP_BITS_H
 #define DCVC_HIP_BITS_H
@@ -56,6 +72,8 @@ extern "C" {
 #define DCVC_BITS_MAX_LABELS 8
 #define DCVC_BITS_BAD_INDEX 1       /* a CDF row out of range (or a row of impossible size) */
 #define DCVC_BITS_BAD_LABEL 2       /* a label >= K */
+#define DCVC_BITS_BAD_VALUE 4       /* sweep: a residual or scale that is not finite, or a symbol that is no int32 */
+#define DCVC_BITS_MAX_LADDER 8      /* sweep: factors per call */
 
 /* Writes exactly N * H * W int32 to `map`.  status: one device int32 the kernels OR DCVC_BITS_BAD_* into (never cleared
  * here).  Refused: a NULL pointer; N outside 1 .. DCVC_BITS_MAX_N; H or W outside 1 .. DCVC_BITS_MAX_SIDE; C odd, < 2 or
@@ -75,6 +93,16 @@ int dcvc_bits_map_factorized(const int32_t *sym, const int32_t *cost, int32_t n_
  * 1 .. DCVC_BITS_MAX_N; hc or wc outside 4 .. DCVC_BITS_MAX_SIDE or no multiple of 4. */
 int dcvc_bits_regions(const int32_t *const *maps, const uint8_t *labels, int32_t K, int64_t *sums, int32_t N, int32_t hc,
                       int32_t wc, int32_t *status, void *stream);
+
+/* The ladder sweep.  factors: HOST array of K floats (read before the launch, not kept).  WRITES all N * K entries of
+ * `est` (8-byte aligned device memory) and nothing else: a memset and one launch on `stream`, one 64-bit integer atomic
+ * add per workgroup and factor.  Refused: a NULL pointer; est not 8-byte aligned; K outside 1 .. DCVC_BITS_MAX_LADDER; a
+ * factor that is not finite or outside [0.1, 10]; N, H, W, n_rows, stride as for dcvc_bits_map_scale; C odd, < 2 or
+ * > DCVC_BITS_MAX_C. */
+int dcvc_bits_sweep_scale(const float *y_res, const float *scales_hat, const float *idx_edges, const float *factors,
+                          int32_t K, const int32_t *cost, int32_t n_rows, int32_t stride, const int32_t *sizes,
+                          const int32_t *offsets, int64_t *est, int32_t N, int32_t C, int32_t H, int32_t W, int32_t *status,
+                          void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,118 @@
+"""Rate control at 1080p on the synthetic clip (the record in profiles/ratectl_1080p.txt).
+
+    python3 tools/ratectl_time.py model [n_frames=32]            how well T_s predicts picture t, and where a controlled
+                                                                 GOP lands against its target (GOP 32, fp16x3)
+    python3 tools/ratectl_time.py files [n_frames=64] [repeats=3]   frames/s of encode_video with and without target_bpp,
+                                                                 alternating in one process (two GOP streams, warm codecs)
+    python3 tools/ratectl_time.py clip FILE.y4m [n_frames=64]    write the clip, for timing `run_codec encode --video` itself
+
+Random (name-seeded) weights: the figures say how the controller behaves on this code, nothing about rate or quality.
+"""
+import os
+import shutil
+import sys
+import tempfile
+import time
+from fractions import Fraction
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from vcm_ts_amd import ratectl  # noqa: E402
+from vcm_ts_amd import run_codec as RC  # noqa: E402
+from vcm_ts_amd import yuv as Y  # noqa: E402
+from vcm_ts_amd.pipeline import GopEncoder, pad_frame  # noqa: E402
+from vcm_ts_amd.synthetic import frames  # noqa: E402
+
+H, W, GOP, STREAMS = 1080, 1920, 32, 2
+DEV = torch.device("cuda:0")
+
+
+def write_clip(path, n):
+    spec = Y.ColorSpec()
+    rgb = frames(0, n, H, W)
+    with Y.Y4MWriter(path, W, H, spec, fps=(30, 1)) as wr:
+        for t in range(n):
+            wr.write(t, Y.rgb_to_yuv420(torch.from_numpy(rgb[t:t + 1]).to(DEV), H, W, spec).cpu().numpy())
+
+
+def model(n):
+    nets = RC._nets(DEV, "fp16x3")
+    rgb = frames(0, n, H, W)
+    xs = [pad_frame(torch.from_numpy(rgb[t:t + 1]).to(DEV)) for t in range(n)]
+    enc = GopEncoder(*nets, gop_size=GOP)
+    with torch.no_grad():
+        coded, total, _ = enc.encode_gop(xs, 1.0, 1.0, 1.0)
+    free = [(len(p) + (14 if k == "I" else 8)) * 8 for k, _, p in coded]
+    print(f"# {n} pictures {W}x{H}, GOP {GOP}, q 1 1 1, fp16x3; free run: {total} bits, {total / (n * H * W):.4f} bpp, "
+          f"I picture {free[0]} bits, P pictures {min(free[1:])} .. {max(free[1:])} bits")
+    for frac in (Fraction(1, 2), Fraction(3, 4), Fraction(3, 2)):
+        target = frac * Fraction(total, n)
+        res = {}
+        with torch.no_grad():
+            _, bits, _ = enc.encode_gop(xs, 1.0, 1.0, 1.0, rate=ratectl.factory(target, GOP), res=res)
+        print(f"# target {float(frac):.2f} x the free run's average = {float(target):.0f} bits per picture "
+              f"({float(target) / (H * W):.4f} bpp): coded {bits} bits, {bits / (n * H * W):.4f} bpp, "
+              f"{bits / float(target * n):.3f} of the target; P pictures from the third on "
+              f"{sum(e[1] for e in res['rate_log'][3:GOP]) / float(sum(e[2] for e in res['rate_log'][3:GOP])):.3f} of their budgets")
+        log = res["rate_log"][:GOP]
+        rc = ratectl.RateControl(target, GOP)
+        ratios = []
+        print("#   picture  q_y   actual bits   budget      predicted from t-2   predicted / actual")
+        for j, (q, a, b, est) in enumerate(log):
+            rc.record(j, q, a, est)  # (a replay of the log: the decisions are the run's)
+            if j >= 3:
+                pred = float(rc.predict(j - 2, q))
+                ratios.append(pred / a)
+                print(f"    {j:4d}   {q / 100:6.2f}  {a:10d}  {float(b):10.0f}  {pred:12.0f}  {pred / a:14.3f}")
+        r = np.array(ratios)
+        print(f"#   predicted / actual over {len(r)} pictures: mean {r.mean():.3f}, min {r.min():.3f}, max {r.max():.3f}")
+
+
+def files(n, repeats):
+    tmp = tempfile.mkdtemp(prefix="dcvc_ratectl_")
+    try:
+        y4m = os.path.join(tmp, "src.y4m")
+        write_clip(y4m, n)
+        nets = [RC._nets(DEV, "fp16x3") for _ in range(STREAMS)]
+        common = dict(gop=GOP, gop_streams=STREAMS, nets=nets)
+
+        def run(target, max_frames=None):
+            out = os.path.join(tmp, "out")
+            shutil.rmtree(out, ignore_errors=True)
+            torch.cuda.synchronize(DEV)
+            t0 = time.time()
+            bits, _ = RC.encode_video(y4m, out, max_frames=max_frames, target_bpp=target, **common)
+            torch.cuda.synchronize(DEV)
+            return len(bits) / (time.time() - t0), sum(bits)
+
+        _, total = run(None)
+        target = 0.75 * total / (n * H * W)
+        run(target)  # (warm-up of both variants done)
+        rates = {None: [], target: []}
+        for _ in range(repeats):
+            for v in (None, target):  # alternating
+                rates[v].append(run(v)[0])
+        print(f"# {n} pictures {W}x{H}, GOP {GOP}, {STREAMS} GOP streams, fp16x3, Y4M file -> .bin folder; frames/s, {repeats} "
+              f"alternating repeats: mean (min .. max)")
+        for v, name in ((None, "without target_bpp"), (target, f"target_bpp={target:.4f}")):
+            a = np.array(rates[v])
+            print(f"  {name:24s} {a.mean():6.2f}  ({a.min():.2f} .. {a.max():.2f})   " + " ".join(f"{x:.2f}" for x in a))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    mode = sys.argv[1] if len(sys.argv) > 1 else ""
+    if mode not in ("model", "files", "clip"):
+        sys.exit(__doc__)
+    if not torch.cuda.is_available():
+        sys.exit("ratectl_time.py measures on the GPU; none is visible")
+    if mode == "model":
+        model(int(sys.argv[2]) if len(sys.argv) > 2 else 32)
+    elif mode == "files":
+        files(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 3)
+    else:
+        write_clip(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 64)

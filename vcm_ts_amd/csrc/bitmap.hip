@@ -5,6 +5,8 @@
 // These are small launches (a 1080p picture has 68 x 120 cells and ~0.8 M symbols) where latency counts, not bandwidth:
 // the planes are (n, k, y, x), so the 64 lanes of a wave read 64 consecutive positions of one channel plane (coalesced),
 // the four waves of a workgroup take every fourth channel, and LDS adds the four partial sums.  No atomics on memory.
+// The ladder sweep (further down) is the one kernel here that divides: two fp32 divisions per element and candidate,
+// integers after them, one 64-bit integer atomic per workgroup and candidate.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -120,6 +122,80 @@ __global__ __launch_bounds__(256) void bits_regions_kernel(const Maps maps, cons
     if (bad) atomicOr(status, DCVC_BITS_BAD_LABEL);
 }
 
+// ---- the ladder sweep ------------------------------------------------------------------------------------------------
+// What the symbols of a scale-coded latent would cost if the quantisation step were f times as large and the prior
+// rescaled with it, for up to DCVC_BITS_MAX_LADDER factors at once.  The planes are dense NHWC, so consecutive lanes
+// read consecutive elements; each lane keeps one int32 sum per factor over its SWEEP_ITEMS elements (a symbol costs
+// less than 2^22 units, so a wave's sum stays below 2^31), the wave adds them by shuffles, the four waves meet in LDS
+// and the workgroup makes ONE 64-bit integer add per factor to est (zeroed by the entry point; integer adds have no
+// order).  Two correctly rounded fp32 divisions per element and factor; everything after them is integer.
+constexpr int SWEEP_THREADS = 256;
+constexpr int SWEEP_ITEMS = 4;
+constexpr int SWEEP_WAVES = SWEEP_THREADS / 64;
+
+struct Factors {
+    float f[DCVC_BITS_MAX_LADDER];
+};
+
+// grid (ceil(per / (SWEEP_THREADS * SWEEP_ITEMS)), N), block SWEEP_THREADS; per = H * W * C elements per sample
+__global__ __launch_bounds__(SWEEP_THREADS) void bits_sweep_kernel(const float *__restrict__ res,
+                                                                   const float *__restrict__ sc,
+                                                                   const float *__restrict__ edges_g, const Factors fac,
+                                                                   const int K, const Table t,
+                                                                   unsigned long long *__restrict__ est, const int64_t per,
+                                                                   int32_t *__restrict__ status) {
+    __shared__ float edges[256];
+    __shared__ int32_t part[SWEEP_WAVES][DCVC_BITS_MAX_LADDER];
+    const int tid = threadIdx.x;
+    edges[tid] = edges_g[tid];
+    __syncthreads();
+    const size_t n = blockIdx.y;
+    const int64_t base = (int64_t)blockIdx.x * (SWEEP_THREADS * SWEEP_ITEMS) + tid;
+    int32_t acc[DCVC_BITS_MAX_LADDER];
+#pragma unroll
+    for (int k = 0; k < DCVC_BITS_MAX_LADDER; ++k) acc[k] = 0;
+    int bad_index = 0, bad_value = 0;
+#pragma unroll
+    for (int j = 0; j < SWEEP_ITEMS; ++j) {
+        const int64_t i = base + (int64_t)j * SWEEP_THREADS;
+        if (i >= per) break;
+        const float r = res[n * per + i], s = sc[n * per + i];
+        // not finite (a NaN compares false), or a symbol that is no int32 for one of the factors: the element costs
+        // nothing for EVERY factor, so that the sums stay comparable with each other
+        bool ok = fabsf(r) <= 3.402823466e38f && fabsf(s) <= 3.402823466e38f;
+        float q[DCVC_BITS_MAX_LADDER];
+#pragma unroll
+        for (int k = 0; k < DCVC_BITS_MAX_LADDER; ++k) {
+            q[k] = k < K ? r / fac.f[k] : 0.f;
+            ok = ok && fabsf(q[k]) < 2147483648.f;
+        }
+        if (!ok) {
+            bad_value = 1;
+            continue;
+        }
+#pragma unroll
+        for (int k = 0; k < DCVC_BITS_MAX_LADDER; ++k)
+            if (k < K) acc[k] += symbol_cost(t, scale_index(s / fac.f[k], edges), (int32_t)rintf(q[k]), bad_index);
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < DCVC_BITS_MAX_LADDER; ++k) {
+        int32_t v = acc[k];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+        if (lane == 0) part[wave][k] = v;
+    }
+    __syncthreads();
+    if (tid < K) {
+        long long v = 0;
+#pragma unroll
+        for (int w = 0; w < SWEEP_WAVES; ++w) v += part[w][tid];
+        if (v) atomicAdd(&est[n * K + tid], (unsigned long long)v);  // (costs are >= 0; est[n][k] was zeroed)
+    }
+    if (bad_index | bad_value)
+        atomicOr(status, (bad_index ? DCVC_BITS_BAD_INDEX : 0) | (bad_value ? DCVC_BITS_BAD_VALUE : 0));
+}
+
 bool map_args_ok(const void *cost, int32_t n_rows, int32_t stride, const void *sizes, const void *offsets, const void *map,
                  int32_t N, int32_t H, int32_t W, const void *status) {
     return cost && sizes && offsets && map && status && n_rows >= 1 && n_rows <= DCVC_BITS_MAX_ROWS && stride >= 2 &&
@@ -163,5 +239,25 @@ extern "C" int dcvc_bits_regions(const int32_t *const *maps, const uint8_t *labe
     if (!maps[0] && !maps[1] && !maps[2] && !maps[3]) return DCVC_E_ARG;
     const Maps m{{maps[0], maps[1], maps[2], maps[3]}};
     bits_regions_kernel<<<dim3(N), dim3(256), 0, (hipStream_t)stream>>>(m, labels, K, sums, hc, wc, status);
+    RET_LAUNCH();
+}
+
+extern "C" int dcvc_bits_sweep_scale(const float *y_res, const float *scales_hat, const float *idx_edges,
+                                     const float *factors, int32_t K, const int32_t *cost, int32_t n_rows, int32_t stride,
+                                     const int32_t *sizes, const int32_t *offsets, int64_t *est, int32_t N, int32_t C,
+                                     int32_t H, int32_t W, int32_t *status, void *stream) {
+    if (!y_res || !scales_hat || !idx_edges || !factors || !map_args_ok(cost, n_rows, stride, sizes, offsets, est, N, H, W, status) ||
+        ((uintptr_t)est & 7) || K < 1 || K > DCVC_BITS_MAX_LADDER || C < 2 || (C & 1) || C > DCVC_BITS_MAX_C)
+        return DCVC_E_ARG;
+    Factors fac{};
+    for (int k = 0; k < K; ++k) {
+        if (!(factors[k] >= 0.1f && factors[k] <= 10.f)) return DCVC_E_ARG;  // (a NaN compares false)
+        fac.f[k] = factors[k];
+    }
+    const Table t{cost, sizes, offsets, n_rows, stride};
+    const int64_t per = (int64_t)H * W * C;
+    if (hipMemsetAsync(est, 0, sizeof(int64_t) * (size_t)N * K, (hipStream_t)stream) != hipSuccess) return DCVC_E_LAUNCH;
+    bits_sweep_kernel<<<dim3(nblk(per, SWEEP_THREADS * SWEEP_ITEMS), N), dim3(SWEEP_THREADS), 0, (hipStream_t)stream>>>(
+        y_res, scales_hat, idx_edges, fac, K, t, (unsigned long long *)est, per, status);
     RET_LAUNCH();
 }

@@ -175,14 +175,7 @@ __global__ void symbols_to_nhwc_kernel(const int32_t *__restrict__ sym, float *_
 // itself (vcm_ts_amd/entropy.py scale_index_edges), so encoder, decoder and reference agree bit
 // for bit.  `edges` has 256 entries, the last one +inf.  Scales below 1e-5 (incl. negatives) sit
 // under every edge -> 0, like the reference's clamp; a NaN compares false everywhere -> 0.
-__device__ __forceinline__ int32_t scale_index(float s, const float *edges) {
-    int lo = 0;  // invariant: edges[0..lo) <= s
-#pragma unroll
-    for (int step = 128; step >= 1; step >>= 1)
-        if (edges[lo + step - 1] <= s) lo += step;
-    return lo;
-}
-
+// (scale_index itself: kernel_common.h -- the ladder sweep of bitmap.hip counts the same edges)
 __global__ void scale_indexes_kernel(const float *__restrict__ scales, int32_t *__restrict__ idx, int64_t n,
                                      const float *__restrict__ edges_g) {
     __shared__ float edges[256];

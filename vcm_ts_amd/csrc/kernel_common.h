@@ -37,6 +37,18 @@ constexpr float ACT_LIMIT = F16_MAX / ACT_SCALE;  // an output beyond it would b
 
 __device__ __forceinline__ float act(float v, float slope) { return v > 0.f ? v : v * slope; }
 
+// ---- CDF row of a scale ------------------------------------------------------------------------------------------------
+// The number of bin edges <= s among edges[0 .. 254] (256 entries, the last one +inf and never read), by bisection; the
+// dual-prior kernels (entropy_kernels.hip, where the edges are explained) and the ladder sweep (bitmap.hip) share it, so
+// that a swept scale lands in the row the coder would use.  A NaN compares false everywhere -> 0.
+__device__ __forceinline__ int32_t scale_index(float s, const float *edges) {
+    int lo = 0;  // invariant: edges[0..lo) <= s
+#pragma unroll
+    for (int step = 128; step >= 1; step >>= 1)
+        if (edges[lo + step - 1] <= s) lo += step;
+    return lo;
+}
+
 // ---- packed weights ---------------------------------------------------------------------------------------------------
 // A weight enters a split-fp16 layout as sv = w * WGT_SCALE clamped to +-F16_MAX, then split_f16(sv).  The CLAMP is each
 // packer's own line, because three policies exist on purpose:

@@ -439,12 +439,37 @@ class CodecBase(nn.Module):
 
         return BitMap.from_planes(self._cost_tables(), planes, N)
 
-    def _compress_result(self, res, pending, defer, check_range, bits=None):
+    def _sweep_arg(self, sweep, graph=False):
+        """The sweep argument of DMC.compress() (include/dcvc_hip_bits.h, ratectl.RateSweep): None, or a ladder of step
+        factors in hundredths -> the checked ladder.  Refused by name: a bad ladder, a sweep with graph replay, a sweep in
+        .train() mode."""
+        if sweep is None:
+            return None
+        from .ratectl import check_ladder
+
+        if graph:
+            raise NotImplementedError("sweep: graph replay with a rate sweep is not supported (pass graph=False)")
+        if self.training:
+            raise ValueError("sweep: a rate sweep is for .eval() mode (training with a sweep is not supported)")
+        return check_ladder(sweep)
+
+    def _rate_sweep(self, ladder, y: View, r):
+        """The ladder sweep of latent `y` (r: its _dual_prior_encode result with stats and residuals), enqueued on the
+        launch stream right behind the second dual-prior step that completed the planes, together with the copy of its
+        (N, K) sums to pinned host memory -- ahead of the symbol planes, so the sums are there when they are."""
+        from .ratectl import RateSweep
+
+        return RateSweep.enqueue(self._cost_tables(), self.engine().index_edges(self._distribution), r["y_res"],
+                                 r["scales_hat"], y.N, y.C, y.H, y.W, ladder)
+
+    def _compress_result(self, res, pending, defer, check_range, bits=None, sweep=None):
         """Tail of compress(): `res` (the codec's own keys) plus "pending" when deferred, else plus the payloads, after
         the split-fp16 range guard (DMC.compress says when a caller reads it itself).  bits: the picture's BitMap, added
-        as "bit_map" when there is one."""
+        as "bit_map" when there is one; sweep: its RateSweep, added as "rate_sweep"."""
         if bits is not None:
             res = {**res, "bit_map": bits}
+        if sweep is not None:
+            res = {**res, "rate_sweep": sweep}
         if defer:
             return {**res, "pending": pending}
         streams = pending.finish_all()
@@ -805,11 +830,12 @@ class DMC(CodecBase):
     def _views_of_dpb(self, dpb):
         return {k: self._dpb_in(k, dpb.get(k)) for k in DPB_KEYS}
 
-    def _run(self, x, dpb, mv_y_q_scale, y_q_scale, mode, tape=None, q_map=None):
+    def _run(self, x, dpb, mv_y_q_scale, y_q_scale, mode, tape=None, q_map=None, sweep=None):
         """mode 'estimate' (forward_one_frame, unclamped recon as video_model.py:535) or
         'compress' (recon clamped to [0, 1] exactly as the decoder will, :413, so that the
         encoder's own DPB is bit-identical to the decoder's and no decode pass is needed).
-        q_map: see compress() -- the step of y only, mv_y keeps its scalar."""
+        q_map: see compress() -- the step of y only, mv_y keeps its scalar.
+        sweep: see compress() -- a checked ladder; the y dual prior then also writes its residual and scale planes."""
         e = self.engine()
         net = self._net
         N, _, H, W = x.shape
@@ -864,8 +890,9 @@ class DMC(CodecBase):
         fusion = self._y_prior(net, dv, c3, z_hat)
         y_hat = net.buf(f"dpb{k}.ref_y", like=y, C=96)
         r_y = self._dual_prior_encode("y", y, fusion, "y_spatial_prior", y_hat, self.P("y_q_basic").reshape(-1), q_y,
-                                      want_stats=(mode != "compress"), want_symbols=(mode == "compress"),
-                                      want_res=(mode == "train"), qkey="y", q_map=q_map)
+                                      want_stats=(mode != "compress" or sweep is not None), want_symbols=(mode == "compress"),
+                                      want_res=(mode == "train" or sweep is not None), qkey="y", q_map=q_map)
+        rate_sweep = self._rate_sweep(sweep, y, r_y) if sweep is not None else None
         dec_feature = net.contextual_decoder(y_hat, c2, c3)
         feature = net.buf(f"dpb{k}.ref_feature", N=N, H=H, W=W, C=64)
         recon = net.buf(f"dpb{k}.ref_frame", N=N, H=H, W=W, C=3)
@@ -873,7 +900,7 @@ class DMC(CodecBase):
         return dict(N=N, H=H, W=W, x3=x3, recon=recon, feature=feature, y_hat=y_hat, mv_y_hat=mv_y_hat,
                     warp_frame=warp_frame, r_mv=r_mv, r_y=r_y, mv_z_hat=mv_z_hat, z_hat=z_hat, sym_mv_z=sym_mv_z,
                     sym_z=sym_z, est_mv=est_mv, mv_hat=mv_hat, c1=c1, c2=c2, c3=c3, y=y, mv_y=mv_y, z=z, mv_z=mv_z,
-                    q_mv=q_mv, q_y=q_y, dv=dv, fusion_y=fusion)
+                    q_mv=q_mv, q_y=q_y, dv=dv, fusion_y=fusion, rate_sweep=rate_sweep)
 
     @staticmethod
     def _dpb_out(o):
@@ -1046,7 +1073,7 @@ class DMC(CodecBase):
 
     @torch.no_grad()
     def compress(self, x, dpb, mv_y_q_scale, y_q_scale, defer=False, coder="host", graph=False, check_range=True,
-                 q_map=None, bit_map=False):
+                 q_map=None, bit_map=False, sweep=None):
         """defer=True returns {"dpb", "pending"}: call pending.finish() later for the bytes.
         check_range: a call that returns bytes (defer=False) raises lib.KernelError if a split-fp16 kernel met an
         activation beyond +-8188 (one status read after the picture is done); pipelined callers (defer=True, or
@@ -1057,10 +1084,16 @@ class DMC(CodecBase):
         q_map: ROI-weighted quantisation (roi.q_map; CodecBase._qmap says what is taken): one factor per 16x16 cell on the
         quantisation step of y.  decompress() needs the same map.  None: exactly the launches and bytes without it.
         bit_map=True: the result also carries "bit_map", a bitmap.BitMap of the picture's six planes (CodecBase._bit_map).
-        False: exactly the launches, bytes and result keys without it."""
+        False: exactly the launches, bytes and result keys without it.
+        sweep: a ladder of step factors in hundredths (ratectl.LADDER) -- the result also carries "rate_sweep", a
+        ratectl.RateSweep: what the latent y would cost, by the coder's own tables, with its quantisation step multiplied
+        by each factor (one row per batch element; the column of 100 is the y total of the bit map).  The y dual prior
+        then also writes its residual and scale planes, and one small kernel follows it.  Bytes and DPB are unchanged.
+        None: exactly the launches, bytes and result keys without it."""
         if self.entropy_coder is None:
             raise RuntimeError("call update() before compress()/decompress()")
         self._qmap(q_map, x.shape[0], x.shape[2], x.shape[3], graph=graph)  # (every refusal, before any GPU work)
+        sweep = self._sweep_arg(sweep, graph=graph)
         bits = None
         if graph:
             self._bit_map(bit_map, None, 0, graph=True)  # (refused, before any GPU work)
@@ -1069,13 +1102,13 @@ class DMC(CodecBase):
             g = self._compress_graph(x, dpb, mv_y_q_scale, y_q_scale)
             d, o, pending = g["out"], g["views"], g["pending"]
         else:
-            o = self._run(x, dpb, mv_y_q_scale, y_q_scale, "compress", q_map=q_map)
+            o = self._run(x, dpb, mv_y_q_scale, y_q_scale, "compress", q_map=q_map, sweep=sweep)
             # N > 1: a batch of rate points, one independent stream per element ("bit_streams")
             planes = self._planes(o)
             bits = self._bit_map(bit_map, planes, o["N"])
             pending = self._stage(planes, o["N"], coder)
             d = self._dpb_out(o)
-        return self._compress_result({"dbp": d, "dpb": d, "_views": o}, pending, defer, check_range, bits)
+        return self._compress_result({"dbp": d, "dpb": d, "_views": o}, pending, defer, check_range, bits, o.get("rate_sweep"))
 
     @torch.no_grad()
     def decompress(self, dpb, string, height, width, mv_y_q_scale, y_q_scale, coder=None, defer_check=False,

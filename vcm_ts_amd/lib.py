@@ -223,6 +223,7 @@ _SIGS = {
     "dcvc_bits_map_scale": [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp],
     "dcvc_bits_map_factorized": [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp],
     "dcvc_bits_regions": [vp, vp, i32, vp, i32, i32, i32, vp, vp],
+    "dcvc_bits_sweep_scale": [vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp],
 }
 
 # include/dcvc_hip_metrics.h (same library; listed apart because HIP_SYMBOLS is what the three kernel headers declare)
@@ -230,7 +231,8 @@ METRICS_SYMBOLS = ["dcvc_ms_ssim", "dcvc_ms_ssim_grad", "dcvc_ms_ssim_workspace_
 COLOR_SYMBOLS = ["dcvc_color_coeffs", "dcvc_yuv420_to_rgb", "dcvc_rgb_to_yuv420"]  # include/dcvc_hip_color.h
 ROI_SYMBOLS = ["dcvc_roi_residual", "dcvc_roi_fuse", "dcvc_roi_sse", "dcvc_roi_qmap"]  # include/dcvc_hip_roi.h
 SCENE_SYMBOLS = ["dcvc_scene_hist"]  # include/dcvc_hip_scene.h
-BITS_SYMBOLS = ["dcvc_bits_map_scale", "dcvc_bits_map_factorized", "dcvc_bits_regions"]  # include/dcvc_hip_bits.h
+BITS_SYMBOLS = ["dcvc_bits_map_scale", "dcvc_bits_map_factorized", "dcvc_bits_regions",
+                "dcvc_bits_sweep_scale"]  # include/dcvc_hip_bits.h
 HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS + ROI_SYMBOLS + SCENE_SYMBOLS + BITS_SYMBOLS] +
                      ["dcvc_cdf_table_cols", "dcvc_conv_pack_size", "dcvc_conv_pack_size_paired", "dcvc_conv_small_pack_bytes", "dcvc_conv_k32_pack_bytes", "dcvc_conv_tile_rows", "dcvc_conv_chan_partial_parts", "dcvc_hip_version", "dcvc_conv_wgrad_scratch_min",
                       "dcvc_drans_default_lanes", "dcvc_drans_scratch_words"])

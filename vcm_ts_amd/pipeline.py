@@ -85,7 +85,8 @@ class GopEncoder:
         self.i_net.update()
         self.p_net.update()
 
-    def encode_gop(self, frames, q_i, q_mv_y, q_y, sink=None, on_recon=None, intra=None, q_maps=None, bit_maps=None):
+    def encode_gop(self, frames, q_i, q_mv_y, q_y, sink=None, on_recon=None, intra=None, q_maps=None, bit_maps=None, rate=None,
+                   res=None):
         """frames: iterable of padded (1, 3, H, W) device tensors, the first coded as an I
         picture.  intra: the set of picture numbers (positions in `frames`) coded as I pictures -- 0 among them, no two
         further apart than gop_size -- instead of every multiple of gop_size (scenecut.GopPlan).  Returns (list of payload bytes with their headers' q indexes, total bits of
@@ -95,17 +96,24 @@ class GopEncoder:
         made on the current stream when the picture is about to be coded) or None for none.  The payloads do not carry
         the maps: decode_picture needs the same ones.
         bit_maps: a callable (picture number, bitmap.BitMap) -> None.  Every picture is then coded with bit_map=True and its
-        map handed over as soon as its kernels are enqueued (nothing is read back here); payloads are unchanged."""
-        res = {}
+        map handed over as soon as its kernels are enqueued (nothing is read back here); payloads are unchanged.
+        rate: rate control (vcm_ts_amd/ratectl.py) -- a callable that makes one ratectl.RateControl per GOP
+        (ratectl.factory).  q_i and q_mv_y stay what they are and q_y becomes the STARTING point: every P picture is coded
+        with sweep= and with the q_y its GOP's controller decides from the pictures already retired (picture t from t - 2:
+        the software pipeline below is untouched), and its header carries that index.  A GOP's bytes depend on its own
+        pictures and the target only.  res: a dictionary that receives "rate_log", the controllers' logs in picture order
+        [(q index, actual bits, budget or None, sweep row or None)].  None: exactly the launches and bytes without it."""
+        res = {} if res is None else res
         for _ in self.encode_steps(frames, q_i, q_mv_y, q_y, res, sink=sink, on_recon=on_recon, intra=intra, q_maps=q_maps,
-                                   bit_maps=bit_maps):
+                                   bit_maps=bit_maps, rate=rate):
             pass
         return res["coded"], res["bits"], res["dpb"]
 
-    def encode_steps(self, frames, q_i, q_mv_y, q_y, res, sink=None, on_recon=None, intra=None, q_maps=None, bit_maps=None):
+    def encode_steps(self, frames, q_i, q_mv_y, q_y, res, sink=None, on_recon=None, intra=None, q_maps=None, bit_maps=None,
+                     rate=None):
         """encode_gop as a generator that yields after every picture it has enqueued, so that several
         encoders can be interleaved by one host thread (ConcurrentGopEncoder).  Fills `res` with
-        "coded", "bits", "dpb" when exhausted."""
+        "coded", "bits", "dpb" (with `rate` also "rate_log") when exhausted."""
         q_i, qi_idx = S.get_rounded_q(q_i)
         q_mv_y, qmv_idx = S.get_rounded_q(q_mv_y)
         q_y, qy_idx = S.get_rounded_q(q_y)
@@ -115,15 +123,22 @@ class GopEncoder:
         if bit_maps is not None and self.graphs:
             raise NotImplementedError("bit_maps: graph replay with a bit map is not supported")
         want_bits = bit_maps is not None
+        if rate is not None and self.graphs:
+            raise NotImplementedError("rate: graph replay with rate control is not supported (GopEncoder(graphs=False))")
+        controls, ctl = [], None  # (rate control: one controller per GOP, made at its I picture)
 
         def retire(item):  # host half of a picture: wait for its planes, rANS-code them
             nonlocal bits
-            kind, q, pending, t, guards = item
+            kind, q, pending, t, guards, rated = item
             payload = pending.finish()
             for check in guards:  # range guard of the split-fp16 kernels: a GOP whose activations were
                 check()           # clamped must not be written out as if it were fine -- raises lib.KernelError
             out.append((kind, q, payload))
-            bits += (len(payload) + (14 if kind == "I" else 8)) * 8  # >IIHI / >HHI headers
+            actual = (len(payload) + (14 if kind == "I" else 8)) * 8  # >IIHI / >HHI headers
+            bits += actual
+            if rated is not None:  # (the sums rode ahead of the planes finish() has just waited for: no new wait)
+                c, j, sweep = rated
+                c.record(j, q[-1], actual, None if sweep is None else sweep.sums()[0])
             if sink is not None:
                 sink(kind, q, payload, t)
 
@@ -137,6 +152,17 @@ class GopEncoder:
                 r = self.i_net.compress(x, q_i, defer=True, coder=self.coder, check_range=False, q_map=qm, bit_map=want_bits)
                 dpb = intra_dpb(r["x_hat"])
                 item = ("I", (qi_idx,), r["pending"], t)
+                if rate is not None:
+                    ctl = rate()
+                    controls.append(ctl)
+                    rated = (ctl, 0, None)
+            elif rate is not None:
+                qy_t = ctl.decide(t - last_i, qy_idx)
+                r = self.p_net.compress(x, dpb, q_mv_y, qy_t / 100, defer=True, coder=self.coder, check_range=False, q_map=qm,
+                                        bit_map=want_bits, sweep=ctl.ladder)
+                dpb = r["dpb"]
+                item = ("P", (qmv_idx, qy_t), r["pending"], t)
+                rated = (ctl, t - last_i, r["rate_sweep"])
             else:
                 r = self.p_net.compress(x, dpb, q_mv_y, q_y, defer=True, coder=self.coder, graph=self.graphs, check_range=False,
                                         q_map=qm, bit_map=want_bits)
@@ -151,7 +177,7 @@ class GopEncoder:
             guards = ()
             if (t % self.gop == self.gop - 1) if intra is None else (t + 1 in intra or t + 1 - last_i >= self.gop):
                 guards = tuple(c for c in (self.i_net.engine().status_snapshot(), self.p_net.engine().status_snapshot()) if c)
-            item = item + (guards,)
+            item = item + (guards, rated if rate is not None else None)
             if on_recon is not None:  # reconstruction == what the decoder will produce (clamped)
                 on_recon(t, dpb["ref_frame"])
             if prev is not None:
@@ -164,6 +190,8 @@ class GopEncoder:
                 self.i_net.engine().check_status()  # after a whole GOP the snapshot above has already covered everything
                 self.p_net.engine().check_status()  # and nothing is drained here)
         res.update(coded=out, bits=bits, dpb=dpb)
+        if rate is not None:
+            res["rate_log"] = [entry for c in controls for entry in c.log]
 
     def decode_gop(self, coded, height, width):
         """Inverse of encode_gop (the reference decoder path): returns the list of x_hat."""
@@ -201,12 +229,15 @@ class ConcurrentGopEncoder:
         self.device = dev
         self.streams = [torch.cuda.Stream(dev) for _ in self.encoders]
 
-    def encode_gops(self, sequences, q_i, q_mv_y, q_y, sinks=None, on_recons=None, intra=None, q_maps=None, bit_maps=None):
+    def encode_gops(self, sequences, q_i, q_mv_y, q_y, sinks=None, on_recons=None, intra=None, q_maps=None, bit_maps=None,
+                    rate=None):
         """sequences: up to `streams` iterables of padded pictures (one sequence of whole GOPs each; an iterable is
         pulled INSIDE its stream, so a generator may upload its pictures there).  Returns a list of
         (coded, bits, dpb) in the same order.  sinks / on_recons: per-sequence callbacks of GopEncoder.encode_gop; intra:
         per-sequence sets of the picture numbers coded as I (GopEncoder.encode_gop), None for every multiple of gop_size.
-        q_maps, bit_maps: per-sequence callables of GopEncoder.encode_gop (each is called inside its sequence's stream)."""
+        q_maps, bit_maps: per-sequence callables of GopEncoder.encode_gop (each is called inside its sequence's stream).
+        rate: ONE factory of GopEncoder.encode_gop for all sequences (a controller belongs to one GOP, so the bytes are
+        those of sequential coding); the sequences' logs are then in self.rate_logs, in the same order."""
         assert len(sequences) <= len(self.encoders)
         cur = torch.cuda.current_stream(self.device)
         results = [{} for _ in sequences]
@@ -217,7 +248,7 @@ class ConcurrentGopEncoder:
                                                       on_recon=on_recons[k] if on_recons else None,
                                                       intra=intra[k] if intra else None,
                                                       q_maps=q_maps[k] if q_maps else None,
-                                                      bit_maps=bit_maps[k] if bit_maps else None))
+                                                      bit_maps=bit_maps[k] if bit_maps else None, rate=rate))
         live = list(range(len(gens)))
         while live:
             for k in list(live):
@@ -228,6 +259,7 @@ class ConcurrentGopEncoder:
                         live.remove(k)
         for s in self.streams[: len(sequences)]:
             cur.wait_stream(s)
+        self.rate_logs = [r.get("rate_log") for r in results]
         return [(r["coded"], r["bits"], r["dpb"]) for r in results]
 
     def decode_gops(self, coded_gops, height, width):

@@ -289,6 +289,19 @@ def _bitmap_args(bit_map, report):
     return os.fspath(bit_map)
 
 
+def _rate_args(target_bpp, q_range, height, width, gop):
+    """target_bpp= / q_range= of an encode loop -> the `rate` factory of GopEncoder.encode_gop (one ratectl.RateControl
+    per GOP, target_bpp * height * width bits per picture of the UNPADDED size) or None, refused by name before any GPU
+    work: a target that is not above 0, a q_range without a target, lowest > highest, q-scales outside [0.01, 655]."""
+    if target_bpp is None:
+        if q_range is not None:
+            raise ValueError("q_range= belongs to target_bpp= (the range the rate control may move q_y in)")
+        return None
+    from . import ratectl
+
+    return ratectl.factory(ratectl.target_bits_of(target_bpp, height, width), int(gop), ratectl.q_index_range(q_range))
+
+
 BIT_KEYS = ("frame_bits_mv_z", "frame_bits_mv_y", "frame_bits_z", "frame_bits_y")  # (bitmap.COMPONENTS' order)
 
 
@@ -383,11 +396,13 @@ class _EncodeRun:
     the bits / quality report.  encode_folder and encode_video supply the pictures and take the reconstructions."""
 
     def __init__(self, bin_dir, plan, size, gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams, log_cls,
-                 bit_log=None):
+                 bit_log=None, rate=None):
         """plan: the GopPlan of the sequence (`gop` is its longest GOP).  nets, gop_streams: see encode_folder.
         log_cls: the _QualityLog to keep per stream, or None for no report.
-        bit_log: None, or (labels_of or None, folder or None) -- keep a _BitLog per stream (encode_folder's bit_map=)."""
+        bit_log: None, or (labels_of or None, folder or None) -- keep a _BitLog per stream (encode_folder's bit_map=).
+        rate: None, or the factory of _rate_args (encode_folder's target_bpp=)."""
         os.makedirs(bin_dir, exist_ok=True)
+        self.rate, self.rate_log = rate, {}
         self.bin_dir, self.plan, self.n_frames, self.size, self.gop = bin_dir, plan, plan.n_frames, size, gop
         self.dev = torch.device(device)
         self.n_gops = plan.n_gops
@@ -440,7 +455,10 @@ class _EncodeRun:
             self.cenc.encode_gops([frames(k) for k in range(self.K)], q[0], q[1], q[2], sinks=[self._sink(k) for k in range(self.K)],
                                   on_recons=[recon_of(k) for k in range(self.K)], intra=[self.intra(k) for k in range(self.K)],
                                   q_maps=[maps_of(k) for k in range(self.K)] if q_map else None,
-                                  bit_maps=[bits_of(k) for k in range(self.K)] if self.bit_logs else None)
+                                  bit_maps=[bits_of(k) for k in range(self.K)] if self.bit_logs else None, rate=self.rate)
+        if self.rate is not None:
+            for k, log in enumerate(self.cenc.rate_logs):
+                self.rate_log.update({self.global_index(k, t): entry for t, entry in enumerate(log)})
 
     def _bit_results(self, order):
         """Collects the bit logs: writes im%05d.npy when a folder was given, returns the report's keys."""
@@ -481,6 +499,9 @@ class _EncodeRun:
             extras(rd, types, [values[g] for g in order])
         if bit_keys:
             rd.update(bit_keys)
+        if self.rate is not None:  # (the q-scale each picture's y was coded with -- an I picture's is q_i -- and the budget
+            rd["frame_q_y"] = [self.rate_log[g][0] / 100 for g in order]  # its controller gave it; null where none was)
+            rd["frame_bits_target"] = [None if self.rate_log[g][2] is None else float(self.rate_log[g][2]) for g in order]
         if isinstance(report, (str, os.PathLike)):
             import json
 
@@ -611,7 +632,8 @@ def read_gop_plan(bin_dir, gop=None):
 
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
-                  report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None):
+                  report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None, target_bpp=None,
+                  q_range=None):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -645,7 +667,13 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     frame_bits_mv_z / _mv_y / _z / _y (floats in bits; the mv entries of an I picture are 0) and, with roi,
     frame_bits_roi / frame_bits_bg / frame_roi_cells: the bits and the number of the cells a box touches -- boxes grown by
     roi_q.grow when roi_q is on, by 0 otherwise.  A folder also receives im%05d.npy, the (1, hc, wc) float64 bits per cell of
-    each picture.  One more host read per GOP; the .bin files are the same with or without.  None: nothing changes."""
+    each picture.  One more host read per GOP; the .bin files are the same with or without.  None: nothing changes.
+    target_bpp: rate control (vcm_ts_amd/ratectl.py) -- a target in bits per pixel of the unpadded picture.
+    `q` is then the starting point: q[0] and q[1] stay the I and mv_y settings of every picture, and q[2] is what the first
+    two P pictures of each GOP are coded with; from the third on the GOP's controller moves q_y inside q_range (a
+    (lowest, highest) pair of q-scales, default the wire range [0.01, 655]).  The I picture is not controlled.  Every .bin
+    header carries its own q indexes, so decoding needs nothing new.  With report the dictionary gains frame_q_y and
+    frame_bits_target (null where nothing was decided).  None: no launch, file, key or byte changes."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
@@ -662,6 +690,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     _roi_args(roi, residuals)
     _roiq_args(roi, roi_q)
     bit_dir = _bitmap_args(bit_map, report)
+    rate = _rate_args(target_bpp, q_range, h, w, gop)
     dev = torch.device(device)
     pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
 
@@ -692,7 +721,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
         run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
                          (_VideoQualityLog if layer else _QualityLog) if report else None,
-                         _bit_log(bit_map, bit_dir, layer, roi_q))
+                         _bit_log(bit_map, bit_dir, layer, roi_q), rate)
         write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
         write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
@@ -1064,7 +1093,7 @@ def _open_source(video, size, bit_depth, fps):
 def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantize8=False, gop=32, q=(1.0, 1.0, 1.0),
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
-                 min_gop=1, roi_q=None, bit_map=None):
+                 min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -1081,7 +1110,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     scenecut, min_gop: as encode_folder; the scan pass reads the file once through the same ring, copy and colour
     conversion (spec, quantize8) as the coding pass.  sequence.json is the same with or without.
     roi_q: as encode_folder (roiq.json beside the .bin files; sequence.json is the same with or without).
-    bit_map: as encode_folder."""
+    bit_map, target_bpp, q_range: as encode_folder."""
     from . import yuv as Y
 
     _roi_args(roi, residuals)
@@ -1092,6 +1121,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     if spec.bit_depth != reader.bit_depth:
         raise ValueError(f"the file holds {reader.bit_depth}-bit samples, the colour description says {spec.bit_depth}")
     h, w = reader.height, reader.width
+    rate = _rate_args(target_bpp, q_range, h, w, gop)
     n_frames = reader.n_frames if max_frames is None else min(reader.n_frames, int(max_frames))
     if n_frames < 1:
         raise ValueError(f"{getattr(reader, 'path', video)}: no frames")
@@ -1109,7 +1139,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: (x for x, _ in converted(range(n_frames))))
     layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
     run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
-                     _VideoQualityLog if report else None, _bit_log(bit_map, bit_dir, layer, roi_q))
+                     _VideoQualityLog if report else None, _bit_log(bit_map, bit_dir, layer, roi_q), rate)
     write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
     write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
     res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
@@ -1244,6 +1274,13 @@ def main(argv=None):
                    help="where the bits of every picture went: --report gains frame_bits_mv_z / _mv_y / _z / _y and, with "
                         "--roi-root, frame_bits_roi / frame_bits_bg / frame_roi_cells; with DIR also im%%05d.npy, the bits per "
                         "16x16 cell of each picture.  Needs --report or DIR; the .bin files are the same with or without")
+    e.add_argument("--target-bpp", type=float, default=None, metavar="B",
+                   help="rate control: aim at B bits per pixel by moving q_y from P picture to P picture inside each GOP "
+                        "(--q, or 1 1 1, is the starting point and stays the I and mv_y setting; the I picture is not "
+                        "controlled).  The step is chosen from a sweep of the picture's own code lengths, no fitted model; "
+                        "--report gains frame_q_y and frame_bits_target; decode needs nothing new")
+    e.add_argument("--q-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="with --target-bpp: the q-scales q_y may take (default the wire range 0.01 655)")
     e.add_argument("--scenecut", type=float, default=None, metavar="T",
                    help="also open a GOP with an I picture where consecutive pictures differ by more than T, 0 < T <= 1 (0: "
                         "identical regional luma histograms, 1: disjoint; no default exists -- the right value depends on "
@@ -1361,6 +1398,15 @@ def main(argv=None):
             ap.error(str(ex))
         if (a.rate_count is None) != (a.quality is None) or (a.q is not None and a.rate_count is not None):
             ap.error("give either --q, or --rate-count together with --quality")
+        if a.q_range is not None and a.target_bpp is None:
+            ap.error("--q-range belongs to --target-bpp")
+        if a.target_bpp is not None:
+            if a.rate_count is not None and a.rate_count > 1:
+                ap.error("--target-bpp controls one rate point; --rate-count selects several (give --q as the starting point)")
+            try:
+                _rate_args(a.target_bpp, a.q_range, 1, 1, a.gop)
+            except ValueError as ex:
+                ap.error(f"--target-bpp / --q-range: {ex}")
         q = tuple(a.q) if a.q is not None else (1.0, 1.0, 1.0)
         if a.rate_count is not None:
             from .dmc import DMC
@@ -1384,12 +1430,12 @@ def main(argv=None):
                                                device=a.device, precision=a.precision, i_ckpt=a.i_ckpt, p_ckpt=a.p_ckpt,
                                                coder=a.coder, gop_streams=a.gop_streams, report=a.report, roi=roi,
                                                residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
-                                               bit_map=a.bit_map)
+                                               bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range)
         else:
             bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
                                             coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
                                             roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
-                                            bit_map=a.bit_map)
+                                            bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range)
         if rd:
             yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
             print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
