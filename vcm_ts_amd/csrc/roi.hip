@@ -16,6 +16,7 @@
 #include "dcvc_hip.h"
 #include "dcvc_hip_roi.h"
 #include "kernel_common.h"
+#include "roi_common.h"
 
 #pragma clang fp contract(off)
 
@@ -47,8 +48,6 @@ struct Tile {
     int count;
     unsigned part[4][3];
 };
-
-__device__ __forceinline__ int code8(float v) { return (int)rintf(255.0f * fminf(fmaxf(v, 0.0f), 1.0f)); }
 
 // the 8-bit codes of this lane's four pixels of one row and plane (0 beyond the width)
 __device__ __forceinline__ void load_codes(const float *row, int x0, int W, int vec, int k[4]) {
@@ -126,28 +125,9 @@ __global__ __launch_bounds__(256) void roi_kernel(const RoiArgs p) {
         if (tid < DCVC_ROI_MAX_CLASSES) t.border[tid] = p.cls[tid].border, t.shrink[tid] = p.cls[tid].shrink;
         __syncthreads();
     }
-    if (wave == 0) {  // cull the list against this tile, in order
-        int count = 0;
-        for (int base = 0; base < p.n; base += 64) {
-            const int i = base + lane;
-            bool keep = false;
-            int4 bx = make_int4(0, 0, 0, 0);
-            int c = 0;
-            if (i < p.n) {
-                const dcvc_roi_box_t rec = p.boxes[i];
-                c = rec.cls & (DCVC_ROI_MAX_CLASSES - 1);
-                const int s = MODE == SSE ? t.shrink[c] : 0;
-                bx = make_int4(rec.x1 + s, rec.y1 + s, rec.x2 - s, rec.y2 - s);
-                keep = bx.z > bx.x && bx.w > bx.y && bx.x < tx0 + TILE_W && bx.z > tx0 && bx.y < ty0 + TILE_H && bx.w > ty0;
-            }
-            const unsigned long long bal = __ballot(keep);
-            if (keep) {
-                const int at = count + __popcll(bal & ((1ull << lane) - 1ull));
-                t.box[at] = bx;
-                t.cls[at] = (uint8_t)c;
-            }
-            count += __popcll(bal);
-        }
+    if (wave == 0) {  // cull the list against this tile, in order (roi_common.h)
+        const int count = roi_cull(p.boxes, p.n, lane, tx0, ty0, tx0 + TILE_W, ty0 + TILE_H, t.box, t.cls,
+                                   [&](int c) { return MODE == SSE ? t.shrink[c] : 0; });
         if (lane == 0) t.count = count;
     }
     __syncthreads();
@@ -304,26 +284,7 @@ __global__ __launch_bounds__(256) void roi_qmap_kernel(const QmapArgs p) {
     p.map[cell] = v;
 }
 
-bool aligned(const void *p, size_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
-bool size_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && H <= DCVC_ROI_MAX_SIDE && W <= DCVC_ROI_MAX_SIDE; }
-
-bool planes_ok(const float *p, int32_t rs, int64_t ps, int32_t H, int32_t W) {
-    return p && rs >= W && ps >= (int64_t)(H - 1) * rs + W;
-}
-
 bool vec_planes(const float *p, int32_t rs, int64_t ps) { return aligned(p, 16) && rs % 4 == 0 && ps % 4 == 0; }
-
-bool boxes_ok(const dcvc_roi_box_t *host, const dcvc_roi_box_t *dev, int32_t n, int32_t H, int32_t W, int32_t n_classes) {
-    if (n < 0 || n > DCVC_ROI_MAX_BOXES || (n > 0 && (!host || !dev))) return false;
-    for (int32_t i = 0; i < n; ++i) {
-        const dcvc_roi_box_t &b = host[i];
-        if (b.x1 < 0 || b.x1 > W || b.x2 < 0 || b.x2 > W || b.y1 < 0 || b.y1 > H || b.y2 < 0 || b.y2 > H || b.cls < 0 ||
-            b.cls >= n_classes)
-            return false;
-    }
-    return true;
-}
 
 bool classes_ok(const dcvc_roi_class_t *cls, int32_t n_classes) {
     if (n_classes < 0 || n_classes > DCVC_ROI_MAX_CLASSES || (n_classes > 0 && !cls)) return false;
@@ -336,9 +297,7 @@ bool classes_ok(const dcvc_roi_class_t *cls, int32_t n_classes) {
 // the 8-bit picture of residual (written) and fuse (read): layout, channel order, and whether 4-byte accesses are aligned
 bool u8_ok(const uint8_t *p, int64_t cs, int64_t rs, int32_t px, int32_t o0, int32_t o1, int32_t o2, int32_t H, int32_t W,
            RoiArgs *a) {
-    if (!p || (px != 1 && px != 3)) return false;
-    if (px == 1 ? (rs < W || cs < (int64_t)(H - 1) * rs + W) : (cs != 1 || rs < 3 * (int64_t)W)) return false;
-    if (o0 < 0 || o0 > 2 || o1 < 0 || o1 > 2 || o2 < 0 || o2 > 2 || o0 == o1 || o0 == o2 || o1 == o2) return false;
+    if (!u8_layout_ok(p, cs, rs, px, H, W) || !order_ok(o0, o1, o2)) return false;
     a->u8 = const_cast<uint8_t *>(p), a->u8_cs = cs, a->u8_rs = rs, a->u8_px = px;
     a->order[0] = o0, a->order[1] = o1, a->order[2] = o2;
     a->vec_u8 = aligned(p, 4) && rs % 4 == 0 && (px == 3 || cs % 4 == 0);

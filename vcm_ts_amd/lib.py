@@ -217,6 +217,11 @@ _SIGS = {
     "dcvc_roi_fuse": [vp, i32, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i64, vp],
     "dcvc_roi_sse": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, vp, i32, vp, vp],
     "dcvc_roi_qmap": [i32, i32, vp, vp, i32, i32, vp, i32, vp, vp],
+    # include/dcvc_hip_roil.h
+    "dcvc_roil_cells": [i32, i32, vp, i32, vp, vp, i32],
+    "dcvc_roil_check": [vp, i64, vp, i32],
+    "dcvc_roil_encode": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, i64, vp, vp],
+    "dcvc_roil_decode": [vp, vp, i64, i32, i32, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32, i32, vp, vp],
     # include/dcvc_hip_scene.h
     "dcvc_scene_hist": [vp, i32, i64, i32, i32, vp, vp],
     # include/dcvc_hip_bits.h
@@ -230,10 +235,11 @@ _SIGS = {
 METRICS_SYMBOLS = ["dcvc_ms_ssim", "dcvc_ms_ssim_grad", "dcvc_ms_ssim_workspace_bytes"]
 COLOR_SYMBOLS = ["dcvc_color_coeffs", "dcvc_yuv420_to_rgb", "dcvc_rgb_to_yuv420"]  # include/dcvc_hip_color.h
 ROI_SYMBOLS = ["dcvc_roi_residual", "dcvc_roi_fuse", "dcvc_roi_sse", "dcvc_roi_qmap"]  # include/dcvc_hip_roi.h
+ROIL_SYMBOLS = ["dcvc_roil_cells", "dcvc_roil_check", "dcvc_roil_encode", "dcvc_roil_decode"]  # include/dcvc_hip_roil.h
 SCENE_SYMBOLS = ["dcvc_scene_hist"]  # include/dcvc_hip_scene.h
 BITS_SYMBOLS = ["dcvc_bits_map_scale", "dcvc_bits_map_factorized", "dcvc_bits_regions",
                 "dcvc_bits_sweep_scale"]  # include/dcvc_hip_bits.h
-HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS + ROI_SYMBOLS + SCENE_SYMBOLS + BITS_SYMBOLS] +
+HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS + ROI_SYMBOLS + ROIL_SYMBOLS + SCENE_SYMBOLS + BITS_SYMBOLS] +
                      ["dcvc_cdf_table_cols", "dcvc_conv_pack_size", "dcvc_conv_pack_size_paired", "dcvc_conv_small_pack_bytes", "dcvc_conv_k32_pack_bytes", "dcvc_conv_tile_rows", "dcvc_conv_chan_partial_parts", "dcvc_hip_version", "dcvc_conv_wgrad_scratch_min",
                       "dcvc_drans_default_lanes", "dcvc_drans_scratch_words"])
 RANS_SYMBOLS = [

@@ -9,6 +9,8 @@
     python -m vcm_ts_amd.run_codec decode --bins DIR --recon-video FILE.y4m
     python -m vcm_ts_amd.run_codec encode ... --roi-root DIR [--plate-border N] [--face-border N] [--residuals FILE.gbrp | DIR]
     python -m vcm_ts_amd.run_codec decode ... --roi-root DIR --residuals FILE.gbrp | DIR
+    python -m vcm_ts_amd.run_codec encode ... --roi-root DIR --residual-bins DIR [--residual-step S]
+    python -m vcm_ts_amd.run_codec decode ... --roi-root DIR --residual-bins DIR
     python -m vcm_ts_amd.run_codec encode ... --scenecut T [--min-gop N]
     python -m vcm_ts_amd.run_codec encode ... --roi-root DIR [--plate-q F] [--face-q F] [--background-q F] [--roi-q-grow N]
     python -m vcm_ts_amd.run_codec encode ... --report JSON --bit-map [DIR]
@@ -20,6 +22,10 @@ GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` be
 With a ROI (vcm_ts_amd/roi.py: the reference's box files under --roi-root) `encode` also writes the residual layer of
 ``video_coder.compute_residuals`` -- raw gbrp planes for an external encoder, or PNGs -- and `decode` fuses a decoded
 residual layer into its output as ``fuse_layers`` does; the .bin files are the same with or without.
+
+With --residual-bins DIR the residual layer is also CODED on the GPU (vcm_ts_amd/roilayer.py: a box-local coder, lossless at
+--residual-step 1, within S // 2 of every sample at step S; not HEVC): one im%05d.rl per picture, which `decode
+--residual-bins DIR` decodes and fuses in place of a --residuals file.  --report then states the layer's and the total bpp.
 
 With --scenecut T an I picture also opens a new GOP wherever consecutive pictures differ by more than T
 (vcm_ts_amd/scenecut.py: a scan pass over the source first, then the coding pass); --gop becomes the longest GOP, and the
@@ -633,7 +639,7 @@ def read_gop_plan(bin_dir, gop=None):
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
                   report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None, target_bpp=None,
-                  q_range=None):
+                  q_range=None, residual_bins=None, residual_step=1):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -673,7 +679,13 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     two P pictures of each GOP are coded with; from the third on the GOP's controller moves q_y inside q_range (a
     (lowest, highest) pair of q-scales, default the wire range [0.01, 655]).  The I picture is not controlled.  Every .bin
     header carries its own q indexes, so decoding needs nothing new.  With report the dictionary gains frame_q_y and
-    frame_bits_target (null where nothing was decided).  None: no launch, file, key or byte changes."""
+    frame_bits_target (null where nothing was decided).  None: no launch, file, key or byte changes.
+    residual_bins (with roi): a folder -- it may be bin_dir -- for the CODED residual layer, im%05d.rl per picture
+    (vcm_ts_amd/roilayer.py, include/dcvc_hip_roil.h): the residual inside the boxes, quantised with the integer
+    residual_step (1 .. 64; 1 is lossless, S keeps every sample within S // 2), coded cell by cell on the stream that coded the
+    picture; decode_folder / decode_video take the same folder in place of residuals=.  It may be given together with
+    residuals=.  With report the dictionary gains frame_bits_enh (8 x the record's size), frame_bpp_enh,
+    ave_all_frame_bpp_enh and ave_all_frame_bpp_total (base + enhancement).  None: no launch, file, key or byte changes."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
@@ -687,7 +699,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         n_frames += 1
     with Image.open(reader.path_of(1)) as first:  # (the header only)
         w, h = first.size
-    _roi_args(roi, residuals)
+    _roi_args(roi, residuals, residual_bins, residual_step)
     _roiq_args(roi, roi_q)
     bit_dir = _bitmap_args(bit_map, report)
     rate = _rate_args(target_bpp, q_range, h, w, gop)
@@ -725,6 +737,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
         write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
+        rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
     except BaseException:
         if pool is not None:
             pool.shutdown(wait=True, cancel_futures=True)
@@ -733,13 +746,15 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
 
     def frames(k):
         for x in uploaded(run.order(k), run.K):
-            if report or res_out:
+            if report or res_out or rec_out:
                 source[k] = x  # (the picture on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
             yield x
 
     def on_recon(k, g, ref_frame):
         if res_out:
             res_out.put(k, g, source[k][..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
+        if rec_out:
+            rec_out.put(k, g, source[k][..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
         if report and layer:
             sums = layer.X.region_sse(ref_frame[..., :h, :w], source[k][..., :h, :w], layer.boxes(g), layer.classes)
             run.quality[k].add_yuv(g, ref_frame, source[k], (h, w), sums)
@@ -751,7 +766,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     failed = True
     try:
         with PNGWriters(io_workers) as savers:
-            run.encode(frames, q, on_recon if (recon_dir or report or res_out) else None,
+            run.encode(frames, q, on_recon if (recon_dir or report or res_out or rec_out) else None,
                        (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None)
         failed = False
     finally:
@@ -759,7 +774,10 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
             pool.shutdown(wait=True, cancel_futures=True)
         if res_out:
             res_out.close(failed)
-    return run.results(report, _roi_report_keys(h, w) if layer else None)
+        if rec_out:
+            rec_out.close(failed)
+    extras = _roi_report_keys(h, w) if layer else None
+    return run.results(report, _enh_report_keys(rec_out, h, w, extras) if rec_out else extras)
 
 
 def _decode_bins(nets, bin_dir, height, width, plan, emit, q_map=None):
@@ -795,20 +813,23 @@ def _decode_bins(nets, bin_dir, height, width, plan, emit, q_map=None):
 
 
 def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
-                  io_workers=8, roi=None, residuals=None):
+                  io_workers=8, roi=None, residuals=None, residual_bins=None):
     """roi, residuals: write video_coder.fuse_layers' picture instead of the reconstruction -- `residuals` is the decoded
     residual layer (a `.gbrp` file or a folder of im%05d.png, as encode_folder writes them) and `roi` the boxes and
     classes it was taken with.  Display side only: the decoder's reference pictures are not touched.
     gop: an I picture every `gop` pictures (default 32) -- unless encode left a gops.json beside the .bin files, which then
     says where the I pictures are; a `gop` given against it is refused (read_gop_plan).
     A roiq.json beside the .bin files (encode_folder's roi_q=) is followed: the q-scale maps are rebuilt from `roi`, which
-    is then required -- with or without residuals."""
-    _roi_args(roi, residuals)
+    is then required -- with or without residuals.
+    residual_bins: in place of residuals=, the folder of im%05d.rl records encode_folder's residual_bins= wrote: each is
+    held against the frame's boxes by name before any GPU work, decoded on the device and fused.  Giving both is refused."""
+    _roi_args(roi, residuals, residual_bins, decode=True)
     plan, _ = read_gop_plan(bin_dir, gop)
     roi_q = read_roiq(bin_dir, roi)
     os.makedirs(recon_dir, exist_ok=True)
     dev = torch.device(device)
-    picture, close = _fused_emit(_fuse_roi(roi, residuals, roi_q), residuals, plan, (height, width), dev)
+    picture, close = _fused_emit(_fuse_roi(roi, residuals, roi_q, residual_bins), residuals, plan, (height, width), dev,
+                                 residual_bins)
     try:
         maps = _decode_maps(roi, roi_q, plan, (height, width), dev)
         nets = _nets(dev, precision, i_ckpt, p_ckpt)
@@ -824,7 +845,7 @@ SEQUENCE_JSON = "sequence.json"
 
 
 def write_sequence_info(bin_dir, width, height, frames, gop, fps, spec, container, chroma=None, interlace=None, aspect=None,
-                        roi=None):
+                        roi=None, residual_step=None):
     """What decode_video needs beside the .bin files (which stay what they are): size, frame count, GOP length, frame
     rate and colour description of the source, and the container it came in."""
     import json
@@ -834,6 +855,8 @@ def write_sequence_info(bin_dir, width, height, frames, gop, fps, spec, containe
             "interlace": interlace, "aspect": aspect}
     if roi is not None:  # class order and borders of the enhancement layer (the boxes themselves stay where they are)
         info["roi"] = roi.to_json()
+    if residual_step is not None:  # the step of the coded residual layer (residual_bins=; every record carries it too)
+        info["residual_step"] = int(residual_step)
     with open(os.path.join(bin_dir, SEQUENCE_JSON), "w") as f:
         json.dump(info, f, indent=2)
     return info
@@ -1025,14 +1048,107 @@ class _ResidualIn:
             self.reader.close()
 
 
-def _roi_args(roi, residuals):
+class _RecordOut:
+    """Where an encode loop's CODED residual layer goes: im%05d.rl in a folder (vcm_ts_amd/roilayer.py).  A picture's record
+    is coded on the stream that coded the picture and leaves the device in one asynchronous copy to a pinned buffer; it is
+    written to its file when its stream's ring comes round to it (or at close), as _VideoOut does, so the host never waits
+    for the picture it has just enqueued, and every file carries its frame's number whatever order the GOP streams finish
+    in.  sizes: {frame number: record bytes} of what has been written."""
+
+    def __init__(self, folder, step, streams, depth=4):
+        from collections import deque
+
+        from . import roilayer as Y
+
+        os.makedirs(folder, exist_ok=True)
+        self.Y, self.folder, self.step, self.depth = Y, folder, step, depth
+        self.busy, self.pool, self.sizes = [deque() for _ in range(streams)], [], {}
+
+    def put(self, k, g, source, recon, boxes):
+        if len(self.busy[k]) >= self.depth:
+            self._retire(k)
+        self.busy[k].append((g, self.Y.encode_layer(source, recon, boxes, self.step, pool=self.pool)))
+
+    def _retire(self, k):
+        g, pending = self.busy[k].popleft()
+        data = pending.bytes()
+        with open(os.path.join(self.folder, f"im{str(g + 1).zfill(5)}{self.Y.FILE_EXT}"), "wb") as f:
+            f.write(data)
+        self.sizes[g] = len(data)
+        self.pool.append(pending.host)
+
+    def close(self, failed=False):
+        if not failed:
+            for k in range(len(self.busy)):
+                while self.busy[k]:
+                    self._retire(k)
+
+
+class _RecordIn:
+    """A coded residual layer (im%05d.rl, _RecordOut's files), per frame decoded on the device into the planar picture
+    roi.fuse reads.  Every file is read and held against the frame's boxes when the loop starts: a missing file or a record
+    that disagrees with the boxes is named before any GPU work."""
+    layout, order = "planar", "rgb"
+
+    def __init__(self, folder, size, layer):
+        from . import roilayer as Y
+
+        self.Y, self.size, self.layer, self.records = Y, size, layer, []
+        for t, boxes in enumerate(layer.frames):
+            path = os.path.join(folder, f"im{str(t + 1).zfill(5)}{Y.FILE_EXT}")
+            if not os.path.exists(path):
+                raise ValueError(f"{folder}: no residual record im{str(t + 1).zfill(5)}{Y.FILE_EXT}")
+            with open(path, "rb") as f:
+                data = f.read()
+            try:
+                Y.check_record(data, Y.active_cells(boxes, size[0], size[1])[1])
+            except Y.RoiLayerError as ex:
+                raise Y.RoiLayerError(f"{path}: {ex}") from None
+            self.records.append(data)
+
+    def frame(self, t):
+        return self.Y.decode_layer(self.records[t], self.layer.boxes(t), self.size[0], self.size[1], layout=self.layout,
+                                   order=self.order, device=self.layer.dev)
+
+    def close(self):
+        pass
+
+
+def _roi_args(roi, residuals, residual_bins=None, residual_step=1, decode=False):
+    """The residual-layer arguments of a file loop against its roi=, refused by name before any GPU work."""
     if residuals is not None and roi is None:
         raise ValueError("residuals= needs roi= (the boxes the residual layer is taken in)")
+    if residual_bins is not None and roi is None:
+        raise ValueError("residual_bins= needs roi= (the boxes the residual layer is coded in)")
+    if decode and residuals is not None and residual_bins is not None:
+        raise ValueError("give one of residuals= (a decoded residual layer) and residual_bins= (a coded one), not both")
+    if residual_bins is not None and not isinstance(residual_bins, (str, os.PathLike)):
+        raise ValueError(f"residual_bins: expected a folder, got {type(residual_bins).__name__}")
+    if not decode:
+        from .roilayer import check_step
+
+        if check_step(residual_step) != 1 and residual_bins is None:
+            raise ValueError("residual_step= belongs to residual_bins= (the coded residual layer)")
 
 
-def _fuse_roi(roi, residuals, roi_q):
+def _enh_report_keys(rec_out, h, w, inner=None):
+    """--report's keys of the enhancement layer, video_coder.calc_bitrate_metrics' three figures: the record's bits and bpp
+    per picture, their average, and base + enhancement."""
+    def keys(rd, types, values):
+        if inner:
+            inner(rd, types, values)
+        bits = [8 * rec_out.sizes[g] for g in sorted(rec_out.sizes)]
+        rd["frame_bits_enh"] = bits
+        rd["frame_bpp_enh"] = [b / (h * w) for b in bits]
+        rd["ave_all_frame_bpp_enh"] = sum(rd["frame_bpp_enh"]) / len(bits) if bits else 0
+        rd["ave_all_frame_bpp_total"] = rd["ave_all_frame_bpp"] + rd["ave_all_frame_bpp_enh"]
+
+    return keys
+
+
+def _fuse_roi(roi, residuals, roi_q, residual_bins=None):
     """The roi a decode loop fuses a residual layer with: none when the roi is only there for the q-scale maps."""
-    return None if (residuals is None and roi_q is not None) else roi
+    return None if (residuals is None and residual_bins is None and roi_q is not None) else roi
 
 
 def _decode_maps(roi, roi_q, plan, size, dev):
@@ -1067,15 +1183,15 @@ def _roi_report_keys(h, w):
     return keys
 
 
-def _fused_emit(roi, residuals, plan, size, dev):
+def _fused_emit(roi, residuals, plan, size, dev, residual_bins=None):
     """(picture(t, ref_frame) -> the fused unpadded picture, close()) of a decode loop; without a ROI the crop itself."""
     h, w = size
     if roi is None:
         return (lambda t, ref_frame: ref_frame[..., :h, :w]), (lambda: None)
-    if residuals is None:
-        raise ValueError("decoding with roi= needs residuals= (the decoded residual layer to fuse)")
+    if residuals is None and residual_bins is None:
+        raise ValueError("decoding with roi= needs residuals= (the decoded residual layer to fuse) or residual_bins= (the coded one)")
     layer = _RoiLayer(roi, plan, size, dev)
-    source = _ResidualIn(residuals, size, plan.n_frames, dev)
+    source = _ResidualIn(residuals, size, plan.n_frames, dev) if residuals is not None else _RecordIn(residual_bins, size, layer)
 
     def picture(t, ref_frame):  # display side only: the DPB keeps the base-layer reconstruction
         return layer.X.fuse(ref_frame[..., :h, :w], source.frame(t), layer.boxes(t), layer.classes, layout=source.layout,
@@ -1093,7 +1209,7 @@ def _open_source(video, size, bit_depth, fps):
 def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantize8=False, gop=32, q=(1.0, 1.0, 1.0),
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
-                 min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None):
+                 min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -1110,10 +1226,11 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     scenecut, min_gop: as encode_folder; the scan pass reads the file once through the same ring, copy and colour
     conversion (spec, quantize8) as the coding pass.  sequence.json is the same with or without.
     roi_q: as encode_folder (roiq.json beside the .bin files; sequence.json is the same with or without).
-    bit_map, target_bpp, q_range: as encode_folder."""
+    bit_map, target_bpp, q_range: as encode_folder.
+    residual_bins, residual_step: as encode_folder; sequence.json then also records residual_step."""
     from . import yuv as Y
 
-    _roi_args(roi, residuals)
+    _roi_args(roi, residuals, residual_bins, residual_step)
     _roiq_args(roi, roi_q)
     bit_dir = _bitmap_args(bit_map, report)
     reader = _open_source(video, size, bit_depth, fps)  # (every refusal about the file happens here, before any GPU work)
@@ -1143,6 +1260,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
     write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
     res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
+    rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
     source = {}
     container = "y4m" if isinstance(reader, Y.Y4MReader) else "yuv"
     extras = dict(chroma=getattr(reader, "chroma", None), interlace=getattr(reader, "interlace", None),
@@ -1159,6 +1277,8 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
         x, samples = source[k]
         if res_out:
             res_out.put(k, g, x[..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
+        if rec_out:
+            rec_out.put(k, g, x[..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
         if report:
             out, sums = Y.rgb_to_yuv420(ref_frame, h, w, spec, source=samples)
             if layer:
@@ -1171,7 +1291,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
 
     failed = True
     try:
-        run.encode(frames, q, on_recon if (outs or report or res_out) else None,
+        run.encode(frames, q, on_recon if (outs or report or res_out or rec_out) else None,
                    (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None)
         for o in outs or []:
             o.close()
@@ -1183,8 +1303,10 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
             reader.close()
         if res_out:
             res_out.close(failed)
+        if rec_out:
+            rec_out.close(failed)
     write_sequence_info(bin_dir, w, h, n_frames, gop, reader.fps, spec, container, **extras,
-                        roi=layer.roi if layer else None)
+                        roi=layer.roi if layer else None, residual_step=residual_step if rec_out else None)
 
     def yuv_keys(rd, types, values):
         per = [Y.psnr_yuv(v[2][:3], h, w, spec.bit_depth) for v in values]
@@ -1196,19 +1318,19 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
             sel = [p[3] for p, k in zip(per, types) if keep(k)]
             rd[f"ave_{name}_frame_psnr_yuv"] = sum(sel) / len(sel) if sel else 0
 
-    return run.results(report, yuv_keys)
+    return run.results(report, _enh_report_keys(rec_out, h, w, yuv_keys) if rec_out else yuv_keys)
 
 
 def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=None, fps=None, device="cuda:0",
-                 precision=None, i_ckpt=None, p_ckpt=None, roi=None, residuals=None):
+                 precision=None, i_ckpt=None, p_ckpt=None, roi=None, residuals=None, residual_bins=None):
     """decode_folder's loop with the video output stage.  Size, GOP length, frame rate and colour description come from
     the sequence.json encode_video left in `bin_dir`; explicit arguments override it, and without the file height and
     width are required (gop then defaults to 32, the colour description to yuv.ColorSpec()).  Returns the picture count.
-    roi, residuals: as decode_folder -- the fused picture is what is converted and written.  A roiq.json beside the .bin
-    files is followed as decode_folder does."""
+    roi, residuals, residual_bins: as decode_folder -- the fused picture is what is converted and written.  A roiq.json
+    beside the .bin files is followed as decode_folder does."""
     from . import yuv as Y
 
-    _roi_args(roi, residuals)
+    _roi_args(roi, residuals, residual_bins, decode=True)
     info = read_sequence_info(bin_dir) or {}
     height, width = height or info.get("height"), width or info.get("width")
     if not height or not width:
@@ -1220,8 +1342,8 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     if os.path.exists(first) and S.decode_i(first)[:2] != (height, width):
         raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {(height, width)}")
     roi_q = read_roiq(bin_dir, roi)
-    fuse_roi = _fuse_roi(roi, residuals, roi_q)
-    picture, close = _fused_emit(fuse_roi, residuals, plan, (height, width), torch.device(device))
+    fuse_roi = _fuse_roi(roi, residuals, roi_q, residual_bins)
+    picture, close = _fused_emit(fuse_roi, residuals, plan, (height, width), torch.device(device), residual_bins)
     try:
         maps = _decode_maps(roi, roi_q, plan, (height, width), torch.device(device))
         nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
@@ -1313,6 +1435,16 @@ def main(argv=None):
                         "or a folder for im%%05d.png")
     d.add_argument("--residuals", metavar="PATH",
                    help="with --roi-root: the decoded residual layer (FILE.gbrp or a folder of im%%05d.png) to fuse into the output")
+    e.add_argument("--residual-bins", metavar="DIR",
+                   help="with --roi-root: code the residual layer on the GPU into DIR/im%%05d.rl (DIR may be --bins): a box-local "
+                        "coder of its own, not HEVC; --report gains frame_bits_enh, frame_bpp_enh, ave_all_frame_bpp_enh and "
+                        "ave_all_frame_bpp_total.  May be given together with --residuals")
+    e.add_argument("--residual-step", type=int, default=None, metavar="S",
+                   help="with --residual-bins: the integer quantisation step of the residual, 1 .. 64 (default 1: lossless; S keeps "
+                        "every sample within S // 2; no tuned value exists)")
+    d.add_argument("--residual-bins", metavar="DIR",
+                   help="with --roi-root: the coded residual layer (DIR/im%%05d.rl) to decode and fuse into the output, in place "
+                        "of --residuals")
     for p in (e, d):
         p.add_argument("--roi-root", metavar="DIR",
                        help="the reference's box files: DIR/liplates_coords/%%05d and DIR/faces_coords/%%05d (either may be absent)")
@@ -1347,13 +1479,21 @@ def main(argv=None):
     elif a.roi_root is None and os.path.exists(os.path.join(a.bins, ROIQ_JSON)):
         ap.error(f"{os.path.join(a.bins, ROIQ_JSON)}: these pictures were coded with q-scale maps made from ROI boxes; "
                  f"decode needs --roi-root")
-    if a.roi_root is None and (a.residuals or a.plate_border is not None or a.face_border is not None):
-        ap.error("--residuals, --plate-border and --face-border belong to --roi-root")
+    if a.roi_root is None and (a.residuals or a.residual_bins or a.plate_border is not None or a.face_border is not None):
+        ap.error("--residuals, --residual-bins, --plate-border and --face-border belong to --roi-root")
+    if a.cmd == "encode":
+        if a.residual_step is not None and not a.residual_bins:
+            ap.error("--residual-step belongs to --residual-bins")
+        a.residual_step = 1 if a.residual_step is None else a.residual_step
+        if not 1 <= a.residual_step <= 64:
+            ap.error("--residual-step must be within 1..64")
+    elif a.residuals and a.residual_bins:
+        ap.error("give one of --residuals and --residual-bins")
     if a.roi_root is not None:
         from . import roi as X
 
-        if a.cmd == "decode" and not a.residuals and not os.path.exists(os.path.join(a.bins, ROIQ_JSON)):
-            ap.error("decode --roi-root needs --residuals (the decoded residual layer)")
+        if a.cmd == "decode" and not a.residuals and not a.residual_bins and not os.path.exists(os.path.join(a.bins, ROIQ_JSON)):
+            ap.error("decode --roi-root needs --residuals (the decoded residual layer) or --residual-bins (the coded one)")
         recorded = {c["name"]: c["border"] for c in ((read_sequence_info(a.bins) or {}).get("roi") or {}).get("classes", [])} \
             if a.cmd == "decode" else {}
         borders = [given if given is not None else recorded.get(name, 0)
@@ -1430,12 +1570,14 @@ def main(argv=None):
                                                device=a.device, precision=a.precision, i_ckpt=a.i_ckpt, p_ckpt=a.p_ckpt,
                                                coder=a.coder, gop_streams=a.gop_streams, report=a.report, roi=roi,
                                                residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
-                                               bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range)
+                                               bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
+                                               residual_bins=a.residual_bins, residual_step=a.residual_step)
         else:
             bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
                                             coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
                                             roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
-                                            bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range)
+                                            bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
+                                            residual_bins=a.residual_bins, residual_step=a.residual_step)
         if rd:
             yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
             print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
@@ -1457,13 +1599,14 @@ def main(argv=None):
                 spec = Y.ColorSpec(a.matrix or base.matrix, base.full_range if a.range is None else a.range == "full",
                                    a.siting or base.siting, a.bit_depth or base.bit_depth)
             n = decode_video(a.bins, a.recon_video, a.height, a.width, a.gop, spec, None, a.device, a.precision, a.i_ckpt, a.p_ckpt,
-                             roi=roi, residuals=a.residuals)
+                             roi=roi, residuals=a.residuals, residual_bins=a.residual_bins)
         else:
             if a.matrix or a.range or a.siting or a.bit_depth:
                 ap.error("--matrix, --range, --siting and --bit-depth belong to --recon-video")
             height, width = a.height or info["height"], a.width or info["width"]
             n = decode_folder(a.bins, a.recon, height, width, a.gop or (info or {}).get("gop"), a.device, a.precision,
-                              a.i_ckpt, a.p_ckpt, io_workers=a.io_workers, roi=roi, residuals=a.residuals)
+                              a.i_ckpt, a.p_ckpt, io_workers=a.io_workers, roi=roi, residuals=a.residuals,
+                              residual_bins=a.residual_bins)
         print(f"{n} pictures decoded")
 
 
