@@ -1,0 +1,421 @@
+"""Decoded-picture hashes on the device: both kernels of csrc/hash.hip against zlib.crc32 of the byte strings
+include/dcvc_hip_hash.h defines (tests/picturehash_ref.py builds them with numpy), and the file loops that record the
+digests and hold a decoder against them.
+
+A digest is a 32-bit integer: every comparison is ==.
+
+Byte lengths aim at the kernel's seams, read from the library: L = DCVC_HASH_CHUNK_BYTES per lane, B = DCVC_HASH_BLOCK_BYTES
+per workgroup, 64 partials per pass of the folding wave; a length that no picture shape within 32768 per side gives is
+replaced by the next one above it that a shape gives.
+
+The end-to-end tests run at 64x64, 16 pictures, GOP 8, on the clip of tests/scenecut_ref.py.
+"""
+import json
+import os
+import warnings
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+from tests import picturehash_ref as R
+from tests import scenecut_ref as SR
+from vcm_ts_amd import lib
+from vcm_ts_amd import picturehash as PH
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+NAN = float("nan")
+L, B = lib.hash_constant("dcvc_hash_chunk_bytes"), lib.hash_constant("dcvc_hash_block_bytes")
+FOLD = 64  # partials one pass of the folding wave takes
+SEAMS = ["3", "4", "12", "L-d", "L", "L+d", "B-d", "B", "B+d", "2B+L+d", "65B+L+d"]
+
+
+def _length(seam, d):
+    """the byte length a seam's name stands for, at the entry point's smallest step d (3: pixels, 4: f32)"""
+    if seam.isdigit():
+        return (int(seam) + d - 1) // d * d
+    return {"L-d": L - d, "L": L, "L+d": L + d, "B-d": B - d, "B": B, "B+d": B + d, "2B+L+d": 2 * B + L + d,
+            "65B+L+d": (FOLD + 1) * B + L + d}[seam]
+
+
+def _shape(units):
+    """(H, W, units') with H * W = units' the first count >= units that sides within 32768 give, H as small as possible"""
+    while True:
+        for H in range(1, 4096):
+            if units % H == 0 and units // H <= 32768:
+                return H, units // H, units
+        units += 1
+
+
+def _view(a, layout):
+    """the (C, H, W) array as a (1, C, H, W) view.  "aligned": contiguous.  "offset": inside a larger NaN-filled buffer
+    at an odd element offset, rows longer than W, slack between the planes (a NaN read in place of a sample, or a sample
+    missed, moves the digest)."""
+    C_, H, W = a.shape
+    if layout == "aligned":
+        return torch.from_numpy(a)[None].to(DEV).contiguous()
+    off, rs = 3, W + 5
+    ps = (H + 2) * rs + 1
+    buf = torch.full((off + C_ * ps + 7,), NAN, dtype=torch.float32, device=DEV)
+    v = buf.as_strided((1, C_, H, W), (C_ * ps, ps, rs, 1), off)
+    v.copy_(torch.from_numpy(a)[None])
+    assert v.data_ptr() % 8 == 4
+    return v
+
+
+def _u32(a):
+    """a uint32 device tensor holding the numpy array `a`"""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32)).to(DEV)
+
+
+def _digest_warnings(rec):
+    return [w for w in rec if "digest" in str(w.message)]
+
+
+def _word(t):
+    assert t.dtype == torch.uint32 and t.numel() == 1 and t.is_cuda
+    return int(t.cpu().numpy().reshape(-1)[0])
+
+
+@pytest.mark.parametrize("layout", ["aligned", "offset"])
+@pytest.mark.parametrize("seam", SEAMS)
+def test_pixels_kernel_equals_zlib_at_every_seam(seam, layout):
+    H, W, pixels = _shape(_length(seam, 3) // 3)
+    a = R.pixel_values(len(seam) + H, H, W)
+    want = zlib.crc32(R.pixel_bytes(a))
+    print(f"{seam}: {3 * pixels} bytes as {H}x{W}")
+    assert _word(PH.crc32_pixels(_view(a, layout))) == want
+
+
+@pytest.mark.parametrize("layout", ["aligned", "offset"])
+@pytest.mark.parametrize("size", [(1, 1), (1, 2), (5, 7), (33, 47), (135, 241), (64, 96)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_pixels_kernel_equals_zlib_on_pictures(size, layout):
+    H, W = size
+    a = R.pixel_values(H * 1000 + W, H, W)
+    if H * W >= 35:
+        half = (np.float32(7.5) / np.float32(255.0)).astype(np.float32)
+        assert a.min() < 0 and a.max() > 1 and 0.0 in a and 1.0 in a and half in a  # (and the other half-way codes)
+    v = _view(a, layout)
+    want = R.crc32_pixels(a)
+    assert _word(PH.crc32_pixels(v)) == want
+    # the crop of a padded picture, read in place: what HashLog does
+    big = torch.full((1, 3, H + 3, W + 9), 0.7, device=DEV)
+    big[..., :H, :W] = v
+    assert _word(PH.crc32_pixels(big, (H, W))) == want
+    if H > 1:
+        assert _word(PH.crc32_pixels(big, (H - 1, W))) == R.crc32_pixels(a[:, :H - 1])
+
+
+@pytest.mark.parametrize("layout", ["aligned", "offset"])
+@pytest.mark.parametrize("seam", SEAMS)
+def test_f32_kernel_equals_zlib_at_every_seam(seam, layout):
+    H, W, words = _shape(_length(seam, 4) // 4)
+    a = R.f32_values(len(seam) + H, 1, H, W)
+    want = zlib.crc32(R.f32_bytes(a))
+    print(f"{seam}: {4 * words} bytes as 1x{H}x{W}")
+    assert _word(PH.crc32_f32(_view(a, layout))) == want
+
+
+@pytest.mark.parametrize("layout", ["aligned", "offset"])
+@pytest.mark.parametrize("shape", [(1, 1, 1), (3, 5, 7), (2, 33, 47), (3, 64, 128), (5, 135, 241)], ids=lambda s: "x".join(map(str, s)))
+def test_f32_kernel_counts_every_bit(shape, layout):
+    a = R.f32_values(sum(shape), *shape)
+    bits = a.view(np.uint32)
+    if a.size >= 10:
+        assert 0x80000000 in bits and 0x00000001 in bits and 0x7F800000 in bits and 0x7FC00001 in bits and 0xFFC12345 in bits
+    v = _view(a, layout)
+    assert np.array_equal(v.cpu().numpy().view(np.uint32)[0], bits)  # (the upload kept the NaN payloads)
+    assert _word(PH.crc32_f32(v)) == R.crc32_f32(a)
+    assert _word(PH.crc32_f32(v[0])) == R.crc32_f32(a)  # (C, H, W) is accepted too
+    if a.size >= 10:
+        flipped = bits.copy().reshape(-1)
+        flipped[flipped == 0x80000000] = 0  # -0.0 -> +0.0, nothing else
+        assert _word(PH.crc32_f32(_view(flipped.view(np.float32).reshape(shape), layout))) != R.crc32_f32(a)
+
+
+def test_two_launches_give_the_same_word_and_write_rather_than_add():
+    a = R.pixel_values(9, 135, 241)
+    v = _view(a, "offset")
+    out = _u32([0xFFFFFFFF])
+    first = _word(PH.crc32_pixels(v, out=out))
+    assert first == R.crc32_pixels(a) and _word(PH.crc32_pixels(v, out=out)) == first and _word(out) == first
+    assert _word(PH.crc32_f32(v, out=out)) == R.crc32_f32(a) == _word(PH.crc32_f32(v, out=out))
+
+
+def test_a_side_stream_writes_only_its_slot():
+    a = R.pixel_values(10, 65, 63)
+    big = torch.full((1, 3, 128, 128), 0.999, device=DEV)
+    big[..., :65, :63] = torch.from_numpy(a).to(DEV)
+    gop = _u32(np.full((8, 2), 0x5A5A5A5A))
+    scratch = PH.new_scratch(DEV)
+    torch.cuda.synchronize(DEV)
+    side = torch.cuda.Stream(DEV)
+    with torch.cuda.stream(side):
+        PH.crc32_pixels(big, (65, 63), out=gop[3, 0:1], scratch=scratch)
+        PH.crc32_f32(big, out=gop[3, 1:2], scratch=scratch)
+        host = gop.cpu().numpy()
+    want = np.full((8, 2), 0x5A5A5A5A, np.uint32)
+    want[3] = R.crc32_pixels(a), R.crc32_f32(big[0].cpu().numpy())
+    assert np.array_equal(host, want)
+
+
+def test_wrong_inputs_are_value_errors():
+    good = torch.zeros((1, 3, 8, 8), device=DEV)
+    for fn in (PH.crc32_pixels, PH.crc32_f32):
+        with pytest.raises(ValueError, match="GPU"):
+            fn(good.cpu())
+        with pytest.raises(ValueError, match="float32"):
+            fn(good.double())
+        with pytest.raises(ValueError, match="float32"):
+            fn(torch.zeros((2, 3, 8, 8), device=DEV))
+        with pytest.raises(ValueError, match="out="):
+            fn(good, out=torch.zeros(2, dtype=torch.uint32, device=DEV))
+        with pytest.raises(ValueError, match="out="):
+            fn(good, out=torch.zeros(1, dtype=torch.int32, device=DEV))
+    with pytest.raises(ValueError, match="float32"):
+        PH.crc32_pixels(torch.zeros((1, 4, 8, 8), device=DEV))
+    with pytest.raises(ValueError, match="crop"):
+        PH.crc32_pixels(good, (9, 8))
+    with pytest.raises(ValueError, match="crop"):
+        PH.crc32_pixels(good, (0, 8))
+    with pytest.raises(ValueError, match="float32"):
+        PH.crc32_f32(torch.zeros((0, 8, 8), device=DEV))
+    with pytest.raises(ValueError, match="float32"):
+        PH.crc32_f32(torch.zeros((8, 8), device=DEV))
+
+
+# ------------------------------------------------------------------------------------------------------- end to end
+GOP, N, H, W = 8, 16, 64, 64
+
+
+def _png(path):
+    from PIL import Image
+
+    return np.asarray(Image.open(path).convert("RGB"))
+
+
+def _bins(folder):
+    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
+
+
+def _record(folder):
+    return json.loads((folder / "hashes.json").read_text())
+
+
+@pytest.fixture(scope="module")
+def nets():
+    from vcm_ts_amd import run_codec as RC
+
+    return [RC._nets(DEV, None) for _ in range(2)]
+
+
+@pytest.fixture(scope="module")
+def e2e(tmp_path_factory, nets):
+    """the clip as PNGs; a plain encode, and the hashed encode with its reconstructions and every ref_frame its on_recon
+    hook was handed (kept as host copies: the reference all tests share)"""
+    from PIL import Image
+
+    from vcm_ts_amd import run_codec as RC
+
+    tmp = tmp_path_factory.mktemp("picturehash_e2e")
+    clip = SR.cut_clip(H, W)
+    os.makedirs(tmp / "png")
+    for t, a in enumerate(clip):
+        Image.fromarray(a).save(tmp / "png" / f"im{t + 1:05d}.png")
+    RC.encode_folder(str(tmp / "png"), str(tmp / "plain"), str(tmp / "plain_rec"), gop=GOP, nets=nets)
+    seen, add = {}, PH.HashLog.add
+
+    def spy(self, g, ref_frame, size):
+        seen[g] = ref_frame.detach().cpu().numpy()[0].copy()
+        return add(self, g, ref_frame, size)
+
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(PH.HashLog, "add", spy)
+        RC.encode_folder(str(tmp / "png"), str(tmp / "hashed"), str(tmp / "hashed_rec"), gop=GOP, nets=nets, picture_hash=True)
+    assert sorted(seen) == list(range(N))
+    return dict(tmp=tmp, clip=clip, ref_frames=seen, bins=tmp / "hashed")
+
+
+def _edited(e2e, name, key=None, t=5):
+    """a copy of the hashed folder with one hex digit of key[t] changed (no .bin file is touched)"""
+    dst = e2e["tmp"] / name
+    os.makedirs(dst)
+    for n, data in _bins(e2e["bins"]).items():
+        (dst / n).write_bytes(data)
+    info = _record(e2e["bins"])
+    if key:
+        d = info[key][t]
+        info[key][t] = d[:3] + ("0" if d[3] != "0" else "1") + d[4:]
+    (dst / "hashes.json").write_text(json.dumps(info))
+    return dst, info
+
+
+def test_encode_records_the_digests_of_its_own_reconstruction(e2e):
+    tmp = e2e["tmp"]
+    assert _bins(tmp / "hashed") == _bins(tmp / "plain") and len(_bins(tmp / "plain")) == N
+    assert sorted(n for n in os.listdir(tmp / "hashed") if not n.endswith(".bin")) == ["hashes.json"]
+    info = _record(tmp / "hashed")
+    assert (info["version"], info["algorithm"], info["frames"], info["height"], info["width"], info["padded"]) == \
+        (1, "crc32", N, H, W, [64, 64])
+    assert info["precision"] == os.environ.get("DCVC_PRECISION", "fp32")
+    for t in range(N):
+        assert int(info["pixels"][t], 16) == zlib.crc32(_png(tmp / "hashed_rec" / f"im{t + 1:05d}.png").tobytes()), t
+        assert int(info["state"][t], 16) == R.crc32_f32(e2e["ref_frames"][t]), t
+        assert int(info["pixels"][t], 16) == R.crc32_pixels(e2e["ref_frames"][t][:, :H, :W]), t
+    assert len(set(info["pixels"])) == N and len(set(info["state"])) == N
+    assert PH.verify_pngs(str(tmp / "hashed"), str(tmp / "hashed_rec")) is None
+    assert PH.verify_pngs(str(tmp / "hashed"), str(tmp / "plain_rec")) is None
+
+
+def test_feature_off_is_free_and_removes_a_stale_record(e2e, nets):
+    from vcm_ts_amd import run_codec as RC
+
+    tmp = e2e["tmp"]
+    assert sorted(os.listdir(tmp / "plain")) == sorted(_bins(tmp / "plain"))  # nothing but the .bin files
+    launches = []
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(PH, "_launch", lambda *a, **k: launches.append(a[0]))
+        assert RC.decode_folder(str(tmp / "plain"), str(tmp / "plain_dec"), H, W, gop=GOP) == N
+        stale, _ = _edited(e2e, "stale")
+        RC.encode_folder(str(tmp / "png"), str(stale), gop=GOP, nets=nets)
+    assert launches == []
+    assert sorted(os.listdir(tmp / "plain_dec")) == [f"im{t + 1:05d}.png" for t in range(N)]
+    assert sorted(os.listdir(stale)) == sorted(_bins(tmp / "plain")) and _bins(stale) == _bins(tmp / "plain")
+    for mode in ("strict", "pixels", "warn"):
+        with pytest.raises(ValueError, match="there is no hashes.json"):
+            RC.decode_folder(str(tmp / "plain"), str(tmp / "never"), H, W, gop=GOP, verify=mode)
+    assert not (tmp / "never").exists()
+    assert RC.decode_folder(str(tmp / "plain"), str(tmp / "plain_off"), H, W, gop=GOP, verify="off") == N
+
+
+def test_two_gop_streams_and_scenecut_record_the_same_digests(e2e, nets):
+    from vcm_ts_amd import run_codec as RC
+
+    tmp = e2e["tmp"]
+    RC.encode_folder(str(tmp / "png"), str(tmp / "two"), gop=GOP, nets=nets, gop_streams=2, picture_hash=True)
+    assert (tmp / "two" / "hashes.json").read_text() == (tmp / "hashed" / "hashes.json").read_text()
+    assert _bins(tmp / "two") == _bins(tmp / "hashed")
+    # scene-cut I pictures at [0, 5, 13] (tests/test_gpu_scenecut.py): the first GOP is the same pictures, and every
+    # digest is of the encode's own reconstruction
+    RC.encode_folder(str(tmp / "png"), str(tmp / "cut"), str(tmp / "cut_rec"), gop=GOP, nets=nets, gop_streams=2, scenecut=0.5,
+                     min_gop=2, picture_hash=True)
+    cut, base = _record(tmp / "cut"), _record(tmp / "hashed")
+    assert json.loads((tmp / "cut" / "gops.json").read_text())["i_pictures"] == [0, 5, 13]
+    assert cut["pixels"][:5] == base["pixels"][:5] and cut["state"][:5] == base["state"][:5]
+    assert cut["pixels"][5] != base["pixels"][5]
+    for t in range(N):
+        assert int(cut["pixels"][t], 16) == zlib.crc32(_png(tmp / "cut_rec" / f"im{t + 1:05d}.png").tobytes()), t
+    assert RC.decode_folder(str(tmp / "cut"), str(tmp / "cut_dec"), H, W, verify="strict") == N
+
+
+def test_y4m_path_records_and_verifies(e2e, nets):
+    from tests import yuv_ref as YR
+    from vcm_ts_amd import run_codec as RC
+
+    tmp = e2e["tmp"]
+    planes = [tuple(p.astype(np.uint8) for p in YR.from_rgb(a.transpose(2, 0, 1).astype(np.float32) / np.float32(255.0), dtype=np.float64))
+              for a in e2e["clip"]]
+    YR.write_y4m(str(tmp / "src.y4m"), planes, W, H, fps="30:1")
+    RC.encode_video(str(tmp / "src.y4m"), str(tmp / "v1"), gop=GOP, nets=nets, picture_hash=True)
+    RC.encode_video(str(tmp / "src.y4m"), str(tmp / "v2"), gop=GOP, nets=nets, gop_streams=2, picture_hash=True)
+    RC.encode_video(str(tmp / "src.y4m"), str(tmp / "v0"), gop=GOP, nets=nets)
+    assert (tmp / "v1" / "hashes.json").read_text() == (tmp / "v2" / "hashes.json").read_text()
+    assert _bins(tmp / "v1") == _bins(tmp / "v0") == _bins(tmp / "v2")
+    assert sorted(n for n in os.listdir(tmp / "v0") if not n.endswith(".bin")) == ["sequence.json"]
+    assert sorted(n for n in os.listdir(tmp / "v1") if not n.endswith(".bin")) == ["hashes.json", "sequence.json"]
+    assert RC.decode_video(str(tmp / "v1"), str(tmp / "v1.y4m"), verify="strict") == N
+    # the digests are of the RGB reconstruction: decoding the same .bin files to PNGs gives the pictures `pixels` is of
+    assert RC.decode_folder(str(tmp / "v1"), str(tmp / "v1_png"), H, W, gop=GOP) == N
+    assert PH.verify_pngs(str(tmp / "v1"), str(tmp / "v1_png")) is None
+
+
+def test_decode_passes_silently_in_strict(e2e):
+    from vcm_ts_amd import run_codec as RC
+
+    tmp = e2e["tmp"]
+    with warnings.catch_warnings(record=True) as rec:
+        warnings.simplefilter("always")
+        assert RC.decode_folder(str(tmp / "hashed"), str(tmp / "dec_strict"), H, W, gop=GOP, verify="strict") == N
+        assert RC.decode_folder(str(tmp / "hashed"), str(tmp / "dec_default"), H, W, gop=GOP) == N
+    assert not _digest_warnings(rec)
+    for t in range(N):
+        name = f"im{t + 1:05d}.png"
+        assert (tmp / "dec_strict" / name).read_bytes() == (tmp / "hashed_rec" / name).read_bytes(), t
+    with pytest.raises(ValueError, match="digests of 64x64 pictures, decoding 64x48"):  # (before any launch)
+        RC.decode_folder(str(tmp / "hashed"), str(tmp / "refused"), 48, W, gop=GOP)
+    assert not (tmp / "refused").exists()
+
+
+def test_an_edited_pixels_digest_stops_the_decoder_at_that_picture(e2e):
+    from vcm_ts_amd import run_codec as RC
+
+    folder, info = _edited(e2e, "px5", "pixels")
+    want = int(_record(e2e["bins"])["pixels"][5], 16)
+    for mode in (None, "pixels", "strict"):
+        with pytest.raises(PH.PictureHashMismatch) as ex:
+            RC.decode_folder(str(folder), str(e2e["tmp"] / "px5_dec"), H, W, gop=GOP, verify=mode)
+        m = ex.value
+        assert (m.picture, m.name, m.which, m.kind, m.gop_start) == (5, "im00006.bin", "pixels", "P", 0)
+        assert m.expected == int(info["pixels"][5], 16) != want and m.actual == want
+        assert "picture 5" in str(m) and info["pixels"][5] in str(m) and ("%08x" % want) in str(m) and "precision" not in str(m)
+    with pytest.warns(UserWarning, match="picture 5 .*pixels digest") as rec:
+        assert RC.decode_folder(str(folder), str(e2e["tmp"] / "px5_warn"), H, W, gop=GOP, verify="warn") == N
+    assert len(_digest_warnings(rec)) == 1
+
+
+def test_an_edited_state_digest_is_a_warning_unless_strict(e2e):
+    from vcm_ts_amd import run_codec as RC
+
+    folder, info = _edited(e2e, "st5", "state")
+    with pytest.raises(PH.PictureHashMismatch) as ex:
+        RC.decode_folder(str(folder), str(e2e["tmp"] / "st5_dec"), H, W, gop=GOP, verify="strict")
+    assert (ex.value.picture, ex.value.which, ex.value.expected) == (5, "state", int(info["state"][5], 16))
+    for mode in ("pixels", "warn"):
+        with pytest.warns(UserWarning, match="picture 5 .*state digest.*drift has begun, not yet visible") as rec:
+            assert RC.decode_folder(str(folder), str(e2e["tmp"] / f"st5_{mode}"), H, W, gop=GOP, verify=mode) == N
+        assert len(_digest_warnings(rec)) == 1
+    launches, real = [], PH._launch
+    with pytest.MonkeyPatch.context() as mp, warnings.catch_warnings(record=True) as rec:
+        warnings.simplefilter("always")
+        mp.setattr(PH, "_launch", lambda *a, **k: launches.append(a[0]) or real(*a, **k))
+        assert RC.decode_folder(str(folder), str(e2e["tmp"] / "st5_off"), H, W, gop=GOP, verify="off") == N
+        assert launches == [] and not _digest_warnings(rec)
+        with pytest.raises(PH.PictureHashMismatch):
+            RC.decode_folder(str(folder), str(e2e["tmp"] / "st5_dec"), H, W, gop=GOP, verify="strict")
+        assert sorted(set(launches)) == ["dcvc_hash_f32", "dcvc_hash_pixels"]  # (the counter does see them)
+
+
+def test_decoding_with_another_precision_stops_where_the_pictures_part(e2e, nets):
+    """The judge is independent of the hashes: both precisions decode the folder through _decode_bins, every ref_frame is
+    kept, t* is the first picture whose fp32 bits differ and p* the first whose 8-bit codes differ."""
+    from vcm_ts_amd import run_codec as RC
+    from vcm_ts_amd.scenecut import GopPlan
+
+    tmp = e2e["tmp"]
+    coded = _record(e2e["bins"])["precision"]
+    other = "fp16x3" if coded == "fp32" else "fp32"
+    plan, frames = GopPlan.fixed(N, GOP), {}
+    for precision, pair in ((coded, nets[0]), (other, RC._nets(DEV, other))):
+        kept = frames[precision] = []
+        RC._decode_bins(pair, str(e2e["bins"]), H, W, plan, lambda t, ref_frame: kept.append(ref_frame.detach().clone()))
+    assert all(np.array_equal(a.cpu().numpy()[0].view(np.uint32), e2e["ref_frames"][t].view(np.uint32))
+               for t, a in enumerate(frames[coded]))
+    differ = [t for t in range(N) if not torch.equal(frames[coded][t], frames[other][t])]
+    codes = lambda x: R.code(x[0, :, :H, :W].cpu().numpy())
+    visible = [t for t in range(N) if not np.array_equal(codes(frames[coded][t]), codes(frames[other][t]))]
+    print("first fp32 difference:", differ[:1], "first 8-bit difference:", visible[:1])
+    for mode, first in (("strict", differ[:1]), ("pixels", visible[:1])):
+        out = str(tmp / f"cross_{mode}")
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            if not first:
+                assert RC.decode_folder(str(e2e["bins"]), out, H, W, gop=GOP, precision=other, verify=mode) == N
+                continue
+            with pytest.raises(PH.PictureHashMismatch) as ex:
+                RC.decode_folder(str(e2e["bins"]), out, H, W, gop=GOP, precision=other, verify=mode)
+        m = ex.value
+        assert m.picture == first[0] and m.which == ("pixels" if first[0] in visible else "state")
+        assert (m.recorded_precision, m.decoding_precision) == (coded, other)
+        assert f"coded with precision {coded}" in str(m) and f"decoded with {other}" in str(m)

@@ -229,6 +229,9 @@ _SIGS = {
     "dcvc_bits_map_factorized": [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp],
     "dcvc_bits_regions": [vp, vp, i32, vp, i32, i32, i32, vp, vp],
     "dcvc_bits_sweep_scale": [vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp],
+    # include/dcvc_hip_hash.h
+    "dcvc_hash_pixels": [vp, i32, i64, i32, i32, vp, vp, vp],
+    "dcvc_hash_f32": [vp, i32, i64, i32, i32, i32, vp, vp, vp],
 }
 
 # include/dcvc_hip_metrics.h (same library; listed apart because HIP_SYMBOLS is what the three kernel headers declare)
@@ -239,7 +242,9 @@ ROIL_SYMBOLS = ["dcvc_roil_cells", "dcvc_roil_check", "dcvc_roil_encode", "dcvc_
 SCENE_SYMBOLS = ["dcvc_scene_hist"]  # include/dcvc_hip_scene.h
 BITS_SYMBOLS = ["dcvc_bits_map_scale", "dcvc_bits_map_factorized", "dcvc_bits_regions",
                 "dcvc_bits_sweep_scale"]  # include/dcvc_hip_bits.h
-HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS + ROI_SYMBOLS + ROIL_SYMBOLS + SCENE_SYMBOLS + BITS_SYMBOLS] +
+HASH_SYMBOLS = ["dcvc_hash_pixels", "dcvc_hash_f32"]  # include/dcvc_hip_hash.h
+HASH_CONSTANTS = ["dcvc_hash_chunk_bytes", "dcvc_hash_block_bytes", "dcvc_hash_scratch_bytes"]  # (int32 data symbols)
+HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS + ROI_SYMBOLS + ROIL_SYMBOLS + SCENE_SYMBOLS + BITS_SYMBOLS + HASH_SYMBOLS] +
                      ["dcvc_cdf_table_cols", "dcvc_conv_pack_size", "dcvc_conv_pack_size_paired", "dcvc_conv_small_pack_bytes", "dcvc_conv_k32_pack_bytes", "dcvc_conv_tile_rows", "dcvc_conv_chan_partial_parts", "dcvc_hip_version", "dcvc_conv_wgrad_scratch_min",
                       "dcvc_drans_default_lanes", "dcvc_drans_scratch_words"])
 RANS_SYMBOLS = [
@@ -284,6 +289,11 @@ def hip():
         L.dcvc_ms_ssim_workspace_bytes.restype = i64
         _hip = L
     return _hip
+
+
+def hash_constant(name):
+    """One of HASH_CONSTANTS: the library's own value, not a copy of the header's."""
+    return int(i32.in_dll(hip(), name).value)
 
 
 def check(code, what):

@@ -14,6 +14,9 @@
     python -m vcm_ts_amd.run_codec encode ... --scenecut T [--min-gop N]
     python -m vcm_ts_amd.run_codec encode ... --roi-root DIR [--plate-q F] [--face-q F] [--background-q F] [--roi-q-grow N]
     python -m vcm_ts_amd.run_codec encode ... --report JSON --bit-map [DIR]
+    python -m vcm_ts_amd.run_codec encode ... --picture-hash
+    python -m vcm_ts_amd.run_codec decode ... [--verify strict|pixels|warn|off]
+    python -m vcm_ts_amd.run_codec verify --bins DIR --recon DIR
 
 Video files are Y4M or raw I420 at 8 or 10 bits (vcm_ts_amd/yuv.py): no PNG detour, the colour conversion runs on the
 GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` beside the `.bin` files from which
@@ -40,6 +43,12 @@ files, and `decode` then needs the same boxes (--roi-root) to rebuild the maps. 
 With --bit-map the report also says where the bits of every picture went (vcm_ts_amd/bitmap.py: the code lengths of the
 coder's own symbols, summed per 16x16-pixel cell on the GPU): per component, and with a ROI inside and outside the
 boxes; with a DIR the per-cell maps are written there as im%05d.npy.  The .bin files are the same with or without.
+
+With --picture-hash `encode` leaves a `hashes.json` beside the `.bin` files: two CRC-32 digests per coded picture, taken on
+the GPU from the encoder's own reconstruction (vcm_ts_amd/picturehash.py) -- `pixels`, of the 8-bit picture a viewer sees,
+and `state`, of the fp32 reference picture the next one is predicted from.  `decode` follows the file when it is there and
+stops at the first picture it rebuilds differently (--verify); `verify` holds a folder of decoded PNGs against it on the host
+alone.  The .bin files are the same with or without.
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
 reference's `.bin` format (an I picture every `gop` frames).  Unlike run_dcvc the encoder does not
@@ -402,12 +411,16 @@ class _EncodeRun:
     the bits / quality report.  encode_folder and encode_video supply the pictures and take the reconstructions."""
 
     def __init__(self, bin_dir, plan, size, gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams, log_cls,
-                 bit_log=None, rate=None):
+                 bit_log=None, rate=None, picture_hash=False):
         """plan: the GopPlan of the sequence (`gop` is its longest GOP).  nets, gop_streams: see encode_folder.
         log_cls: the _QualityLog to keep per stream, or None for no report.
         bit_log: None, or (labels_of or None, folder or None) -- keep a _BitLog per stream (encode_folder's bit_map=).
-        rate: None, or the factory of _rate_args (encode_folder's target_bpp=)."""
+        rate: None, or the factory of _rate_args (encode_folder's target_bpp=).
+        picture_hash: keep a picturehash.HashLog per stream and write hashes.json (encode_folder's picture_hash=)."""
+        from . import picturehash as PH
+
         os.makedirs(bin_dir, exist_ok=True)
+        PH.remove_hashes(bin_dir)  # (a stale record must not describe these .bin files; ours is written by results())
         self.rate, self.rate_log = rate, {}
         self.bin_dir, self.plan, self.n_frames, self.size, self.gop = bin_dir, plan, plan.n_frames, size, gop
         self.dev = torch.device(device)
@@ -424,6 +437,7 @@ class _EncodeRun:
         if self.bit_dir:
             os.makedirs(self.bit_dir, exist_ok=True)
         self.orders = [plan.order(k, K) for k in range(K)]
+        self.hash_logs = [PH.HashLog(plan) for _ in range(K)] if picture_hash else None
 
     def global_index(self, k, t):  # picture t of stream k's sequence -> 0-based frame number in the sequence
         return self.orders[k][t]
@@ -453,7 +467,18 @@ class _EncodeRun:
         reconstruction of frame g while it is valid (and before stream k's next picture is pulled from frames(k)).
         q_map(g): the q-scale map frame g is coded with, made on the stream that codes it (None: no maps, no launch)."""
         maps_of = lambda k: (lambda t: q_map(self.global_index(k, t))) if q_map else None
-        recon_of = lambda k: (lambda t, ref_frame: on_recon(k, self.global_index(k, t), ref_frame)) if on_recon else None
+        def recon_of(k):
+            if self.hash_logs is None:
+                return (lambda t, ref_frame: on_recon(k, self.global_index(k, t), ref_frame)) if on_recon else None
+
+            def hashed(t, ref_frame):  # (on the stream that coded the picture: two launches each, nothing waited for)
+                g = self.global_index(k, t)
+                self.hash_logs[k].add(g, ref_frame, self.size)
+                if on_recon:
+                    on_recon(k, g, ref_frame)
+
+            return hashed
+
         bits_of = lambda k: (lambda t, bits: self.bit_logs[k].add(self.global_index(k, t), bits))
         # (GopEncoder reads the split-fp16 range guard once per GOP and raises lib.KernelError: no .bin of a clamped GOP
         # is reported as a success)
@@ -485,11 +510,26 @@ class _EncodeRun:
             keys["frame_roi_cells"] = [values[g][1] for g in order]
         return keys
 
+    def _write_hashes(self):
+        """hashes.json: once, when everything has been coded."""
+        from . import picturehash as PH
+
+        digests = {}
+        for k, log in enumerate(self.hash_logs):
+            with torch.cuda.stream(self.cenc.streams[k]):
+                log.flush()  # a trailing partial GOP
+            digests.update(log.collect())
+        h, w = self.size
+        l, r, t, b = S.get_padding_size(h, w)
+        PH.write_hashes(self.bin_dir, digests, h, w, (h + t + b, w + l + r), self.cenc.encoders[0].p_net.engine().precision)
+
     def results(self, report, extras=None):
         """(bits per frame list, size) -- with a report also the rd_report() dictionary, which extras(rd, frame types,
         [the logs' value per frame]) may extend before it is written to `report` (if that is a path)."""
         order = sorted(self.bits)
         bit_list = [self.bits[g] for g in order]
+        if self.hash_logs:
+            self._write_hashes()
         bit_keys = self._bit_results(order) if self.bit_logs else None
         if self.quality is None:
             return bit_list, self.size
@@ -639,7 +679,7 @@ def read_gop_plan(bin_dir, gop=None):
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
                   report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None, target_bpp=None,
-                  q_range=None, residual_bins=None, residual_step=1):
+                  q_range=None, residual_bins=None, residual_step=1, picture_hash=False):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -685,7 +725,13 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     residual_step (1 .. 64; 1 is lossless, S keeps every sample within S // 2), coded cell by cell on the stream that coded the
     picture; decode_folder / decode_video take the same folder in place of residuals=.  It may be given together with
     residuals=.  With report the dictionary gains frame_bits_enh (8 x the record's size), frame_bpp_enh,
-    ave_all_frame_bpp_enh and ave_all_frame_bpp_total (base + enhancement).  None: no launch, file, key or byte changes."""
+    ave_all_frame_bpp_enh and ave_all_frame_bpp_total (base + enhancement).  None: no launch, file, key or byte changes.
+    picture_hash: write hashes.json beside the .bin files (vcm_ts_amd/picturehash.py): per coded picture the CRC-32 of the
+    8-bit codes of the unpadded reconstruction (`pixels`: the bytes of its PNG) and of the fp32 bits of the padded
+    reference picture (`state`), taken on the stream that coded the picture -- two small launches each, one host read per
+    GOP -- and the engine's precision.  Written once, after everything was coded; decode_folder / decode_video follow it.
+    The .bin files are the same with or without.  False: no launch, key or byte changes and no file (a stale one is
+    removed)."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
@@ -733,7 +779,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
         run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
                          (_VideoQualityLog if layer else _QualityLog) if report else None,
-                         _bit_log(bit_map, bit_dir, layer, roi_q), rate)
+                         _bit_log(bit_map, bit_dir, layer, roi_q), rate, picture_hash)
         write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
         write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
@@ -812,8 +858,29 @@ def _decode_bins(nets, bin_dir, height, width, plan, emit, q_map=None):
     return plan.n_frames
 
 
+def _verify_args(verify, bin_dir, plan, height, width):
+    """verify= of a decode loop -> (the folder's hashes.json record or None, the mode), refused by name before any GPU
+    work (picturehash.verify_mode, check_record).  Mode "off" reads no file."""
+    from . import picturehash as PH
+
+    if verify == "off":
+        return None, "off"
+    record = PH.read_hashes(bin_dir)
+    mode = PH.verify_mode(verify, record, bin_dir)
+    if mode != "off":
+        l, r, t, b = S.get_padding_size(height, width)
+        PH.check_record(record, plan, height, width, (height + t + b, width + l + r), os.path.join(bin_dir, PH.HASHES_JSON))
+    return record, mode
+
+
+def _verifier(record, mode, plan, size, nets):
+    from . import picturehash as PH
+
+    return PH.Verifier(record, mode, plan, size, nets[1].engine().precision) if mode != "off" else None
+
+
 def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
-                  io_workers=8, roi=None, residuals=None, residual_bins=None):
+                  io_workers=8, roi=None, residuals=None, residual_bins=None, verify=None):
     """roi, residuals: write video_coder.fuse_layers' picture instead of the reconstruction -- `residuals` is the decoded
     residual layer (a `.gbrp` file or a folder of im%05d.png, as encode_folder writes them) and `roi` the boxes and
     classes it was taken with.  Display side only: the decoder's reference pictures are not touched.
@@ -822,10 +889,19 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", 
     A roiq.json beside the .bin files (encode_folder's roi_q=) is followed: the q-scale maps are rebuilt from `roi`, which
     is then required -- with or without residuals.
     residual_bins: in place of residuals=, the folder of im%05d.rl records encode_folder's residual_bins= wrote: each is
-    held against the frame's boxes by name before any GPU work, decoded on the device and fused.  Giving both is refused."""
+    held against the frame's boxes by name before any GPU work, decoded on the device and fused.  Giving both is refused.
+    verify: "strict", "pixels", "warn" or "off" -- what to do with a hashes.json beside the .bin files (encode_folder's
+    picture_hash=), which is followed without any option: None means "pixels" with the file and "off" without.  Both
+    digests of every decoded base-layer reconstruction (before ROI fusion) are taken on the device and compared GOP by GOP
+    as their copies complete -- the pictures of the GOP in flight, and of the one being compared, may already have been
+    written.  "pixels": picturehash.PictureHashMismatch at the first picture whose `pixels` digest differs, one warning at
+    the first whose `state` alone differs; "strict": raises on either; "warn": never raises; "off": launches nothing.
+    Refused by name before any launch: a mode other than "off" without the file, and a record of another frame count,
+    picture size or padded size."""
     _roi_args(roi, residuals, residual_bins, decode=True)
     plan, _ = read_gop_plan(bin_dir, gop)
     roi_q = read_roiq(bin_dir, roi)
+    record, verify = _verify_args(verify, bin_dir, plan, height, width)
     os.makedirs(recon_dir, exist_ok=True)
     dev = torch.device(device)
     picture, close = _fused_emit(_fuse_roi(roi, residuals, roi_q, residual_bins), residuals, plan, (height, width), dev,
@@ -833,9 +909,18 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", 
     try:
         maps = _decode_maps(roi, roi_q, plan, (height, width), dev)
         nets = _nets(dev, precision, i_ckpt, p_ckpt)
+        checker = _verifier(record, verify, plan, (height, width), nets)
+
+        def emit(t, ref_frame):
+            if checker:
+                checker.add(t, ref_frame)
+            save_torch_image(picture(t, ref_frame), os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"), savers)
+
         with PNGWriters(io_workers) as savers:
-            return _decode_bins(nets, bin_dir, height, width, plan, lambda t, ref_frame: save_torch_image(
-                picture(t, ref_frame), os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"), savers), maps)
+            n = _decode_bins(nets, bin_dir, height, width, plan, emit, maps)
+            if checker:
+                checker.finish()
+            return n
     finally:
         close()
 
@@ -1209,7 +1294,8 @@ def _open_source(video, size, bit_depth, fps):
 def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantize8=False, gop=32, q=(1.0, 1.0, 1.0),
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
-                 min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1):
+                 min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1,
+                 picture_hash=False):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -1227,7 +1313,8 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     conversion (spec, quantize8) as the coding pass.  sequence.json is the same with or without.
     roi_q: as encode_folder (roiq.json beside the .bin files; sequence.json is the same with or without).
     bit_map, target_bpp, q_range: as encode_folder.
-    residual_bins, residual_step: as encode_folder; sequence.json then also records residual_step."""
+    residual_bins, residual_step: as encode_folder; sequence.json then also records residual_step.
+    picture_hash: as encode_folder (the digests are of the RGB reconstruction, before any conversion back to YUV)."""
     from . import yuv as Y
 
     _roi_args(roi, residuals, residual_bins, residual_step)
@@ -1256,7 +1343,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: (x for x, _ in converted(range(n_frames))))
     layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
     run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
-                     _VideoQualityLog if report else None, _bit_log(bit_map, bit_dir, layer, roi_q), rate)
+                     _VideoQualityLog if report else None, _bit_log(bit_map, bit_dir, layer, roi_q), rate, picture_hash)
     write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
     write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
     res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
@@ -1322,12 +1409,13 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
 
 
 def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=None, fps=None, device="cuda:0",
-                 precision=None, i_ckpt=None, p_ckpt=None, roi=None, residuals=None, residual_bins=None):
+                 precision=None, i_ckpt=None, p_ckpt=None, roi=None, residuals=None, residual_bins=None, verify=None):
     """decode_folder's loop with the video output stage.  Size, GOP length, frame rate and colour description come from
     the sequence.json encode_video left in `bin_dir`; explicit arguments override it, and without the file height and
     width are required (gop then defaults to 32, the colour description to yuv.ColorSpec()).  Returns the picture count.
     roi, residuals, residual_bins: as decode_folder -- the fused picture is what is converted and written.  A roiq.json
-    beside the .bin files is followed as decode_folder does."""
+    beside the .bin files is followed as decode_folder does.
+    verify: as decode_folder (the digests are of the RGB reconstruction, before the conversion to YUV)."""
     from . import yuv as Y
 
     _roi_args(roi, residuals, residual_bins, decode=True)
@@ -1342,6 +1430,7 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     if os.path.exists(first) and S.decode_i(first)[:2] != (height, width):
         raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {(height, width)}")
     roi_q = read_roiq(bin_dir, roi)
+    record, verify = _verify_args(verify, bin_dir, plan, height, width)
     fuse_roi = _fuse_roi(roi, residuals, roi_q, residual_bins)
     picture, close = _fused_emit(fuse_roi, residuals, plan, (height, width), torch.device(device), residual_bins)
     try:
@@ -1351,9 +1440,17 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
                                 interlace=info.get("interlace"), aspect=info.get("aspect"))
         try:
             out = _VideoOut(writer)
-            # (without a ROI the padded reconstruction itself: rgb_to_yuv420 reads its top-left corner in place)
-            t = _decode_bins(nets, bin_dir, height, width, plan, lambda t, ref_frame: out.put(t, Y.rgb_to_yuv420(
-                ref_frame if fuse_roi is None else picture(t, ref_frame), height, width, spec)), maps)
+            checker = _verifier(record, verify, plan, (height, width), nets)
+
+            def emit(t, ref_frame):
+                if checker:
+                    checker.add(t, ref_frame)
+                # (without a ROI the padded reconstruction itself: rgb_to_yuv420 reads its top-left corner in place)
+                out.put(t, Y.rgb_to_yuv420(ref_frame if fuse_roi is None else picture(t, ref_frame), height, width, spec))
+
+            t = _decode_bins(nets, bin_dir, height, width, plan, emit, maps)
+            if checker:
+                checker.finish()
             out.close()
         finally:
             writer.close()
@@ -1420,7 +1517,22 @@ def main(argv=None):
     e.add_argument("--background-q", type=float, default=None, metavar="F", help="the factor of the cells no box touches")
     e.add_argument("--roi-q-grow", type=int, default=None, metavar="N",
                    help="with one of the three above: grow every box by N pixels (0 .. 255, default 0) before it is laid on the cells")
+    e.add_argument("--picture-hash", action="store_true",
+                   help="write hashes.json beside the .bin files: two CRC-32 digests per coded picture, taken on the GPU from the "
+                        "encoder's own reconstruction -- of the 8-bit picture (the bytes of its PNG) and of the fp32 reference "
+                        "picture -- which decode follows; the .bin files are the same with or without")
     d = sub.add_parser("decode")
+    d.add_argument("--verify", default=None, choices=["strict", "pixels", "warn", "off"],
+                   help="what to do with a hashes.json beside the .bin files (encode --picture-hash), which is followed without "
+                        "this option as 'pixels': stop at the first picture whose 8-bit digest differs and warn once when only "
+                        "the reference picture's does; strict: stop on either; warn: never stop; off: launch nothing.  "
+                        "Refused without the file, except off")
+    v = sub.add_parser("verify", description="Hold a folder of decoded PNGs against the `pixels` digests of a hashes.json, on "
+                       "the host alone (zlib.crc32 of every picture's RGB bytes; no GPU).  For unfused base-layer PNG folders "
+                       "only: a picture fused with a ROI residual layer is not the picture the digests are of.")
+    v.add_argument("--bins", required=True, help="the folder whose hashes.json encode --picture-hash wrote")
+    v.add_argument("--recon", required=True, help="a folder of im%%05d.png as decode --recon (or encode --recon) writes them, "
+                                                  "unfused base layer only")
     d.add_argument("--bins", required=True)
     d.add_argument("--recon", help="folder for PNGs (exactly one of --recon and --recon-video)")
     d.add_argument("--recon-video", metavar="FILE", help=".y4m / .yuv output; size and colour from the bins' sequence.json")
@@ -1460,6 +1572,19 @@ def main(argv=None):
         p.add_argument("--i-ckpt")
         p.add_argument("--p-ckpt")
     a = ap.parse_args(argv)
+    if a.cmd == "verify":
+        from . import picturehash as PH
+
+        try:
+            first = PH.verify_pngs(a.bins, a.recon)
+        except ValueError as ex:
+            ap.error(str(ex))
+        if first is not None:
+            t, name, want, got = first
+            print(f"picture {t} ({name}): the pixels digest is {got:08x}, {PH.HASHES_JSON} says {want:08x}")
+            raise SystemExit(1)
+        print(f"{len(PH.read_hashes(a.bins)['pixels'])} pictures verified")
+        return
     roi = roi_q = None
     factors = [getattr(a, n, None) for n in ("plate_q", "face_q", "background_q")]
     if a.cmd == "encode":
@@ -1571,13 +1696,15 @@ def main(argv=None):
                                                coder=a.coder, gop_streams=a.gop_streams, report=a.report, roi=roi,
                                                residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
                                                bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
-                                               residual_bins=a.residual_bins, residual_step=a.residual_step)
+                                               residual_bins=a.residual_bins, residual_step=a.residual_step,
+                                               picture_hash=a.picture_hash)
         else:
             bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
                                             coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
                                             roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
                                             bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
-                                            residual_bins=a.residual_bins, residual_step=a.residual_step)
+                                            residual_bins=a.residual_bins, residual_step=a.residual_step,
+                                            picture_hash=a.picture_hash)
         if rd:
             yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
             print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
@@ -1599,16 +1726,21 @@ def main(argv=None):
                 spec = Y.ColorSpec(a.matrix or base.matrix, base.full_range if a.range is None else a.range == "full",
                                    a.siting or base.siting, a.bit_depth or base.bit_depth)
             n = decode_video(a.bins, a.recon_video, a.height, a.width, a.gop, spec, None, a.device, a.precision, a.i_ckpt, a.p_ckpt,
-                             roi=roi, residuals=a.residuals, residual_bins=a.residual_bins)
+                             roi=roi, residuals=a.residuals, residual_bins=a.residual_bins, verify=a.verify)
         else:
             if a.matrix or a.range or a.siting or a.bit_depth:
                 ap.error("--matrix, --range, --siting and --bit-depth belong to --recon-video")
             height, width = a.height or info["height"], a.width or info["width"]
             n = decode_folder(a.bins, a.recon, height, width, a.gop or (info or {}).get("gop"), a.device, a.precision,
                               a.i_ckpt, a.p_ckpt, io_workers=a.io_workers, roi=roi, residuals=a.residuals,
-                              residual_bins=a.residual_bins)
+                              residual_bins=a.residual_bins, verify=a.verify)
         print(f"{n} pictures decoded")
 
 
 if __name__ == "__main__":
-    main()
+    from .picturehash import PictureHashMismatch
+
+    try:
+        main()
+    except PictureHashMismatch as ex:  # (the pictures before it, and maybe some after, have been written)
+        raise SystemExit(f"run_codec decode: {ex}") from None
