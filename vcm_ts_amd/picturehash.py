@@ -115,8 +115,9 @@ class HashLog:
     def __init__(self, plan):
         self.plan, self.buf, self.idx, self.done, self.scratch = plan, None, [], [], None
 
-    def add(self, g, ref_frame, size):
-        """Picture g: `pixels` of the size = (height, width) crop of ref_frame, `state` of all of it."""
+    def add(self, g, ref_frame, size, display=None):
+        """Picture g: `pixels` of the size = (height, width) crop of ref_frame, `state` of all of it.  display (with a
+        base scale): the picture a viewer sees, whose crop `pixels` is taken from instead."""
         import torch
 
         if self.scratch is None:
@@ -127,7 +128,7 @@ class HashLog:
         i = len(self.idx)
         if i >= self.buf.shape[0]:
             raise ValueError(f"HashLog: picture {g} does not belong to the GOP of picture {self.idx[0]}")
-        crc32_pixels(ref_frame, size, out=self.buf[i, 0:1], scratch=self.scratch)
+        crc32_pixels(ref_frame if display is None else display, size, out=self.buf[i, 0:1], scratch=self.scratch)
         crc32_f32(ref_frame, out=self.buf[i, 1:2], scratch=self.scratch)
         self.idx.append(g)
         if self.plan.is_gop_end(g):
@@ -283,15 +284,20 @@ class Verifier:
     """A decode loop's check: add(t, ref_frame) enqueues the two launches of picture t and compares every GOP whose
     digests have arrived meanwhile; finish() compares the rest.  Mode "pixels": PictureHashMismatch at the first picture
     whose `pixels` digest differs, one warning at the first whose `state` alone differs; "strict": raises on either;
-    "warn": warns once, never raises.  (Mode "off" builds no Verifier.)"""
+    "warn": warns once, never raises.  (Mode "off" builds no Verifier.)  check_pixels=False (a base-only decode of a
+    scaled sequence, which never builds the picture `pixels` is of): only `state` is compared."""
 
-    def __init__(self, record, mode, plan, size, decoding_precision):
+    def __init__(self, record, mode, plan, size, decoding_precision, check_pixels=True):
         assert mode in MODES and mode != "off"
         self.record, self.mode, self.plan, self.size, self.precision = record, mode, plan, size, decoding_precision
-        self.log, self.warned = HashLog(plan), False
+        self.log, self.warned, self.check_pixels = HashLog(plan), False, check_pixels
 
-    def add(self, t, ref_frame):
-        self.log.add(t, ref_frame, self.size)
+    def add(self, t, ref_frame, display=None):
+        """display (with a base scale): the up-scaled picture `pixels` is of; self.size is then its size."""
+        if display is None:
+            self.log.add(t, ref_frame, self.size)
+        else:
+            self.log.add(t, ref_frame, self.size, display=display)
         self._compare(self.log.poll())
 
     def finish(self):
@@ -302,7 +308,7 @@ class Verifier:
         for t, pixels, state in rows:
             for which, got in (("pixels", pixels), ("state", state)):
                 want = self.record[which][t]
-                if got == want:
+                if got == want or (which == "pixels" and not self.check_pixels):
                     continue
                 m = PictureHashMismatch(t, which, want, got, "I" if self.plan.is_intra(t) else "P",
                                         self.plan.i_pictures[self.plan.gop_of(t)], self.record["precision"], self.precision)

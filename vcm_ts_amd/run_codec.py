@@ -17,6 +17,8 @@
     python -m vcm_ts_amd.run_codec encode ... --picture-hash
     python -m vcm_ts_amd.run_codec decode ... [--verify strict|pixels|warn|off]
     python -m vcm_ts_amd.run_codec verify --bins DIR --recon DIR
+    python -m vcm_ts_amd.run_codec encode ... --base-scale N/D
+    python -m vcm_ts_amd.run_codec decode ... [--base-only]
 
 Video files are Y4M or raw I420 at 8 or 10 bits (vcm_ts_amd/yuv.py): no PNG detour, the colour conversion runs on the
 GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` beside the `.bin` files from which
@@ -49,6 +51,13 @@ the GPU from the encoder's own reconstruction (vcm_ts_amd/picturehash.py) -- `pi
 and `state`, of the fp32 reference picture the next one is predicted from.  `decode` follows the file when it is there and
 stops at the first picture it rebuilds differently (--verify); `verify` holds a folder of decoded PNGs against it on the host
 alone.  The .bin files are the same with or without.
+
+With --base-scale N/D (1/4 <= N/D < 1) the base layer is coded at reduced size: every picture is scaled down on the GPU before
+the codec sees it and the reconstruction is scaled up again for everything that looks at it (vcm_ts_amd/scale.py: a separable
+Lanczos-3 with integer taps whose arithmetic is part of the interface, so that encoder and decoder rebuild the same full-size
+picture bit for bit and the residual layer stays lossless).  The .bin files are an ordinary sequence of base-size pictures; a
+`scale.json` beside them says how they are scaled up, which `decode` follows (`decode --base-only` ignores it and writes the
+base-size pictures).  Reports, residuals, boxes, --target-bpp, --height / --width and sequence.json all speak of the full size.
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
 reference's `.bin` format (an I picture every `gop` frames).  Unlike run_dcvc the encoder does not
@@ -411,8 +420,10 @@ class _EncodeRun:
     the bits / quality report.  encode_folder and encode_video supply the pictures and take the reconstructions."""
 
     def __init__(self, bin_dir, plan, size, gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams, log_cls,
-                 bit_log=None, rate=None, picture_hash=False):
+                 bit_log=None, rate=None, picture_hash=False, base=None):
         """plan: the GopPlan of the sequence (`gop` is its longest GOP).  nets, gop_streams: see encode_folder.
+        base: None, or the _BaseLayer of encode_folder's base_scale= -- `size` is then the BASE size (what the .bin files
+        hold); the report, hashes.json and the returned size speak of base.full, and `pixels` is of base.shown().
         log_cls: the _QualityLog to keep per stream, or None for no report.
         bit_log: None, or (labels_of or None, folder or None) -- keep a _BitLog per stream (encode_folder's bit_map=).
         rate: None, or the factory of _rate_args (encode_folder's target_bpp=).
@@ -423,6 +434,7 @@ class _EncodeRun:
         PH.remove_hashes(bin_dir)  # (a stale record must not describe these .bin files; ours is written by results())
         self.rate, self.rate_log = rate, {}
         self.bin_dir, self.plan, self.n_frames, self.size, self.gop = bin_dir, plan, plan.n_frames, size, gop
+        self.base, self.full = base, (base.full if base else size)
         self.dev = torch.device(device)
         self.n_gops = plan.n_gops
         self.K = K = max(1, min(int(gop_streams), self.n_gops))
@@ -473,7 +485,10 @@ class _EncodeRun:
 
             def hashed(t, ref_frame):  # (on the stream that coded the picture: two launches each, nothing waited for)
                 g = self.global_index(k, t)
-                self.hash_logs[k].add(g, ref_frame, self.size)
+                if self.base:
+                    self.hash_logs[k].add(g, ref_frame, self.full, display=self.base.shown(k, g, ref_frame))
+                else:
+                    self.hash_logs[k].add(g, ref_frame, self.size)
                 if on_recon:
                     on_recon(k, g, ref_frame)
 
@@ -519,7 +534,7 @@ class _EncodeRun:
             with torch.cuda.stream(self.cenc.streams[k]):
                 log.flush()  # a trailing partial GOP
             digests.update(log.collect())
-        h, w = self.size
+        h, w = self.full  # (with a base scale: the display size `pixels` is of; `state` is of the base reference picture)
         l, r, t, b = S.get_padding_size(h, w)
         PH.write_hashes(self.bin_dir, digests, h, w, (h + t + b, w + l + r), self.cenc.encoders[0].p_net.engine().precision)
 
@@ -532,8 +547,8 @@ class _EncodeRun:
             self._write_hashes()
         bit_keys = self._bit_results(order) if self.bit_logs else None
         if self.quality is None:
-            return bit_list, self.size
-        h, w = self.size
+            return bit_list, self.full
+        h, w = self.full
         values = {}
         for k, log in enumerate(self.quality):
             with torch.cuda.stream(self.cenc.streams[k]):
@@ -553,7 +568,7 @@ class _EncodeRun:
 
             with open(report, "w") as f:
                 json.dump(rd, f, indent=2)
-        return bit_list, self.size, rd
+        return bit_list, self.full, rd
 
 
 GOPS_JSON = "gops.json"
@@ -625,6 +640,13 @@ def write_roiq(bin_dir, roi_q, names=()):
         json.dump(info, f, indent=2)
 
 
+def _write_scale(bin_dir, base):
+    """scale.json beside the .bin files of an encode with a base scale; without one a stale file is removed."""
+    from . import scale as SC
+
+    SC.write_scale(bin_dir, base.scale if base else None)
+
+
 def read_roiq(bin_dir, roi=None):
     """The roi.RoiQ the .bin files of `bin_dir` were coded with, or None without a roiq.json.  Refused by name: the file
     without `roi` (the maps are rebuilt from the boxes), class names that are not the roi's, values out of range."""
@@ -676,10 +698,88 @@ def read_gop_plan(bin_dir, gop=None):
     return plan, int(info.get("gop") or longest)
 
 
+class _BaseLayer:
+    """The reduced-resolution base layer of a file loop (base_scale=, vcm_ts_amd/scale.py): full-size pictures go down to
+    the codec's size on the stream that codes them, reconstructions come up again for whatever looks at them.  The DPB
+    keeps the base picture: up() is display side only."""
+
+    def __init__(self, scale):
+        self.scale, self.full, self.size, self.cur = scale, scale.full, scale.base, {}
+        l, r, t, b = S.get_padding_size(*self.size)
+        self.padded = (self.size[0] + t + b, self.size[1] + l + r)
+
+    def down(self, x):
+        """The zeroed, 64-padded base picture the codec takes of a (padded) full-size picture: one launch into its interior."""
+        (h, w), (hb, wb) = self.full, self.size
+        out = torch.zeros((1, 3) + self.padded, dtype=torch.float32, device=x.device)
+        self.scale.down(x[..., :h, :w], out=out[..., :hb, :wb])
+        return out
+
+    def shown(self, k, g, ref_frame):
+        """The full-size picture of frame g's base reconstruction, made once per picture on stream k's current stream."""
+        if self.cur.get(k, (None, None))[0] != g:
+            self.cur[k] = (g, self.scale.up(ref_frame[..., :self.size[0], :self.size[1]]))
+        return self.cur[k][1]
+
+
+def _base_args(base_scale, roi, roi_q, bit_map, size, dev):
+    """base_scale= of an encode loop -> its _BaseLayer (None without), refused by name before any other GPU work."""
+    if base_scale is None:
+        return None
+    from . import scale as SC
+
+    ratio = SC.as_ratio(base_scale)
+    if roi_q is not None:
+        raise NotImplementedError("base_scale= with roi_q= (--plate-q / --face-q / --background-q): q-scale maps of boxes on "
+                                  "the base grid are not implemented")
+    if bit_map and roi is not None:
+        raise NotImplementedError("base_scale= with bit_map= and roi= (--bit-map with --roi-root): regional bit counts of "
+                                  "boxes on the base grid are not implemented")
+    return _BaseLayer(SC.Scale(size, ratio, dev))
+
+
+def _decode_scale(bin_dir, height, width, base_scale, roi, residuals, residual_bins):
+    """base_scale= of a decode loop ("file": follow the folder's scale.json; None: ignore it, --base-only) ->
+    (scale.read_scale's record of the scaler to build, or None when nothing is scaled up; the (height, width) of the coded
+    pictures).  height, width: the display size.  Host work only (_up_layer builds the tables on the device, once every
+    refusal has had its turn).  Refused by name: a scale.json of another display size or whose base is not what the .bin
+    files hold, a base-only decode with a ROI, anything but "file" and None.  A base-only decode does not read the file:
+    the first .bin file's header says what size the pictures are."""
+    from . import scale as SC
+
+    if base_scale not in ("file", None):
+        raise ValueError(f"base_scale: expected 'file' (follow {SC.SCALE_JSON}) or None (base only), got {base_scale!r}")
+    where, first = os.path.join(bin_dir, SC.SCALE_JSON), os.path.join(bin_dir, "im00001.bin")
+    if base_scale is None:
+        if not (os.path.exists(where) and os.path.exists(first)):
+            return None, (height, width)
+        if roi is not None or residuals is not None or residual_bins is not None:
+            raise ValueError("a base-only decode (base_scale=None, --base-only) takes no roi=, residuals= or residual_bins=: "
+                             "boxes and the residual layer live at full size")
+        return None, tuple(S.decode_i(first)[:2])
+    info = SC.read_scale(bin_dir)
+    if info is None:
+        return None, (height, width)
+    if info["full"] != (int(height), int(width)):
+        raise ValueError(f"{where}: a base layer of {info['full'][1]}x{info['full'][0]} pictures, decoding {width}x{height}")
+    if os.path.exists(first) and tuple(S.decode_i(first)[:2]) != info["base"]:
+        coded = S.decode_i(first)[:2]
+        raise ValueError(f"{where}: a base layer of {info['base'][1]}x{info['base'][0]} pictures (ratio {info['ratio']}), the "
+                         f".bin files hold {coded[1]}x{coded[0]}")
+    return info, info["base"]
+
+
+def _up_layer(info, dev):
+    """The _BaseLayer of _decode_scale's record (None: none)."""
+    from . import scale as SC
+
+    return _BaseLayer(SC.Scale(info["full"], info["ratio"], dev)) if info else None
+
+
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
                   report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None, target_bpp=None,
-                  q_range=None, residual_bins=None, residual_step=1, picture_hash=False):
+                  q_range=None, residual_bins=None, residual_step=1, picture_hash=False, base_scale=None):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -731,7 +831,17 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     reference picture (`state`), taken on the stream that coded the picture -- two small launches each, one host read per
     GOP -- and the engine's precision.  Written once, after everything was coded; decode_folder / decode_video follow it.
     The .bin files are the same with or without.  False: no launch, key or byte changes and no file (a stale one is
-    removed)."""
+    removed).
+    base_scale: a ratio n/d with 1/4 <= n/d < 1 (a Fraction, an (n, d) pair or "n/d") -- code the base layer at reduced size
+    (vcm_ts_amd/scale.py, DESIGN.md 4m).  Each side becomes (2 side n + d) // (2 d); every picture is scaled down on the stream
+    that codes it (one launch) and then padded as usual, so the .bin files are an ordinary sequence of base-size pictures,
+    and scale.json beside them says how decode_folder / decode_video scale them up.  Everything that looks at a
+    reconstruction sees it scaled up to the full size, on the same stream, only when something does: recon_dir, report
+    (PSNR, MS-SSIM and the ROI figures against the full-size source; every bpp per full-size pixel), residuals and
+    residual_bins (taken against the up-scaled picture, boxes in full-size coordinates) and picture_hash (`pixels` is of the
+    up-scaled picture, `state` of the base reference picture).  target_bpp counts full-size pixels; the scene-cut scan sees
+    the full-size source; bit_map without roi maps the base grid.  With roi_q, or bit_map with roi: NotImplementedError.
+    None: no launch, file, key or byte changes (a stale scale.json is removed)."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
@@ -750,6 +860,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     bit_dir = _bitmap_args(bit_map, report)
     rate = _rate_args(target_bpp, q_range, h, w, gop)
     dev = torch.device(device)
+    base = _base_args(base_scale, roi, roi_q, bit_map, (h, w), dev)
     pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
 
     def raw_frames(order, sharers):
@@ -777,11 +888,12 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     try:
         plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: uploaded(range(n_frames), 1))
         layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
-        run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
-                         (_VideoQualityLog if layer else _QualityLog) if report else None,
-                         _bit_log(bit_map, bit_dir, layer, roi_q), rate, picture_hash)
+        run = _EncodeRun(bin_dir, plan, base.size if base else (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets,
+                         gop_streams, (_VideoQualityLog if layer else _QualityLog) if report else None,
+                         _bit_log(bit_map, bit_dir, layer, roi_q), rate, picture_hash, base)
         write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
         write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
+        _write_scale(bin_dir, base)
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
         rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
     except BaseException:
@@ -794,9 +906,11 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         for x in uploaded(run.order(k), run.K):
             if report or res_out or rec_out:
                 source[k] = x  # (the picture on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
-            yield x
+            yield base.down(x) if base else x
 
     def on_recon(k, g, ref_frame):
+        if base:  # (everything below looks at the full-size picture; the DPB keeps the base one)
+            ref_frame = base.shown(k, g, ref_frame)
         if res_out:
             res_out.put(k, g, source[k][..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
         if rec_out:
@@ -873,14 +987,14 @@ def _verify_args(verify, bin_dir, plan, height, width):
     return record, mode
 
 
-def _verifier(record, mode, plan, size, nets):
+def _verifier(record, mode, plan, size, nets, check_pixels=True):
     from . import picturehash as PH
 
-    return PH.Verifier(record, mode, plan, size, nets[1].engine().precision) if mode != "off" else None
+    return PH.Verifier(record, mode, plan, size, nets[1].engine().precision, check_pixels) if mode != "off" else None
 
 
 def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
-                  io_workers=8, roi=None, residuals=None, residual_bins=None, verify=None):
+                  io_workers=8, roi=None, residuals=None, residual_bins=None, verify=None, base_scale="file"):
     """roi, residuals: write video_coder.fuse_layers' picture instead of the reconstruction -- `residuals` is the decoded
     residual layer (a `.gbrp` file or a folder of im%05d.png, as encode_folder writes them) and `roi` the boxes and
     classes it was taken with.  Display side only: the decoder's reference pictures are not touched.
@@ -897,27 +1011,38 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", 
     written.  "pixels": picturehash.PictureHashMismatch at the first picture whose `pixels` digest differs, one warning at
     the first whose `state` alone differs; "strict": raises on either; "warn": never raises; "off": launches nothing.
     Refused by name before any launch: a mode other than "off" without the file, and a record of another frame count,
-    picture size or padded size."""
+    picture size or padded size.
+    base_scale: "file" -- a scale.json beside the .bin files (encode_folder's base_scale=) is followed: height and width stay
+    the DISPLAY size, the .bin files hold the base-size pictures, and every reconstruction is scaled up on the device
+    before it is fused and written (display side only: the DPB keeps the base picture); the `pixels` digest is of the
+    up-scaled, unfused picture.  None: ignore the file and write the base-size pictures -- what a decoder that knows
+    nothing of it gets anyway; `pixels` is then not checked, and a ROI is refused.  Also refused by name before any launch: a
+    scale.json of another display size, of another base size than the .bin files', or whose tables this host builds
+    differently (scale.read_scale)."""
     _roi_args(roi, residuals, residual_bins, decode=True)
     plan, _ = read_gop_plan(bin_dir, gop)
     roi_q = read_roiq(bin_dir, roi)
     record, verify = _verify_args(verify, bin_dir, plan, height, width)
-    os.makedirs(recon_dir, exist_ok=True)
     dev = torch.device(device)
-    picture, close = _fused_emit(_fuse_roi(roi, residuals, roi_q, residual_bins), residuals, plan, (height, width), dev,
-                                 residual_bins)
+    scaled, coded = _decode_scale(bin_dir, height, width, base_scale, roi, residuals, residual_bins)
+    shown = (height, width) if scaled else coded  # (the size of what is written)
+    os.makedirs(recon_dir, exist_ok=True)
+    base = _up_layer(scaled, dev)
+    picture, close = _fused_emit(_fuse_roi(roi, residuals, roi_q, residual_bins), residuals, plan, shown, dev, residual_bins)
     try:
         maps = _decode_maps(roi, roi_q, plan, (height, width), dev)
         nets = _nets(dev, precision, i_ckpt, p_ckpt)
-        checker = _verifier(record, verify, plan, (height, width), nets)
+        checker = _verifier(record, verify, plan, shown, nets, check_pixels=shown == (height, width))
 
         def emit(t, ref_frame):
+            full = base.shown(0, t, ref_frame) if base else None
             if checker:
-                checker.add(t, ref_frame)
-            save_torch_image(picture(t, ref_frame), os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"), savers)
+                checker.add(t, ref_frame, display=full)
+            save_torch_image(picture(t, ref_frame if full is None else full), os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"),
+                             savers)
 
         with PNGWriters(io_workers) as savers:
-            n = _decode_bins(nets, bin_dir, height, width, plan, emit, maps)
+            n = _decode_bins(nets, bin_dir, coded[0], coded[1], plan, emit, maps)
             if checker:
                 checker.finish()
             return n
@@ -1295,7 +1420,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
                  min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1,
-                 picture_hash=False):
+                 picture_hash=False, base_scale=None):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -1314,7 +1439,9 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     roi_q: as encode_folder (roiq.json beside the .bin files; sequence.json is the same with or without).
     bit_map, target_bpp, q_range: as encode_folder.
     residual_bins, residual_step: as encode_folder; sequence.json then also records residual_step.
-    picture_hash: as encode_folder (the digests are of the RGB reconstruction, before any conversion back to YUV)."""
+    picture_hash: as encode_folder (the digests are of the RGB reconstruction, before any conversion back to YUV).
+    base_scale: as encode_folder -- the scaling comes after the colour conversion (RGB only); sequence.json keeps the
+    source's size, scale.json lies beside it."""
     from . import yuv as Y
 
     _roi_args(roi, residuals, residual_bins, residual_step)
@@ -1330,6 +1457,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     if n_frames < 1:
         raise ValueError(f"{getattr(reader, 'path', video)}: no frames")
     dev = torch.device(device)
+    base = _base_args(base_scale, roi, roi_q, bit_map, (h, w), dev)
     sample_dtype = torch.uint8 if spec.bit_depth == 8 else torch.int16
 
     def converted(order):
@@ -1342,10 +1470,12 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
 
     plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: (x for x, _ in converted(range(n_frames))))
     layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
-    run = _EncodeRun(bin_dir, plan, (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams,
-                     _VideoQualityLog if report else None, _bit_log(bit_map, bit_dir, layer, roi_q), rate, picture_hash)
+    run = _EncodeRun(bin_dir, plan, base.size if base else (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets,
+                     gop_streams, _VideoQualityLog if report else None, _bit_log(bit_map, bit_dir, layer, roi_q), rate,
+                     picture_hash, base)
     write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
     write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
+    _write_scale(bin_dir, base)
     res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
     rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
     source = {}
@@ -1358,10 +1488,12 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     def frames(k):
         for x, samples in converted(run.order(k)):
             source[k] = (x, samples)  # (what on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
-            yield x
+            yield base.down(x) if base else x
 
     def on_recon(k, g, ref_frame):
         x, samples = source[k]
+        if base:  # (everything below looks at the full-size picture; the DPB keeps the base one)
+            ref_frame = base.shown(k, g, ref_frame)
         if res_out:
             res_out.put(k, g, x[..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
         if rec_out:
@@ -1409,13 +1541,15 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
 
 
 def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=None, fps=None, device="cuda:0",
-                 precision=None, i_ckpt=None, p_ckpt=None, roi=None, residuals=None, residual_bins=None, verify=None):
+                 precision=None, i_ckpt=None, p_ckpt=None, roi=None, residuals=None, residual_bins=None, verify=None,
+                 base_scale="file"):
     """decode_folder's loop with the video output stage.  Size, GOP length, frame rate and colour description come from
     the sequence.json encode_video left in `bin_dir`; explicit arguments override it, and without the file height and
     width are required (gop then defaults to 32, the colour description to yuv.ColorSpec()).  Returns the picture count.
     roi, residuals, residual_bins: as decode_folder -- the fused picture is what is converted and written.  A roiq.json
     beside the .bin files is followed as decode_folder does.
-    verify: as decode_folder (the digests are of the RGB reconstruction, before the conversion to YUV)."""
+    verify: as decode_folder (the digests are of the RGB reconstruction, before the conversion to YUV).
+    base_scale: as decode_folder (None writes a video of the base size)."""
     from . import yuv as Y
 
     _roi_args(roi, residuals, residual_bins, decode=True)
@@ -1425,30 +1559,36 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
         raise ValueError(f"no {SEQUENCE_JSON} in {bin_dir}: height and width are required")
     plan, _ = read_gop_plan(bin_dir, gop or info.get("gop"))  # (gops.json, when encode left one, says where the I pictures are)
     spec = spec or info.get("color") or Y.ColorSpec()
-    Y.check_size(height, width)
+    scaled, coded = _decode_scale(bin_dir, height, width, base_scale, roi, residuals, residual_bins)
+    shown_h, shown_w = (height, width) if scaled else coded  # (the size of what is written)
+    Y.check_size(shown_h, shown_w)
     first = os.path.join(bin_dir, "im00001.bin")
-    if os.path.exists(first) and S.decode_i(first)[:2] != (height, width):
-        raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {(height, width)}")
+    if not scaled and os.path.exists(first) and S.decode_i(first)[:2] != coded:  # (with a scale.json: _decode_scale's check)
+        raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {coded}")
     roi_q = read_roiq(bin_dir, roi)
     record, verify = _verify_args(verify, bin_dir, plan, height, width)
     fuse_roi = _fuse_roi(roi, residuals, roi_q, residual_bins)
-    picture, close = _fused_emit(fuse_roi, residuals, plan, (height, width), torch.device(device), residual_bins)
+    base = _up_layer(scaled, torch.device(device))
+    picture, close = _fused_emit(fuse_roi, residuals, plan, (shown_h, shown_w), torch.device(device), residual_bins)
     try:
         maps = _decode_maps(roi, roi_q, plan, (height, width), torch.device(device))
         nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
-        writer = Y.create_video(recon_video, width, height, spec, fps or info.get("fps"), chroma=info.get("chroma"),
+        writer = Y.create_video(recon_video, shown_w, shown_h, spec, fps or info.get("fps"), chroma=info.get("chroma"),
                                 interlace=info.get("interlace"), aspect=info.get("aspect"))
         try:
             out = _VideoOut(writer)
-            checker = _verifier(record, verify, plan, (height, width), nets)
+            checker = _verifier(record, verify, plan, (shown_h, shown_w), nets, check_pixels=(shown_h, shown_w) == (height, width))
 
             def emit(t, ref_frame):
+                full = base.shown(0, t, ref_frame) if base else None
                 if checker:
-                    checker.add(t, ref_frame)
+                    checker.add(t, ref_frame, display=full)
+                if full is not None:
+                    ref_frame = full
                 # (without a ROI the padded reconstruction itself: rgb_to_yuv420 reads its top-left corner in place)
-                out.put(t, Y.rgb_to_yuv420(ref_frame if fuse_roi is None else picture(t, ref_frame), height, width, spec))
+                out.put(t, Y.rgb_to_yuv420(ref_frame if fuse_roi is None else picture(t, ref_frame), shown_h, shown_w, spec))
 
-            t = _decode_bins(nets, bin_dir, height, width, plan, emit, maps)
+            t = _decode_bins(nets, bin_dir, coded[0], coded[1], plan, emit, maps)
             if checker:
                 checker.finish()
             out.close()
@@ -1521,7 +1661,16 @@ def main(argv=None):
                    help="write hashes.json beside the .bin files: two CRC-32 digests per coded picture, taken on the GPU from the "
                         "encoder's own reconstruction -- of the 8-bit picture (the bytes of its PNG) and of the fp32 reference "
                         "picture -- which decode follows; the .bin files are the same with or without")
+    e.add_argument("--base-scale", default=None, metavar="N/D",
+                   help="code the base layer at N/D of the source's size, 1/4 <= N/D < 1 (each side rounded to the nearest "
+                        "sample): pictures are scaled down on the GPU before the codec and up again for --recon, --recon-video, "
+                        "--report, --residuals, --residual-bins and --picture-hash, all of which keep speaking of the full "
+                        "size, as does --target-bpp; scale.json beside the .bin files tells decode.  Not with --plate-q, "
+                        "--face-q, --background-q, nor with --bit-map and --roi-root together")
     d = sub.add_parser("decode")
+    d.add_argument("--base-only", action="store_true",
+                   help="ignore a scale.json beside the .bin files (encode --base-scale) and write the base-size pictures; "
+                        "--height / --width stay the full size.  Not with --roi-root")
     d.add_argument("--verify", default=None, choices=["strict", "pixels", "warn", "off"],
                    help="what to do with a hashes.json beside the .bin files (encode --picture-hash), which is followed without "
                         "this option as 'pixels': stop at the first picture whose 8-bit digest differs and warn once when only "
@@ -1587,6 +1736,15 @@ def main(argv=None):
         return
     roi = roi_q = None
     factors = [getattr(a, n, None) for n in ("plate_q", "face_q", "background_q")]
+    if a.cmd == "encode" and a.base_scale is not None:
+        from . import scale as SC
+
+        try:
+            a.base_scale = SC.as_ratio(a.base_scale)
+        except ValueError as ex:
+            ap.error(f"--base-scale: {ex}")
+    if a.cmd == "decode" and a.base_only and a.roi_root is not None:
+        ap.error("--base-only takes no --roi-root: boxes and the residual layer live at full size")
     if a.cmd == "encode":
         if a.roi_root is None and (any(f is not None for f in factors) or a.roi_q_grow is not None):
             ap.error("--plate-q, --face-q, --background-q and --roi-q-grow belong to --roi-root")
@@ -1697,14 +1855,14 @@ def main(argv=None):
                                                residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
                                                bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
                                                residual_bins=a.residual_bins, residual_step=a.residual_step,
-                                               picture_hash=a.picture_hash)
+                                               picture_hash=a.picture_hash, base_scale=a.base_scale)
         else:
             bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
                                             coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
                                             roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
                                             bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
                                             residual_bins=a.residual_bins, residual_step=a.residual_step,
-                                            picture_hash=a.picture_hash)
+                                            picture_hash=a.picture_hash, base_scale=a.base_scale)
         if rd:
             yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
             print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
@@ -1726,14 +1884,15 @@ def main(argv=None):
                 spec = Y.ColorSpec(a.matrix or base.matrix, base.full_range if a.range is None else a.range == "full",
                                    a.siting or base.siting, a.bit_depth or base.bit_depth)
             n = decode_video(a.bins, a.recon_video, a.height, a.width, a.gop, spec, None, a.device, a.precision, a.i_ckpt, a.p_ckpt,
-                             roi=roi, residuals=a.residuals, residual_bins=a.residual_bins, verify=a.verify)
+                             roi=roi, residuals=a.residuals, residual_bins=a.residual_bins, verify=a.verify,
+                             base_scale=None if a.base_only else "file")
         else:
             if a.matrix or a.range or a.siting or a.bit_depth:
                 ap.error("--matrix, --range, --siting and --bit-depth belong to --recon-video")
             height, width = a.height or info["height"], a.width or info["width"]
             n = decode_folder(a.bins, a.recon, height, width, a.gop or (info or {}).get("gop"), a.device, a.precision,
                               a.i_ckpt, a.p_ckpt, io_workers=a.io_workers, roi=roi, residuals=a.residuals,
-                              residual_bins=a.residual_bins, verify=a.verify)
+                              residual_bins=a.residual_bins, verify=a.verify, base_scale=None if a.base_only else "file")
         print(f"{n} pictures decoded")
 
 
