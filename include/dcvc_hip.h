@@ -52,6 +52,9 @@ extern "C" {
 
 /* bits of the optional device status word of the split-fp16 kernels */
 #define DCVC_STATUS_ACT_SATURATED 1  /* an activation with |v| > 8188 was clamped while being stored split */
+/* A NaN output sets the bit in dcvc_conv2d_small only, which tests every element with !(|v| <= 8188); dcvc_conv2d and
+ * dcvc_conv2d_k32 fold the magnitudes through fmaxf, which drops a NaN, so there a NaN output leaves the word as it was
+ * unless an infinite or out-of-range output of the same launch sets it (tests/test_gpu_conv_exact.py). */
 
 #define DCVC_MAX_SEG 3
 

@@ -86,10 +86,11 @@ __host__ __device__ inline size_t mfma_wpack_f16(int cg, int T, int t, int cc, i
 }
 
 // ---- entry points of the three convolution kernels ---------------------------------------------------------------------
-// what dcvc_conv2d, dcvc_conv2d_k32 and dcvc_conv2d_small all demand: the pointers, and per input segment a 16-byte
+// what dcvc_conv2d, dcvc_conv2d_k32 and dcvc_conv2d_small all demand: the pointers, positive sizes, and per input segment a 16-byte
 // aligned base and a channel stride that is a multiple of 4 and covers the channels
 inline bool conv_args_ok(const dcvc_conv_args *a) {
     if (!a || a->nseg < 1 || a->nseg > DCVC_MAX_SEG || !a->out || !a->wpack || !a->bpack) return false;
+    if (a->N <= 0 || a->Hin <= 0 || a->Win <= 0 || a->Cout <= 0) return false;  // an empty grid is no launch
     for (int s = 0; s < a->nseg; ++s)
         if (!a->seg[s].ptr || (a->seg[s].cs & 3) || a->seg[s].cs < round_up(a->seg[s].C, 4) || ((uintptr_t)a->seg[s].ptr & 15))
             return false;

@@ -356,6 +356,12 @@ class Engine:
         w = w.contiguous().numpy()
         Cout, Cin, ks, _ = w.shape
         assert sum(seg_C) == Cin, (key, seg_C, Cin)
+        # The plain packer keeps a NaN weight, conv_mfma's range guard does not see a NaN output and the next split-fp16
+        # layer's clamp on load turns it into a finite number: a broken checkpoint would code garbage silently.  fp32
+        # mode propagates the NaN as the reference does.
+        if self.precision == "fp16x3" and not np.isfinite(w).all():
+            raise lib.KernelError(f"{pack_fn[5:]}({key}): {int((~np.isfinite(w)).sum())} non-finite weight(s) cannot be "
+                                  f"represented in split fp16, use precision='fp32'")
         b = None if bias is None else bias.detach().float().cpu().contiguous().numpy()
         segs = (C.c_int32 * len(seg_C))(*seg_C)
         layer = (Cout, Cin) if variant == "paired" else (Cout, ks, len(seg_C), segs)
