@@ -63,13 +63,17 @@ def intra_dpb(x_hat):
     return {"ref_frame": x_hat, "ref_feature": None, "ref_y": None, "ref_mv_y": None}
 
 
-def decode_picture(i_net, p_net, kind, q, payload, dpb, height, width, defer_check=False, q_map=None):
+def decode_picture(i_net, p_net, kind, q, payload, dpb, height, width, defer_check=False, q_map=None, aq=None):
     """Decode one coded picture ("I" with q = (q index,), "P" with q = (mv_y index, y index)) against `dpb`; returns the
     DPB it leaves.  The split-fp16 range guard is left to the caller (once per GOP, not per picture).
-    q_map: the q-scale map the picture was coded with (roi.q_map), None for none."""
+    q_map: the q-scale map the picture was coded with (roi.q_map), None for none.
+    aq: the aq.AqMaps of backward-adaptive quantisation the sequence was coded with (None: none) -- a P picture's map is
+    then rebuilt from dpb["ref_frame"] (and multiplied into q_map); an I picture has no reference and keeps q_map."""
     if kind == "I":
         return intra_dpb(i_net.decompress(payload, height, width, q[0] / 100, defer_check=defer_check, check_range=False,
                                           q_map=q_map)["x_hat"])
+    if aq is not None:
+        q_map = aq.map(dpb["ref_frame"], q_map)
     return p_net.decompress(dpb, payload, height, width, q[0] / 100, q[1] / 100, defer_check=defer_check,
                             check_range=False, q_map=q_map)["dpb"]
 
@@ -86,7 +90,7 @@ class GopEncoder:
         self.p_net.update()
 
     def encode_gop(self, frames, q_i, q_mv_y, q_y, sink=None, on_recon=None, intra=None, q_maps=None, bit_maps=None, rate=None,
-                   res=None):
+                   res=None, aq=None):
         """frames: iterable of padded (1, 3, H, W) device tensors, the first coded as an I
         picture.  intra: the set of picture numbers (positions in `frames`) coded as I pictures -- 0 among them, no two
         further apart than gop_size -- instead of every multiple of gop_size (scenecut.GopPlan).  Returns (list of payload bytes with their headers' q indexes, total bits of
@@ -102,15 +106,20 @@ class GopEncoder:
         with sweep= and with the q_y its GOP's controller decides from the pictures already retired (picture t from t - 2:
         the software pipeline below is untouched), and its header carries that index.  A GOP's bytes depend on its own
         pictures and the target only.  res: a dictionary that receives "rate_log", the controllers' logs in picture order
-        [(q index, actual bits, budget or None, sweep row or None)].  None: exactly the launches and bytes without it."""
+        [(q index, actual bits, budget or None, sweep row or None)].  None: exactly the launches and bytes without it.
+        aq: backward-adaptive quantisation (vcm_ts_amd/aq.py) -- an aq.AQ, or the aq.AqMaps of this encoder's
+        stream.  Every P picture is coded with the map made from its reference picture, dpb["ref_frame"], multiplied into
+        its q_maps map if it has one (a memset and two launches on the current stream); I pictures keep their q_maps map.
+        The payloads do not carry the maps: decode_picture / decode_gop need the same aq.  Refused with graphs=True
+        (NotImplementedError, as a q-scale map is).  None: no launch, allocation or byte changes."""
         res = {} if res is None else res
         for _ in self.encode_steps(frames, q_i, q_mv_y, q_y, res, sink=sink, on_recon=on_recon, intra=intra, q_maps=q_maps,
-                                   bit_maps=bit_maps, rate=rate):
+                                   bit_maps=bit_maps, rate=rate, aq=aq):
             pass
         return res["coded"], res["bits"], res["dpb"]
 
     def encode_steps(self, frames, q_i, q_mv_y, q_y, res, sink=None, on_recon=None, intra=None, q_maps=None, bit_maps=None,
-                     rate=None):
+                     rate=None, aq=None):
         """encode_gop as a generator that yields after every picture it has enqueued, so that several
         encoders can be interleaved by one host thread (ConcurrentGopEncoder).  Fills `res` with
         "coded", "bits", "dpb" (with `rate` also "rate_log") when exhausted."""
@@ -126,6 +135,12 @@ class GopEncoder:
         if rate is not None and self.graphs:
             raise NotImplementedError("rate: graph replay with rate control is not supported (GopEncoder(graphs=False))")
         controls, ctl = [], None  # (rate control: one controller per GOP, made at its I picture)
+        if aq is not None:
+            if self.graphs:
+                raise NotImplementedError("aq: graph replay with a q-scale map is not supported (GopEncoder(graphs=False))")
+            from .aq import as_maps
+
+            aq = as_maps(aq, self.p_net.device)
 
         def retire(item):  # host half of a picture: wait for its planes, rANS-code them
             nonlocal bits
@@ -157,6 +172,8 @@ class GopEncoder:
                     controls.append(ctl)
                     rated = (ctl, 0, None)
             elif rate is not None:
+                if aq is not None:
+                    qm = aq.map(dpb["ref_frame"], qm)
                 qy_t = ctl.decide(t - last_i, qy_idx)
                 r = self.p_net.compress(x, dpb, q_mv_y, qy_t / 100, defer=True, coder=self.coder, check_range=False, q_map=qm,
                                         bit_map=want_bits, sweep=ctl.ladder)
@@ -164,6 +181,8 @@ class GopEncoder:
                 item = ("P", (qmv_idx, qy_t), r["pending"], t)
                 rated = (ctl, t - last_i, r["rate_sweep"])
             else:
+                if aq is not None:  # (from the reference picture both sides hold: the decoder makes the same map)
+                    qm = aq.map(dpb["ref_frame"], qm)
                 r = self.p_net.compress(x, dpb, q_mv_y, q_y, defer=True, coder=self.coder, graph=self.graphs, check_range=False,
                                         q_map=qm, bit_map=want_bits)
                 dpb = r["dpb"]
@@ -193,9 +212,12 @@ class GopEncoder:
         if rate is not None:
             res["rate_log"] = [entry for c in controls for entry in c.log]
 
-    def decode_gop(self, coded, height, width):
-        """Inverse of encode_gop (the reference decoder path): returns the list of x_hat."""
+    def decode_gop(self, coded, height, width, aq=None):
+        """Inverse of encode_gop (the reference decoder path): returns the list of x_hat.  aq: what encode_gop was given."""
+        from .aq import as_maps
         from .entropy import DRANS_MAGIC
+
+        aq = as_maps(aq, self.p_net.device)
 
         recs, dpb, deferred = [], None, set()
         for kind, q, payload in coded:
@@ -203,7 +225,7 @@ class GopEncoder:
             dev_fmt = payload[:4] == DRANS_MAGIC
             if dev_fmt:
                 deferred.add(self.i_net if kind == "I" else self.p_net)
-            dpb = decode_picture(self.i_net, self.p_net, kind, q, payload, dpb, height, width, defer_check=dev_fmt)
+            dpb = decode_picture(self.i_net, self.p_net, kind, q, payload, dpb, height, width, defer_check=dev_fmt, aq=aq)
             recs.append(dpb["ref_frame"].clone())
         for net in deferred:
             net.device_coder().check()
@@ -228,17 +250,24 @@ class ConcurrentGopEncoder:
         dev = self.encoders[0].p_net.device
         self.device = dev
         self.streams = [torch.cuda.Stream(dev) for _ in self.encoders]
+        self._aq = (None, None)  # (the aq.AQ the streams' AqMaps were last made for, the AqMaps)
 
     def encode_gops(self, sequences, q_i, q_mv_y, q_y, sinks=None, on_recons=None, intra=None, q_maps=None, bit_maps=None,
-                    rate=None):
+                    rate=None, aq=None):
         """sequences: up to `streams` iterables of padded pictures (one sequence of whole GOPs each; an iterable is
         pulled INSIDE its stream, so a generator may upload its pictures there).  Returns a list of
         (coded, bits, dpb) in the same order.  sinks / on_recons: per-sequence callbacks of GopEncoder.encode_gop; intra:
         per-sequence sets of the picture numbers coded as I (GopEncoder.encode_gop), None for every multiple of gop_size.
         q_maps, bit_maps: per-sequence callables of GopEncoder.encode_gop (each is called inside its sequence's stream).
         rate: ONE factory of GopEncoder.encode_gop for all sequences (a controller belongs to one GOP, so the bytes are
-        those of sequential coding); the sequences' logs are then in self.rate_logs, in the same order."""
+        those of sequential coding); the sequences' logs are then in self.rate_logs, in the same order.
+        aq: ONE aq.AQ of GopEncoder.encode_gop for all sequences; every stream gets an aq.AqMaps of its own (tables and
+        scratch, made once per setting and kept)."""
         assert len(sequences) <= len(self.encoders)
+        if aq is not None and self._aq[0] != aq:
+            from .aq import AqMaps
+
+            self._aq = (aq, [AqMaps(aq, self.device) for _ in self.encoders])
         cur = torch.cuda.current_stream(self.device)
         results = [{} for _ in sequences]
         gens = []
@@ -248,7 +277,8 @@ class ConcurrentGopEncoder:
                                                       on_recon=on_recons[k] if on_recons else None,
                                                       intra=intra[k] if intra else None,
                                                       q_maps=q_maps[k] if q_maps else None,
-                                                      bit_maps=bit_maps[k] if bit_maps else None, rate=rate))
+                                                      bit_maps=bit_maps[k] if bit_maps else None, rate=rate,
+                                                      aq=self._aq[1][k] if aq is not None else None))
         live = list(range(len(gens)))
         while live:
             for k in list(live):

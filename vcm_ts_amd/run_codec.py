@@ -19,6 +19,7 @@
     python -m vcm_ts_amd.run_codec verify --bins DIR --recon DIR
     python -m vcm_ts_amd.run_codec encode ... --base-scale N/D
     python -m vcm_ts_amd.run_codec decode ... [--base-only]
+    python -m vcm_ts_amd.run_codec encode ... --aq-strength A [--aq-clamp LO HI]
 
 Video files are Y4M or raw I420 at 8 or 10 bits (vcm_ts_amd/yuv.py): no PNG detour, the colour conversion runs on the
 GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` beside the `.bin` files from which
@@ -58,6 +59,13 @@ Lanczos-3 with integer taps whose arithmetic is part of the interface, so that e
 picture bit for bit and the residual layer stays lossless).  The .bin files are an ordinary sequence of base-size pictures; a
 `scale.json` beside them says how they are scaled up, which `decode` follows (`decode --base-only` ignores it and writes the
 base-size pictures).  Reports, residuals, boxes, --target-bpp, --height / --width and sequence.json all speak of the full size.
+
+With --aq-strength A (hundredths of a QP per doubling of a cell's variance, 1 .. 400) every P picture is coded under a q-scale
+map made on the GPU from its own reference picture (vcm_ts_amd/aq.py: backward-adaptive quantisation, an integer function of the
+picture's 8-bit codes): cells flatter than the reference's mean get a finer step of the latent y, busier ones a coarser one.  The
+decoder holds the same reference picture and rebuilds the map: the .bin format is unchanged and nothing is stored per picture; an
+`aq.json` beside the .bin files carries the setting, which `decode` follows without any option.  I pictures are not adapted.
+There is no tuned value.
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
 reference's `.bin` format (an I picture every `gop` frames).  Unlike run_dcvc the encoder does not
@@ -474,10 +482,11 @@ class _EncodeRun:
 
         return sink
 
-    def encode(self, frames, q, on_recon=None, q_map=None):
+    def encode(self, frames, q, on_recon=None, q_map=None, aq=None):
         """frames(k): generator of stream k's padded pictures, those of order(k).  on_recon(k, g, ref_frame): sees the
         reconstruction of frame g while it is valid (and before stream k's next picture is pulled from frames(k)).
-        q_map(g): the q-scale map frame g is coded with, made on the stream that codes it (None: no maps, no launch)."""
+        q_map(g): the q-scale map frame g is coded with, made on the stream that codes it (None: no maps, no launch).
+        aq: the aq.AQ of backward-adaptive quantisation (encode_folder's aq=), None for none."""
         maps_of = lambda k: (lambda t: q_map(self.global_index(k, t))) if q_map else None
         def recon_of(k):
             if self.hash_logs is None:
@@ -501,7 +510,8 @@ class _EncodeRun:
             self.cenc.encode_gops([frames(k) for k in range(self.K)], q[0], q[1], q[2], sinks=[self._sink(k) for k in range(self.K)],
                                   on_recons=[recon_of(k) for k in range(self.K)], intra=[self.intra(k) for k in range(self.K)],
                                   q_maps=[maps_of(k) for k in range(self.K)] if q_map else None,
-                                  bit_maps=[bits_of(k) for k in range(self.K)] if self.bit_logs else None, rate=self.rate)
+                                  bit_maps=[bits_of(k) for k in range(self.K)] if self.bit_logs else None, rate=self.rate,
+                                  aq=aq)
         if self.rate is not None:
             for k, log in enumerate(self.cenc.rate_logs):
                 self.rate_log.update({self.global_index(k, t): entry for t, entry in enumerate(log)})
@@ -647,6 +657,37 @@ def _write_scale(bin_dir, base):
     SC.write_scale(bin_dir, base.scale if base else None)
 
 
+def _aq_args(aq):
+    """aq= of an encode loop, refused by name before any GPU work."""
+    from . import aq as A
+
+    if aq is not None and not isinstance(aq, A.AQ):
+        raise ValueError(f"aq: expected an aq.AQ, got {type(aq).__name__}")
+    return aq
+
+
+def _write_aq(bin_dir, aq):
+    """aq.json beside the .bin files of an encode with backward-adaptive quantisation; without it a stale file is removed."""
+    from . import aq as A
+
+    A.write_aq(bin_dir, aq)
+
+
+def _read_aq(bin_dir):
+    """The aq.AQ of the folder's aq.json, None without the file: host work only, so that the refusals of aq.read_aq (an
+    unknown version, a value out of range, tables this host builds differently) come before any launch or output."""
+    from . import aq as A
+
+    return A.read_aq(bin_dir)
+
+
+def _decode_aq(aq, dev):
+    """aq= of _decode_bins: the aq.AqMaps of _read_aq's record on `dev` (None: none)."""
+    from . import aq as A
+
+    return A.AqMaps(aq, dev) if aq is not None else None
+
+
 def read_roiq(bin_dir, roi=None):
     """The roi.RoiQ the .bin files of `bin_dir` were coded with, or None without a roiq.json.  Refused by name: the file
     without `roi` (the maps are rebuilt from the boxes), class names that are not the roi's, values out of range."""
@@ -779,7 +820,7 @@ def _up_layer(info, dev):
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
                   report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None, target_bpp=None,
-                  q_range=None, residual_bins=None, residual_step=1, picture_hash=False, base_scale=None):
+                  q_range=None, residual_bins=None, residual_step=1, picture_hash=False, base_scale=None, aq=None):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -841,7 +882,15 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     residual_bins (taken against the up-scaled picture, boxes in full-size coordinates) and picture_hash (`pixels` is of the
     up-scaled picture, `state` of the base reference picture).  target_bpp counts full-size pixels; the scene-cut scan sees
     the full-size source; bit_map without roi maps the base grid.  With roi_q, or bit_map with roi: NotImplementedError.
-    None: no launch, file, key or byte changes (a stale scale.json is removed)."""
+    None: no launch, file, key or byte changes (a stale scale.json is removed).
+    aq: an aq.AQ -- backward-adaptive quantisation (vcm_ts_amd/aq.py).  Every P picture is coded with a
+    q-scale map made on the stream that codes it from its own reference picture (a memset and two launches per picture):
+    cells flatter than the reference's mean activity get a finer step of the latent y, busier ones a coarser one.  The
+    decoder holds the same reference picture and rebuilds the map, so the .bin format is unchanged and no map is stored;
+    aq.json beside the .bin files records the setting and the digests of its two tables, and decode_folder / decode_video
+    follow it.  I pictures are not adapted.  With roi_q the two factors multiply; with base_scale the map is taken from the
+    base-size reference; target_bpp prices every picture under its map.  None: no launch, file or byte changes (a stale
+    aq.json is removed)."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
@@ -857,6 +906,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         w, h = first.size
     _roi_args(roi, residuals, residual_bins, residual_step)
     _roiq_args(roi, roi_q)
+    _aq_args(aq)
     bit_dir = _bitmap_args(bit_map, report)
     rate = _rate_args(target_bpp, q_range, h, w, gop)
     dev = torch.device(device)
@@ -894,6 +944,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
         write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
         _write_scale(bin_dir, base)
+        _write_aq(bin_dir, aq)
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
         rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
     except BaseException:
@@ -927,7 +978,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     try:
         with PNGWriters(io_workers) as savers:
             run.encode(frames, q, on_recon if (recon_dir or report or res_out or rec_out) else None,
-                       (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None)
+                       (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None, aq)
         failed = False
     finally:
         if pool is not None:
@@ -940,10 +991,10 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     return run.results(report, _enh_report_keys(rec_out, h, w, extras) if rec_out else extras)
 
 
-def _decode_bins(nets, bin_dir, height, width, plan, emit, q_map=None):
+def _decode_bins(nets, bin_dir, height, width, plan, emit, q_map=None, aq=None):
     """Decode im00001.bin ... of `bin_dir` (I pictures where `plan`, read_gop_plan's, has them) in order, handing every
     reconstruction to emit(t, ref_frame) while it is valid.  q_map(t): the q-scale map picture t was coded with (None: no
-    maps).  Returns the picture count."""
+    maps).  aq: _decode_aq's AqMaps (None: none).  Returns the picture count."""
     i_net, p_net = nets
     i_net.update()
     p_net.update()
@@ -965,7 +1016,8 @@ def _decode_bins(nets, bin_dir, height, width, plan, emit, q_map=None):
             else:
                 qmv, qy, payload = S.decode_p(path)
                 kind, q = "P", (qmv, qy)
-            dpb = decode_picture(i_net, p_net, kind, q, payload, dpb, height, width, q_map=q_map(t) if q_map else None)
+            dpb = decode_picture(i_net, p_net, kind, q, payload, dpb, height, width, q_map=q_map(t) if q_map else None,
+                                 aq=aq)
             emit(t, dpb["ref_frame"])
         if plan.n_frames:
             range_guard()
@@ -1018,10 +1070,15 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", 
     up-scaled, unfused picture.  None: ignore the file and write the base-size pictures -- what a decoder that knows
     nothing of it gets anyway; `pixels` is then not checked, and a ROI is refused.  Also refused by name before any launch: a
     scale.json of another display size, of another base size than the .bin files', or whose tables this host builds
-    differently (scale.read_scale)."""
+    differently (scale.read_scale).
+    An aq.json beside the .bin files (encode_folder's aq=) is followed without any option: every P picture's q-scale map is
+    rebuilt from the decoder's own reference picture (also in a base-only decode, from the base-size one).  Refused by
+    name before any launch: an aq.json of an unknown version, with a value out of range, or whose tables this host builds
+    differently (aq.read_aq)."""
     _roi_args(roi, residuals, residual_bins, decode=True)
     plan, _ = read_gop_plan(bin_dir, gop)
     roi_q = read_roiq(bin_dir, roi)
+    aq = _read_aq(bin_dir)
     record, verify = _verify_args(verify, bin_dir, plan, height, width)
     dev = torch.device(device)
     scaled, coded = _decode_scale(bin_dir, height, width, base_scale, roi, residuals, residual_bins)
@@ -1031,6 +1088,7 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", 
     picture, close = _fused_emit(_fuse_roi(roi, residuals, roi_q, residual_bins), residuals, plan, shown, dev, residual_bins)
     try:
         maps = _decode_maps(roi, roi_q, plan, (height, width), dev)
+        aq = _decode_aq(aq, dev)
         nets = _nets(dev, precision, i_ckpt, p_ckpt)
         checker = _verifier(record, verify, plan, shown, nets, check_pixels=shown == (height, width))
 
@@ -1042,7 +1100,7 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", 
                              savers)
 
         with PNGWriters(io_workers) as savers:
-            n = _decode_bins(nets, bin_dir, coded[0], coded[1], plan, emit, maps)
+            n = _decode_bins(nets, bin_dir, coded[0], coded[1], plan, emit, maps, aq)
             if checker:
                 checker.finish()
             return n
@@ -1420,7 +1478,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
                  min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1,
-                 picture_hash=False, base_scale=None):
+                 picture_hash=False, base_scale=None, aq=None):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -1441,11 +1499,13 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     residual_bins, residual_step: as encode_folder; sequence.json then also records residual_step.
     picture_hash: as encode_folder (the digests are of the RGB reconstruction, before any conversion back to YUV).
     base_scale: as encode_folder -- the scaling comes after the colour conversion (RGB only); sequence.json keeps the
-    source's size, scale.json lies beside it."""
+    source's size, scale.json lies beside it.
+    aq: as encode_folder (aq.json beside the .bin files; sequence.json is the same with or without)."""
     from . import yuv as Y
 
     _roi_args(roi, residuals, residual_bins, residual_step)
     _roiq_args(roi, roi_q)
+    _aq_args(aq)
     bit_dir = _bitmap_args(bit_map, report)
     reader = _open_source(video, size, bit_depth, fps)  # (every refusal about the file happens here, before any GPU work)
     spec = spec or reader.spec()
@@ -1476,6 +1536,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
     write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
     _write_scale(bin_dir, base)
+    _write_aq(bin_dir, aq)
     res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
     rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
     source = {}
@@ -1511,7 +1572,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     failed = True
     try:
         run.encode(frames, q, on_recon if (outs or report or res_out or rec_out) else None,
-                   (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None)
+                   (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None, aq)
         for o in outs or []:
             o.close()
         failed = False
@@ -1549,7 +1610,8 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     roi, residuals, residual_bins: as decode_folder -- the fused picture is what is converted and written.  A roiq.json
     beside the .bin files is followed as decode_folder does.
     verify: as decode_folder (the digests are of the RGB reconstruction, before the conversion to YUV).
-    base_scale: as decode_folder (None writes a video of the base size)."""
+    base_scale: as decode_folder (None writes a video of the base size).
+    An aq.json beside the .bin files is followed as decode_folder does."""
     from . import yuv as Y
 
     _roi_args(roi, residuals, residual_bins, decode=True)
@@ -1566,12 +1628,14 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     if not scaled and os.path.exists(first) and S.decode_i(first)[:2] != coded:  # (with a scale.json: _decode_scale's check)
         raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {coded}")
     roi_q = read_roiq(bin_dir, roi)
+    aq = _read_aq(bin_dir)
     record, verify = _verify_args(verify, bin_dir, plan, height, width)
     fuse_roi = _fuse_roi(roi, residuals, roi_q, residual_bins)
     base = _up_layer(scaled, torch.device(device))
     picture, close = _fused_emit(fuse_roi, residuals, plan, (shown_h, shown_w), torch.device(device), residual_bins)
     try:
         maps = _decode_maps(roi, roi_q, plan, (height, width), torch.device(device))
+        aq = _decode_aq(aq, torch.device(device))
         nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
         writer = Y.create_video(recon_video, shown_w, shown_h, spec, fps or info.get("fps"), chroma=info.get("chroma"),
                                 interlace=info.get("interlace"), aspect=info.get("aspect"))
@@ -1588,7 +1652,7 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
                 # (without a ROI the padded reconstruction itself: rgb_to_yuv420 reads its top-left corner in place)
                 out.put(t, Y.rgb_to_yuv420(ref_frame if fuse_roi is None else picture(t, ref_frame), shown_h, shown_w, spec))
 
-            t = _decode_bins(nets, bin_dir, coded[0], coded[1], plan, emit, maps)
+            t = _decode_bins(nets, bin_dir, coded[0], coded[1], plan, emit, maps, aq)
             if checker:
                 checker.finish()
             out.close()
@@ -1667,6 +1731,16 @@ def main(argv=None):
                         "--report, --residuals, --residual-bins and --picture-hash, all of which keep speaking of the full "
                         "size, as does --target-bpp; scale.json beside the .bin files tells decode.  Not with --plate-q, "
                         "--face-q, --background-q, nor with --bit-map and --roi-root together")
+    e.add_argument("--aq-strength", type=int, default=None, metavar="A",
+                   help="backward-adaptive quantisation: code every P picture with a q-scale map made on the GPU from its own "
+                        "reference picture -- a 16x16 cell flatter than the reference's mean activity gets a finer step of the "
+                        "latent y, a busier one a coarser step; A, 1 .. 400, is in hundredths of a QP per doubling of the cell's "
+                        "variance (x265's --aq-strength times 100; no tuned value exists).  The decoder rebuilds the maps from its "
+                        "own reference pictures: the .bin format is unchanged, nothing is stored per picture, and aq.json beside "
+                        "the .bin files tells decode.  I pictures are not adapted")
+    e.add_argument("--aq-clamp", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="with --aq-strength: the factors a cell may get, in hundredths, 10 <= LO <= 100 <= HI <= 1000 "
+                        "(default 10 1000)")
     d = sub.add_parser("decode")
     d.add_argument("--base-only", action="store_true",
                    help="ignore a scale.json beside the .bin files (encode --base-scale) and write the base-size pictures; "
@@ -1734,7 +1808,17 @@ def main(argv=None):
             raise SystemExit(1)
         print(f"{len(PH.read_hashes(a.bins)['pixels'])} pictures verified")
         return
-    roi = roi_q = None
+    roi = roi_q = aq = None
+    if a.cmd == "encode":
+        if a.aq_clamp is not None and a.aq_strength is None:
+            ap.error("--aq-clamp belongs to --aq-strength")
+        if a.aq_strength is not None:
+            from . import aq as A
+
+            try:
+                aq = A.AQ(a.aq_strength, *(a.aq_clamp or (A.MIN_Q, A.MAX_Q)))
+            except ValueError as ex:
+                ap.error(f"--aq-strength / --aq-clamp: {ex}")
     factors = [getattr(a, n, None) for n in ("plate_q", "face_q", "background_q")]
     if a.cmd == "encode" and a.base_scale is not None:
         from . import scale as SC
@@ -1855,14 +1939,14 @@ def main(argv=None):
                                                residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
                                                bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
                                                residual_bins=a.residual_bins, residual_step=a.residual_step,
-                                               picture_hash=a.picture_hash, base_scale=a.base_scale)
+                                               picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq)
         else:
             bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
                                             coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
                                             roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
                                             bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
                                             residual_bins=a.residual_bins, residual_step=a.residual_step,
-                                            picture_hash=a.picture_hash, base_scale=a.base_scale)
+                                            picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq)
         if rd:
             yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
             print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
