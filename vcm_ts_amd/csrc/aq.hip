@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void aq_activity_kernel(const ActivityArgs p) 
         for (int g = 0; g < 4; ++g)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const unsigned Y = (unsigned)(54 * code8(f[g][0][i]) + 183 * code8(f[g][1][i]) + 19 * code8(f[g][2][i]) + 128) >> 8;
+                const unsigned Y = (unsigned)luma8(code8(f[g][0][i]), code8(f[g][1][i]), code8(f[g][2][i]));
                 s1 += Y, s2 += Y * Y;
             }
         s1 = fold(fold(fold(fold(s1, 1), 2), 16), 32);

@@ -1,4 +1,5 @@
-// roi_common.h -- what roi.hip and roil.hip share: the 8-bit code of a float sample, the cull of a picture's box list
+// roi_common.h -- what roi.hip, roil.hip, aq.hip and motion.hip share: the 8-bit code of a float sample and the luma of three
+// codes, the cull of a picture's box list
 // against a rectangle into LDS, and the entry points' checks of pictures and box lists (include/dcvc_hip_roi.h).
 // Internal, like kernel_common.h: every unit is compiled on its own, hence the unnamed namespace.
 #ifndef DCVC_ROI_COMMON_H
@@ -13,6 +14,9 @@
 namespace {
 
 __device__ __forceinline__ int code8(float v) { return (int)rintf(255.0f * fminf(fmaxf(v, 0.0f), 1.0f)); }
+
+// the luma of dcvc_hip_scene.h on three 8-bit codes
+__device__ __forceinline__ int luma8(int r, int g, int b) { return (54 * r + 183 * g + 19 * b + 128) >> 8; }
 
 // ONE wave culls the list against the rectangle [rx0, rx1) x [ry0, ry1) into box[] / cls[] KEEPING LIST ORDER (ballot +
 // prefix popcount per round of 64 boxes) and returns how many it kept.  shrink(c): what class c's boxes lose on every

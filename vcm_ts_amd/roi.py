@@ -429,19 +429,28 @@ class _ArrayUnpickler(pickle.Unpickler):
 class PickleBoxes:
     """The reference's coordinate files: `root`/liplates_coords/%05d and `root`/faces_coords/%05d (numbered from 1), each
     a pickled np.uint16 (n, 4) array of x1, y1, x2, y2.  Plates come before faces in the list (the reference's order of
-    assignment) with cls 0 and 1.  Either folder may be absent; a folder that is there must hold every frame asked for."""
+    assignment) with cls 0 and 1.  Either folder may be absent; a folder that is there must hold every frame asked for.
+    A third, optional folder `root`/motion_coords (motionroi.write_boxes: the same files) adds the class "motion" with
+    cls 2, last in the list; `names` and `classes` have three entries only when it exists, and it may be the only one."""
     FOLDERS = (("liplates", "liplates_coords"), ("faces", "faces_coords"))
+    MOTION = ("motion", "motion_coords")
 
     def __init__(self, root, classes=None):
         self.root = root
-        self.folders = [(cls, name, os.path.join(root, sub)) for cls, (name, sub) in enumerate(self.FOLDERS)
+        known = self.FOLDERS + ((self.MOTION,) if self.has_motion(root) else ())
+        self.folders = [(cls, name, os.path.join(root, sub)) for cls, (name, sub) in enumerate(known)
                         if os.path.isdir(os.path.join(root, sub))]
         if not self.folders:
             raise FileNotFoundError(f"{root}: neither liplates_coords nor faces_coords")
-        self.names = tuple(name for name, _ in self.FOLDERS)
-        self.classes = tuple(classes) if classes is not None else (RoiClass(0), RoiClass(0))
-        if len(self.classes) != 2:
-            raise ValueError("PickleBoxes takes two classes: plates, faces")
+        self.names = tuple(name for name, _ in known)
+        self.classes = tuple(classes) if classes is not None else tuple(RoiClass(0) for _ in known)
+        if len(self.classes) != len(known):
+            raise ValueError("PickleBoxes takes two classes: plates, faces" if len(known) == 2 else
+                             "PickleBoxes takes three classes with a motion_coords folder: plates, faces, motion")
+
+    @classmethod
+    def has_motion(cls, root):
+        return os.path.isdir(os.path.join(root, cls.MOTION[1]))
 
     @staticmethod
     def _load(path):

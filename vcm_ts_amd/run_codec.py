@@ -20,6 +20,9 @@
     python -m vcm_ts_amd.run_codec encode ... --base-scale N/D
     python -m vcm_ts_amd.run_codec decode ... [--base-only]
     python -m vcm_ts_amd.run_codec encode ... --aq-strength A [--aq-clamp LO HI]
+    python -m vcm_ts_amd.run_codec boxes (--frames DIR | --video FILE [--size WxH]) --out ROOT --threshold T [--learn KB KF]
+                                         [--min-pixels P] [--grow G] [--min-cells C] [--max-boxes N]
+    python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT [--motion-border N] [--motion-q F]
 
 Video files are Y4M or raw I420 at 8 or 10 bits (vcm_ts_amd/yuv.py): no PNG detour, the colour conversion runs on the
 GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` beside the `.bin` files from which
@@ -66,6 +69,12 @@ picture's 8-bit codes): cells flatter than the reference's mean get a finer step
 decoder holds the same reference picture and rebuilds the map: the .bin format is unchanged and nothing is stored per picture; an
 `aq.json` beside the .bin files carries the setting, which `decode` follows without any option.  I pictures are not adapted.
 There is no tuned value.
+
+`boxes` makes a --roi-root from the source alone (vcm_ts_amd/motionroi.py: a background model of the luma on the GPU, a
+scan pass of its own like --scenecut's, boxes around the 16x16 cells that differ from the model): ROOT/motion_coords/%05d
+in the reference's coordinate format and ROOT/motion.json.  A root that holds motion_coords has a third box class, "motion",
+with --motion-border and --motion-q beside the plates' and faces' options; without the folder nothing changes.  There is no
+default T, the other parameters are untuned placeholders, and nothing is claimed about detection quality.
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
 reference's `.bin` format (an I picture every `gop` frames).  Unlike run_dcvc the encoder does not
@@ -817,6 +826,47 @@ def _up_layer(info, dev):
     return _BaseLayer(SC.Scale(info["full"], info["ratio"], dev)) if info else None
 
 
+def _png_pictures(reader, order, size, dev, pool, io_workers, sharers):
+    """The pictures of a PNG folder that `order` names, on the device, as the padded float32 pictures the codec takes: what
+    the coding pass, the scene-cut scan and the motion scan all read.  The (H, W, 3) uint8 arrays are decoded up to `depth`
+    ahead by the shared `pool` (which `sharers` such generators draw on together; None: inline)."""
+    from collections import deque
+
+    h, w = size
+
+    def raw_frames():
+        if pool is None:
+            for g in order:
+                yield reader.load_u8(reader.path_of(g + 1))
+            return
+        depth, pending, nxt = max(2, 2 * io_workers // sharers), deque(), 0
+        while nxt < len(order) or pending:
+            while nxt < len(order) and len(pending) < depth:
+                pending.append(pool.submit(reader.load_u8, reader.path_of(order[nxt] + 1)))
+                nxt += 1
+            yield pending.popleft().result()
+
+    ring = _PinnedRing(dev, (h, w, 3))
+    for rgb in raw_frames():
+        assert tuple(rgb.shape) == (h, w, 3), "all frames must have one size"
+        ring.host()[...] = rgb
+        yield pad_frame(u8_to_unit_float(ring.upload()))
+
+
+def _video_pictures(reader, order, spec, quantize8, dev):
+    """(the padded RGB picture the codec takes, the file's samples on the device) of every frame of a yuv reader that
+    `order` names: the one path from the file to the codec (a ring of pinned buffers, one asynchronous copy, the colour
+    conversion on the device) of the coding pass, the scene-cut scan and the motion scan."""
+    from . import yuv as Y
+
+    sample_dtype = torch.uint8 if spec.bit_depth == 8 else torch.int16
+    ring = _PinnedRing(dev, reader.frame_bytes)
+    for g in order:
+        reader.read_into(g, ring.host())
+        samples = ring.upload().view(sample_dtype)
+        yield Y.yuv420_to_rgb(samples, reader.height, reader.width, spec, pad=True, quantize8=quantize8), samples
+
+
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
                   report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None, target_bpp=None,
@@ -891,7 +941,6 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     follow it.  I pictures are not adapted.  With roi_q the two factors multiply; with base_scale the map is taken from the
     base-size reference; target_bpp prices every picture under its map.  None: no launch, file or byte changes (a stale
     aq.json is removed)."""
-    from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
     from PIL import Image
@@ -913,27 +962,8 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     base = _base_args(base_scale, roi, roi_q, bit_map, (h, w), dev)
     pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
 
-    def raw_frames(order, sharers):
-        """The pictures `order` names as (H, W, 3) uint8 arrays, decoded up to `depth` ahead by the shared pool (which
-        `sharers` such generators draw on together)."""
-        if pool is None:
-            for g in order:
-                yield reader.load_u8(reader.path_of(g + 1))
-            return
-        depth, pending, nxt = max(2, 2 * io_workers // sharers), deque(), 0
-        while nxt < len(order) or pending:
-            while nxt < len(order) and len(pending) < depth:
-                pending.append(pool.submit(reader.load_u8, reader.path_of(order[nxt] + 1)))
-                nxt += 1
-            yield pending.popleft().result()
-
     def uploaded(order, sharers):
-        """raw_frames on the device, as the padded float32 pictures the codec takes."""
-        ring = _PinnedRing(dev, (h, w, 3))
-        for rgb in raw_frames(order, sharers):
-            assert tuple(rgb.shape) == (h, w, 3), "all frames must have one size"
-            ring.host()[...] = rgb
-            yield pad_frame(u8_to_unit_float(ring.upload()))
+        return _png_pictures(reader, order, (h, w), dev, pool, io_workers, sharers)
 
     try:
         plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: uploaded(range(n_frames), 1))
@@ -1518,15 +1548,9 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
         raise ValueError(f"{getattr(reader, 'path', video)}: no frames")
     dev = torch.device(device)
     base = _base_args(base_scale, roi, roi_q, bit_map, (h, w), dev)
-    sample_dtype = torch.uint8 if spec.bit_depth == 8 else torch.int16
 
     def converted(order):
-        """(the padded RGB picture the codec takes, the file's samples on the device) of every frame `order` names"""
-        ring = _PinnedRing(dev, reader.frame_bytes)
-        for g in order:
-            reader.read_into(g, ring.host())
-            samples = ring.upload().view(sample_dtype)
-            yield Y.yuv420_to_rgb(samples, h, w, spec, pad=True, quantize8=quantize8), samples
+        return _video_pictures(reader, order, spec, quantize8, dev)
 
     plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: (x for x, _ in converted(range(n_frames))))
     layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
@@ -1663,20 +1687,111 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     return t
 
 
+def _has_motion(root):
+    from .roi import PickleBoxes
+
+    return PickleBoxes.has_motion(root)
+
+
+def _video_args(ap, a):
+    """(size, fps) of the --video, --size and --fps options of encode and boxes, refused through ap.error."""
+    from . import yuv as Y
+
+    ext = os.path.splitext(a.video)[1].lower()
+    if ext not in (".y4m", ".yuv"):
+        ap.error("--video takes a .y4m or a .yuv file")
+    if ext == ".yuv" and not a.size:
+        ap.error("a raw .yuv file needs --size WxH")
+    try:
+        return (Y.parse_size(a.size) if a.size else None,
+                tuple(int(v) for v in (a.fps.split(":") + ["1"])[:2]) if a.fps else None)
+    except ValueError as ex:
+        ap.error(str(ex))
+
+
+def motion_boxes_folder(frames_dir, root, params, device="cuda:0", io_workers=8, max_frames=None):
+    """run_codec boxes --frames: the motion boxes (vcm_ts_amd/motionroi.py) of a PNG folder, written to `root` as
+    motion_coords/%05d and motion.json -- then a roi.PickleBoxes root.  A pass of its own over the source, for the reason
+    the scene-cut scan is one: the background model is a recursion over the whole sequence, while GOP streams and GOP
+    sharding code GOPs independently.  The pictures come through the reader and conversion of encode_folder's coding
+    pass.  Returns the list of (n, 4) box arrays."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from PIL import Image
+
+    from . import motionroi as M
+
+    reader = PNGReader(frames_dir)
+    n_frames = 0
+    while os.path.exists(reader.path_of(n_frames + 1)) and (max_frames is None or n_frames < max_frames):
+        n_frames += 1
+    with Image.open(reader.path_of(1)) as first:  # (the header only)
+        w, h = first.size
+    dev = torch.device(device)
+    pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
+    try:
+        boxes = M.scan(_png_pictures(reader, range(n_frames), (h, w), dev, pool, io_workers, 1), n_frames, (h, w), dev, params)
+    finally:
+        if pool is not None:
+            pool.shutdown(wait=True, cancel_futures=True)
+    M.write_boxes(root, boxes, params, h, w)
+    return boxes
+
+
+def motion_boxes_video(video, root, params, device="cuda:0", size=None, spec=None, quantize8=False, bit_depth=8, fps=None,
+                       max_frames=None):
+    """motion_boxes_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height): the pictures come
+    through the ring, copy and colour conversion (spec, quantize8) of encode_video's coding pass."""
+    from . import motionroi as M
+
+    reader = _open_source(video, size, bit_depth, fps)
+    spec = spec or reader.spec()
+    if spec.bit_depth != reader.bit_depth:
+        raise ValueError(f"the file holds {reader.bit_depth}-bit samples, the colour description says {spec.bit_depth}")
+    h, w = reader.height, reader.width
+    n_frames = reader.n_frames if max_frames is None else min(reader.n_frames, int(max_frames))
+    if n_frames < 1:
+        raise ValueError(f"{getattr(reader, 'path', video)}: no frames")
+    dev = torch.device(device)
+    boxes = M.scan((x for x, _ in _video_pictures(reader, range(n_frames), spec, quantize8, dev)), n_frames, (h, w), dev, params)
+    M.write_boxes(root, boxes, params, h, w)
+    return boxes
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
     e = sub.add_parser("encode")
-    e.add_argument("--frames", help="folder of im1.png / im00001.png ... (exactly one of --frames and --video)")
-    e.add_argument("--video", metavar="FILE", help="a .y4m file, or a raw I420 .yuv file with --size")
-    e.add_argument("--size", metavar="WxH", help="picture size of a raw .yuv file")
-    e.add_argument("--bit-depth", type=int, default=8, choices=[8, 10], help="sample depth of a raw .yuv file")
-    e.add_argument("--fps", default=None, help="frame rate of a raw .yuv file, N or N:D (recorded, and written to a .y4m output)")
-    e.add_argument("--matrix", default=None, choices=["bt709", "bt601"], help="default bt709")
-    e.add_argument("--range", default=None, choices=["limited", "full"], help="default: the Y4M header's XCOLORRANGE, else limited")
-    e.add_argument("--siting", default=None, choices=["left", "center"], help="chroma siting; default: the Y4M header's, else left")
-    e.add_argument("--quantize8", action="store_true",
-                   help="with --video: round the converted picture to 8-bit RGB before coding it (what a PNG of it would hold)")
+    b = sub.add_parser("boxes", description="Motion ROI boxes of a fixed-camera sequence: a scan pass of its own over the "
+                       "source (a background model of the luma on the GPU, vcm_ts_amd/motionroi.py) that writes "
+                       "ROOT/motion_coords/%%05d and ROOT/motion.json; ROOT is then an ordinary --roi-root whose third box "
+                       "class is \"motion\".  The mechanism only: nothing is claimed about detection quality")
+    for p in (e, b):
+        p.add_argument("--frames", help="folder of im1.png / im00001.png ... (exactly one of --frames and --video)")
+        p.add_argument("--video", metavar="FILE", help="a .y4m file, or a raw I420 .yuv file with --size")
+        p.add_argument("--size", metavar="WxH", help="picture size of a raw .yuv file")
+        p.add_argument("--bit-depth", type=int, default=8, choices=[8, 10], help="sample depth of a raw .yuv file")
+        p.add_argument("--fps", default=None, help="frame rate of a raw .yuv file, N or N:D (recorded, and written to a .y4m output)")
+        p.add_argument("--matrix", default=None, choices=["bt709", "bt601"], help="default bt709")
+        p.add_argument("--range", default=None, choices=["limited", "full"], help="default: the Y4M header's XCOLORRANGE, else limited")
+        p.add_argument("--siting", default=None, choices=["left", "center"], help="chroma siting; default: the Y4M header's, else left")
+        p.add_argument("--quantize8", action="store_true",
+                       help="with --video: round the converted picture to 8-bit RGB before coding it (what a PNG of it would hold)")
+    b.add_argument("--out", required=True, metavar="ROOT", help="where motion_coords/ and motion.json go")
+    b.add_argument("--threshold", type=int, required=True, metavar="T",
+                   help="a pixel is foreground when its luma is more than T 8-bit codes from the background model, 1 .. 254 "
+                        "(no default exists -- the right value depends on the content)")
+    b.add_argument("--learn", type=int, nargs=2, default=None, metavar=("KB", "KF"),
+                   help="the model moves by |difference| >> K toward each picture: KB at background pixels, KF at foreground "
+                        "ones, 0 .. 16 each (default 4 8, untuned placeholders)")
+    b.add_argument("--min-pixels", type=int, default=None, metavar="P",
+                   help="a 16x16 cell is active from P foreground pixels, 1 .. 256 (default 8, an untuned placeholder)")
+    b.add_argument("--grow", type=int, default=None, metavar="G",
+                   help="dilate the active cells by G cells before joining them, 0 .. 8 (default 1, an untuned placeholder)")
+    b.add_argument("--min-cells", type=int, default=None, metavar="C", help="drop a region of fewer than C active cells (default 1)")
+    b.add_argument("--max-boxes", type=int, default=None, metavar="N", help="keep the N strongest boxes of a picture (default 64)")
+    b.add_argument("--device", default="cuda:0")
+    b.add_argument("--io-workers", type=int, default=8, help="host threads for PNG decoding (0: inline)")
     e.add_argument("--bins", required=True)
     e.add_argument("--recon")
     e.add_argument("--recon-video", metavar="FILE", help="with --video: reconstructions as .y4m / .yuv")
@@ -1718,6 +1833,8 @@ def main(argv=None):
                         "--plate-q, --face-q, --background-q switches it on, the others default to 1.00 (no tuned values "
                         "exist); the factors go to roiq.json beside the .bin files and decode then needs --roi-root")
     e.add_argument("--face-q", type=float, default=None, metavar="F", help="the same for face boxes")
+    e.add_argument("--motion-q", type=float, default=None, metavar="F",
+                   help="the same for motion boxes; only with a --roi-root that holds motion_coords (run_codec boxes)")
     e.add_argument("--background-q", type=float, default=None, metavar="F", help="the factor of the cells no box touches")
     e.add_argument("--roi-q-grow", type=int, default=None, metavar="N",
                    help="with one of the three above: grow every box by N pixels (0 .. 255, default 0) before it is laid on the cells")
@@ -1787,6 +1904,8 @@ def main(argv=None):
                        help="the reference's LIPLATES.PADDING: feather width and metric shrink of plate boxes "
                             "(default 0; decode: the sequence.json's)")
         p.add_argument("--face-border", type=int, default=None, metavar="N", help="the same for face boxes")
+        p.add_argument("--motion-border", type=int, default=None, metavar="N",
+                       help="the same for motion boxes; only with a --roi-root that holds motion_coords (run_codec boxes)")
         p.add_argument("--gop", type=int, default=None,
                        help="default 32 (decode: the sequence.json's, else 32; refused if a gops.json beside the .bin files says otherwise)")
         p.add_argument("--io-workers", type=int, default=8, help="host threads for PNG decoding / encoding (0: inline)")
@@ -1808,7 +1927,36 @@ def main(argv=None):
             raise SystemExit(1)
         print(f"{len(PH.read_hashes(a.bins)['pixels'])} pictures verified")
         return
+    if a.cmd == "boxes":
+        from . import motionroi as M
+
+        if (a.frames is None) == (a.video is None):
+            ap.error("give exactly one of --frames and --video")
+        if a.video is None and (a.size or a.quantize8 or a.matrix or a.range or a.siting):
+            ap.error("--size, --quantize8, --matrix, --range and --siting belong to --video")
+        given = {k: v for k, v in (("learn", None if a.learn is None else tuple(a.learn)), ("min_pixels", a.min_pixels),
+                                   ("grow", a.grow), ("min_cells", a.min_cells), ("max_boxes", a.max_boxes)) if v is not None}
+        try:
+            params = M.MotionParams(a.threshold, **given)
+        except ValueError as ex:
+            ap.error(f"boxes: {ex}")
+        try:
+            if a.video is not None:
+                size, fps = _video_args(ap, a)
+                reader = _open_source(a.video, size, a.bit_depth, fps)
+                with reader:
+                    boxes = motion_boxes_video(reader, a.out, params, a.device, quantize8=a.quantize8,
+                                               spec=reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting))
+            else:
+                boxes = motion_boxes_folder(a.frames, a.out, params, a.device, io_workers=a.io_workers)
+        except (ValueError, OSError) as ex:
+            ap.error(f"boxes: {ex}")
+        print(f"{len(boxes)} pictures, {sum(len(x) for x in boxes)} boxes -> {os.path.join(a.out, M.COORDS)}")
+        return
     roi = roi_q = aq = None
+    motion = a.roi_root is not None and _has_motion(a.roi_root)
+    if not motion and (a.motion_border is not None or getattr(a, "motion_q", None) is not None):
+        ap.error("--motion-border and --motion-q need a --roi-root that holds motion_coords (run_codec boxes writes one)")
     if a.cmd == "encode":
         if a.aq_clamp is not None and a.aq_strength is None:
             ap.error("--aq-clamp belongs to --aq-strength")
@@ -1819,7 +1967,7 @@ def main(argv=None):
                 aq = A.AQ(a.aq_strength, *(a.aq_clamp or (A.MIN_Q, A.MAX_Q)))
             except ValueError as ex:
                 ap.error(f"--aq-strength / --aq-clamp: {ex}")
-    factors = [getattr(a, n, None) for n in ("plate_q", "face_q", "background_q")]
+    factors = [getattr(a, n, None) for n in ("plate_q", "face_q", "background_q")] + ([a.motion_q] if motion and a.cmd == "encode" else [])
     if a.cmd == "encode" and a.base_scale is not None:
         from . import scale as SC
 
@@ -1838,9 +1986,9 @@ def main(argv=None):
             from . import roi as X
 
             try:
-                plate, face, ground = (100 if f is None else X.RoiQ.hundredths(f, n) for f, n in
-                                       zip(factors, ("--plate-q", "--face-q", "--background-q")))
-                roi_q = X.RoiQ(ground, (plate, face), 0 if a.roi_q_grow is None else a.roi_q_grow)
+                plate, face, ground, *moving = (100 if f is None else X.RoiQ.hundredths(f, n) for f, n in
+                                                zip(factors, ("--plate-q", "--face-q", "--background-q", "--motion-q")))
+                roi_q = X.RoiQ(ground, (plate, face, *moving), 0 if a.roi_q_grow is None else a.roi_q_grow)
             except ValueError as ex:
                 ap.error(f"ROI-weighted quantisation: {ex}")
     elif a.roi_root is None and os.path.exists(os.path.join(a.bins, ROIQ_JSON)):
@@ -1864,7 +2012,8 @@ def main(argv=None):
         recorded = {c["name"]: c["border"] for c in ((read_sequence_info(a.bins) or {}).get("roi") or {}).get("classes", [])} \
             if a.cmd == "decode" else {}
         borders = [given if given is not None else recorded.get(name, 0)
-                   for given, name in ((a.plate_border, "liplates"), (a.face_border, "faces"))]
+                   for given, name in ((a.plate_border, "liplates"), (a.face_border, "faces")) +
+                   (((a.motion_border, "motion"),) if motion else ())]
         try:
             classes = tuple(X.RoiClass(b) for b in borders)
             roi = X.Roi(X.PickleBoxes(a.roi_root, classes), classes)
@@ -1883,16 +2032,7 @@ def main(argv=None):
         if a.video is not None:
             from . import yuv as Y
 
-            ext = os.path.splitext(a.video)[1].lower()
-            if ext not in (".y4m", ".yuv"):
-                ap.error("--video takes a .y4m or a .yuv file")
-            if ext == ".yuv" and not a.size:
-                ap.error("a raw .yuv file needs --size WxH")
-            try:
-                size = Y.parse_size(a.size) if a.size else None
-                fps = tuple(int(v) for v in (a.fps.split(":") + ["1"])[:2]) if a.fps else None
-            except ValueError as ex:
-                ap.error(str(ex))
+            size, fps = _video_args(ap, a)
         a.gop = a.gop or 32
         if a.min_gop is not None and a.scenecut is None:
             ap.error("--min-gop belongs to --scenecut")
