@@ -23,6 +23,8 @@ whose backward runs the gradient kernels of include/dcvc_hip_grad.h through vcm_
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import math
 import time
 
@@ -123,6 +125,21 @@ class PendingStream:
 
     def finish(self) -> bytes:
         return self.finish_all()[0]
+
+
+@contextlib.contextmanager
+def _no_collector():
+    """No pass of Python's cyclic collector while a stream is capturing: a finaliser that runs there (a pinned buffer, an
+    event, a library handle let go of by whatever ran earlier in the process) makes runtime calls a capture does not allow,
+    and the process has been seen to abort inside such a pass.  torch.cuda.graph collects once BEFORE the capture begins;
+    what becomes garbage during the capture waits until it has ended."""
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 def _load_upstream(tape, named_grads):
@@ -714,13 +731,13 @@ class _FrameGraph:
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self.fwd = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.fwd):
+        with torch.no_grad(), _no_collector(), torch.cuda.graph(self.fwd):
             self.tape, o, sums = forward()
         self.sums = tuple(sums[k] for k in self.SUMS)
         d = model._dpb_out(o)
         self.dpb_out = tuple(d[k] for k in DPB_KEYS)
         self.bwd = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.bwd, pool=self.fwd.pool()):
+        with torch.no_grad(), _no_collector(), torch.cuda.graph(self.bwd, pool=self.fwd.pool()):
             backward(self.tape, o)
         self.dq = {k: self.tape.q[k]["dq_scale"] for k in ("mv", "y")}
 
@@ -1042,7 +1059,7 @@ class DMC(CodecBase):
             torch.cuda.synchronize(self.device)
             self._flip = flip0
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with _no_collector(), torch.cuda.graph(graph):
                 o = self._run(xs, dpb, mv_y_q_scale, y_q_scale, "compress")
                 PendingStream.copy_planes(host, layout, self._planes(o))
             g = dict(graph=graph, xs=xs, host=host, layout=layout, out=self._dpb_out(o), views=o, flip_after=self._flip,

@@ -23,6 +23,7 @@
     python -m vcm_ts_amd.run_codec boxes (--frames DIR | --video FILE [--size WxH]) --out ROOT --threshold T [--learn KB KF]
                                          [--min-pixels P] [--grow G] [--min-cells C] [--max-boxes N]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT [--motion-border N] [--motion-q F]
+    python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P]
 
 Video files are Y4M or raw I420 at 8 or 10 bits (vcm_ts_amd/yuv.py): no PNG detour, the colour conversion runs on the
 GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` beside the `.bin` files from which
@@ -75,6 +76,14 @@ scan pass of its own like --scenecut's, boxes around the 16x16 cells that differ
 in the reference's coordinate format and ROOT/motion.json.  A root that holds motion_coords has a third box class, "motion",
 with --motion-border and --motion-q beside the plates' and faces' options; without the folder nothing changes.  There is no
 default T, the other parameters are untuned placeholders, and nothing is claimed about detection quality.
+
+With --tnr T (1 .. 64 luma codes) the codec is handed a temporally filtered picture in place of every P picture
+(vcm_ts_amd/tnr.py: a motion-adaptive noise prefilter for fixed-camera content, one kernel per picture on the GPU): the source
+blended with the previous filtered picture wherever their luma differs by fewer than T codes on average over a 5x5 window, the
+source itself wherever something moves.  The filter restarts at every I picture.  It is encoder side only: the .bin format is
+unchanged, no file is written and `decode` needs nothing; --report keeps measuring against the unfiltered source and gains
+`tnr`, `frame_tnr_held` and `frame_tnr_mad`.  There is no default T, --tnr-floor and --tnr-pixel are untuned placeholders, there
+is no motion compensation, and nothing is claimed about rate or quality.
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
 reference's `.bin` format (an I picture every `gop` frames).  Unlike run_dcvc the encoder does not
@@ -870,7 +879,7 @@ def _video_pictures(reader, order, spec, quantize8, dev):
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
                   report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None, target_bpp=None,
-                  q_range=None, residual_bins=None, residual_step=1, picture_hash=False, base_scale=None, aq=None):
+                  q_range=None, residual_bins=None, residual_step=1, picture_hash=False, base_scale=None, aq=None, tnr=None):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -940,7 +949,17 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     aq.json beside the .bin files records the setting and the digests of its two tables, and decode_folder / decode_video
     follow it.  I pictures are not adapted.  With roi_q the two factors multiply; with base_scale the map is taken from the
     base-size reference; target_bpp prices every picture under its map.  None: no launch, file or byte changes (a stale
-    aq.json is removed)."""
+    aq.json is removed).
+    tnr: a tnr.TNR -- the motion-adaptive temporal noise prefilter (vcm_ts_amd/tnr.py).  Every P picture
+    the codec is handed is the source blended with the previous filtered picture where the luma of the two stays close
+    over a 5 x 5 window, and the source itself where something moves (one launch per P picture on the stream that codes
+    it, before base_scale's scaling); the filter restarts at every I picture of the plan, so gop_streams and scenecut keep
+    giving the bytes of sequential coding.  Encoder side only: no file is written and decode_folder / decode_video need
+    nothing.  The report's PSNR / MS-SSIM / ROI figures, residuals / residual_bins, the scene-cut scan and `boxes` keep
+    looking at the UNFILTERED source; aq, target_bpp, roi_q, bit_map, picture_hash and base_scale simply code the filtered
+    picture.  With report the dictionary gains tnr (the setting), frame_tnr_held (the fraction of the picture's pixels that
+    were blended) and frame_tnr_mad (the mean absolute luma difference to the previous filtered picture, in codes), both 0.0
+    for an I picture.  None: no launch, allocation, key or byte changes."""
     from concurrent.futures import ThreadPoolExecutor
 
     from PIL import Image
@@ -956,6 +975,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     _roi_args(roi, residuals, residual_bins, residual_step)
     _roiq_args(roi, roi_q)
     _aq_args(aq)
+    _tnr_args(tnr)
     bit_dir = _bitmap_args(bit_map, report)
     rate = _rate_args(target_bpp, q_range, h, w, gop)
     dev = torch.device(device)
@@ -977,6 +997,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         _write_aq(bin_dir, aq)
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
         rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
+        filters = _tnr_filters(tnr, run, (h, w), report)
     except BaseException:
         if pool is not None:
             pool.shutdown(wait=True, cancel_futures=True)
@@ -984,9 +1005,12 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     source = {}
 
     def frames(k):
-        for x in uploaded(run.order(k), run.K):
+        intra = run.intra(k) if filters else ()
+        for t, x in enumerate(uploaded(run.order(k), run.K)):
             if report or res_out or rec_out:
                 source[k] = x  # (the picture on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
+            if filters:  # (the codec sees the filtered picture; source[k] stays the unfiltered one)
+                x = filters[k].step(x, t in intra)
             yield base.down(x) if base else x
 
     def on_recon(k, g, ref_frame):
@@ -1018,7 +1042,8 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         if rec_out:
             rec_out.close(failed)
     extras = _roi_report_keys(h, w) if layer else None
-    return run.results(report, _enh_report_keys(rec_out, h, w, extras) if rec_out else extras)
+    extras = _enh_report_keys(rec_out, h, w, extras) if rec_out else extras
+    return run.results(report, _tnr_report_keys(tnr, filters, run, h, w, extras) if filters else extras)
 
 
 def _decode_bins(nets, bin_dir, height, width, plan, emit, q_map=None, aq=None):
@@ -1444,6 +1469,45 @@ def _enh_report_keys(rec_out, h, w, inner=None):
     return keys
 
 
+def _tnr_filters(tnr, run, size, report):
+    """tnr= of an encode loop -> one tnr.TnrFilter per GOP stream (None without: nothing is allocated).  Per-picture totals
+    are kept only for a report."""
+    if tnr is None:
+        return None
+    from .tnr import TnrFilter
+
+    return [TnrFilter(tnr, size, run.dev, totals=bool(report)) for _ in range(run.K)]
+
+
+def _tnr_args(tnr):
+    """tnr= of an encode loop, refused by name before any GPU work."""
+    if tnr is not None:
+        from .tnr import TNR
+
+        if not isinstance(tnr, TNR):
+            raise ValueError(f"tnr: expected a tnr.TNR, got {type(tnr).__name__}")
+
+
+def _tnr_report_keys(tnr, filters, run, h, w, inner=None):
+    """--report's keys of the temporal noise prefilter: the setting, and per picture the fraction of its pixels that were
+    blended and the mean absolute luma difference to the previous filtered picture, both 0.0 for an I picture.  The
+    totals of each stream were copied to the host GOP by GOP; this waits for those copies only."""
+    def keys(rd, types, values):
+        if inner:
+            inner(rd, types, values)
+        totals = {}
+        for k, f in enumerate(filters):
+            with torch.cuda.stream(run.cenc.streams[k]):
+                per = f.totals()  # (flushes a trailing partial GOP)
+            totals.update({run.global_index(k, t): v for t, v in enumerate(per)})
+        order = sorted(totals)
+        rd["tnr"] = tnr.to_json()
+        rd["frame_tnr_held"] = [totals[g][0] / (h * w) for g in order]
+        rd["frame_tnr_mad"] = [totals[g][1] / (h * w) for g in order]
+
+    return keys
+
+
 def _fuse_roi(roi, residuals, roi_q, residual_bins=None):
     """The roi a decode loop fuses a residual layer with: none when the roi is only there for the q-scale maps."""
     return None if (residuals is None and residual_bins is None and roi_q is not None) else roi
@@ -1508,7 +1572,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
                  min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1,
-                 picture_hash=False, base_scale=None, aq=None):
+                 picture_hash=False, base_scale=None, aq=None, tnr=None):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -1530,12 +1594,15 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     picture_hash: as encode_folder (the digests are of the RGB reconstruction, before any conversion back to YUV).
     base_scale: as encode_folder -- the scaling comes after the colour conversion (RGB only); sequence.json keeps the
     source's size, scale.json lies beside it.
-    aq: as encode_folder (aq.json beside the .bin files; sequence.json is the same with or without)."""
+    aq: as encode_folder (aq.json beside the .bin files; sequence.json is the same with or without).
+    tnr: as encode_folder -- the filter comes after the colour conversion (RGB only); the YUV figures of the report stay
+    against the file's own samples; sequence.json is the same with or without."""
     from . import yuv as Y
 
     _roi_args(roi, residuals, residual_bins, residual_step)
     _roiq_args(roi, roi_q)
     _aq_args(aq)
+    _tnr_args(tnr)
     bit_dir = _bitmap_args(bit_map, report)
     reader = _open_source(video, size, bit_depth, fps)  # (every refusal about the file happens here, before any GPU work)
     spec = spec or reader.spec()
@@ -1563,6 +1630,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     _write_aq(bin_dir, aq)
     res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
     rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
+    filters = _tnr_filters(tnr, run, (h, w), report)
     source = {}
     container = "y4m" if isinstance(reader, Y.Y4MReader) else "yuv"
     extras = dict(chroma=getattr(reader, "chroma", None), interlace=getattr(reader, "interlace", None),
@@ -1571,8 +1639,11 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     outs = [_VideoOut(writer) for _ in range(run.K)] if writer else None
 
     def frames(k):
-        for x, samples in converted(run.order(k)):
+        intra = run.intra(k) if filters else ()
+        for t, (x, samples) in enumerate(converted(run.order(k))):
             source[k] = (x, samples)  # (what on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
+            if filters:  # (the codec sees the filtered picture; source[k] stays the unfiltered one)
+                x = filters[k].step(x, t in intra)
             yield base.down(x) if base else x
 
     def on_recon(k, g, ref_frame):
@@ -1622,7 +1693,8 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
             sel = [p[3] for p, k in zip(per, types) if keep(k)]
             rd[f"ave_{name}_frame_psnr_yuv"] = sum(sel) / len(sel) if sel else 0
 
-    return run.results(report, _enh_report_keys(rec_out, h, w, yuv_keys) if rec_out else yuv_keys)
+    keys = _enh_report_keys(rec_out, h, w, yuv_keys) if rec_out else yuv_keys
+    return run.results(report, _tnr_report_keys(tnr, filters, run, h, w, keys) if filters else keys)
 
 
 def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=None, fps=None, device="cuda:0",
@@ -1858,6 +1930,20 @@ def main(argv=None):
     e.add_argument("--aq-clamp", type=int, nargs=2, default=None, metavar=("LO", "HI"),
                    help="with --aq-strength: the factors a cell may get, in hundredths, 10 <= LO <= 100 <= HI <= 1000 "
                         "(default 10 1000)")
+    e.add_argument("--tnr", type=int, default=None, metavar="T",
+                   help="motion-adaptive temporal noise prefilter for fixed-camera content: hand the codec every P picture "
+                        "blended on the GPU with the previous filtered picture wherever their luma differs by fewer than T 8-bit "
+                        "codes on average over a 5x5 window, and untouched wherever something moves; T, 1 .. 64 (no default "
+                        "exists -- the right value depends on the noise).  Encoder side only: the .bin format is unchanged, no "
+                        "file is written and decode needs nothing; --report keeps measuring against the unfiltered source and "
+                        "gains tnr, frame_tnr_held and frame_tnr_mad.  No motion compensation; nothing is claimed about rate or "
+                        "quality")
+    e.add_argument("--tnr-floor", type=int, default=None, metavar="W",
+                   help="with --tnr: the weight of the current picture, in 1/256ths, where nothing differs, 1 .. 255 (default 64, "
+                        "an untuned placeholder)")
+    e.add_argument("--tnr-pixel", type=int, default=None, metavar="P",
+                   help="with --tnr: a pixel whose own luma differs by more than P codes is passed through whatever its window "
+                        "says, 0 .. 255 (default min(255, 3 T), an untuned placeholder)")
     d = sub.add_parser("decode")
     d.add_argument("--base-only", action="store_true",
                    help="ignore a scale.json beside the .bin files (encode --base-scale) and write the base-size pictures; "
@@ -1953,7 +2039,7 @@ def main(argv=None):
             ap.error(f"boxes: {ex}")
         print(f"{len(boxes)} pictures, {sum(len(x) for x in boxes)} boxes -> {os.path.join(a.out, M.COORDS)}")
         return
-    roi = roi_q = aq = None
+    roi = roi_q = aq = tnr = None
     motion = a.roi_root is not None and _has_motion(a.roi_root)
     if not motion and (a.motion_border is not None or getattr(a, "motion_q", None) is not None):
         ap.error("--motion-border and --motion-q need a --roi-root that holds motion_coords (run_codec boxes writes one)")
@@ -1967,6 +2053,15 @@ def main(argv=None):
                 aq = A.AQ(a.aq_strength, *(a.aq_clamp or (A.MIN_Q, A.MAX_Q)))
             except ValueError as ex:
                 ap.error(f"--aq-strength / --aq-clamp: {ex}")
+        if a.tnr is None and (a.tnr_floor is not None or a.tnr_pixel is not None):
+            ap.error("--tnr-floor and --tnr-pixel belong to --tnr")
+        if a.tnr is not None:
+            from . import tnr as N
+
+            try:
+                tnr = N.TNR(a.tnr, **({} if a.tnr_floor is None else {"floor": a.tnr_floor}), pixel=a.tnr_pixel)
+            except ValueError as ex:
+                ap.error(f"--tnr / --tnr-floor / --tnr-pixel: {ex}")
     factors = [getattr(a, n, None) for n in ("plate_q", "face_q", "background_q")] + ([a.motion_q] if motion and a.cmd == "encode" else [])
     if a.cmd == "encode" and a.base_scale is not None:
         from . import scale as SC
@@ -2079,14 +2174,14 @@ def main(argv=None):
                                                residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
                                                bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
                                                residual_bins=a.residual_bins, residual_step=a.residual_step,
-                                               picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq)
+                                               picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq, tnr=tnr)
         else:
             bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
                                             coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
                                             roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
                                             bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
                                             residual_bins=a.residual_bins, residual_step=a.residual_step,
-                                            picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq)
+                                            picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq, tnr=tnr)
         if rd:
             yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
             print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
