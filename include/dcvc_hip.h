@@ -145,6 +145,11 @@ int64_t dcvc_conv_pack_size_paired(int32_t Cout, int32_t Cin, int32_t *cout_pad)
 int dcvc_conv_pack_weights_paired(const float *w, const float *b, int32_t Cout, int32_t Cin, float *wpack, float *bpack);
 
 int dcvc_conv2d(const dcvc_conv_args *a, void *stream);
+/* Developer A/B hook: how far ahead dcvc_conv2d's kernel requests its input.  1: every input patch one step before it is
+ * staged (the only schedule up to round 4); 2 (the default): 3x3 stride-2 and 7x7 layers request the next chunk's patch a
+ * whole chunk ahead (every other layer runs the schedule of mode 1 either way).  Any other value: DCVC_E_ARG, nothing
+ * changes.  Scheduling only -- results are bit-identical either way; process-wide, not thread-safe. */
+int dcvc_conv_set_lookahead(int32_t mode);
 
 /* ---- layers with at most 16 output channels (DCVC_PREC_FP16X3 only) -------------------------------------
  * SpyNet's 32->16 and 16->2 7x7 layers, the 64->3 reconstruction layer (video_net.py:99-115,

@@ -26,6 +26,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 #include "dcvc_hip.h"
@@ -67,6 +68,10 @@ struct ConvK {
     int band_rows;        // tile rows of the band (0: all)
 };
 
+// Developer A/B hook dcvc_conv_set_lookahead: 1 = every input patch is requested one step before it is stored (the
+// schedule up to round 4), 2 = the AHEAD schedule of conv_mfma below.  Scheduling only, never a result bit.
+int g_lookahead = 2;
+
 // Developer A/B switches of this file change launch geometry only (never a result bit) and are honoured only in a process
 // that declares itself a developer run with DCVC_DEV=1, like the routing switches of vcm_ts_amd/engine.py (a
 // stray variable must not reconfigure a product process).
@@ -83,7 +88,23 @@ inline long dev_env_long(const char *name, long dflt) {
 // the 8 channels of (y, x + 1) in its upper half, and the filter is packed in tap PAIRS (kx = 2j, 2j + 1; the pair of
 // kx = 6 is a zero tap): 4 K steps per filter row instead of 7, the fragment reads unchanged.  Weights from
 // dcvc_conv_pack_weights_paired; selected by dcvc_conv_args.pair_taps.
-template <int KS, int S, int RPW, int NT, bool SPLIT, bool PAIR = false>
+//
+// AHEAD (dcvc_conv_set_lookahead(2), the default; 3x3 stride 2, 7x7 and tap-paired 7x7, where a chunk takes NST > 1 steps)
+// moves global loads earlier and changes nothing else: every accumulator still receives the same MFMAs in the same order.
+// Without it the patch of chunk c + 1 is requested in the LAST step of chunk c, and that step's MFMAs (18 per wave at
+// stride 2, 42 in a 7x7 layer with 32 outputs) are short against a memory round trip of 900+ cycles; what is worse, the
+// filter-row copies run under a branch (`i < TPS * 4 * BN`), which makes the compiler wait for EVERY load in flight
+// before the filter-row request that follows the patch request -- the round trip is not covered at all.  With AHEAD
+//   - the patch of chunk c + 1 is requested in the FIRST step of chunk c, right after chunk c's patch has left the staging
+//     registers and behind that step's filter-row request.  Loads return in order, so the patch has to be back when the
+//     NEXT filter row (requested behind it) is waited for: two whole steps of cover;
+//   - the first two steps of a chunk are straight-line code and the last chunk of a tile is a copy without the request,
+//     because the compiler's wait counts fall back to "everything" wherever paths with different loads in flight meet;
+//   - the filter-row copies are branch-free (w_slot).
+// Measured on MI355X (profiles/conv_mfma_lookahead.txt): 3x3 stride 2 -21 %, 7x7 -12 % of their time inside a 1080p P
+// picture.  The 1x1 stride-1 layers were tried with their chunks requested in groups of four (one round trip per group)
+// and lost 3 %: they stay on the one-step schedule.
+template <int KS, int S, int RPW, int NT, bool SPLIT, bool PAIR = false, bool AHEAD = false>
 __global__ __launch_bounds__(256, 2) void conv_mfma(const ConvK a) {
     static_assert(!PAIR || (KS == 7 && S == 1 && SPLIT), "tap pairing is built for the 7x7 split-fp16 layers");
     constexpr int BH = 4 * RPW, BW = 32, BN = 32 * NT;
@@ -121,6 +142,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma(const ConvK a) {
     // (rp: input patch, only when the chunk changes; rw: filter slab) and are written to LDS
     // after the barrier that ends step k.
     constexpr int NP = (PH * PW * 4 + 255) / 256, NW = (TPS * 4 * BN + 255) / 256;
+    static_assert(!AHEAD || NST >= 3, "AHEAD: two straight-line steps and a loop over the rest of a chunk");
     f32x4 rp[NP], rw[NW];
     struct Cursor {
         int s, c0, cg, st;
@@ -194,38 +216,34 @@ __global__ __launch_bounds__(256, 2) void conv_mfma(const ConvK a) {
             }
         }
     };
+    // The float4 of the filter slab that this thread copies as its u-th.  AHEAD: the threads past the slab's end copy a
+    // float4 of its last 256 a second time (the same value to the same place) instead of sitting the copy out: a load or
+    // a store under a branch makes the compiler wait for EVERY load in flight at the next access to that register.
+    constexpr int W_OVER = NW * 256 - TPS * 4 * BN;
+    static_assert(!AHEAD || TPS * 4 * BN >= W_OVER, "the doubled float4 must lie inside the slab");
+    auto w_slot = [&](const int u) {
+        const int i = tid + u * 256;
+        return AHEAD && W_OVER > 0 && u == NW - 1 && i >= TPS * 4 * BN ? i - W_OVER : i;
+    };
     auto load_w = [&](const Cursor &k) {
         const float *wsrc = a.wpack + ((size_t)(k.cg * T + k.st * TPS) * 4) * a.Cout_pad * 4 + (size_t)n0 * 4;
 #pragma unroll
         for (int u = 0; u < NW; ++u) {
-            const int i = tid + u * 256;
+            const int i = w_slot(u);
             const int row = i / BN, col = i - row * BN;
-            if (i < TPS * 4 * BN) rw[u] = *(const f32x4 *)(wsrc + ((size_t)row * a.Cout_pad + col) * 4);
+            if (AHEAD || i < TPS * 4 * BN) rw[u] = *(const f32x4 *)(wsrc + ((size_t)row * a.Cout_pad + col) * 4);
         }
     };
     auto store_w = [&]() {
 #pragma unroll
         for (int u = 0; u < NW; ++u) {
-            const int i = tid + u * 256;
-            if (i < TPS * 4 * BN) *(f32x4 *)&wl[i * 4] = rw[u];
+            const int i = w_slot(u);
+            if (AHEAD || i < TPS * 4 * BN) *(f32x4 *)&wl[i * 4] = rw[u];
         }
     };
-
-    Cursor cur = {0, 0, 0, 0};
-    load_patch(cur);
-    load_w(cur);
-    while (cur.s < a.nseg) {
-        __syncthreads();  // every wave is done reading the previous step's LDS
-        if (cur.st == 0) store_patch(cur);
-        store_w();
-        __syncthreads();
-        Cursor nxt = cur;
-        advance(nxt);
-        if (nxt.s < a.nseg) {
-            if (nxt.st == 0) load_patch(nxt);
-            load_w(nxt);
-        }
-        const int a_st = (TPS == T) ? 0 : cur.st * PW * LDK;  // staged by filter row
+    // the MFMAs of tap stage st of the chunk in LDS
+    auto mfma_step = [&](const int st) {
+        const int a_st = (TPS == T) ? 0 : st * PW * LDK;  // staged by filter row
 #pragma unroll
         for (int tt = 0; tt < TPS; ++tt) {
             const int ky = (TPS == T) ? tt / KS : 0, kx = PAIR ? 2 * tt : (TPS == T) ? tt % KS : tt;
@@ -272,7 +290,63 @@ __global__ __launch_bounds__(256, 2) void conv_mfma(const ConvK a) {
                     }
             }
         }
-        cur = nxt;
+    };
+
+    Cursor cur = {0, 0, 0, 0};
+    if constexpr (AHEAD) {
+        auto chunk = [&](auto more, const Cursor &nc) {  // nc: the first step of the next chunk
+            constexpr bool MORE = decltype(more)::value;
+            __syncthreads();  // every wave is done reading the previous step's LDS
+            store_patch(cur);
+            store_w();
+            __syncthreads();
+            advance(cur);
+            load_w(cur);
+            if (MORE) load_patch(nc);  // behind the filter row: step 1 waits for the row alone
+            mfma_step(0);
+            auto row_step = [&](const int st) {
+                __syncthreads();
+                store_w();
+                __syncthreads();
+                if (st + 1 < NST) {
+                    advance(cur);
+                    load_w(cur);
+                } else if (MORE) {
+                    load_w(nc);
+                }
+                mfma_step(st);
+            };
+            row_step(1);  // on its own: its wait leaves the patch in flight, the loop's waits cannot
+            for (int st = 2; st < NST; ++st) row_step(st);
+        };
+        load_patch(cur);
+        load_w(cur);
+        for (;;) {
+            Cursor nc = cur;
+            nc.st = NST - 1;
+            advance(nc);
+            if (nc.s >= a.nseg) break;
+            chunk(std::true_type{}, nc);
+            cur = nc;
+        }
+        chunk(std::false_type{}, cur);
+    } else {
+        load_patch(cur);
+        load_w(cur);
+        while (cur.s < a.nseg) {
+            __syncthreads();  // every wave is done reading the previous step's LDS
+            if (cur.st == 0) store_patch(cur);
+            store_w();
+            __syncthreads();
+            Cursor nxt = cur;
+            advance(nxt);
+            if (nxt.s < a.nseg) {
+                if (nxt.st == 0) load_patch(nxt);
+                load_w(nxt);
+            }
+            mfma_step(cur.st);
+            cur = nxt;
+        }
     }
 
     // ---- epilogue: bias, activation, (gated) residual(s), NHWC or pixel-shuffled store.
@@ -465,6 +539,19 @@ int launch(ConvK &k, int N, hipStream_t st, int precision) {
     if (k.ty0 < 0 || k.ty0 >= k.nty) return DCVC_E_ARG;
     const int rows = k.band_rows > 0 ? (k.band_rows < k.nty - k.ty0 ? k.band_rows : k.nty - k.ty0) : k.nty;
     dim3 grid(gx, (unsigned)rows, (unsigned)N);
+    // the instantiations with more than one step per chunk have an AHEAD schedule (3x3 stride 1 stages a whole chunk per step)
+    constexpr bool HAS_AHEAD = (KS == 3 && S == 2) || KS == 7;
+    if constexpr (HAS_AHEAD) {
+        if (g_lookahead == 2) {
+            if (PAIR)
+                hipLaunchKernelGGL((conv_mfma<KS, S, RPW, NT, true, PAIR, true>), grid, dim3(256), 0, st, k);
+            else if (precision == DCVC_PREC_FP16X3)
+                hipLaunchKernelGGL((conv_mfma<KS, S, RPW, NT, true, false, true>), grid, dim3(256), 0, st, k);
+            else  // (exact fp32, 7x7, 8 x 32 x 64 tile: the longer live range spills, the layer stays on the schedule of mode 1)
+                hipLaunchKernelGGL((conv_mfma<KS, S, RPW, NT, false, false, !(KS == 7 && RPW == 2 && NT == 2)>), grid, dim3(256), 0, st, k);
+            RET_LAUNCH();
+        }
+    }
     if (PAIR)
         hipLaunchKernelGGL((conv_mfma<KS, S, RPW, NT, true, PAIR>), grid, dim3(256), 0, st, k);
     else if (precision == DCVC_PREC_FP16X3)
@@ -568,6 +655,12 @@ extern "C" int32_t dcvc_conv_chan_partial_parts(int32_t ks, int32_t stride, int3
     if (Hout <= 0 || Wout <= 0 || (stride != 1 && stride != 2)) return DCVC_E_ARG;
     const int bh = tile_rows(ks, stride);
     return ((Wout + 31) / 32) * ((Hout + bh - 1) / bh);
+}
+
+extern "C" int dcvc_conv_set_lookahead(int32_t mode) {
+    if (mode != 1 && mode != 2) return DCVC_E_ARG;
+    g_lookahead = mode;
+    return DCVC_OK;
 }
 
 extern "C" int dcvc_conv2d(const dcvc_conv_args *a, void *stream) {

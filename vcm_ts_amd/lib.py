@@ -151,6 +151,7 @@ _SIGS = {
     "dcvc_conv2d": [C.POINTER(ConvArgs), vp],
     "dcvc_conv_pack_weights": [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp],
     "dcvc_conv_pack_weights_paired": [vp, vp, i32, i32, vp, vp],
+    "dcvc_conv_set_lookahead": [i32],
     "dcvc_conv2d_small": [C.POINTER(ConvArgs), vp],
     "dcvc_conv_small_pack_weights": [vp, vp, i32, i32, i32, vp, vp, vp],
     "dcvc_conv2d_k32": [C.POINTER(ConvArgs), vp],
