@@ -242,6 +242,8 @@ _SIGS = {
     "dcvc_motion_step": [vp, i32, i64, i32, i32, vp, i32, i32, i32, i32, vp, vp],
     # include/dcvc_hip_tnr.h
     "dcvc_tnr_step": [vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp, i32, vp, vp, vp],
+    # include/dcvc_hip_redact.h
+    "dcvc_redact": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp],
 }
 
 # include/dcvc_hip_metrics.h (same library; listed apart because HIP_SYMBOLS is what the three kernel headers declare)
@@ -258,7 +260,8 @@ SCALE_SYMBOLS = ["dcvc_scale_planes"]  # include/dcvc_hip_scale.h
 AQ_SYMBOLS = ["dcvc_aq_activity", "dcvc_aq_map"]  # include/dcvc_hip_aq.h
 MOTION_SYMBOLS = ["dcvc_motion_step"]  # include/dcvc_hip_motion.h
 TNR_SYMBOLS = ["dcvc_tnr_step"]  # include/dcvc_hip_tnr.h
-HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS + ROI_SYMBOLS + ROIL_SYMBOLS + SCENE_SYMBOLS + BITS_SYMBOLS + HASH_SYMBOLS + SCALE_SYMBOLS + AQ_SYMBOLS + MOTION_SYMBOLS + TNR_SYMBOLS] +
+REDACT_SYMBOLS = ["dcvc_redact"]  # include/dcvc_hip_redact.h
+HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS + ROI_SYMBOLS + ROIL_SYMBOLS + SCENE_SYMBOLS + BITS_SYMBOLS + HASH_SYMBOLS + SCALE_SYMBOLS + AQ_SYMBOLS + MOTION_SYMBOLS + TNR_SYMBOLS + REDACT_SYMBOLS] +
                      ["dcvc_cdf_table_cols", "dcvc_conv_pack_size", "dcvc_conv_pack_size_paired", "dcvc_conv_small_pack_bytes", "dcvc_conv_k32_pack_bytes", "dcvc_conv_tile_rows", "dcvc_conv_chan_partial_parts", "dcvc_hip_version", "dcvc_conv_wgrad_scratch_min",
                       "dcvc_drans_default_lanes", "dcvc_drans_scratch_words"])
 RANS_SYMBOLS = [

@@ -24,6 +24,8 @@
                                          [--min-pixels P] [--grow G] [--min-cells C] [--max-boxes N]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT [--motion-border N] [--motion-q F]
     python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P]
+    python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT --redact NAME [NAME ...] (--redact-tile N | --redact-fill K)
+                                              [--redact-grow G] [--redact-hold N] [--redact-restorable]
 
 Video files are Y4M or raw I420 at 8 or 10 bits (vcm_ts_amd/yuv.py): no PNG detour, the colour conversion runs on the
 GPU (include/dcvc_hip_color.h), and `encode --video` leaves a `sequence.json` beside the `.bin` files from which
@@ -84,6 +86,14 @@ source itself wherever something moves.  The filter restarts at every I picture.
 unchanged, no file is written and `decode` needs nothing; --report keeps measuring against the unfiltered source and gains
 `tnr`, `frame_tnr_held` and `frame_tnr_mad`.  There is no default T, --tnr-floor and --tnr-pixel are untuned placeholders, there
 is no motion compensation, and nothing is claimed about rate or quality.
+
+With --redact NAME ... (and a ROI) the codec is handed every picture with the boxes of the named classes made unreadable
+(vcm_ts_amd/redact.py: one kernel per picture that has such a box): a mosaic of N x N tiles on a picture-aligned grid
+(--redact-tile N), or a solid fill (--redact-fill K); neither has a default.  It is encoder side only: the .bin format is
+unchanged and `decode` needs nothing; a `redact.json` beside the .bin files tells a receiver; --report keeps measuring against
+the unredacted source and gains `redact` and `frame_redacted`.  --residuals / --residual-bins would hold what was removed and
+are refused beside it unless --redact-restorable says that this is wanted.  A mosaic is not a security guarantee, boxes are
+taken as given (--redact-hold narrows, not closes, the gap a detector leaves), and nothing is claimed about rate or quality.
 
 Frames are ``im1.png`` / ``im00001.png`` ...; coded pictures are ``im00001.bin`` ... in the
 reference's `.bin` format (an I picture every `gop` frames).  Unlike run_dcvc the encoder does not
@@ -879,7 +889,8 @@ def _video_pictures(reader, order, spec, quantize8, dev):
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
                   report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None, target_bpp=None,
-                  q_range=None, residual_bins=None, residual_step=1, picture_hash=False, base_scale=None, aq=None, tnr=None):
+                  q_range=None, residual_bins=None, residual_step=1, picture_hash=False, base_scale=None, aq=None, tnr=None,
+                  redact=None):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -959,7 +970,18 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     looking at the UNFILTERED source; aq, target_bpp, roi_q, bit_map, picture_hash and base_scale simply code the filtered
     picture.  With report the dictionary gains tnr (the setting), frame_tnr_held (the fraction of the picture's pixels that
     were blended) and frame_tnr_mad (the mean absolute luma difference to the previous filtered picture, in codes), both 0.0
-    for an I picture.  None: no launch, allocation, key or byte changes."""
+    for an I picture.  None: no launch, allocation, key or byte changes.
+    redact (with roi): a redact.Redact -- ROI redaction (vcm_ts_amd/redact.py).  Inside the boxes of the named
+    classes (grown by redact.grow; with redact.hold also the boxes of that many pictures before and after) the picture the
+    codec is handed is a mosaic of the source on a picture-aligned grid, or a solid fill: one launch per picture that has
+    such a box on the stream that codes it, after tnr and before base_scale's scaling; a picture without one launches
+    nothing.  I and P pictures alike.  Encoder side only: the .bin format is unchanged and decode_folder / decode_video need
+    nothing; redact.json beside the .bin files records the setting for whoever receives them.  The report's PSNR / MS-SSIM /
+    ROI figures, the scene-cut scan and `boxes` keep looking at the UNREDACTED source; with report the dictionary gains
+    redact (the setting) and frame_redacted (the fraction of the picture's pixels that were replaced).  residuals /
+    residual_bins are taken from the unredacted source too, so those files would hold what was removed inside the boxes
+    themselves: that combination is a ValueError unless redact.restorable is set.  A mosaic is not a security guarantee.
+    None: no launch, allocation, file, key or byte changes (a stale redact.json is removed)."""
     from concurrent.futures import ThreadPoolExecutor
 
     from PIL import Image
@@ -976,6 +998,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     _roiq_args(roi, roi_q)
     _aq_args(aq)
     _tnr_args(tnr)
+    _redact_args(redact, roi, residuals, residual_bins)
     bit_dir = _bitmap_args(bit_map, report)
     rate = _rate_args(target_bpp, q_range, h, w, gop)
     dev = torch.device(device)
@@ -988,6 +1011,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     try:
         plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: uploaded(range(n_frames), 1))
         layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
+        held = _redact_frames(redact, layer)
         run = _EncodeRun(bin_dir, plan, base.size if base else (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets,
                          gop_streams, (_VideoQualityLog if layer else _QualityLog) if report else None,
                          _bit_log(bit_map, bit_dir, layer, roi_q), rate, picture_hash, base)
@@ -998,6 +1022,8 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
         rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
         filters = _tnr_filters(tnr, run, (h, w), report)
+        _write_redact(bin_dir, redact)
+        redaction = _Redaction(redact, layer, held, run, report) if redact is not None else None
     except BaseException:
         if pool is not None:
             pool.shutdown(wait=True, cancel_futures=True)
@@ -1005,12 +1031,14 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     source = {}
 
     def frames(k):
-        intra = run.intra(k) if filters else ()
+        intra = run.intra(k) if filters or redaction else ()
         for t, x in enumerate(uploaded(run.order(k), run.K)):
             if report or res_out or rec_out:
                 source[k] = x  # (the picture on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
             if filters:  # (the codec sees the filtered picture; source[k] stays the unfiltered one)
                 x = filters[k].step(x, t in intra)
+            if redaction:  # (after the filter, whose own state stays unredacted; source[k] stays the unredacted one)
+                x = redaction.step(k, run.global_index(k, t), x, t in intra)
             yield base.down(x) if base else x
 
     def on_recon(k, g, ref_frame):
@@ -1043,7 +1071,8 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
             rec_out.close(failed)
     extras = _roi_report_keys(h, w) if layer else None
     extras = _enh_report_keys(rec_out, h, w, extras) if rec_out else extras
-    return run.results(report, _tnr_report_keys(tnr, filters, run, h, w, extras) if filters else extras)
+    extras = _tnr_report_keys(tnr, filters, run, h, w, extras) if filters else extras
+    return run.results(report, _redact_report_keys(redact, redaction, run, h, w, extras) if redaction else extras)
 
 
 def _decode_bins(nets, bin_dir, height, width, plan, emit, q_map=None, aq=None):
@@ -1266,14 +1295,15 @@ class _RoiLayer:
     by name before any GPU work); the lists of one GOP go to the device in ONE pinned asynchronous copy, on the stream
     that codes the GOP, when its first picture asks."""
 
-    def __init__(self, roi, plan, size, dev):
+    def __init__(self, roi, plan, size, dev, frames=None):
+        """frames: the lists to serve in place of the roi's own (the merged lists of a redaction)."""
         from . import roi as X
 
         if dev.index is None:
             dev = torch.device(dev.type, torch.cuda.current_device())
         self.X, self.roi, self.plan, self.dev, self.size = X, X.as_roi(roi), plan, dev, size
         self.classes = self.roi.classes
-        self.frames = [self.roi.frame(g, size[0], size[1]) for g in range(plan.n_frames)]
+        self.frames = [self.roi.frame(g, size[0], size[1]) for g in range(plan.n_frames)] if frames is None else list(frames)
 
     def q_map(self, g, roi_q):
         """The q-scale map of frame g on the current stream (roi.q_map: one launch, nothing synchronised)."""
@@ -1508,6 +1538,83 @@ def _tnr_report_keys(tnr, filters, run, h, w, inner=None):
     return keys
 
 
+REDACT_JSON = "redact.json"
+
+
+def _redact_args(redact, roi, residuals, residual_bins):
+    """redact= of an encode loop against its roi= and residual outputs, refused by name before any GPU work."""
+    if redact is None:
+        return
+    from . import roi as X
+    from .redact import Redact
+
+    if not isinstance(redact, Redact):
+        raise ValueError(f"redact: expected a redact.Redact, got {type(redact).__name__}")
+    if roi is None:
+        raise ValueError("redact= needs roi= (the boxes to redact)")
+    redact.mask(X.as_roi(roi).names)
+    if (residuals is not None or residual_bins is not None) and not redact.restorable:
+        raise ValueError("redact= with residuals= / residual_bins=: the residual layer is taken from the unredacted source, so "
+                         "its files would hold what the redaction removes; say so with restorable=True (--redact-restorable) "
+                         "and guard those files, or leave them out")
+
+
+def _redact_frames(redact, layer):
+    """The merged list of every picture (redact.held_boxes), or None without redact=: host work, before any launch."""
+    if redact is None:
+        return None
+    from .redact import held_boxes
+
+    mask = redact.mask(layer.roi.names)
+    return [held_boxes(layer.frames, g, mask, redact.hold) for g in range(layer.plan.n_frames)]
+
+
+def _write_redact(bin_dir, redact):
+    """redact.json beside the .bin files of a redacted encode -- so that a receiver knows; decode ignores it.  Without
+    redact= a stale file is removed."""
+    import json
+
+    path = os.path.join(bin_dir, REDACT_JSON)
+    if redact is None:
+        if os.path.exists(path):
+            os.remove(path)
+        return
+    with open(path, "w") as f:
+        json.dump(redact.to_json(), f, indent=2)
+
+
+class _Redaction:
+    """redact= of an encode loop: the merged lists (uploaded GOP by GOP like the roi's own) and one redact.Redactor per GOP
+    stream.  Per-picture totals are kept only for a report."""
+
+    def __init__(self, redact, layer, held, run, report):
+        from .redact import Redactor
+
+        self.layer = _RoiLayer(layer.roi, layer.plan, layer.size, layer.dev, held)
+        self.steps = [Redactor(redact, layer.roi, layer.size, run.dev, totals=bool(report)) for _ in range(run.K)]
+
+    def step(self, k, g, x, intra):
+        if intra:
+            self.steps[k].flush()  # (the GOP before this one: its totals, if any are kept, go to the host in one copy)
+        return self.steps[k].step(x, self.layer.boxes(g))
+
+
+def _redact_report_keys(redact, redaction, run, h, w, inner=None):
+    """--report's keys of the redaction: the setting, and per picture the fraction of its pixels that were replaced."""
+    def keys(rd, types, values):
+        if inner:
+            inner(rd, types, values)
+        totals = {}
+        for k, f in enumerate(redaction.steps):
+            with torch.cuda.stream(run.cenc.streams[k]):
+                per = f.totals()  # (flushes a trailing partial GOP)
+            totals.update({run.global_index(k, t): v for t, v in enumerate(per)})
+        rd["redact"] = redact.to_json()
+        rd["frame_redacted"] = [totals[g] / (h * w) for g in sorted(totals)]
+
+    return keys
+
+
 def _fuse_roi(roi, residuals, roi_q, residual_bins=None):
     """The roi a decode loop fuses a residual layer with: none when the roi is only there for the q-scale maps."""
     return None if (residuals is None and residual_bins is None and roi_q is not None) else roi
@@ -1572,7 +1679,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
                  min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1,
-                 picture_hash=False, base_scale=None, aq=None, tnr=None):
+                 picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -1596,13 +1703,16 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     source's size, scale.json lies beside it.
     aq: as encode_folder (aq.json beside the .bin files; sequence.json is the same with or without).
     tnr: as encode_folder -- the filter comes after the colour conversion (RGB only); the YUV figures of the report stay
-    against the file's own samples; sequence.json is the same with or without."""
+    against the file's own samples; sequence.json is the same with or without.
+    redact: as encode_folder -- after the colour conversion and tnr (RGB only); redact.json lies beside sequence.json, which
+    is the same with or without."""
     from . import yuv as Y
 
     _roi_args(roi, residuals, residual_bins, residual_step)
     _roiq_args(roi, roi_q)
     _aq_args(aq)
     _tnr_args(tnr)
+    _redact_args(redact, roi, residuals, residual_bins)
     bit_dir = _bitmap_args(bit_map, report)
     reader = _open_source(video, size, bit_depth, fps)  # (every refusal about the file happens here, before any GPU work)
     spec = spec or reader.spec()
@@ -1621,6 +1731,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
 
     plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: (x for x, _ in converted(range(n_frames))))
     layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
+    held = _redact_frames(redact, layer)
     run = _EncodeRun(bin_dir, plan, base.size if base else (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets,
                      gop_streams, _VideoQualityLog if report else None, _bit_log(bit_map, bit_dir, layer, roi_q), rate,
                      picture_hash, base)
@@ -1631,6 +1742,8 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
     rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
     filters = _tnr_filters(tnr, run, (h, w), report)
+    _write_redact(bin_dir, redact)
+    redaction = _Redaction(redact, layer, held, run, report) if redact is not None else None
     source = {}
     container = "y4m" if isinstance(reader, Y.Y4MReader) else "yuv"
     extras = dict(chroma=getattr(reader, "chroma", None), interlace=getattr(reader, "interlace", None),
@@ -1639,11 +1752,13 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     outs = [_VideoOut(writer) for _ in range(run.K)] if writer else None
 
     def frames(k):
-        intra = run.intra(k) if filters else ()
+        intra = run.intra(k) if filters or redaction else ()
         for t, (x, samples) in enumerate(converted(run.order(k))):
             source[k] = (x, samples)  # (what on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
             if filters:  # (the codec sees the filtered picture; source[k] stays the unfiltered one)
                 x = filters[k].step(x, t in intra)
+            if redaction:  # (after the filter, whose own state stays unredacted; source[k] stays the unredacted one)
+                x = redaction.step(k, run.global_index(k, t), x, t in intra)
             yield base.down(x) if base else x
 
     def on_recon(k, g, ref_frame):
@@ -1694,7 +1809,8 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
             rd[f"ave_{name}_frame_psnr_yuv"] = sum(sel) / len(sel) if sel else 0
 
     keys = _enh_report_keys(rec_out, h, w, yuv_keys) if rec_out else yuv_keys
-    return run.results(report, _tnr_report_keys(tnr, filters, run, h, w, keys) if filters else keys)
+    keys = _tnr_report_keys(tnr, filters, run, h, w, keys) if filters else keys
+    return run.results(report, _redact_report_keys(redact, redaction, run, h, w, keys) if redaction else keys)
 
 
 def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=None, fps=None, device="cuda:0",
@@ -1944,6 +2060,25 @@ def main(argv=None):
     e.add_argument("--tnr-pixel", type=int, default=None, metavar="P",
                    help="with --tnr: a pixel whose own luma differs by more than P codes is passed through whatever its window "
                         "says, 0 .. 255 (default min(255, 3 T), an untuned placeholder)")
+    e.add_argument("--redact", nargs="+", default=None, metavar="NAME",
+                   help="with --roi-root: ROI redaction -- hand the codec every picture with the boxes of the named classes "
+                        "(liplates, faces, motion) replaced on the GPU by a mosaic (--redact-tile) or a solid fill "
+                        "(--redact-fill); exactly one of the two must be given, neither has a default.  Encoder side only: the "
+                        ".bin format is unchanged and decode needs nothing; redact.json beside the .bin files records the "
+                        "setting; --report keeps measuring against the unredacted source and gains redact and frame_redacted.  "
+                        "A mosaic is not a security guarantee (small tiles over text can be partly inverted: use the fill); "
+                        "boxes are taken as given, so whatever the detector misses stays untouched")
+    e.add_argument("--redact-tile", type=int, default=None, metavar="N",
+                   help="with --redact: a mosaic of N x N tiles on a picture-aligned grid, N one of 2, 4, 8, 16, 32, 64")
+    e.add_argument("--redact-fill", type=int, default=None, metavar="K",
+                   help="with --redact: a solid fill of the 8-bit code K, 0 .. 255, on all three channels")
+    e.add_argument("--redact-grow", type=int, default=None, metavar="G", help="with --redact: grow every box by G pixels, 0 .. 255 (default 0)")
+    e.add_argument("--redact-hold", type=int, default=None, metavar="N",
+                   help="with --redact: also redact inside the boxes of the N pictures before and after, 0 .. 32 (default 0): "
+                        "narrows, not closes, the gap a detector leaves when it misses a picture")
+    e.add_argument("--redact-restorable", action="store_true",
+                   help="with --redact: allow --residuals / --residual-bins, whose files then hold what was removed inside the "
+                        "boxes (decode --roi-root --residual-bins puts it back); whoever holds them holds the content")
     d = sub.add_parser("decode")
     d.add_argument("--base-only", action="store_true",
                    help="ignore a scale.json beside the .bin files (encode --base-scale) and write the base-size pictures; "
@@ -2039,7 +2174,7 @@ def main(argv=None):
             ap.error(f"boxes: {ex}")
         print(f"{len(boxes)} pictures, {sum(len(x) for x in boxes)} boxes -> {os.path.join(a.out, M.COORDS)}")
         return
-    roi = roi_q = aq = tnr = None
+    roi = roi_q = aq = tnr = redact = None
     motion = a.roi_root is not None and _has_motion(a.roi_root)
     if not motion and (a.motion_border is not None or getattr(a, "motion_q", None) is not None):
         ap.error("--motion-border and --motion-q need a --roi-root that holds motion_coords (run_codec boxes writes one)")
@@ -2115,6 +2250,20 @@ def main(argv=None):
         except (ValueError, OSError) as ex:
             ap.error(str(ex))
     if a.cmd == "encode":
+        if a.redact is None and (a.redact_tile is not None or a.redact_fill is not None or a.redact_grow is not None or
+                                 a.redact_hold is not None or a.redact_restorable):
+            ap.error("--redact-tile, --redact-fill, --redact-grow, --redact-hold and --redact-restorable belong to --redact")
+        if a.redact is not None:
+            from . import redact as RD
+
+            if roi is None:
+                ap.error("--redact needs --roi-root (the boxes to redact)")
+            try:
+                redact = RD.Redact(tuple(a.redact), a.redact_tile, a.redact_fill, a.redact_grow or 0, a.redact_hold or 0,
+                                   a.redact_restorable)
+                _redact_args(redact, roi, a.residuals, a.residual_bins)
+            except ValueError as ex:
+                ap.error(f"--redact: {ex}")
         if (a.frames is None) == (a.video is None):
             ap.error("give exactly one of --frames and --video")
         if a.bit_map is True and not a.report:
@@ -2174,14 +2323,14 @@ def main(argv=None):
                                                residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
                                                bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
                                                residual_bins=a.residual_bins, residual_step=a.residual_step,
-                                               picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq, tnr=tnr)
+                                               picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq, tnr=tnr, redact=redact)
         else:
             bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
                                             coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
                                             roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
                                             bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
                                             residual_bins=a.residual_bins, residual_step=a.residual_step,
-                                            picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq, tnr=tnr)
+                                            picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq, tnr=tnr, redact=redact)
         if rd:
             yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
             print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
