@@ -46,7 +46,13 @@ int32_t dcvc_drans_default_lanes(int64_t n);
 int64_t dcvc_drans_scratch_words(int64_t n, int32_t lanes);
 
 /* HOST helper: lut (n_cdfs x 256 bytes) for dcvc_drans_decode: lut[row][b] = the bin that holds
- * cumulative count b << 8 (the decoder's search starts there).  Upload it once per table. */
+ * cumulative count b << 8 (the decoder's search starts there).  Upload it once per table.
+ * It is also the validity check of a table for BOTH kernels, which stage rows as 16-bit values and
+ * validate nothing themselves: n_cdfs <= 256, cdf_stride <= 256 and every row has
+ * 3 <= size <= cdf_stride, cdf[0] == 0, cdf[size - 1] == 65536 and strictly increasing entries in
+ * between (at least two bins, none empty, so every width is in 1..65535).  Anything else returns
+ * DCVC_E_ARG and leaves the lut's contents unspecified; pass only tables it accepted to
+ * dcvc_drans_encode / dcvc_drans_decode (a width of 0 or 65536 divides by zero in the encoder). */
 int dcvc_drans_build_lut(const int32_t *cdfs, int32_t n_cdfs, int32_t cdf_stride, const int32_t *cdf_sizes,
                          uint8_t *lut);
 

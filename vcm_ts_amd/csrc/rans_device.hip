@@ -29,7 +29,8 @@ struct Tables {
 // The CDF table of the call is copied into LDS as 16-bit values first (256 x 103 entries = 52 KB for
 // the scale table): the serial per-lane loops then chase LDS, not L2.  The one value that does not
 // fit 16 bits, 65536 at the end of a row, wraps to 0; widths are taken mod 2^16 (a width is < 65536
-// because every row has at least two non-empty bins) and the decoder never compares the last entry.
+// because every row has at least two non-empty bins: dcvc_drans_build_lut refuses any other table)
+// and the decoder never compares the last entry.
 //
 // Work split: a workgroup is ONE wave of 64 lanes (the per-symbol state update is ~100-250 serial
 // instructions, so lanes of one plane are spread over lanes/64 compute units instead of queueing
@@ -400,8 +401,12 @@ extern "C" int dcvc_drans_build_lut(const int32_t *cdfs, int32_t n_cdfs, int32_t
     if (!cdfs || !cdf_sizes || !lut || n_cdfs <= 0 || n_cdfs > kMaxRows || cdf_stride < 2 || cdf_stride > 256) return DCVC_E_ARG;
     for (int row = 0; row < n_cdfs; ++row) {
         const int size = cdf_sizes[row];
-        if (size < 2 || size > cdf_stride) return DCVC_E_ARG;
+        // the kernels' 16-bit image of a row needs at least two bins, each of width 1..65535 (see load_tables)
+        if (size < 3 || size > cdf_stride) return DCVC_E_ARG;
         const int32_t *cdf = cdfs + (size_t)row * cdf_stride;
+        if (cdf[0] != 0 || cdf[size - 1] != 65536) return DCVC_E_ARG;
+        for (int i = 0; i + 1 < size; ++i)
+            if (cdf[i + 1] <= cdf[i]) return DCVC_E_ARG;
         int s = 0;
         for (int b = 0; b < 256; ++b) {
             while (s + 2 < size && (uint32_t)cdf[s + 1] <= (uint32_t)b << 8) ++s;
