@@ -210,15 +210,9 @@ def as_maps(aq, device):
 def write_aq(bin_dir, aq):
     """aq.json beside the .bin files -- only for an encode with backward-adaptive quantisation: without it none is needed
     (and a stale file of an earlier encode into the same folder must not describe these .bin files)."""
-    path = os.path.join(bin_dir, AQ_JSON)
-    if aq is None:
-        if os.path.exists(path):
-            os.remove(path)
-        return None
-    info = aq.to_json()
-    with open(path, "w") as f:
-        json.dump(info, f, indent=2)
-    return info
+    from .stream import write_sidecar
+
+    return write_sidecar(bin_dir, AQ_JSON, None if aq is None else aq.to_json())
 
 
 def read_aq(bin_dir):

@@ -22,6 +22,7 @@ import warnings
 import zlib
 
 from . import lib
+from .stream import write_sidecar
 
 HASHES_JSON = "hashes.json"
 VERSION, ALGORITHM = 1, "crc32"
@@ -113,7 +114,9 @@ class HashLog:
     asynchronous copy behind its last picture and are looked at later: the host never waits for a picture."""
 
     def __init__(self, plan):
-        self.plan, self.buf, self.idx, self.done, self.scratch = plan, None, [], [], None
+        from .goplog import GopLog
+
+        self.plan, self.buf, self.log, self.scratch = plan, None, GopLog(), None
 
     def add(self, g, ref_frame, size, display=None):
         """Picture g: `pixels` of the size = (height, width) crop of ref_frame, `state` of all of it.  display (with a
@@ -122,39 +125,29 @@ class HashLog:
 
         if self.scratch is None:
             self.scratch = new_scratch(ref_frame.device)
-        if not self.idx:
+        if not self.log.keys:
             n = len(self.plan.gop_range(self.plan.gop_of(g)))
             self.buf = torch.empty((n, 2), dtype=torch.uint32, device=ref_frame.device)
-        i = len(self.idx)
+        i = len(self.log.keys)
         if i >= self.buf.shape[0]:
-            raise ValueError(f"HashLog: picture {g} does not belong to the GOP of picture {self.idx[0]}")
+            raise ValueError(f"HashLog: picture {g} does not belong to the GOP of picture {self.log.keys[0]}")
         crc32_pixels(ref_frame if display is None else display, size, out=self.buf[i, 0:1], scratch=self.scratch)
         crc32_f32(ref_frame, out=self.buf[i, 1:2], scratch=self.scratch)
-        self.idx.append(g)
+        self.log.add(g)
         if self.plan.is_gop_end(g):
             self.flush()
 
     def flush(self):
-        import torch
-
-        if self.idx:
-            dev = self.buf[:len(self.idx)]
-            host = torch.empty(dev.shape, dtype=dev.dtype).pin_memory()
-            host.copy_(dev, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev.device))
-            self.done.append((ev, host, self.buf, self.idx))
-            self.buf, self.idx = None, []
+        if self.log.keys:
+            self.log.flush(self.buf[:len(self.log.keys)])
 
     def poll(self, wait=False):
         """[(frame number, pixels, state)] of the GOPs whose copies have completed since the last call, in coding order;
         wait=True waits for every flushed GOP."""
         out = []
-        while self.done and (wait or self.done[0][0].query()):
-            ev, host, _, idx = self.done.pop(0)
-            ev.synchronize()
+        for keys, (host,) in self.log.poll(wait):
             rows = host.numpy()
-            out.extend((g, int(rows[n, 0]), int(rows[n, 1])) for n, g in enumerate(idx))
+            out.extend((g, int(rows[n, 0]), int(rows[n, 1])) for n, g in enumerate(keys))
         return out
 
     def collect(self):
@@ -169,9 +162,7 @@ def _hex(v):
 
 def remove_hashes(bin_dir):
     """A stale file of an earlier encode into the same folder must not describe these .bin files."""
-    path = os.path.join(bin_dir, HASHES_JSON)
-    if os.path.exists(path):
-        os.remove(path)
+    write_sidecar(bin_dir, HASHES_JSON, None)
 
 
 def write_hashes(bin_dir, digests, height, width, padded, precision):
@@ -182,9 +173,7 @@ def write_hashes(bin_dir, digests, height, width, padded, precision):
     info = {"version": VERSION, "algorithm": ALGORITHM, "frames": n, "height": int(height), "width": int(width),
             "padded": [int(padded[0]), int(padded[1])], "precision": str(precision),
             "pixels": [_hex(digests[g][0]) for g in range(n)], "state": [_hex(digests[g][1]) for g in range(n)]}
-    with open(os.path.join(bin_dir, HASHES_JSON), "w") as f:
-        json.dump(info, f, indent=2)
-    return info
+    return write_sidecar(bin_dir, HASHES_JSON, info)
 
 
 def parse_hashes(info, where=HASHES_JSON):

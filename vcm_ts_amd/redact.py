@@ -24,16 +24,10 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import lib
-from .roi import MAX_BOXES, MAX_CLASSES, MAX_GROW, MAX_SIDE, FrameBoxes, as_boxes, grid_of
+from .roi import MAX_BOXES, MAX_CLASSES, MAX_GROW, FrameBoxes, as_boxes, grid_of
+from .tnr import StreamFilter, _whole
 
 TILES, MAX_FILL, MAX_HOLD = (2, 4, 8, 16, 32, 64), 255, 32
-ROWS = 64  # pictures' totals kept on the device between two copies to the host
-
-
-def _whole(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-        raise ValueError(f"{name} must be an integer within {lo}..{hi}, got {v!r}")
-    return int(v)
 
 
 @dataclass(frozen=True)
@@ -119,52 +113,25 @@ def _launch(src, out, out_rs, out_ps, h, w, boxes, mask, redact, count, device):
                                     mask, redact.grow, tile, fill, count.data_ptr(), C.c_void_p(_raw_stream(device.index))), "redact")
 
 
-class Redactor:
-    """The redaction of one GOP stream of `size` = (height, width) pictures on `device`: two zero-initialised padded
-    pictures written alternately and the cells' counts.  I pictures and P pictures are treated alike, and no state passes
-    from one picture to the next.  One Redactor serves one stream at a time.  totals=False keeps no per-picture totals: a
-    step is then the one launch and nothing else, no pinned memory and no event is ever made, and .totals() is refused."""
+class Redactor(StreamFilter):
+    """The redaction of one GOP stream: tnr.StreamFilter's two pictures and the cells' counts.  I pictures and P pictures
+    are treated alike, and no state passes from one picture to the next.  One Redactor serves one stream at a time.
+    .totals(): |R| of every step, 0 for a picture that was not touched."""
+    noun, untouched = "redactor", 0
 
     def __init__(self, redact, roi, size, device, totals=True):
         import torch
 
-        from . import stream as S
         from .roi import as_roi
 
         if not isinstance(redact, Redact):
             raise ValueError(f"redact: expected a redact.Redact, got {type(redact).__name__}")
-        self.redact, self.device = redact, torch.device(device)
+        self.redact = redact
         self.names = tuple(as_roi(roi).names)
         self.mask = redact.mask(self.names)
-        if self.device.type != "cuda":
-            raise ValueError("Redactor: pictures live on the GPU (no CPU fallback exists)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.height, self.width = int(size[0]), int(size[1])
-        if not (0 < self.height <= MAX_SIDE and 0 < self.width <= MAX_SIDE):
-            raise ValueError(f"picture sides must be within 1..{MAX_SIDE}, got {self.width}x{self.height}")
-        l, r, t, b = S.get_padding_size(self.height, self.width)
-        self.padded = (self.height + t + b, self.width + l + r)
-        self.grid = grid_of(self.height, self.width)
-        # (the crop is written in place by every step and the padding never: it stays the zero pad_frame would give)
-        self.bufs = [torch.zeros((1, 3) + self.padded, dtype=torch.float32, device=self.device) for _ in range(2)]
+        super().__init__(size, device, 1, totals)
         self.count = torch.empty(self.grid[0] * self.grid[1], dtype=torch.int16, device=self.device)  # (uint16 words, <= 256)
-        self.n, self.launches = 0, 0
-        # |R| of the redacted pictures not yet flushed; the values already read, by step number
-        self._rows = torch.zeros(ROWS, dtype=torch.int64, device=self.device) if totals else None
-        self._idx, self._done, self._read = [], [], {}
         torch.cuda.synchronize(self.device)  # (the fills above: a stream that uses them afterwards cannot race them)
-
-    def _check(self, x):
-        import torch
-
-        if not torch.is_tensor(x) or not x.is_cuda:
-            raise ValueError("Redactor.step: pictures live on the GPU (no CPU fallback exists)")
-        if x.device != self.device:
-            raise ValueError(f"Redactor.step: the picture is on {x.device}, the redactor on {self.device}")
-        if x.dtype != torch.float32 or tuple(x.shape) != (1, 3) + self.padded:
-            raise ValueError(f"Redactor.step: expected a (1, 3, {self.padded[0]}, {self.padded[1]}) float32 picture, got "
-                             f"{tuple(x.shape)} {x.dtype}")
 
     def step(self, x_padded, boxes):
         """The padded picture to code in place of `x_padded`.  boxes: the picture's merged list (held_boxes).  A picture
@@ -183,39 +150,8 @@ class Redactor:
         with torch.cuda.device(self.device):
             _launch(x_padded.detach()[..., :h, :w], out, Wp, Hp * Wp, h, w, boxes, self.mask, self.redact, self.count, self.device)
         self.launches += 1
-        if self._rows is not None:
-            # (one small reduction behind the launch; the host looks at it per GOP)
-            self._rows[len(self._idx)].copy_(self.count.sum(dtype=torch.int64))
-            self._idx.append(t)
-            if len(self._idx) == ROWS:  # (a GOP with more redacted pictures than rows: its totals travel in more than one copy)
-                self.flush()
+        self._keep(t, self.count)
         return out
-
-    def flush(self):
-        """The totals of the pictures redacted since the last flush, to pinned host memory in ONE asynchronous copy on the
-        current stream: no kernel, and nothing is waited for.  The file loops call it at every GOP's first picture."""
-        import torch
-
-        if self._idx:
-            host = torch.empty(len(self._idx), dtype=torch.int64).pin_memory()
-            host.copy_(self._rows[:len(self._idx)], non_blocking=True)  # (the next step's rows follow it in stream order)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-            self._done.append((ev, host, self._idx))
-            self._idx = []
-
-    def totals(self):
-        """|R| of every step so far, in order, as Python integers; 0 for a picture that was not touched.  Flushes on the
-        current stream and waits for the copies; their pinned buffers and events are let go of here, at a known point, and
-        only the integers are kept."""
-        if self._rows is None:
-            raise ValueError("Redactor.totals: this redactor was made with totals=False")
-        self.flush()
-        for ev, host, idx in self._done:
-            ev.synchronize()
-            self._read.update(dict(zip(idx, (int(v) for v in host.tolist()))))
-        self._done = []
-        return [self._read.get(t, 0) for t in range(self.n)]
 
 
 def redact_picture(x, boxes, redact, names):

@@ -108,6 +108,7 @@ import numpy as np
 import torch
 
 from . import stream as S
+from .goplog import GopLog
 from .scenecut import GopPlan
 from .pipeline import ConcurrentGopEncoder, decode_picture, pad_frame
 
@@ -301,38 +302,36 @@ class _QualityLog:
     picture's metric."""
 
     def __init__(self, plan):
-        self.plan, self.cur, self.idx, self.done = plan, [], [], []
+        self.plan, self.log = plan, GopLog()
 
     def add(self, g, recon, source, size):
+        self._add(g, recon, source, size)
+
+    def _add(self, g, recon, source, size, *more):
         from . import metrics
 
         h, w = size
         ms, _, sse = metrics.measure(recon[..., :h, :w], source[..., :h, :w], 1.0, clamp01=True)
-        self.cur.append(torch.cat([ms, sse]))
-        self.idx.append(g)
+        self.log.add(g, torch.cat([ms, sse, *more]))
         if self.plan.is_gop_end(g):
             self.flush()
 
     def flush(self):
-        if self.cur:
-            dev = torch.stack(self.cur)
-            host = torch.empty(dev.shape, dtype=dev.dtype).pin_memory()
-            host.copy_(dev, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev.device))
-            self.done.append((ev, host, dev, self.idx))
-            self.cur, self.idx = [], []
+        self.log.flush()
 
     def collect(self, elements):
         """{frame number: (psnr dB, ms-ssim)}"""
         import math
 
         out = {}
-        for ev, host, _, idx in self.done:
-            ev.synchronize()
-            for g, (ms, sse) in zip(idx, host.double().tolist()):
-                out[g] = (10.0 * math.log10(elements / sse) if sse > 0 else float("inf"), ms)
+        for idx, (host,) in self.log.collect():
+            for g, (ms, sse), more in zip(idx, host[:, :2].double().tolist(), self._more(host)):
+                out[g] = (10.0 * math.log10(elements / sse) if sse > 0 else float("inf"), ms, *more)
         return out
+
+    def _more(self, host):
+        """What a row holds behind its two metrics, per picture: nothing."""
+        return [()] * host.shape[0]
 
 
 def _bitmap_args(bit_map, report):
@@ -374,7 +373,7 @@ class _BitLog:
     def __init__(self, plan, labels_of, keep_cells):
         self.plan, self.labels_of, self.keep_cells = plan, labels_of, keep_cells
         self.K = 2 if labels_of else 1
-        self.cur, self.cells, self.idx, self.done, self._one = [], [], [], [], None
+        self.log, self.cells, self._one = GopLog(), [], None
 
     def add(self, g, bits):
         if self.labels_of:
@@ -384,35 +383,23 @@ class _BitLog:
                 self._one = torch.zeros((1, bits.hc, bits.wc), dtype=torch.uint8, device=bits.status.device)
             labels = self._one
         row = bits.regions_enqueue(labels, self.K)
-        self.cur.append(torch.cat([row, labels.sum(dtype=torch.int64).reshape(1)]))
+        self.log.add(g, torch.cat([row, labels.sum(dtype=torch.int64).reshape(1)]))
         if self.keep_cells:
             self.cells.append(bits.cells_device())
-        self.idx.append(g)
         if self.plan.is_gop_end(g):
             self.flush()
 
     def flush(self):
-        if self.cur:
-            pair = []
-            for dev in (torch.stack(self.cur), torch.stack(self.cells) if self.cells else None):
-                if dev is None:
-                    pair.append((None, None))
-                    continue
-                host = torch.empty(dev.shape, dtype=dev.dtype).pin_memory()
-                host.copy_(dev, non_blocking=True)
-                pair.append((host, dev))
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(pair[0][1].device))
-            self.done.append((ev, pair, self.idx))
-            self.cur, self.cells, self.idx = [], [], []
+        if self.log.keys:
+            self.log.flush(torch.stack(self.log.rows), torch.stack(self.cells) if self.cells else None)
+            self.cells = []
 
     def collect(self):
         """{frame number: ((K, 4) int64 sums in 2^-20 bit, cells of label 1, the (1, hc, wc) float64 cell map or None)}"""
         from .bitmap import BitMap
 
         out = {}
-        for ev, ((rows, _), (cells, _)), idx in self.done:
-            ev.synchronize()
+        for idx, (rows, cells) in self.log.collect():
             for n, g in enumerate(idx):
                 row = rows[n].numpy()
                 out[g] = (BitMap.decode(row[:-1], 1, self.K)[0], int(row[-1]), None if cells is None else cells[n].numpy())
@@ -453,7 +440,7 @@ class _PinnedRing:
 class _EncodeRun:
     """What encoding a sequence of `n_frames` pictures of `size` = (height, width) into `bin_dir` is, whatever the
     pictures come from: the GOP streams and their codecs, which frame numbers each stream codes, the .bin sink and
-    the bits / quality report.  encode_folder and encode_video supply the pictures and take the reconstructions."""
+    the bits / quality report.  _encode_sequence supplies the pictures and takes the reconstructions."""
 
     def __init__(self, bin_dir, plan, size, gop, device, precision, i_ckpt, p_ckpt, coder, nets, gop_streams, log_cls,
                  bit_log=None, rate=None, picture_hash=False, base=None):
@@ -577,8 +564,9 @@ class _EncodeRun:
         PH.write_hashes(self.bin_dir, digests, h, w, (h + t + b, w + l + r), self.cenc.encoders[0].p_net.engine().precision)
 
     def results(self, report, extras=None):
-        """(bits per frame list, size) -- with a report also the rd_report() dictionary, which extras(rd, frame types,
-        [the logs' value per frame]) may extend before it is written to `report` (if that is a path)."""
+        """(bits per frame list, size) -- with a report also the rd_report() dictionary, which every keys(rd, frame types,
+        [the logs' value per frame]) of the list `extras` extends, in order, before the bit and rate keys are added and it is
+        written to `report` (if that is a path)."""
         order = sorted(self.bits)
         bit_list = [self.bits[g] for g in order]
         if self.hash_logs:
@@ -594,8 +582,8 @@ class _EncodeRun:
             values.update(log.collect(3 * h * w))
         types = [0 if self.plan.is_intra(g) else 1 for g in order]
         rd = rd_report(types, bit_list, [values[g][0] for g in order], [values[g][1] for g in order], h * w)
-        if extras:
-            extras(rd, types, [values[g] for g in order])
+        for keys in extras or ():
+            keys(rd, types, [values[g] for g in order])
         if bit_keys:
             rd.update(bit_keys)
         if self.rate is not None:  # (the q-scale each picture's y was coded with -- an I picture's is q_i -- and the budget
@@ -612,19 +600,20 @@ class _EncodeRun:
 GOPS_JSON = "gops.json"
 
 
-def _scene_plan(n_frames, size, gop, scenecut, min_gop, device, pictures):
-    """The GopPlan of an encode loop.  Without `scenecut` the fixed one, and `pictures` is not touched.  With it the scan
-    pass: pictures() yields every picture of the sequence once, in order, as the coding pass will see it (same reader,
-    same conversion); each is summarised on the device (scenecut.SceneScan: one kernel per picture, nothing
-    synchronised) and the distances are read back in one copy at the end."""
+def _scene_plan(source, gop, scenecut, min_gop):
+    """The GopPlan of an encode loop.  Without `scenecut` the fixed one, and the source is not read.  With it the scan
+    pass: every picture of the source once, in order, as the coding pass will see it (same reader, same conversion);
+    each is summarised on the device (scenecut.SceneScan: one kernel per picture, nothing synchronised) and the
+    distances are read back in one copy at the end."""
     from . import scenecut as SC
 
+    n_frames = source.n_frames
     SC.check_options(gop, scenecut, min_gop)
     if scenecut is None:
         return GopPlan.fixed(n_frames, gop)
-    scan = SC.SceneScan(device, size[0], size[1], n_frames)
+    scan = SC.SceneScan(source.dev, source.size[0], source.size[1], n_frames)
     with torch.no_grad():
-        for x in pictures():
+        for x, _ in source.pictures(range(n_frames)):
             scan.add(x)
     if scan.n != n_frames:
         raise ValueError(f"the scan pass saw {scan.n} pictures of {n_frames}")
@@ -634,15 +623,8 @@ def _scene_plan(n_frames, size, gop, scenecut, min_gop, device, pictures):
 def write_gop_plan(bin_dir, plan, gop, scenecut, min_gop):
     """gops.json beside the .bin files -- only for a plan that came from a scan: a fixed plan needs none (and a stale
     file of an earlier encode into the same folder must not describe these .bin files)."""
-    import json
-
-    path = os.path.join(bin_dir, GOPS_JSON)
-    if scenecut is None:
-        if os.path.exists(path):
-            os.remove(path)
-        return
-    with open(path, "w") as f:
-        json.dump(dict(plan.to_json(), gop=int(gop), min_gop=int(min_gop), scenecut=float(scenecut)), f, indent=2)
+    S.write_sidecar(bin_dir, GOPS_JSON, None if scenecut is None else
+                    dict(plan.to_json(), gop=int(gop), min_gop=int(min_gop), scenecut=float(scenecut)))
 
 
 ROIQ_JSON = "roiq.json"
@@ -666,23 +648,7 @@ def _roiq_args(roi, roi_q):
 def write_roiq(bin_dir, roi_q, names=()):
     """roiq.json beside the .bin files -- only for an encode with q-scale maps: without them none is needed (and a stale
     file of an earlier encode into the same folder must not describe these .bin files)."""
-    import json
-
-    path = os.path.join(bin_dir, ROIQ_JSON)
-    if roi_q is None:
-        if os.path.exists(path):
-            os.remove(path)
-        return
-    info = roi_q.to_json(names)
-    with open(path, "w") as f:
-        json.dump(info, f, indent=2)
-
-
-def _write_scale(bin_dir, base):
-    """scale.json beside the .bin files of an encode with a base scale; without one a stale file is removed."""
-    from . import scale as SC
-
-    SC.write_scale(bin_dir, base.scale if base else None)
+    S.write_sidecar(bin_dir, ROIQ_JSON, None if roi_q is None else roi_q.to_json(names))
 
 
 def _aq_args(aq):
@@ -692,28 +658,6 @@ def _aq_args(aq):
     if aq is not None and not isinstance(aq, A.AQ):
         raise ValueError(f"aq: expected an aq.AQ, got {type(aq).__name__}")
     return aq
-
-
-def _write_aq(bin_dir, aq):
-    """aq.json beside the .bin files of an encode with backward-adaptive quantisation; without it a stale file is removed."""
-    from . import aq as A
-
-    A.write_aq(bin_dir, aq)
-
-
-def _read_aq(bin_dir):
-    """The aq.AQ of the folder's aq.json, None without the file: host work only, so that the refusals of aq.read_aq (an
-    unknown version, a value out of range, tables this host builds differently) come before any launch or output."""
-    from . import aq as A
-
-    return A.read_aq(bin_dir)
-
-
-def _decode_aq(aq, dev):
-    """aq= of _decode_bins: the aq.AqMaps of _read_aq's record on `dev` (None: none)."""
-    from . import aq as A
-
-    return A.AqMaps(aq, dev) if aq is not None else None
 
 
 def read_roiq(bin_dir, roi=None):
@@ -810,7 +754,7 @@ def _base_args(base_scale, roi, roi_q, bit_map, size, dev):
 def _decode_scale(bin_dir, height, width, base_scale, roi, residuals, residual_bins):
     """base_scale= of a decode loop ("file": follow the folder's scale.json; None: ignore it, --base-only) ->
     (scale.read_scale's record of the scaler to build, or None when nothing is scaled up; the (height, width) of the coded
-    pictures).  height, width: the display size.  Host work only (_up_layer builds the tables on the device, once every
+    pictures).  height, width: the display size.  Host work only (_decode_sequence builds the tables on the device, once every
     refusal has had its turn).  Refused by name: a scale.json of another display size or whose base is not what the .bin
     files hold, a base-only decode with a ROI, anything but "file" and None.  A base-only decode does not read the file:
     the first .bin file's header says what size the pictures are."""
@@ -836,13 +780,6 @@ def _decode_scale(bin_dir, height, width, base_scale, roi, residuals, residual_b
         raise ValueError(f"{where}: a base layer of {info['base'][1]}x{info['base'][0]} pictures (ratio {info['ratio']}), the "
                          f".bin files hold {coded[1]}x{coded[0]}")
     return info, info["base"]
-
-
-def _up_layer(info, dev):
-    """The _BaseLayer of _decode_scale's record (None: none)."""
-    from . import scale as SC
-
-    return _BaseLayer(SC.Scale(info["full"], info["ratio"], dev)) if info else None
 
 
 def _png_pictures(reader, order, size, dev, pool, io_workers, sharers):
@@ -884,6 +821,258 @@ def _video_pictures(reader, order, spec, quantize8, dev):
         reader.read_into(g, ring.host())
         samples = ring.upload().view(sample_dtype)
         yield Y.yuv420_to_rgb(samples, reader.height, reader.width, spec, pad=True, quantize8=quantize8), samples
+
+
+class _PngSource:
+    """A PNG folder as the source of a file loop.  open() reads the folder: the reader, `size` = (height, width),
+    `n_frames` and the shared pool of PNG-decoding threads.  Refused by name there: a folder that has neither im1.png nor
+    im00001.png."""
+
+    def __init__(self, frames_dir, device, io_workers=8, max_frames=None):
+        self.frames_dir, self.dev, self.io_workers, self.max_frames = frames_dir, torch.device(device), io_workers, max_frames
+        self.pool = None
+
+    def open(self):
+        from concurrent.futures import ThreadPoolExecutor
+
+        from PIL import Image
+
+        self.reader, self.n_frames = PNGReader(self.frames_dir), 0
+        while os.path.exists(self.reader.path_of(self.n_frames + 1)) and (self.max_frames is None or self.n_frames < self.max_frames):
+            self.n_frames += 1
+        with Image.open(self.reader.path_of(1)) as first:  # (the header only)
+            self.size = first.size[::-1]
+        self.pool = ThreadPoolExecutor(max_workers=self.io_workers) if self.io_workers > 0 else None
+
+    def pictures(self, order, sharers=1):
+        """(the padded picture the codec takes, None) of every frame `order` names; `sharers` such generators draw on
+        the pool together."""
+        for x in _png_pictures(self.reader, order, self.size, self.dev, self.pool, self.io_workers, sharers):
+            yield x, None
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown(wait=True, cancel_futures=True)
+
+
+class _VideoSource:
+    """A `.y4m` / raw `.yuv` file (or an open yuv reader, which then stays the caller's to close) as the source of a file
+    loop.  open() opens the file: the reader, the colour description, `size` and `n_frames`.  Every refusal about the file
+    happens there, before any GPU work: what yuv.open_video refuses, a bit depth that is not the description's, a file
+    without frames."""
+
+    def __init__(self, video, device, size=None, spec=None, quantize8=False, bit_depth=8, fps=None, max_frames=None):
+        self.video, self.dev, self.args, self.spec, self.quantize8 = video, torch.device(device), (size, bit_depth, fps), spec, quantize8
+        self.max_frames, self.reader = max_frames, None
+
+    def open(self):
+        from . import yuv as Y
+
+        self.reader = reader = Y.open_video(self.video, *self.args) if isinstance(self.video, (str, os.PathLike)) else self.video
+        self.spec = self.spec or reader.spec()
+        if self.spec.bit_depth != reader.bit_depth:
+            raise ValueError(f"the file holds {reader.bit_depth}-bit samples, the colour description says {self.spec.bit_depth}")
+        self.size = (reader.height, reader.width)
+        self.n_frames = reader.n_frames if self.max_frames is None else min(reader.n_frames, int(self.max_frames))
+        if self.n_frames < 1:
+            raise ValueError(f"{getattr(reader, 'path', self.video)}: no frames")
+
+    def pictures(self, order, sharers=1):
+        """(the padded picture the codec takes, the file's samples on the device) of every frame `order` names."""
+        return _video_pictures(self.reader, order, self.spec, self.quantize8, self.dev)
+
+    def close(self):
+        if self.reader is not None and self.reader is not self.video:
+            self.reader.close()
+
+
+class _PngStage:
+    """Output stage "PNG folder" of a file loop -- or, without a folder, nothing: put() writes the unpadded picture as
+    im%05d.png through a pool of PNG-encoding threads."""
+    sums = 0  # (integer sums measure() adds to a picture's report row)
+
+    def __init__(self, path, io_workers):
+        self.path, self.io_workers, self.savers = path, io_workers, None
+
+    def open(self, size, streams=1, source=None):
+        self.size = size
+        if self.path:
+            os.makedirs(self.path, exist_ok=True)
+            self.savers = PNGWriters(self.io_workers)
+
+    def put(self, k, g, frame):
+        if self.path:
+            h, w = self.size
+            save_torch_image(frame[..., :h, :w], os.path.join(self.path, f"im{str(g + 1).zfill(5)}.png"), self.savers)
+
+    def flush(self):
+        if self.savers:
+            self.savers.close()  # (re-raises a writer's exception)
+
+    def close(self, failed):
+        if self.savers and failed:  # (already failing: do not mask the first error with a writer's)
+            self.savers.__exit__(RuntimeError, None, None)
+
+    def report_keys(self):
+        return None
+
+    def finish(self, bin_dir, n_frames, gop, roi, residual_step):
+        pass
+
+
+class _VideoStage:
+    """Output stage "video file" of a file loop -- or, without a path, no file: put() converts the picture to 4:2:0 on the
+    stream that made it and hands it to that stream's _VideoOut.  For an encode it also owns what only a video source has:
+    the sample-domain sums and keys of the report, and sequence.json."""
+    sums = 3
+
+    def __init__(self, path, spec=None, fps=None, **extras):
+        """spec, fps, extras (chroma, interlace, aspect): of the file to write; an encode takes them from its source."""
+        self.path, self.spec, self.fps, self.container, self.extras = path, spec, fps, None, extras
+        self.writer, self.outs, self.cur = None, None, {}
+
+    def open(self, size, streams=1, source=None):
+        from . import yuv as Y
+
+        self.Y, self.size = Y, size
+        if source is not None:  # (an encode: the output file and sequence.json describe the source)
+            reader = source.reader
+            self.spec, self.fps, self.container = source.spec, reader.fps, "y4m" if isinstance(reader, Y.Y4MReader) else "yuv"
+            self.extras = {name: getattr(reader, name, None) for name in ("chroma", "interlace", "aspect")}
+        if self.path:
+            self.writer = Y.create_video(self.path, size[1], size[0], self.spec, self.fps, **self.extras)
+            self.outs = [_VideoOut(self.writer) for _ in range(streams)]
+
+    def measure(self, k, frame, samples):
+        """The three integer sums of the picture's samples against the file's: the ONE conversion of a reported picture,
+        whose samples put() then writes."""
+        self.cur[k], sums = self.Y.rgb_to_yuv420(frame, self.size[0], self.size[1], self.spec, source=samples)
+        return sums
+
+    def put(self, k, g, frame):
+        """frame: padded or not -- rgb_to_yuv420 reads its top-left corner in place."""
+        out = self.cur.pop(k, None)
+        if self.outs:
+            self.outs[k].put(g, self.Y.rgb_to_yuv420(frame, self.size[0], self.size[1], self.spec) if out is None else out)
+
+    def flush(self):
+        for o in self.outs or []:
+            o.close()
+
+    def close(self, failed):
+        if self.writer:
+            self.writer.close()
+
+    def report_keys(self):
+        (h, w), Y, depth = self.size, self.Y, self.spec.bit_depth
+
+        def keys(rd, types, values):
+            per = [Y.psnr_yuv(v[2][:3], h, w, depth) for v in values]
+            for n, name in enumerate(("y", "u", "v", "yuv")):
+                rd[f"frame_psnr_{name}"] = [p[n] for p in per]
+            for name, keep in (("i", lambda k: k == 0), ("p", lambda k: k != 0), ("all", lambda k: True)):
+                sel = [p[3] for p, k in zip(per, types) if keep(k)]
+                rd[f"ave_{name}_frame_psnr_yuv"] = sum(sel) / len(sel) if sel else 0
+
+        return keys
+
+    def finish(self, bin_dir, n_frames, gop, roi, residual_step):
+        write_sequence_info(bin_dir, self.size[1], self.size[0], n_frames, gop, self.fps, self.spec, self.container, **self.extras,
+                            roi=roi, residual_step=residual_step)
+
+
+def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
+                     coder="host", io_workers=8, nets=None, gop_streams=1, report=None, roi=None, residuals=None, scenecut=None,
+                     min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1,
+                     picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None):
+    """The one encode loop: the pictures of `source` (a _PngSource or a _VideoSource, opened here and closed on every exit)
+    through tnr, redact and the base layer's scaling into an _EncodeRun, and every reconstruction through the base layer's
+    up-scaling to the residual outputs, the report and `out` (a _PngStage or a _VideoStage).  The options are
+    encode_folder's.  Refusals in this order, all before any launch or file: the residual layer's arguments, roi_q, aq, tnr,
+    redact, bit_map; then what the source refuses about its files; the rate control's, base_scale, the scene cut's options,
+    the boxes of every frame, the redaction's merged lists."""
+    from . import aq as A
+    from . import scale as SC
+
+    _roi_args(roi, residuals, residual_bins, residual_step)
+    _roiq_args(roi, roi_q)
+    _aq_args(aq)
+    _tnr_args(tnr)
+    _redact_args(redact, roi, residuals, residual_bins)
+    bit_dir = _bitmap_args(bit_map, report)
+    try:
+        source.open()
+        h, w = source.size
+        rate = _rate_args(target_bpp, q_range, h, w, gop)
+        dev = torch.device(device)
+        base = _base_args(base_scale, roi, roi_q, bit_map, (h, w), dev)
+        plan = _scene_plan(source, gop, scenecut, min_gop)
+        layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
+        held = _redact_frames(redact, layer)
+        run = _EncodeRun(bin_dir, plan, base.size if base else (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets,
+                         gop_streams, (_VideoQualityLog if layer or out.sums else _QualityLog) if report else None,
+                         _bit_log(bit_map, bit_dir, layer, roi_q), rate, picture_hash, base)
+        write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
+        write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
+        SC.write_scale(bin_dir, base.scale if base else None)
+        A.write_aq(bin_dir, aq)
+        res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
+        rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
+        filters = _tnr_filters(tnr, run, (h, w), report)
+        _write_redact(bin_dir, redact)
+        redaction = _Redaction(redact, layer, held, run, report) if redact is not None else None
+        out.open((h, w), run.K, source)
+        compared = bool(report or res_out or rec_out)  # (something will look at the source beside the reconstruction)
+        current = {}
+
+        def frames(k):
+            intra = run.intra(k) if filters or redaction else ()
+            for t, (x, aux) in enumerate(source.pictures(run.order(k), run.K)):
+                if compared:
+                    current[k] = (x, aux)  # (what on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
+                if filters:  # (the codec sees the filtered picture; current[k] stays the unfiltered one)
+                    x = filters[k].step(x, t in intra)
+                if redaction:  # (after the filter, whose own state stays unredacted; current[k] stays the unredacted one)
+                    x = redaction.step(k, run.global_index(k, t), x, t in intra)
+                yield base.down(x) if base else x
+
+        def on_recon(k, g, ref_frame):
+            x, aux = current.get(k, (None, None))
+            if base:  # (everything below looks at the full-size picture; the DPB keeps the base one)
+                ref_frame = base.shown(k, g, ref_frame)
+            if res_out:
+                res_out.put(k, g, x[..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
+            if rec_out:
+                rec_out.put(k, g, x[..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
+            if report:
+                sums = [out.measure(k, ref_frame, aux)] if out.sums else []
+                if layer:
+                    sums.append(layer.X.region_sse(ref_frame[..., :h, :w], x[..., :h, :w], layer.boxes(g), layer.classes))
+                if sums:
+                    run.quality[k].add_yuv(g, ref_frame, x, (h, w), torch.cat(sums) if len(sums) > 1 else sums[0])
+                else:
+                    run.quality[k].add(g, ref_frame, x, (h, w))
+            out.put(k, g, ref_frame)
+
+        failed = True
+        try:
+            run.encode(frames, q, on_recon if (out.path or compared) else None,
+                       (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None, aq)
+            out.flush()
+            failed = False
+        finally:
+            out.close(failed)
+            if res_out:
+                res_out.close(failed)
+            if rec_out:
+                rec_out.close(failed)
+    finally:
+        source.close()
+    out.finish(bin_dir, plan.n_frames, gop, layer.roi if layer else None, residual_step if rec_out else None)
+    keys = [_roi_report_keys(h, w) if layer else None, out.report_keys(), _enh_report_keys(rec_out, h, w) if rec_out else None,
+            _tnr_report_keys(tnr, filters, run, h, w) if filters else None,
+            _redact_report_keys(redact, redaction, run, h, w) if redaction else None]
+    return run.results(report, [k for k in keys if k])
 
 
 def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None,
@@ -982,103 +1171,15 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     residual_bins are taken from the unredacted source too, so those files would hold what was removed inside the boxes
     themselves: that combination is a ValueError unless redact.restorable is set.  A mosaic is not a security guarantee.
     None: no launch, allocation, file, key or byte changes (a stale redact.json is removed)."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    from PIL import Image
-
-    if recon_dir:
-        os.makedirs(recon_dir, exist_ok=True)
-    reader = PNGReader(frames_dir)
-    n_frames = 0
-    while os.path.exists(reader.path_of(n_frames + 1)) and (max_frames is None or n_frames < max_frames):
-        n_frames += 1
-    with Image.open(reader.path_of(1)) as first:  # (the header only)
-        w, h = first.size
-    _roi_args(roi, residuals, residual_bins, residual_step)
-    _roiq_args(roi, roi_q)
-    _aq_args(aq)
-    _tnr_args(tnr)
-    _redact_args(redact, roi, residuals, residual_bins)
-    bit_dir = _bitmap_args(bit_map, report)
-    rate = _rate_args(target_bpp, q_range, h, w, gop)
-    dev = torch.device(device)
-    base = _base_args(base_scale, roi, roi_q, bit_map, (h, w), dev)
-    pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
-
-    def uploaded(order, sharers):
-        return _png_pictures(reader, order, (h, w), dev, pool, io_workers, sharers)
-
-    try:
-        plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: uploaded(range(n_frames), 1))
-        layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
-        held = _redact_frames(redact, layer)
-        run = _EncodeRun(bin_dir, plan, base.size if base else (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets,
-                         gop_streams, (_VideoQualityLog if layer else _QualityLog) if report else None,
-                         _bit_log(bit_map, bit_dir, layer, roi_q), rate, picture_hash, base)
-        write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
-        write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
-        _write_scale(bin_dir, base)
-        _write_aq(bin_dir, aq)
-        res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
-        rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
-        filters = _tnr_filters(tnr, run, (h, w), report)
-        _write_redact(bin_dir, redact)
-        redaction = _Redaction(redact, layer, held, run, report) if redact is not None else None
-    except BaseException:
-        if pool is not None:
-            pool.shutdown(wait=True, cancel_futures=True)
-        raise
-    source = {}
-
-    def frames(k):
-        intra = run.intra(k) if filters or redaction else ()
-        for t, x in enumerate(uploaded(run.order(k), run.K)):
-            if report or res_out or rec_out:
-                source[k] = x  # (the picture on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
-            if filters:  # (the codec sees the filtered picture; source[k] stays the unfiltered one)
-                x = filters[k].step(x, t in intra)
-            if redaction:  # (after the filter, whose own state stays unredacted; source[k] stays the unredacted one)
-                x = redaction.step(k, run.global_index(k, t), x, t in intra)
-            yield base.down(x) if base else x
-
-    def on_recon(k, g, ref_frame):
-        if base:  # (everything below looks at the full-size picture; the DPB keeps the base one)
-            ref_frame = base.shown(k, g, ref_frame)
-        if res_out:
-            res_out.put(k, g, source[k][..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
-        if rec_out:
-            rec_out.put(k, g, source[k][..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
-        if report and layer:
-            sums = layer.X.region_sse(ref_frame[..., :h, :w], source[k][..., :h, :w], layer.boxes(g), layer.classes)
-            run.quality[k].add_yuv(g, ref_frame, source[k], (h, w), sums)
-        elif report:
-            run.quality[k].add(g, ref_frame, source[k], (h, w))
-        if recon_dir:
-            save_torch_image(ref_frame[..., :h, :w], os.path.join(recon_dir, f"im{str(g + 1).zfill(5)}.png"), savers)
-
-    failed = True
-    try:
-        with PNGWriters(io_workers) as savers:
-            run.encode(frames, q, on_recon if (recon_dir or report or res_out or rec_out) else None,
-                       (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None, aq)
-        failed = False
-    finally:
-        if pool is not None:
-            pool.shutdown(wait=True, cancel_futures=True)
-        if res_out:
-            res_out.close(failed)
-        if rec_out:
-            rec_out.close(failed)
-    extras = _roi_report_keys(h, w) if layer else None
-    extras = _enh_report_keys(rec_out, h, w, extras) if rec_out else extras
-    extras = _tnr_report_keys(tnr, filters, run, h, w, extras) if filters else extras
-    return run.results(report, _redact_report_keys(redact, redaction, run, h, w, extras) if redaction else extras)
+    options = locals()
+    frames_dir, recon_dir, max_frames = (options.pop(name) for name in ("frames_dir", "recon_dir", "max_frames"))
+    return _encode_sequence(_PngSource(frames_dir, device, io_workers, max_frames), _PngStage(recon_dir, io_workers), **options)
 
 
 def _decode_bins(nets, bin_dir, height, width, plan, emit, q_map=None, aq=None):
     """Decode im00001.bin ... of `bin_dir` (I pictures where `plan`, read_gop_plan's, has them) in order, handing every
     reconstruction to emit(t, ref_frame) while it is valid.  q_map(t): the q-scale map picture t was coded with (None: no
-    maps).  aq: _decode_aq's AqMaps (None: none).  Returns the picture count."""
+    maps).  aq: the aq.AqMaps of the folder's aq.json (None: none).  Returns the picture count."""
     i_net, p_net = nets
     i_net.update()
     p_net.update()
@@ -1123,10 +1224,59 @@ def _verify_args(verify, bin_dir, plan, height, width):
     return record, mode
 
 
-def _verifier(record, mode, plan, size, nets, check_pixels=True):
+def _decode_sequence(bin_dir, size, out, gop=None, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, roi=None,
+                     residuals=None, residual_bins=None, verify=None, base_scale="file", check=None):
+    """The one decode loop: the .bin files of `bin_dir`, pictures of the display `size` = (height, width), through the
+    verifier, the base layer's up-scaling and the ROI fusion into `out` (a _PngStage or a _VideoStage).  The options are
+    decode_folder's.  check(shown, coded, scaled): the caller's own refusals once the size of what is written is known.
+    Every refusal comes before any launch and before `out` is opened."""
+    from . import aq as A
     from . import picturehash as PH
+    from . import scale as SC
 
-    return PH.Verifier(record, mode, plan, size, nets[1].engine().precision, check_pixels) if mode != "off" else None
+    height, width = size
+    _roi_args(roi, residuals, residual_bins, decode=True)
+    plan, _ = read_gop_plan(bin_dir, gop)
+    roi_q = read_roiq(bin_dir, roi)
+    aq = A.read_aq(bin_dir)  # (host work only: its refusals come here, the maps are made once every refusal has had its turn)
+    record, verify = _verify_args(verify, bin_dir, plan, height, width)
+    dev = torch.device(device)
+    scaled, coded = _decode_scale(bin_dir, height, width, base_scale, roi, residuals, residual_bins)
+    shown = (height, width) if scaled else coded  # (the size of what is written)
+    if check:
+        check(shown, coded, scaled)
+    base = _BaseLayer(SC.Scale(scaled["full"], scaled["ratio"], dev)) if scaled else None
+    fuse_roi = _fuse_roi(roi, residuals, roi_q, residual_bins)
+    picture, close = _fused_emit(fuse_roi, residuals, plan, shown, dev, residual_bins)
+    try:
+        maps = _decode_maps(roi, roi_q, plan, (height, width), dev)
+        aq = A.AqMaps(aq, dev) if aq is not None else None
+        nets = _nets(dev, precision, i_ckpt, p_ckpt)
+        checker = PH.Verifier(record, verify, plan, shown, nets[1].engine().precision, shown == (height, width)) \
+            if verify != "off" else None
+        out.open(shown)
+
+        def emit(t, ref_frame):
+            full = base.shown(0, t, ref_frame) if base else None
+            if checker:
+                checker.add(t, ref_frame, display=full)
+            if full is not None:
+                ref_frame = full
+            # (without a ROI the padded reconstruction itself: the stage reads its top-left corner in place)
+            out.put(0, t, ref_frame if fuse_roi is None else picture(t, ref_frame))
+
+        failed = True
+        try:
+            n = _decode_bins(nets, bin_dir, coded[0], coded[1], plan, emit, maps, aq)
+            if checker:
+                checker.finish()
+            out.flush()
+            failed = False
+        finally:
+            out.close(failed)
+        return n
+    finally:
+        close()
 
 
 def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
@@ -1159,37 +1309,8 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", 
     rebuilt from the decoder's own reference picture (also in a base-only decode, from the base-size one).  Refused by
     name before any launch: an aq.json of an unknown version, with a value out of range, or whose tables this host builds
     differently (aq.read_aq)."""
-    _roi_args(roi, residuals, residual_bins, decode=True)
-    plan, _ = read_gop_plan(bin_dir, gop)
-    roi_q = read_roiq(bin_dir, roi)
-    aq = _read_aq(bin_dir)
-    record, verify = _verify_args(verify, bin_dir, plan, height, width)
-    dev = torch.device(device)
-    scaled, coded = _decode_scale(bin_dir, height, width, base_scale, roi, residuals, residual_bins)
-    shown = (height, width) if scaled else coded  # (the size of what is written)
-    os.makedirs(recon_dir, exist_ok=True)
-    base = _up_layer(scaled, dev)
-    picture, close = _fused_emit(_fuse_roi(roi, residuals, roi_q, residual_bins), residuals, plan, shown, dev, residual_bins)
-    try:
-        maps = _decode_maps(roi, roi_q, plan, (height, width), dev)
-        aq = _decode_aq(aq, dev)
-        nets = _nets(dev, precision, i_ckpt, p_ckpt)
-        checker = _verifier(record, verify, plan, shown, nets, check_pixels=shown == (height, width))
-
-        def emit(t, ref_frame):
-            full = base.shown(0, t, ref_frame) if base else None
-            if checker:
-                checker.add(t, ref_frame, display=full)
-            save_torch_image(picture(t, ref_frame if full is None else full), os.path.join(recon_dir, f"im{str(t + 1).zfill(5)}.png"),
-                             savers)
-
-        with PNGWriters(io_workers) as savers:
-            n = _decode_bins(nets, bin_dir, coded[0], coded[1], plan, emit, maps, aq)
-            if checker:
-                checker.finish()
-            return n
-    finally:
-        close()
+    return _decode_sequence(bin_dir, (height, width), _PngStage(recon_dir, io_workers), gop, device, precision, i_ckpt, p_ckpt, roi,
+                            residuals, residual_bins, verify, base_scale)
 
 
 # ------------------------------------------------------------------------------------------------- Y4M / raw YUV files
@@ -1200,8 +1321,6 @@ def write_sequence_info(bin_dir, width, height, frames, gop, fps, spec, containe
                         roi=None, residual_step=None):
     """What decode_video needs beside the .bin files (which stay what they are): size, frame count, GOP length, frame
     rate and colour description of the source, and the container it came in."""
-    import json
-
     info = {"width": int(width), "height": int(height), "frames": int(frames), "gop": int(gop),
             "fps": list(fps) if fps else None, "color": spec.to_json(), "container": container, "chroma": chroma,
             "interlace": interlace, "aspect": aspect}
@@ -1209,9 +1328,7 @@ def write_sequence_info(bin_dir, width, height, frames, gop, fps, spec, containe
         info["roi"] = roi.to_json()
     if residual_step is not None:  # the step of the coded residual layer (residual_bins=; every record carries it too)
         info["residual_step"] = int(residual_step)
-    with open(os.path.join(bin_dir, SEQUENCE_JSON), "w") as f:
-        json.dump(info, f, indent=2)
-    return info
+    return S.write_sidecar(bin_dir, SEQUENCE_JSON, info)
 
 
 def read_sequence_info(bin_dir):
@@ -1268,26 +1385,11 @@ class _VideoQualityLog(_QualityLog):
     two float32 lanes of the row; nothing computes on them)."""
 
     def add_yuv(self, g, recon, source, size, sums):
-        from . import metrics
+        self._add(g, recon, source, size, sums.view(torch.float32))
 
-        h, w = size
-        ms, _, sse = metrics.measure(recon[..., :h, :w], source[..., :h, :w], 1.0, clamp01=True)
-        self.cur.append(torch.cat([ms, sse, sums.view(torch.float32)]))
-        self.idx.append(g)
-        if self.plan.is_gop_end(g):
-            self.flush()
-
-    def collect(self, elements):
-        """{frame number: (psnr dB, ms-ssim, the integer sums as a tuple)}"""
-        import math
-
-        out = {}
-        for ev, host, _, idx in self.done:
-            ev.synchronize()
-            sums = host[:, 2:].contiguous().view(torch.int64).tolist()
-            for g, (ms, sse), s in zip(idx, host[:, :2].double().tolist(), sums):
-                out[g] = (10.0 * math.log10(elements / sse) if sse > 0 else float("inf"), ms, tuple(s))
-        return out
+    def _more(self, host):
+        """collect() gives {frame number: (psnr dB, ms-ssim, the integer sums as a tuple)}"""
+        return [(tuple(s),) for s in host[:, 2:].contiguous().view(torch.int64).tolist()]
 
 
 class _RoiLayer:
@@ -1484,12 +1586,10 @@ def _roi_args(roi, residuals, residual_bins=None, residual_step=1, decode=False)
             raise ValueError("residual_step= belongs to residual_bins= (the coded residual layer)")
 
 
-def _enh_report_keys(rec_out, h, w, inner=None):
+def _enh_report_keys(rec_out, h, w):
     """--report's keys of the enhancement layer, video_coder.calc_bitrate_metrics' three figures: the record's bits and bpp
     per picture, their average, and base + enhancement."""
     def keys(rd, types, values):
-        if inner:
-            inner(rd, types, values)
         bits = [8 * rec_out.sizes[g] for g in sorted(rec_out.sizes)]
         rd["frame_bits_enh"] = bits
         rd["frame_bpp_enh"] = [b / (h * w) for b in bits]
@@ -1518,18 +1618,22 @@ def _tnr_args(tnr):
             raise ValueError(f"tnr: expected a tnr.TNR, got {type(tnr).__name__}")
 
 
-def _tnr_report_keys(tnr, filters, run, h, w, inner=None):
+def _stream_totals(steps, run):
+    """{frame number: its totals} of the tnr.StreamFilters of the GOP streams.  The totals of each stream were copied to
+    the host GOP by GOP; this waits for those copies only."""
+    totals = {}
+    for k, f in enumerate(steps):
+        with torch.cuda.stream(run.cenc.streams[k]):
+            per = f.totals()  # (flushes a trailing partial GOP)
+        totals.update({run.global_index(k, t): v for t, v in enumerate(per)})
+    return totals
+
+
+def _tnr_report_keys(tnr, filters, run, h, w):
     """--report's keys of the temporal noise prefilter: the setting, and per picture the fraction of its pixels that were
-    blended and the mean absolute luma difference to the previous filtered picture, both 0.0 for an I picture.  The
-    totals of each stream were copied to the host GOP by GOP; this waits for those copies only."""
+    blended and the mean absolute luma difference to the previous filtered picture, both 0.0 for an I picture."""
     def keys(rd, types, values):
-        if inner:
-            inner(rd, types, values)
-        totals = {}
-        for k, f in enumerate(filters):
-            with torch.cuda.stream(run.cenc.streams[k]):
-                per = f.totals()  # (flushes a trailing partial GOP)
-            totals.update({run.global_index(k, t): v for t, v in enumerate(per)})
+        totals = _stream_totals(filters, run)
         order = sorted(totals)
         rd["tnr"] = tnr.to_json()
         rd["frame_tnr_held"] = [totals[g][0] / (h * w) for g in order]
@@ -1572,15 +1676,7 @@ def _redact_frames(redact, layer):
 def _write_redact(bin_dir, redact):
     """redact.json beside the .bin files of a redacted encode -- so that a receiver knows; decode ignores it.  Without
     redact= a stale file is removed."""
-    import json
-
-    path = os.path.join(bin_dir, REDACT_JSON)
-    if redact is None:
-        if os.path.exists(path):
-            os.remove(path)
-        return
-    with open(path, "w") as f:
-        json.dump(redact.to_json(), f, indent=2)
+    S.write_sidecar(bin_dir, REDACT_JSON, None if redact is None else redact.to_json())
 
 
 class _Redaction:
@@ -1599,16 +1695,10 @@ class _Redaction:
         return self.steps[k].step(x, self.layer.boxes(g))
 
 
-def _redact_report_keys(redact, redaction, run, h, w, inner=None):
+def _redact_report_keys(redact, redaction, run, h, w):
     """--report's keys of the redaction: the setting, and per picture the fraction of its pixels that were replaced."""
     def keys(rd, types, values):
-        if inner:
-            inner(rd, types, values)
-        totals = {}
-        for k, f in enumerate(redaction.steps):
-            with torch.cuda.stream(run.cenc.streams[k]):
-                per = f.totals()  # (flushes a trailing partial GOP)
-            totals.update({run.global_index(k, t): v for t, v in enumerate(per)})
+        totals = _stream_totals(redaction.steps, run)
         rd["redact"] = redact.to_json()
         rd["frame_redacted"] = [totals[g] / (h * w) for g in sorted(totals)]
 
@@ -1669,12 +1759,6 @@ def _fused_emit(roi, residuals, plan, size, dev, residual_bins=None):
     return picture, source.close
 
 
-def _open_source(video, size, bit_depth, fps):
-    from . import yuv as Y
-
-    return Y.open_video(video, size, bit_depth, fps) if isinstance(video, (str, os.PathLike)) else video
-
-
 def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantize8=False, gop=32, q=(1.0, 1.0, 1.0),
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
@@ -1706,111 +1790,11 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     against the file's own samples; sequence.json is the same with or without.
     redact: as encode_folder -- after the colour conversion and tnr (RGB only); redact.json lies beside sequence.json, which
     is the same with or without."""
-    from . import yuv as Y
-
-    _roi_args(roi, residuals, residual_bins, residual_step)
-    _roiq_args(roi, roi_q)
-    _aq_args(aq)
-    _tnr_args(tnr)
-    _redact_args(redact, roi, residuals, residual_bins)
-    bit_dir = _bitmap_args(bit_map, report)
-    reader = _open_source(video, size, bit_depth, fps)  # (every refusal about the file happens here, before any GPU work)
-    spec = spec or reader.spec()
-    if spec.bit_depth != reader.bit_depth:
-        raise ValueError(f"the file holds {reader.bit_depth}-bit samples, the colour description says {spec.bit_depth}")
-    h, w = reader.height, reader.width
-    rate = _rate_args(target_bpp, q_range, h, w, gop)
-    n_frames = reader.n_frames if max_frames is None else min(reader.n_frames, int(max_frames))
-    if n_frames < 1:
-        raise ValueError(f"{getattr(reader, 'path', video)}: no frames")
-    dev = torch.device(device)
-    base = _base_args(base_scale, roi, roi_q, bit_map, (h, w), dev)
-
-    def converted(order):
-        return _video_pictures(reader, order, spec, quantize8, dev)
-
-    plan = _scene_plan(n_frames, (h, w), gop, scenecut, min_gop, dev, lambda: (x for x, _ in converted(range(n_frames))))
-    layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
-    held = _redact_frames(redact, layer)
-    run = _EncodeRun(bin_dir, plan, base.size if base else (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets,
-                     gop_streams, _VideoQualityLog if report else None, _bit_log(bit_map, bit_dir, layer, roi_q), rate,
-                     picture_hash, base)
-    write_gop_plan(bin_dir, plan, gop, scenecut, min_gop)
-    write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
-    _write_scale(bin_dir, base)
-    _write_aq(bin_dir, aq)
-    res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
-    rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
-    filters = _tnr_filters(tnr, run, (h, w), report)
-    _write_redact(bin_dir, redact)
-    redaction = _Redaction(redact, layer, held, run, report) if redact is not None else None
-    source = {}
-    container = "y4m" if isinstance(reader, Y.Y4MReader) else "yuv"
-    extras = dict(chroma=getattr(reader, "chroma", None), interlace=getattr(reader, "interlace", None),
-                  aspect=getattr(reader, "aspect", None))
-    writer = Y.create_video(recon_video, w, h, spec, reader.fps, **extras) if recon_video else None
-    outs = [_VideoOut(writer) for _ in range(run.K)] if writer else None
-
-    def frames(k):
-        intra = run.intra(k) if filters or redaction else ()
-        for t, (x, samples) in enumerate(converted(run.order(k))):
-            source[k] = (x, samples)  # (what on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
-            if filters:  # (the codec sees the filtered picture; source[k] stays the unfiltered one)
-                x = filters[k].step(x, t in intra)
-            if redaction:  # (after the filter, whose own state stays unredacted; source[k] stays the unredacted one)
-                x = redaction.step(k, run.global_index(k, t), x, t in intra)
-            yield base.down(x) if base else x
-
-    def on_recon(k, g, ref_frame):
-        x, samples = source[k]
-        if base:  # (everything below looks at the full-size picture; the DPB keeps the base one)
-            ref_frame = base.shown(k, g, ref_frame)
-        if res_out:
-            res_out.put(k, g, x[..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
-        if rec_out:
-            rec_out.put(k, g, x[..., :h, :w], ref_frame[..., :h, :w], layer.boxes(g))
-        if report:
-            out, sums = Y.rgb_to_yuv420(ref_frame, h, w, spec, source=samples)
-            if layer:
-                sums = torch.cat([sums, layer.X.region_sse(ref_frame[..., :h, :w], x[..., :h, :w], layer.boxes(g), layer.classes)])
-            run.quality[k].add_yuv(g, ref_frame, x, (h, w), sums)
-        elif outs:
-            out = Y.rgb_to_yuv420(ref_frame, h, w, spec)
-        if outs:
-            outs[k].put(g, out)
-
-    failed = True
-    try:
-        run.encode(frames, q, on_recon if (outs or report or res_out or rec_out) else None,
-                   (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None, aq)
-        for o in outs or []:
-            o.close()
-        failed = False
-    finally:
-        if writer:
-            writer.close()
-        if reader is not video:
-            reader.close()
-        if res_out:
-            res_out.close(failed)
-        if rec_out:
-            rec_out.close(failed)
-    write_sequence_info(bin_dir, w, h, n_frames, gop, reader.fps, spec, container, **extras,
-                        roi=layer.roi if layer else None, residual_step=residual_step if rec_out else None)
-
-    def yuv_keys(rd, types, values):
-        per = [Y.psnr_yuv(v[2][:3], h, w, spec.bit_depth) for v in values]
-        if layer:
-            _roi_report_keys(h, w)(rd, types, values)
-        for n, name in enumerate(("y", "u", "v", "yuv")):
-            rd[f"frame_psnr_{name}"] = [p[n] for p in per]
-        for name, keep in (("i", lambda k: k == 0), ("p", lambda k: k != 0), ("all", lambda k: True)):
-            sel = [p[3] for p, k in zip(per, types) if keep(k)]
-            rd[f"ave_{name}_frame_psnr_yuv"] = sum(sel) / len(sel) if sel else 0
-
-    keys = _enh_report_keys(rec_out, h, w, yuv_keys) if rec_out else yuv_keys
-    keys = _tnr_report_keys(tnr, filters, run, h, w, keys) if filters else keys
-    return run.results(report, _redact_report_keys(redact, redaction, run, h, w, keys) if redaction else keys)
+    options = locals()
+    video, recon_video = options.pop("video"), options.pop("recon_video")
+    source = _VideoSource(video, device, **{name: options.pop(name) for name in ("size", "spec", "quantize8", "bit_depth", "fps",
+                                                                                 "max_frames")})
+    return _encode_sequence(source, _VideoStage(recon_video), **options)
 
 
 def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=None, fps=None, device="cuda:0",
@@ -1826,59 +1810,22 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     An aq.json beside the .bin files is followed as decode_folder does."""
     from . import yuv as Y
 
-    _roi_args(roi, residuals, residual_bins, decode=True)
     info = read_sequence_info(bin_dir) or {}
     height, width = height or info.get("height"), width or info.get("width")
     if not height or not width:
         raise ValueError(f"no {SEQUENCE_JSON} in {bin_dir}: height and width are required")
-    plan, _ = read_gop_plan(bin_dir, gop or info.get("gop"))  # (gops.json, when encode left one, says where the I pictures are)
-    spec = spec or info.get("color") or Y.ColorSpec()
-    scaled, coded = _decode_scale(bin_dir, height, width, base_scale, roi, residuals, residual_bins)
-    shown_h, shown_w = (height, width) if scaled else coded  # (the size of what is written)
-    Y.check_size(shown_h, shown_w)
-    first = os.path.join(bin_dir, "im00001.bin")
-    if not scaled and os.path.exists(first) and S.decode_i(first)[:2] != coded:  # (with a scale.json: _decode_scale's check)
-        raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {coded}")
-    roi_q = read_roiq(bin_dir, roi)
-    aq = _read_aq(bin_dir)
-    record, verify = _verify_args(verify, bin_dir, plan, height, width)
-    fuse_roi = _fuse_roi(roi, residuals, roi_q, residual_bins)
-    base = _up_layer(scaled, torch.device(device))
-    picture, close = _fused_emit(fuse_roi, residuals, plan, (shown_h, shown_w), torch.device(device), residual_bins)
-    try:
-        maps = _decode_maps(roi, roi_q, plan, (height, width), torch.device(device))
-        aq = _decode_aq(aq, torch.device(device))
-        nets = _nets(torch.device(device), precision, i_ckpt, p_ckpt)
-        writer = Y.create_video(recon_video, shown_w, shown_h, spec, fps or info.get("fps"), chroma=info.get("chroma"),
-                                interlace=info.get("interlace"), aspect=info.get("aspect"))
-        try:
-            out = _VideoOut(writer)
-            checker = _verifier(record, verify, plan, (shown_h, shown_w), nets, check_pixels=(shown_h, shown_w) == (height, width))
 
-            def emit(t, ref_frame):
-                full = base.shown(0, t, ref_frame) if base else None
-                if checker:
-                    checker.add(t, ref_frame, display=full)
-                if full is not None:
-                    ref_frame = full
-                # (without a ROI the padded reconstruction itself: rgb_to_yuv420 reads its top-left corner in place)
-                out.put(t, Y.rgb_to_yuv420(ref_frame if fuse_roi is None else picture(t, ref_frame), shown_h, shown_w, spec))
+    def check(shown, coded, scaled):
+        Y.check_size(*shown)
+        first = os.path.join(bin_dir, "im00001.bin")
+        if not scaled and os.path.exists(first) and S.decode_i(first)[:2] != coded:  # (with a scale.json: _decode_scale's check)
+            raise ValueError(f"the pictures in {bin_dir} are {S.decode_i(first)[:2]}, not {coded}")
 
-            t = _decode_bins(nets, bin_dir, coded[0], coded[1], plan, emit, maps, aq)
-            if checker:
-                checker.finish()
-            out.close()
-        finally:
-            writer.close()
-    finally:
-        close()
-    return t
-
-
-def _has_motion(root):
-    from .roi import PickleBoxes
-
-    return PickleBoxes.has_motion(root)
+    stage = _VideoStage(recon_video, spec or info.get("color") or Y.ColorSpec(), fps or info.get("fps"), chroma=info.get("chroma"),
+                        interlace=info.get("interlace"), aspect=info.get("aspect"))
+    # (gops.json, when encode left one, says where the I pictures are)
+    return _decode_sequence(bin_dir, (height, width), stage, gop or info.get("gop"), device, precision, i_ckpt, p_ckpt, roi, residuals,
+                            residual_bins, verify, base_scale, check)
 
 
 def _video_args(ap, a):
@@ -1897,56 +1844,37 @@ def _video_args(ap, a):
         ap.error(str(ex))
 
 
+def _motion_boxes(source, root, params):
+    """The motion scan of motion_boxes_folder / motion_boxes_video over a source, which is closed on every exit."""
+    from . import motionroi as M
+
+    try:
+        source.open()
+        n, (h, w) = source.n_frames, source.size
+        boxes = M.scan((x for x, _ in source.pictures(range(n))), n, (h, w), source.dev, params)
+    finally:
+        source.close()
+    M.write_boxes(root, boxes, params, h, w)
+    return boxes
+
+
 def motion_boxes_folder(frames_dir, root, params, device="cuda:0", io_workers=8, max_frames=None):
     """run_codec boxes --frames: the motion boxes (vcm_ts_amd/motionroi.py) of a PNG folder, written to `root` as
     motion_coords/%05d and motion.json -- then a roi.PickleBoxes root.  A pass of its own over the source, for the reason
     the scene-cut scan is one: the background model is a recursion over the whole sequence, while GOP streams and GOP
     sharding code GOPs independently.  The pictures come through the reader and conversion of encode_folder's coding
     pass.  Returns the list of (n, 4) box arrays."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    from PIL import Image
-
-    from . import motionroi as M
-
-    reader = PNGReader(frames_dir)
-    n_frames = 0
-    while os.path.exists(reader.path_of(n_frames + 1)) and (max_frames is None or n_frames < max_frames):
-        n_frames += 1
-    with Image.open(reader.path_of(1)) as first:  # (the header only)
-        w, h = first.size
-    dev = torch.device(device)
-    pool = ThreadPoolExecutor(max_workers=io_workers) if io_workers > 0 else None
-    try:
-        boxes = M.scan(_png_pictures(reader, range(n_frames), (h, w), dev, pool, io_workers, 1), n_frames, (h, w), dev, params)
-    finally:
-        if pool is not None:
-            pool.shutdown(wait=True, cancel_futures=True)
-    M.write_boxes(root, boxes, params, h, w)
-    return boxes
+    return _motion_boxes(_PngSource(frames_dir, device, io_workers, max_frames), root, params)
 
 
 def motion_boxes_video(video, root, params, device="cuda:0", size=None, spec=None, quantize8=False, bit_depth=8, fps=None,
                        max_frames=None):
     """motion_boxes_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height): the pictures come
     through the ring, copy and colour conversion (spec, quantize8) of encode_video's coding pass."""
-    from . import motionroi as M
-
-    reader = _open_source(video, size, bit_depth, fps)
-    spec = spec or reader.spec()
-    if spec.bit_depth != reader.bit_depth:
-        raise ValueError(f"the file holds {reader.bit_depth}-bit samples, the colour description says {spec.bit_depth}")
-    h, w = reader.height, reader.width
-    n_frames = reader.n_frames if max_frames is None else min(reader.n_frames, int(max_frames))
-    if n_frames < 1:
-        raise ValueError(f"{getattr(reader, 'path', video)}: no frames")
-    dev = torch.device(device)
-    boxes = M.scan((x for x, _ in _video_pictures(reader, range(n_frames), spec, quantize8, dev)), n_frames, (h, w), dev, params)
-    M.write_boxes(root, boxes, params, h, w)
-    return boxes
+    return _motion_boxes(_VideoSource(video, device, size, spec, quantize8, bit_depth, fps, max_frames), root, params)
 
 
-def main(argv=None):
+def _parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
     e = sub.add_parser("encode")
@@ -2134,234 +2062,256 @@ def main(argv=None):
         p.add_argument("--precision", default=None, choices=["fp32", "fp16x3"])
         p.add_argument("--i-ckpt")
         p.add_argument("--p-ckpt")
-    a = ap.parse_args(argv)
-    if a.cmd == "verify":
-        from . import picturehash as PH
+    return ap
 
-        try:
-            first = PH.verify_pngs(a.bins, a.recon)
-        except ValueError as ex:
-            ap.error(str(ex))
-        if first is not None:
-            t, name, want, got = first
-            print(f"picture {t} ({name}): the pixels digest is {got:08x}, {PH.HASHES_JSON} says {want:08x}")
-            raise SystemExit(1)
-        print(f"{len(PH.read_hashes(a.bins)['pixels'])} pictures verified")
-        return
-    if a.cmd == "boxes":
-        from . import motionroi as M
 
-        if (a.frames is None) == (a.video is None):
-            ap.error("give exactly one of --frames and --video")
-        if a.video is None and (a.size or a.quantize8 or a.matrix or a.range or a.siting):
-            ap.error("--size, --quantize8, --matrix, --range and --siting belong to --video")
-        given = {k: v for k, v in (("learn", None if a.learn is None else tuple(a.learn)), ("min_pixels", a.min_pixels),
-                                   ("grow", a.grow), ("min_cells", a.min_cells), ("max_boxes", a.max_boxes)) if v is not None}
-        try:
-            params = M.MotionParams(a.threshold, **given)
-        except ValueError as ex:
-            ap.error(f"boxes: {ex}")
-        try:
-            if a.video is not None:
-                size, fps = _video_args(ap, a)
-                reader = _open_source(a.video, size, a.bit_depth, fps)
-                with reader:
-                    boxes = motion_boxes_video(reader, a.out, params, a.device, quantize8=a.quantize8,
-                                               spec=reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting))
-            else:
-                boxes = motion_boxes_folder(a.frames, a.out, params, a.device, io_workers=a.io_workers)
-        except (ValueError, OSError) as ex:
-            ap.error(f"boxes: {ex}")
-        print(f"{len(boxes)} pictures, {sum(len(x) for x in boxes)} boxes -> {os.path.join(a.out, M.COORDS)}")
-        return
-    roi = roi_q = aq = tnr = redact = None
-    motion = a.roi_root is not None and _has_motion(a.roi_root)
+def _verify_command(ap, a):
+    from . import picturehash as PH
+
+    try:
+        first = PH.verify_pngs(a.bins, a.recon)
+    except ValueError as ex:
+        ap.error(str(ex))
+    if first is not None:
+        t, name, want, got = first
+        print(f"picture {t} ({name}): the pixels digest is {got:08x}, {PH.HASHES_JSON} says {want:08x}")
+        raise SystemExit(1)
+    print(f"{len(PH.read_hashes(a.bins)['pixels'])} pictures verified")
+
+
+def _boxes_command(ap, a):
+    from . import motionroi as M
+    from . import yuv as Y
+
+    if (a.frames is None) == (a.video is None):
+        ap.error("give exactly one of --frames and --video")
+    if a.video is None and (a.size or a.quantize8 or a.matrix or a.range or a.siting):
+        ap.error("--size, --quantize8, --matrix, --range and --siting belong to --video")
+    given = {k: v for k, v in (("learn", None if a.learn is None else tuple(a.learn)), ("min_pixels", a.min_pixels),
+                               ("grow", a.grow), ("min_cells", a.min_cells), ("max_boxes", a.max_boxes)) if v is not None}
+    try:
+        params = M.MotionParams(a.threshold, **given)
+    except ValueError as ex:
+        ap.error(f"boxes: {ex}")
+    try:
+        if a.video is not None:
+            size, fps = _video_args(ap, a)
+            with Y.open_video(a.video, size, a.bit_depth, fps) as reader:
+                boxes = motion_boxes_video(reader, a.out, params, a.device, quantize8=a.quantize8,
+                                           spec=reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting))
+        else:
+            boxes = motion_boxes_folder(a.frames, a.out, params, a.device, io_workers=a.io_workers)
+    except (ValueError, OSError) as ex:
+        ap.error(f"boxes: {ex}")
+    print(f"{len(boxes)} pictures, {sum(len(x) for x in boxes)} boxes -> {os.path.join(a.out, M.COORDS)}")
+
+
+def _motion_option(ap, a):
+    """Whether --roi-root holds motion boxes; --motion-border and --motion-q are refused without them."""
+    from .roi import PickleBoxes
+
+    motion = a.roi_root is not None and PickleBoxes.has_motion(a.roi_root)
     if not motion and (a.motion_border is not None or getattr(a, "motion_q", None) is not None):
         ap.error("--motion-border and --motion-q need a --roi-root that holds motion_coords (run_codec boxes writes one)")
-    if a.cmd == "encode":
-        if a.aq_clamp is not None and a.aq_strength is None:
-            ap.error("--aq-clamp belongs to --aq-strength")
-        if a.aq_strength is not None:
-            from . import aq as A
+    return motion
 
-            try:
-                aq = A.AQ(a.aq_strength, *(a.aq_clamp or (A.MIN_Q, A.MAX_Q)))
-            except ValueError as ex:
-                ap.error(f"--aq-strength / --aq-clamp: {ex}")
-        if a.tnr is None and (a.tnr_floor is not None or a.tnr_pixel is not None):
-            ap.error("--tnr-floor and --tnr-pixel belong to --tnr")
-        if a.tnr is not None:
-            from . import tnr as N
 
-            try:
-                tnr = N.TNR(a.tnr, **({} if a.tnr_floor is None else {"floor": a.tnr_floor}), pixel=a.tnr_pixel)
-            except ValueError as ex:
-                ap.error(f"--tnr / --tnr-floor / --tnr-pixel: {ex}")
-    factors = [getattr(a, n, None) for n in ("plate_q", "face_q", "background_q")] + ([a.motion_q] if motion and a.cmd == "encode" else [])
-    if a.cmd == "encode" and a.base_scale is not None:
+def _needs_roi_root(ap, a):
+    if a.roi_root is None and (a.residuals or a.residual_bins or a.plate_border is not None or a.face_border is not None):
+        ap.error("--residuals, --residual-bins, --plate-border and --face-border belong to --roi-root")
+
+
+def _roi_option(ap, a, motion, recorded):
+    """The roi.Roi of --roi-root (None without); recorded: {class name: border} where an option does not say."""
+    if a.roi_root is None:
+        return None
+    from . import roi as X
+
+    borders = [given if given is not None else recorded.get(name, 0)
+               for given, name in ((a.plate_border, "liplates"), (a.face_border, "faces")) +
+               (((a.motion_border, "motion"),) if motion else ())]
+    try:
+        classes = tuple(X.RoiClass(b) for b in borders)
+        return X.Roi(X.PickleBoxes(a.roi_root, classes), classes)
+    except (ValueError, OSError) as ex:
+        ap.error(str(ex))
+
+
+def _encode_command(ap, a):
+    roi_q = aq = tnr = redact = None
+    motion = _motion_option(ap, a)
+    if a.aq_clamp is not None and a.aq_strength is None:
+        ap.error("--aq-clamp belongs to --aq-strength")
+    if a.aq_strength is not None:
+        from . import aq as A
+
+        try:
+            aq = A.AQ(a.aq_strength, *(a.aq_clamp or (A.MIN_Q, A.MAX_Q)))
+        except ValueError as ex:
+            ap.error(f"--aq-strength / --aq-clamp: {ex}")
+    if a.tnr is None and (a.tnr_floor is not None or a.tnr_pixel is not None):
+        ap.error("--tnr-floor and --tnr-pixel belong to --tnr")
+    if a.tnr is not None:
+        from . import tnr as N
+
+        try:
+            tnr = N.TNR(a.tnr, **({} if a.tnr_floor is None else {"floor": a.tnr_floor}), pixel=a.tnr_pixel)
+        except ValueError as ex:
+            ap.error(f"--tnr / --tnr-floor / --tnr-pixel: {ex}")
+    factors = [a.plate_q, a.face_q, a.background_q] + ([a.motion_q] if motion else [])
+    if a.base_scale is not None:
         from . import scale as SC
 
         try:
             a.base_scale = SC.as_ratio(a.base_scale)
         except ValueError as ex:
             ap.error(f"--base-scale: {ex}")
-    if a.cmd == "decode" and a.base_only and a.roi_root is not None:
-        ap.error("--base-only takes no --roi-root: boxes and the residual layer live at full size")
-    if a.cmd == "encode":
-        if a.roi_root is None and (any(f is not None for f in factors) or a.roi_q_grow is not None):
-            ap.error("--plate-q, --face-q, --background-q and --roi-q-grow belong to --roi-root")
-        if a.roi_q_grow is not None and all(f is None for f in factors):
-            ap.error("--roi-q-grow belongs to --plate-q, --face-q or --background-q")
-        if any(f is not None for f in factors):
-            from . import roi as X
-
-            try:
-                plate, face, ground, *moving = (100 if f is None else X.RoiQ.hundredths(f, n) for f, n in
-                                                zip(factors, ("--plate-q", "--face-q", "--background-q", "--motion-q")))
-                roi_q = X.RoiQ(ground, (plate, face, *moving), 0 if a.roi_q_grow is None else a.roi_q_grow)
-            except ValueError as ex:
-                ap.error(f"ROI-weighted quantisation: {ex}")
-    elif a.roi_root is None and os.path.exists(os.path.join(a.bins, ROIQ_JSON)):
-        ap.error(f"{os.path.join(a.bins, ROIQ_JSON)}: these pictures were coded with q-scale maps made from ROI boxes; "
-                 f"decode needs --roi-root")
-    if a.roi_root is None and (a.residuals or a.residual_bins or a.plate_border is not None or a.face_border is not None):
-        ap.error("--residuals, --residual-bins, --plate-border and --face-border belong to --roi-root")
-    if a.cmd == "encode":
-        if a.residual_step is not None and not a.residual_bins:
-            ap.error("--residual-step belongs to --residual-bins")
-        a.residual_step = 1 if a.residual_step is None else a.residual_step
-        if not 1 <= a.residual_step <= 64:
-            ap.error("--residual-step must be within 1..64")
-    elif a.residuals and a.residual_bins:
-        ap.error("give one of --residuals and --residual-bins")
-    if a.roi_root is not None:
+    if a.roi_root is None and (any(f is not None for f in factors) or a.roi_q_grow is not None):
+        ap.error("--plate-q, --face-q, --background-q and --roi-q-grow belong to --roi-root")
+    if a.roi_q_grow is not None and all(f is None for f in factors):
+        ap.error("--roi-q-grow belongs to --plate-q, --face-q or --background-q")
+    if any(f is not None for f in factors):
         from . import roi as X
 
-        if a.cmd == "decode" and not a.residuals and not a.residual_bins and not os.path.exists(os.path.join(a.bins, ROIQ_JSON)):
-            ap.error("decode --roi-root needs --residuals (the decoded residual layer) or --residual-bins (the coded one)")
-        recorded = {c["name"]: c["border"] for c in ((read_sequence_info(a.bins) or {}).get("roi") or {}).get("classes", [])} \
-            if a.cmd == "decode" else {}
-        borders = [given if given is not None else recorded.get(name, 0)
-                   for given, name in ((a.plate_border, "liplates"), (a.face_border, "faces")) +
-                   (((a.motion_border, "motion"),) if motion else ())]
         try:
-            classes = tuple(X.RoiClass(b) for b in borders)
-            roi = X.Roi(X.PickleBoxes(a.roi_root, classes), classes)
-        except (ValueError, OSError) as ex:
-            ap.error(str(ex))
-    if a.cmd == "encode":
-        if a.redact is None and (a.redact_tile is not None or a.redact_fill is not None or a.redact_grow is not None or
-                                 a.redact_hold is not None or a.redact_restorable):
-            ap.error("--redact-tile, --redact-fill, --redact-grow, --redact-hold and --redact-restorable belong to --redact")
-        if a.redact is not None:
-            from . import redact as RD
-
-            if roi is None:
-                ap.error("--redact needs --roi-root (the boxes to redact)")
-            try:
-                redact = RD.Redact(tuple(a.redact), a.redact_tile, a.redact_fill, a.redact_grow or 0, a.redact_hold or 0,
-                                   a.redact_restorable)
-                _redact_args(redact, roi, a.residuals, a.residual_bins)
-            except ValueError as ex:
-                ap.error(f"--redact: {ex}")
-        if (a.frames is None) == (a.video is None):
-            ap.error("give exactly one of --frames and --video")
-        if a.bit_map is True and not a.report:
-            ap.error("--bit-map needs --report (where the regional bit counts go) or a DIR for the per-cell maps")
-        if a.video is None and (a.recon_video or a.size or a.quantize8 or a.matrix or a.range or a.siting):
-            ap.error("--recon-video, --size, --quantize8, --matrix, --range and --siting belong to --video")
-        if a.video is not None and a.recon:
-            ap.error("--recon (a PNG folder) belongs to --frames; use --recon-video with --video")
-        size = fps = None
-        if a.video is not None:
-            from . import yuv as Y
-
-            size, fps = _video_args(ap, a)
-        a.gop = a.gop or 32
-        if a.min_gop is not None and a.scenecut is None:
-            ap.error("--min-gop belongs to --scenecut")
-        a.min_gop = 1 if a.min_gop is None else a.min_gop
-        try:
-            from .scenecut import check_options
-
-            check_options(a.gop, a.scenecut, a.min_gop)
+            plate, face, ground, *moving = (100 if f is None else X.RoiQ.hundredths(f, n) for f, n in
+                                            zip(factors, ("--plate-q", "--face-q", "--background-q", "--motion-q")))
+            roi_q = X.RoiQ(ground, (plate, face, *moving), 0 if a.roi_q_grow is None else a.roi_q_grow)
         except ValueError as ex:
-            ap.error(str(ex))
-        if (a.rate_count is None) != (a.quality is None) or (a.q is not None and a.rate_count is not None):
-            ap.error("give either --q, or --rate-count together with --quality")
-        if a.q_range is not None and a.target_bpp is None:
-            ap.error("--q-range belongs to --target-bpp")
-        if a.target_bpp is not None:
-            if a.rate_count is not None and a.rate_count > 1:
-                ap.error("--target-bpp controls one rate point; --rate-count selects several (give --q as the starting point)")
-            try:
-                _rate_args(a.target_bpp, a.q_range, 1, 1, a.gop)
-            except ValueError as ex:
-                ap.error(f"--target-bpp / --q-range: {ex}")
-        q = tuple(a.q) if a.q is not None else (1.0, 1.0, 1.0)
-        if a.rate_count is not None:
-            from .dmc import DMC
-            from .intra import IntraNoAR
-            from .params import dmc_spec, intra_spec, seeded_state_dict
+            ap.error(f"ROI-weighted quantisation: {ex}")
+    _needs_roi_root(ap, a)
+    if a.residual_step is not None and not a.residual_bins:
+        ap.error("--residual-step belongs to --residual-bins")
+    a.residual_step = 1 if a.residual_step is None else a.residual_step
+    if not 1 <= a.residual_step <= 64:
+        ap.error("--residual-step must be within 1..64")
+    roi = _roi_option(ap, a, motion, {})
+    if a.redact is None and (a.redact_tile is not None or a.redact_fill is not None or a.redact_grow is not None or
+                             a.redact_hold is not None or a.redact_restorable):
+        ap.error("--redact-tile, --redact-fill, --redact-grow, --redact-hold and --redact-restorable belong to --redact")
+    if a.redact is not None:
+        from . import redact as RD
 
-            if a.i_ckpt and a.p_ckpt:
-                i_qs = IntraNoAR.get_q_scales_from_ckpt(a.i_ckpt)
-                y_qs, mv_qs = DMC.get_q_scales_from_ckpt(a.p_ckpt)
-            else:  # no checkpoint: the anchors of the name-seeded synthetic weights the nets are built with
-                i_qs = seeded_state_dict(intra_spec())["q_scale"].reshape(-1)
-                sd = seeded_state_dict(dmc_spec())
-                y_qs, mv_qs = sd["y_q_scale"].reshape(-1), sd["mv_y_q_scale"].reshape(-1)
-            q = rate_point_q_scales(i_qs, y_qs, mv_qs, a.rate_count, a.quality)
-            print(f"rate point {a.quality} of {a.rate_count}: q_i {q[0]:.4f}  q_mv_y {q[1]:.4f}  q_y {q[2]:.4f}")
-        if a.video is not None:
-            reader = Y.open_video(a.video, size, a.bit_depth, fps)
+        if roi is None:
+            ap.error("--redact needs --roi-root (the boxes to redact)")
+        try:
+            redact = RD.Redact(tuple(a.redact), a.redact_tile, a.redact_fill, a.redact_grow or 0, a.redact_hold or 0,
+                               a.redact_restorable)
+            _redact_args(redact, roi, a.residuals, a.residual_bins)
+        except ValueError as ex:
+            ap.error(f"--redact: {ex}")
+    if (a.frames is None) == (a.video is None):
+        ap.error("give exactly one of --frames and --video")
+    if a.bit_map is True and not a.report:
+        ap.error("--bit-map needs --report (where the regional bit counts go) or a DIR for the per-cell maps")
+    if a.video is None and (a.recon_video or a.size or a.quantize8 or a.matrix or a.range or a.siting):
+        ap.error("--recon-video, --size, --quantize8, --matrix, --range and --siting belong to --video")
+    if a.video is not None and a.recon:
+        ap.error("--recon (a PNG folder) belongs to --frames; use --recon-video with --video")
+    size = fps = None
+    if a.video is not None:
+        from . import yuv as Y
+
+        size, fps = _video_args(ap, a)
+    a.gop = a.gop or 32
+    if a.min_gop is not None and a.scenecut is None:
+        ap.error("--min-gop belongs to --scenecut")
+    a.min_gop = 1 if a.min_gop is None else a.min_gop
+    try:
+        from .scenecut import check_options
+
+        check_options(a.gop, a.scenecut, a.min_gop)
+    except ValueError as ex:
+        ap.error(str(ex))
+    if (a.rate_count is None) != (a.quality is None) or (a.q is not None and a.rate_count is not None):
+        ap.error("give either --q, or --rate-count together with --quality")
+    if a.q_range is not None and a.target_bpp is None:
+        ap.error("--q-range belongs to --target-bpp")
+    if a.target_bpp is not None:
+        if a.rate_count is not None and a.rate_count > 1:
+            ap.error("--target-bpp controls one rate point; --rate-count selects several (give --q as the starting point)")
+        try:
+            _rate_args(a.target_bpp, a.q_range, 1, 1, a.gop)
+        except ValueError as ex:
+            ap.error(f"--target-bpp / --q-range: {ex}")
+    q = tuple(a.q) if a.q is not None else (1.0, 1.0, 1.0)
+    if a.rate_count is not None:
+        from .dmc import DMC
+        from .intra import IntraNoAR
+        from .params import dmc_spec, intra_spec, seeded_state_dict
+
+        if a.i_ckpt and a.p_ckpt:
+            i_qs = IntraNoAR.get_q_scales_from_ckpt(a.i_ckpt)
+            y_qs, mv_qs = DMC.get_q_scales_from_ckpt(a.p_ckpt)
+        else:  # no checkpoint: the anchors of the name-seeded synthetic weights the nets are built with
+            i_qs = seeded_state_dict(intra_spec())["q_scale"].reshape(-1)
+            sd = seeded_state_dict(dmc_spec())
+            y_qs, mv_qs = sd["y_q_scale"].reshape(-1), sd["mv_y_q_scale"].reshape(-1)
+        q = rate_point_q_scales(i_qs, y_qs, mv_qs, a.rate_count, a.quality)
+        print(f"rate point {a.quality} of {a.rate_count}: q_i {q[0]:.4f}  q_mv_y {q[1]:.4f}  q_y {q[2]:.4f}")
+    options = dict(gop=a.gop, q=q, device=a.device, precision=a.precision, i_ckpt=a.i_ckpt, p_ckpt=a.p_ckpt, coder=a.coder,
+                   io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report, roi=roi, residuals=a.residuals,
+                   scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q, bit_map=a.bit_map, target_bpp=a.target_bpp,
+                   q_range=a.q_range, residual_bins=a.residual_bins, residual_step=a.residual_step, picture_hash=a.picture_hash,
+                   base_scale=a.base_scale, aq=aq, tnr=tnr, redact=redact)
+    if a.video is not None:
+        with Y.open_video(a.video, size, a.bit_depth, fps) as reader:
             spec = reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting)
-            with reader:
-                bits, size, *rd = encode_video(reader, a.bins, a.recon_video, spec=spec, quantize8=a.quantize8, gop=a.gop, q=q,
-                                               device=a.device, precision=a.precision, i_ckpt=a.i_ckpt, p_ckpt=a.p_ckpt,
-                                               coder=a.coder, gop_streams=a.gop_streams, report=a.report, roi=roi,
-                                               residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
-                                               bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
-                                               residual_bins=a.residual_bins, residual_step=a.residual_step,
-                                               picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq, tnr=tnr, redact=redact)
-        else:
-            bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, a.gop, q, a.device, a.precision, a.i_ckpt, a.p_ckpt,
-                                            coder=a.coder, io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report,
-                                            roi=roi, residuals=a.residuals, scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q,
-                                            bit_map=a.bit_map, target_bpp=a.target_bpp, q_range=a.q_range,
-                                            residual_bins=a.residual_bins, residual_step=a.residual_step,
-                                            picture_hash=a.picture_hash, base_scale=a.base_scale, aq=aq, tnr=tnr, redact=redact)
-        if rd:
-            yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
-            print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
-        print(f"{len(bits)} pictures, {size[0]}x{size[1]}, {sum(bits)} bits, {sum(bits) / (len(bits) * size[0] * size[1]):.4f} bpp")
+            bits, size, *rd = encode_video(reader, a.bins, a.recon_video, spec=spec, quantize8=a.quantize8, **options)
     else:
-        if (a.recon is None) == (a.recon_video is None):
-            ap.error("give exactly one of --recon and --recon-video")
-        info = read_sequence_info(a.bins)
-        if info is None and (a.height is None or a.width is None):
-            ap.error(f"--height and --width are required (no {SEQUENCE_JSON} beside the .bin files)")
-        if a.recon_video is not None:
-            from . import yuv as Y
+        bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, **options)
+    if rd:
+        yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
+        print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
+    print(f"{len(bits)} pictures, {size[0]}x{size[1]}, {sum(bits)} bits, {sum(bits) / (len(bits) * size[0] * size[1]):.4f} bpp")
 
-            if os.path.splitext(a.recon_video)[1].lower() not in (".y4m", ".yuv"):
-                ap.error("--recon-video takes a .y4m or a .yuv file")
-            spec = None
-            if a.matrix or a.range or a.siting or a.bit_depth:
-                base = info["color"] if info else Y.ColorSpec()
-                spec = Y.ColorSpec(a.matrix or base.matrix, base.full_range if a.range is None else a.range == "full",
-                                   a.siting or base.siting, a.bit_depth or base.bit_depth)
-            n = decode_video(a.bins, a.recon_video, a.height, a.width, a.gop, spec, None, a.device, a.precision, a.i_ckpt, a.p_ckpt,
-                             roi=roi, residuals=a.residuals, residual_bins=a.residual_bins, verify=a.verify,
-                             base_scale=None if a.base_only else "file")
-        else:
-            if a.matrix or a.range or a.siting or a.bit_depth:
-                ap.error("--matrix, --range, --siting and --bit-depth belong to --recon-video")
-            height, width = a.height or info["height"], a.width or info["width"]
-            n = decode_folder(a.bins, a.recon, height, width, a.gop or (info or {}).get("gop"), a.device, a.precision,
-                              a.i_ckpt, a.p_ckpt, io_workers=a.io_workers, roi=roi, residuals=a.residuals,
-                              residual_bins=a.residual_bins, verify=a.verify, base_scale=None if a.base_only else "file")
-        print(f"{n} pictures decoded")
+
+def _decode_command(ap, a):
+    motion = _motion_option(ap, a)
+    if a.base_only and a.roi_root is not None:
+        ap.error("--base-only takes no --roi-root: boxes and the residual layer live at full size")
+    if a.roi_root is None and os.path.exists(os.path.join(a.bins, ROIQ_JSON)):
+        ap.error(f"{os.path.join(a.bins, ROIQ_JSON)}: these pictures were coded with q-scale maps made from ROI boxes; "
+                 f"decode needs --roi-root")
+    _needs_roi_root(ap, a)
+    if a.residuals and a.residual_bins:
+        ap.error("give one of --residuals and --residual-bins")
+    if a.roi_root is not None and not a.residuals and not a.residual_bins and not os.path.exists(os.path.join(a.bins, ROIQ_JSON)):
+        ap.error("decode --roi-root needs --residuals (the decoded residual layer) or --residual-bins (the coded one)")
+    roi = _roi_option(ap, a, motion, {c["name"]: c["border"] for c in
+                                      ((read_sequence_info(a.bins) or {}).get("roi") or {}).get("classes", [])})
+    if (a.recon is None) == (a.recon_video is None):
+        ap.error("give exactly one of --recon and --recon-video")
+    info = read_sequence_info(a.bins)
+    if info is None and (a.height is None or a.width is None):
+        ap.error(f"--height and --width are required (no {SEQUENCE_JSON} beside the .bin files)")
+    if a.recon_video is not None:
+        from . import yuv as Y
+
+        if os.path.splitext(a.recon_video)[1].lower() not in (".y4m", ".yuv"):
+            ap.error("--recon-video takes a .y4m or a .yuv file")
+        spec = None
+        if a.matrix or a.range or a.siting or a.bit_depth:
+            base = info["color"] if info else Y.ColorSpec()
+            spec = Y.ColorSpec(a.matrix or base.matrix, base.full_range if a.range is None else a.range == "full",
+                               a.siting or base.siting, a.bit_depth or base.bit_depth)
+        n = decode_video(a.bins, a.recon_video, a.height, a.width, a.gop, spec, None, a.device, a.precision, a.i_ckpt, a.p_ckpt,
+                         roi=roi, residuals=a.residuals, residual_bins=a.residual_bins, verify=a.verify,
+                         base_scale=None if a.base_only else "file")
+    else:
+        if a.matrix or a.range or a.siting or a.bit_depth:
+            ap.error("--matrix, --range, --siting and --bit-depth belong to --recon-video")
+        height, width = a.height or info["height"], a.width or info["width"]
+        n = decode_folder(a.bins, a.recon, height, width, a.gop or (info or {}).get("gop"), a.device, a.precision,
+                          a.i_ckpt, a.p_ckpt, io_workers=a.io_workers, roi=roi, residuals=a.residuals,
+                          residual_bins=a.residual_bins, verify=a.verify, base_scale=None if a.base_only else "file")
+    print(f"{n} pictures decoded")
+
+
+def main(argv=None):
+    ap = _parser()
+    a = ap.parse_args(argv)
+    {"verify": _verify_command, "boxes": _boxes_command, "encode": _encode_command, "decode": _decode_command}[a.cmd](ap, a)
 
 
 if __name__ == "__main__":

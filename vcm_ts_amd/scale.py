@@ -227,15 +227,9 @@ class Scale:
 def write_scale(bin_dir, scale):
     """scale.json beside the .bin files -- only for an encode with a base scale: without one none is needed (and a stale
     file of an earlier encode into the same folder must not describe these .bin files)."""
-    path = os.path.join(bin_dir, SCALE_JSON)
-    if scale is None:
-        if os.path.exists(path):
-            os.remove(path)
-        return None
-    info = scale.to_json()
-    with open(path, "w") as f:
-        json.dump(info, f, indent=2)
-    return info
+    from .stream import write_sidecar
+
+    return write_sidecar(bin_dir, SCALE_JSON, None if scale is None else scale.to_json())
 
 
 def parse_scale(info, where=SCALE_JSON):

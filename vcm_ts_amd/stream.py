@@ -52,6 +52,21 @@ def filesize(filepath) -> int:
     return os.stat(filepath).st_size
 
 
+def write_sidecar(bin_dir, name, info):
+    """The JSON file `name` beside the .bin files of `bin_dir`: written from `info`, or -- info None: this encode has
+    nothing to say there -- removed if an earlier encode into the same folder left one, which must not describe these .bin
+    files.  Returns info."""
+    import json
+
+    path = os.path.join(bin_dir, name)
+    if info is not None:
+        with open(path, "w") as f:
+            json.dump(info, f, indent=2)
+    elif os.path.exists(path):
+        os.remove(path)
+    return info
+
+
 def encode_i(height, width, q_index, bit_stream, output):
     with open(output, "wb") as f:
         f.write(_I_HEAD.pack(height, width, q_index, len(bit_stream)))

@@ -7,6 +7,7 @@ in numpy.
 
     TNR(threshold, floor=64, pixel=None)     the setting; .table() the 256 weights
     TnrFilter(tnr, size, device)             the state of ONE GOP stream on the device; .step(x_padded, intra)
+    StreamFilter                             what TnrFilter shares with redact.Redactor: validation, pictures, totals
 
 There is deliberately NO default threshold, and `floor` and `pixel` are UNTUNED PLACEHOLDERS: no machine of the project
 holds a real video.  This is the mechanism -- filtered, coded, decoded by an unchanged decoder -- not a claim about rate
@@ -61,23 +62,25 @@ class TNR:
         return {"threshold": self.threshold, "floor": self.floor, "pixel": self.pixel}
 
 
-class TnrFilter:
-    """The filter of one GOP stream of `size` = (height, width) pictures on `device`: two zero-initialised padded
-    pictures written alternately, the table, and the cells' sad / held.  The filter restarts at every I picture, so what a
-    GOP is coded from depends on its own pictures and the setting only.  One TnrFilter serves one stream at a time.
-    totals=False keeps no per-picture totals: a step is then the one launch and nothing else, no pinned memory and no
-    event is ever made, and .totals() is refused."""
+class StreamFilter:
+    """What TnrFilter and redact.Redactor share: a filter of the padded pictures of ONE GOP stream of `size` = (height,
+    width) on `device` -- the validation of both, two zero-initialised padded pictures written alternately, and the
+    per-picture totals: `row` int64 sums per filtered picture, written in place into ROWS rows on the device and sent to the
+    host through a goplog.GopLog.  totals=False keeps none: a step is then the one launch and nothing else, no pinned memory
+    and no event is ever made, and .totals() is refused.  noun: what the messages call the object; untouched: the totals
+    of a step that launched nothing."""
+    noun, untouched = "filter", (0, 0)
 
-    def __init__(self, tnr, size, device, totals=True):
+    def __init__(self, size, device, row, totals):
         import torch
 
         from . import stream as S
+        from .goplog import GopLog
 
-        if not isinstance(tnr, TNR):
-            raise ValueError(f"tnr: expected a tnr.TNR, got {type(tnr).__name__}")
-        self.tnr, self.device = tnr, torch.device(device)
+        name = type(self).__name__
+        self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise ValueError("TnrFilter: pictures live on the GPU (no CPU fallback exists)")
+            raise ValueError(f"{name}: pictures live on the GPU (no CPU fallback exists)")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.height, self.width = int(size[0]), int(size[1])
@@ -86,28 +89,77 @@ class TnrFilter:
         l, r, t, b = S.get_padding_size(self.height, self.width)
         self.padded = (self.height + t + b, self.width + l + r)
         self.grid = grid_of(self.height, self.width)
-        cells = self.grid[0] * self.grid[1]
         # (the crop is written in place by every step and the padding never: it stays the zero pad_frame would give)
         self.bufs = [torch.zeros((1, 3) + self.padded, dtype=torch.float32, device=self.device) for _ in range(2)]
-        self.wtab = torch.from_numpy(tnr.table().view(np.int16)).to(self.device)  # (the bits of the uint16 table)
-        self.sad = torch.empty(cells, dtype=torch.int32, device=self.device)   # (uint32 words; a cell's sum is < 2^16)
-        self.held = torch.empty(cells, dtype=torch.int16, device=self.device)  # (uint16 words; a cell's count is <= 256)
-        self.ref, self.n, self.launches = None, 0, 0
-        # (held, sad) of the P pictures not yet flushed; the values already read, by step number
-        self._rows = torch.zeros((ROWS, 2), dtype=torch.int64, device=self.device) if totals else None
-        self._idx, self._done, self._read = [], [], {}
-        torch.cuda.synchronize(self.device)  # (the uploads above: a stream that uses them afterwards cannot race them)
+        self.n, self.launches = 0, 0
+        # the sums of the filtered pictures not yet flushed; the values already read, by step number
+        self._rows = torch.zeros((ROWS, row), dtype=torch.int64, device=self.device) if totals else None
+        self._log, self._read = GopLog(), {}
+
+    @property
+    def _done(self):
+        """The flushes nobody has read yet."""
+        return self._log.done
 
     def _check(self, x):
         import torch
 
+        name = type(self).__name__
         if not torch.is_tensor(x) or not x.is_cuda:
-            raise ValueError("TnrFilter.step: pictures live on the GPU (no CPU fallback exists)")
+            raise ValueError(f"{name}.step: pictures live on the GPU (no CPU fallback exists)")
         if x.device != self.device:
-            raise ValueError(f"TnrFilter.step: the picture is on {x.device}, the filter on {self.device}")
+            raise ValueError(f"{name}.step: the picture is on {x.device}, the {self.noun} on {self.device}")
         if x.dtype != torch.float32 or tuple(x.shape) != (1, 3) + self.padded:
-            raise ValueError(f"TnrFilter.step: expected a (1, 3, {self.padded[0]}, {self.padded[1]}) float32 picture, got "
+            raise ValueError(f"{name}.step: expected a (1, 3, {self.padded[0]}, {self.padded[1]}) float32 picture, got "
                              f"{tuple(x.shape)} {x.dtype}")
+
+    def _keep(self, t, *cells):
+        """Step t's totals: one small reduction per tensor of `cells` behind the launch; the host looks at them per GOP."""
+        import torch
+
+        if self._rows is not None:
+            row = self._rows[len(self._log.keys)]
+            for i, c in enumerate(cells):
+                row[i].copy_(c.sum(dtype=torch.int64))
+            if self._log.add(t) == ROWS:  # (a GOP with more filtered pictures than rows: its totals travel in more than one copy)
+                self.flush()
+
+    def flush(self):
+        """The totals of the pictures filtered since the last flush, to pinned host memory in ONE asynchronous copy on the
+        current stream: no kernel, and nothing is waited for.  The file loops call it at every GOP's first picture."""
+        if self._log.keys:
+            self._log.flush(self._rows[:len(self._log.keys)])  # (the next step's rows follow the copy in stream order)
+
+    def totals(self):
+        """The totals of every step so far, in order, as Python integers; `untouched` for a step that launched nothing.
+        Flushes on the current stream and waits for the copies; their pinned buffers and events are let go of here, at a
+        known point, and only the integers are kept."""
+        if self._rows is None:
+            raise ValueError(f"{type(self).__name__}.totals: this {self.noun} was made with totals=False")
+        self.flush()
+        for keys, (host,) in self._log.collect():
+            self._read.update(zip(keys, (v[0] if len(v) == 1 else tuple(v) for v in host.tolist())))
+        return [self._read.get(t, self.untouched) for t in range(self.n)]
+
+
+class TnrFilter(StreamFilter):
+    """The filter of one GOP stream: StreamFilter's two pictures, the table, and the cells' sad / held.  The filter restarts at
+    every I picture, so what a GOP is coded from depends on its own pictures and the setting only.  One TnrFilter serves one
+    stream at a time.  .totals(): [(held pixels, sum of d)] of every step, (0, 0) for an I picture."""
+
+    def __init__(self, tnr, size, device, totals=True):
+        import torch
+
+        if not isinstance(tnr, TNR):
+            raise ValueError(f"tnr: expected a tnr.TNR, got {type(tnr).__name__}")
+        self.tnr = tnr
+        super().__init__(size, device, 2, totals)
+        cells = self.grid[0] * self.grid[1]
+        self.wtab = torch.from_numpy(tnr.table().view(np.int16)).to(self.device)  # (the bits of the uint16 table)
+        self.sad = torch.empty(cells, dtype=torch.int32, device=self.device)   # (uint32 words; a cell's sum is < 2^16)
+        self.held = torch.empty(cells, dtype=torch.int16, device=self.device)  # (uint16 words; a cell's count is <= 256)
+        self.ref = None
+        torch.cuda.synchronize(self.device)  # (the uploads above: a stream that uses them afterwards cannot race them)
 
     def step(self, x_padded, intra):
         """The padded picture to code in place of `x_padded`.  An I picture (intra=True) launches nothing and is returned
@@ -136,38 +188,6 @@ class TnrFilter:
                                               self.wtab.data_ptr(), self.tnr.pixel, self.sad.data_ptr(), self.held.data_ptr(),
                                               C.c_void_p(_raw_stream(self.device.index))), "tnr_step")
         self.launches += 1
-        if self._rows is not None:
-            row = self._rows[len(self._idx)]  # (two small reductions behind the launch; the host looks at them per GOP)
-            row[0].copy_(self.held.sum(dtype=torch.int64))
-            row[1].copy_(self.sad.sum(dtype=torch.int64))
-            self._idx.append(t)
-            if len(self._idx) == ROWS:  # (a GOP longer than the rows kept: its totals travel in more than one copy)
-                self.flush()
+        self._keep(t, self.held, self.sad)
         self.ref = out
         return out
-
-    def flush(self):
-        """The totals of the P pictures since the last flush, to pinned host memory in ONE asynchronous copy on the
-        current stream: no kernel, and nothing is waited for."""
-        import torch
-
-        if self._idx:
-            host = torch.empty((len(self._idx), 2), dtype=torch.int64).pin_memory()
-            host.copy_(self._rows[:len(self._idx)], non_blocking=True)  # (the next step's rows follow it in stream order)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-            self._done.append((ev, host, self._idx))
-            self._idx = []
-
-    def totals(self):
-        """[(held pixels, sum of d)] of every step so far, in order, as Python integers; (0, 0) for an I picture.  Flushes
-        on the current stream and waits for the copies; their pinned buffers and events are let go of here, at a known
-        point, and only the integers are kept."""
-        if self._rows is None:
-            raise ValueError("TnrFilter.totals: this filter was made with totals=False")
-        self.flush()
-        for ev, host, idx in self._done:
-            ev.synchronize()
-            self._read.update({t: (int(held), int(sad)) for t, (held, sad) in zip(idx, host.tolist())})
-        self._done = []
-        return [self._read.get(t, (0, 0)) for t in range(self.n)]
