@@ -13,20 +13,17 @@ torch fallback: anything the kernels do not take is a ValueError.
 """
 from __future__ import annotations
 
-import ctypes as C
-import json
-import math
-import os
 import zlib
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import lib
+from . import devargs
+from .devargs import MAX_SIDE, whole
 
 AQ_JSON = "aq.json"
 VERSION, CELL = 1, 16
-MAX_L, MAX_STRENGTH, MIN_Q, MAX_Q, MAX_SIDE = 7935, 400, 10, 1000, 32768
+MAX_L, MAX_STRENGTH, MIN_Q, MAX_Q = 7935, 400, 10, 1000
 KTAB, FTAB = 2 * MAX_L + 1, MAX_Q - MIN_Q + 1  # entries of the two tables
 QP_PER_DOUBLING = 6  # of the step: d is in 1/256 of a doubling of the variance, A in 1/100 QP per doubling
 
@@ -41,21 +38,14 @@ class AQ:
     hi: int = MAX_Q
 
     def __post_init__(self):
-        def whole(name, v, lo, hi):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-                raise ValueError(f"{name} must be an integer within {lo}..{hi} (hundredths), got {v!r}")
-            return int(v)
-
-        object.__setattr__(self, "strength", whole("strength", self.strength, 1, MAX_STRENGTH))
-        object.__setattr__(self, "lo", whole("lo", self.lo, MIN_Q, 100))
-        object.__setattr__(self, "hi", whole("hi", self.hi, 100, MAX_Q))
+        object.__setattr__(self, "strength", whole("strength", self.strength, 1, MAX_STRENGTH, "hundredths"))
+        object.__setattr__(self, "lo", whole("lo", self.lo, MIN_Q, 100, "hundredths"))
+        object.__setattr__(self, "hi", whole("hi", self.hi, 100, MAX_Q, "hundredths"))
 
     @staticmethod
     def hundredths(value, name="value"):
         """A plain number snapped to hundredths (1.0 -> 100), as roi.RoiQ.hundredths does."""
-        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not math.isfinite(value):
-            raise ValueError(f"{name} must be a finite number, got {value!r}")
-        return int(round(float(value) * 100.0))
+        return devargs.hundredths(value, name)
 
     @classmethod
     def snapped(cls, strength, lo=0.1, hi=10.0):
@@ -134,11 +124,7 @@ class AqMaps:
 
         if not isinstance(aq, AQ):
             raise ValueError(f"aq: expected an aq.AQ, got {type(aq).__name__}")
-        self.aq, self.device = aq, torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("AqMaps: the maps are made on the GPU (no CPU fallback exists)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.aq, self.device = aq, devargs.cuda_device(device, "AqMaps")
         self.ktab = torch.from_numpy(aq.ktab().view(np.int16)).to(self.device)  # (the bits of the uint16 table)
         self.ftab = torch.from_numpy(aq.ftab()).to(self.device)
         self.sum = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -150,24 +136,14 @@ class AqMaps:
         scratch of this object, valid until the next call.  A memset and one launch on the current stream."""
         import torch
 
-        from .engine import _raw_stream
-        from .metrics import _planar
-
-        t = ref_frame
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError("aq: the reference picture lives on the GPU (no CPU fallback exists)")
-        if t.device != self.device:
-            raise ValueError(f"aq: the reference picture is on {t.device}, the tables on {self.device}")
-        if t.dtype != torch.float32 or t.dim() != 4 or t.shape[0] != 1 or t.shape[1] != 3:
-            raise ValueError(f"aq: expected a (1, 3, Hp, Wp) float32 reference picture, got {tuple(t.shape)} {t.dtype}")
+        t = devargs.checked(ref_frame, "aq", device=self.device, noun="reference picture")
         hc, wc = grid_of(*t.shape[2:])
-        p, rs, ps = _planar(t.detach())
+        p, rs, ps = devargs.planar(t)
         if self.L is None or self.L.numel() != hc * wc:
             self.L = torch.empty(hc * wc, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            self.sum.zero_()
-            lib.check(lib.hip().dcvc_aq_activity(p.data_ptr(), rs, ps, t.shape[2], t.shape[3], self.L.data_ptr(),
-                                                 self.sum.data_ptr(), C.c_void_p(_raw_stream(self.device.index))), "aq_activity")
+        self.sum.zero_()
+        devargs.launch("dcvc_aq_activity", self.device, p.data_ptr(), rs, ps, t.shape[2], t.shape[3], self.L.data_ptr(),
+                       self.sum.data_ptr())
         return self.L.view(hc, wc), self.sum
 
     def map(self, ref_frame, roi_map=None):
@@ -175,8 +151,6 @@ class AqMaps:
         multiplied into `roi_map` (roi.q_map's, hc * wc float32 on the same device) when one is given: what DMC
         .compress / .decompress take as q_map=.  A memset and two launches on the current stream, nothing synchronised."""
         import torch
-
-        from .engine import _raw_stream
 
         L, total = self.activity(ref_frame)
         hc, wc = L.shape
@@ -193,9 +167,8 @@ class AqMaps:
             roi_map = r.detach().contiguous()
             roi_ptr = roi_map.data_ptr()
         out = torch.empty((hc, wc), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            lib.check(lib.hip().dcvc_aq_map(L.data_ptr(), total.data_ptr(), hc, wc, self.ktab.data_ptr(), self.ftab.data_ptr(),
-                                            roi_ptr, out.data_ptr(), C.c_void_p(_raw_stream(self.device.index))), "aq_map")
+        devargs.launch("dcvc_aq_map", self.device, L.data_ptr(), total.data_ptr(), hc, wc, self.ktab.data_ptr(),
+                       self.ftab.data_ptr(), roi_ptr, out.data_ptr())
         return out
 
 
@@ -217,12 +190,7 @@ def write_aq(bin_dir, aq):
 
 def read_aq(bin_dir):
     """AQ.from_json of the folder's aq.json, or None without the file."""
-    path = os.path.join(bin_dir, AQ_JSON)
-    if not os.path.exists(path):
-        return None
-    with open(path) as f:
-        try:
-            info = json.load(f)
-        except ValueError as ex:
-            raise ValueError(f"{path}: not JSON ({ex})") from None
-    return AQ.from_json(info, path)
+    from .stream import read_sidecar
+
+    found = read_sidecar(bin_dir, AQ_JSON)
+    return None if found is None else AQ.from_json(found[1], found[0])

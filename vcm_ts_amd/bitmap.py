@@ -20,7 +20,7 @@ import math
 
 import numpy as np
 
-from . import lib
+from . import devargs
 
 UNIT = 65536            # map units per bit
 REGION_UNIT = 16 * UNIT  # region-sum units per bit
@@ -98,16 +98,9 @@ class CostTables:
         return d
 
 
-def _stream(device):
-    from .engine import _raw_stream
-
-    return C.c_void_p(_raw_stream(device.index))
-
-
 def _check_labels(labels, K, N, hc, wc):
     """Argument checks of BitMap.regions that need no GPU; returns the (n, hc, wc) shape labels have (n is 1 or N)."""
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= MAX_LABELS:
-        raise ValueError(f"K: the number of labels must be an integer within 1..{MAX_LABELS}, got {K!r}")
+    devargs.whole("K: the number of labels", K, 1, MAX_LABELS)
     shape = tuple(getattr(labels, "shape", ()))
     dtype = str(getattr(labels, "dtype", type(labels).__name__)).replace("torch.", "")
     if dtype != "uint8":
@@ -147,11 +140,9 @@ class BitMap:
 
         if len(planes) not in (3, 6):
             raise ValueError(f"expected 3 or 6 symbol planes, got {len(planes)}")
-        L = lib.hip()
         dev = planes[0][1].device
         names = COMPONENTS[2:] if len(planes) == 3 else COMPONENTS
         status = torch.zeros(2, dtype=torch.int32, device=dev)  # (8 bytes: it travels in one int64 slot of a read-back)
-        stream = _stream(dev)
         maps = {}
         for g in range(len(planes) // 3):
             (zt, zsym, _, (zn, zc, zh, zw)), (st, s0, i0, _), (_, s1, i1, _) = planes[3 * g : 3 * g + 3]
@@ -164,14 +155,12 @@ class BitMap:
                 raise ValueError(f"bit maps take an even number of at most {MAX_C} channels, got {Cy} and {zc}")
             cost, sizes, offsets, rows, stride = tables[zt]
             zmap = torch.empty((N, zh, zw), dtype=torch.int32, device=dev)
-            lib.check(L.dcvc_bits_map_factorized(zsym.data_ptr(), cost.data_ptr(), rows, stride, sizes.data_ptr(),
-                                                 offsets.data_ptr(), zmap.data_ptr(), N, zc, zh, zw, status.data_ptr(),
-                                                 stream), "bits_map_factorized")
+            devargs.launch("dcvc_bits_map_factorized", dev, zsym.data_ptr(), cost.data_ptr(), rows, stride, sizes.data_ptr(),
+                           offsets.data_ptr(), zmap.data_ptr(), N, zc, zh, zw, status.data_ptr())
             cost, sizes, offsets, rows, stride = tables[st]
             ymap = torch.empty((N, H, W), dtype=torch.int32, device=dev)
-            lib.check(L.dcvc_bits_map_scale(s0.data_ptr(), i0.data_ptr(), s1.data_ptr(), i1.data_ptr(), cost.data_ptr(), rows,
-                                            stride, sizes.data_ptr(), offsets.data_ptr(), ymap.data_ptr(), N, Cy, H, W,
-                                            status.data_ptr(), stream), "bits_map_scale")
+            devargs.launch("dcvc_bits_map_scale", dev, s0.data_ptr(), i0.data_ptr(), s1.data_ptr(), i1.data_ptr(), cost.data_ptr(),
+                           rows, stride, sizes.data_ptr(), offsets.data_ptr(), ymap.data_ptr(), N, Cy, H, W, status.data_ptr())
             maps[names[2 * g]], maps[names[2 * g + 1]] = zmap, ymap
         m = maps["y"]
         return cls(maps, status, N, m.shape[1], m.shape[2])
@@ -201,10 +190,9 @@ class BitMap:
         n = self.N * int(K) * 4
         out = torch.empty(n + 1, dtype=torch.int64, device=dev)
         ptrs = (C.c_void_p * 4)(*[None if self.maps[k] is None else self.maps[k].data_ptr() for k in COMPONENTS])
-        with torch.cuda.device(dev):
-            lib.check(lib.hip().dcvc_bits_regions(ptrs, lab.data_ptr(), int(K), out.data_ptr(), self.N, self.hc, self.wc,
-                                                  self.status.data_ptr(), _stream(dev)), "bits_regions")
-            out[n:].view(torch.int32).copy_(self.status)
+        devargs.launch("dcvc_bits_regions", dev, ptrs, lab.data_ptr(), int(K), out.data_ptr(), self.N, self.hc, self.wc,
+                       self.status.data_ptr())
+        out[n:].view(torch.int32).copy_(self.status)
         return out
 
     @staticmethod
@@ -257,8 +245,7 @@ def labels_from_boxes(boxes, height, width, grow=0, device=None):
     every class 0.50 is made by dcvc_roi_qmap and compared with 0.75.  height, width: the UNPADDED picture."""
     from . import roi as X
 
-    if isinstance(grow, bool) or not isinstance(grow, (int, np.integer)) or not 0 <= grow <= X.MAX_GROW:
-        raise ValueError(f"grow must be an integer within 0..{X.MAX_GROW} (pixels), got {grow!r}")
+    devargs.whole("grow", grow, 0, X.MAX_GROW, "pixels")
     import torch
 
     boxes = X.as_boxes(boxes).validate(int(height), int(width), X.MAX_CLASSES)  # (by name, before any GPU work)

@@ -140,12 +140,6 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_kernel(const ToRgb p) {
         }
 }
 
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_xor((int)v, off);
-    return v;
-}
-
 __device__ __forceinline__ int to_code(float v, float range, float off, int max_code) {
     return (int)fminf(fmaxf(rintf(v * range + off), 0.0f), (float)max_code);
 }

@@ -23,6 +23,7 @@
 #include "dcvc_hip.h"
 #include "dcvc_hip_hash.h"
 #include "kernel_common.h"
+#include "roi_common.h"
 
 #pragma clang fp contract(off)
 
@@ -74,8 +75,6 @@ struct FoldArgs {
     int32_t per_lane, front;  // front: the virtual zero partials before the first
     uint32_t xblock, xlane[LEVELS], init;  // x^(8 * BLOCK); x^(8 * BLOCK * per_lane * 2^k); 0xFFFFFFFF * x^(8 |M|)
 };
-
-__device__ __forceinline__ int code8(float v) { return (int)rintf(255.0f * fminf(fmaxf(v, 0.0f), 1.0f)); }
 
 // entry (k, t): the register after byte t and k zero bytes
 __device__ __forceinline__ void make_tables(uint32_t *T, int tid) {

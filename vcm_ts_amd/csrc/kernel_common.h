@@ -37,6 +37,13 @@ constexpr float ACT_LIMIT = F16_MAX / ACT_SCALE;  // an output beyond it would b
 
 __device__ __forceinline__ float act(float v, float slope) { return v > 0.f ? v : v * slope; }
 
+// the sum of v over the 64 lanes of a wave, in every lane (roi.hip, roil.hip, scene.hip, color.hip)
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_xor((int)v, off);
+    return v;
+}
+
 // ---- CDF row of a scale ------------------------------------------------------------------------------------------------
 // The number of bin edges <= s among edges[0 .. 254] (256 entries, the last one +inf and never read), by bisection; the
 // dual-prior kernels (entropy_kernels.hip, where the edges are explained) and the ladder sweep (bitmap.hip) share it, so

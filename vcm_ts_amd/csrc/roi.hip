@@ -107,12 +107,6 @@ __device__ __forceinline__ void load_u8(const uint8_t *at, int64_t cs, int px, i
     }
 }
 
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_xor((int)v, off);
-    return v;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(256) void roi_kernel(const RoiArgs p) {
     __shared__ Tile t;

@@ -1,6 +1,7 @@
-// roi_common.h -- what roi.hip, roil.hip, aq.hip and motion.hip share: the 8-bit code of a float sample and the luma of three
-// codes, the cull of a picture's box list
-// against a rectangle into LDS, and the entry points' checks of pictures and box lists (include/dcvc_hip_roi.h).
+// roi_common.h -- what the picture tools (roi.hip, roil.hip, aq.hip, motion.hip, tnr.hip, redact.hip, hash.hip, scene.hip)
+// share: the 8-bit code of a float sample and the luma of three codes, the cull of a picture's box list against a rectangle
+// into LDS, and the entry points' checks of pictures (size, strides, overlap, vector loads) and box lists
+// (include/dcvc_hip_roi.h).
 // Internal, like kernel_common.h: every unit is compiled on its own, hence the unnamed namespace.
 #ifndef DCVC_ROI_COMMON_H
 #define DCVC_ROI_COMMON_H
@@ -55,6 +56,17 @@ inline bool size_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && H <= DCVC_R
 inline bool planes_ok(const float *p, int32_t rs, int64_t ps, int32_t H, int32_t W) {
     return p && rs >= W && ps >= (int64_t)(H - 1) * rs + W;
 }
+
+// [p, p + 2 ps + (H - 1) rs + W) in bytes: what a picture's three planes span
+inline bool extents_overlap(const float *a, int32_t ars, int64_t aps, const float *b, int32_t brs, int64_t bps, int32_t H, int32_t W) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    // (unsigned: a plane stride near 2^63 wraps instead of overflowing, and such a picture overlaps nothing real)
+    const uintptr_t a1 = a0 + 4 * (2 * (uintptr_t)aps + (uintptr_t)(H - 1) * (uintptr_t)ars + (uintptr_t)W);
+    const uintptr_t b1 = b0 + 4 * (2 * (uintptr_t)bps + (uintptr_t)(H - 1) * (uintptr_t)brs + (uintptr_t)W);
+    return a0 < b1 && b0 < a1;
+}
+
+inline int vec_ok(const float *p, int32_t rs, int64_t ps) { return aligned(p, 16) && rs % 4 == 0 && ps % 4 == 0; }
 
 inline bool boxes_ok(const dcvc_roi_box_t *host, const dcvc_roi_box_t *dev, int32_t n, int32_t H, int32_t W, int32_t n_classes) {
     if (n < 0 || n > DCVC_ROI_MAX_BOXES || (n > 0 && (!host || !dev))) return false;

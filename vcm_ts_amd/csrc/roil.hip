@@ -73,12 +73,6 @@ __device__ __forceinline__ bool cell_mask(CellList &t, const dcvc_roi_box_t *box
     return in;
 }
 
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_xor((int)v, off);
-    return v;
-}
-
 __device__ __forceinline__ unsigned wave_scan(unsigned v, int lane) {  // inclusive
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {

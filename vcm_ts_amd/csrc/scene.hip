@@ -24,6 +24,7 @@
 #include "dcvc_hip.h"
 #include "dcvc_hip_scene.h"
 #include "kernel_common.h"
+#include "roi_common.h"
 
 #pragma clang fp contract(off)
 
@@ -38,16 +39,8 @@ struct SceneArgs {
     int32_t rs, H, W, vec;
 };
 
-__device__ __forceinline__ int code8(float v) { return (int)rintf(255.0f * fminf(fmaxf(v, 0.0f), 1.0f)); }
-
 // first row (column) of cell c of a side of n pixels: the smallest y with (4 * y) / n == c
 __host__ __device__ __forceinline__ int cell_begin(int c, int n) { return (c * n + GRID - 1) / GRID; }
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_xor((int)v, off);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void scene_hist_kernel(const SceneArgs p) {
     __shared__ unsigned h[BINS * 64];  // counter (bin, lane replica) at bin * 64 + lane
@@ -102,7 +95,6 @@ __global__ __launch_bounds__(256) void scene_hist_kernel(const SceneArgs p) {
     }
 }
 
-bool aligned(const void *p, size_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
 
 }  // namespace
 

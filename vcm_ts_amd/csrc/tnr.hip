@@ -194,17 +194,6 @@ __global__ __launch_bounds__(64 * WAVES) void tnr_step_kernel(const TnrArgs p) {
     }
 }
 
-// [p, p + 2 ps + (H - 1) rs + W) in bytes: what a picture's three planes span
-inline bool extents_overlap(const float *a, int32_t ars, int64_t aps, const float *b, int32_t brs, int64_t bps, int32_t H, int32_t W) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    // (unsigned: a plane stride near 2^63 wraps instead of overflowing, and such a picture overlaps nothing real)
-    const uintptr_t a1 = a0 + 4 * (2 * (uintptr_t)aps + (uintptr_t)(H - 1) * (uintptr_t)ars + (uintptr_t)W);
-    const uintptr_t b1 = b0 + 4 * (2 * (uintptr_t)bps + (uintptr_t)(H - 1) * (uintptr_t)brs + (uintptr_t)W);
-    return a0 < b1 && b0 < a1;
-}
-
-inline int vec_ok(const float *p, int32_t rs, int64_t ps) { return aligned(p, 16) && rs % 4 == 0 && ps % 4 == 0; }
-
 }  // namespace
 
 extern "C" int dcvc_tnr_step(const float *cur, int32_t cur_rs, int64_t cur_ps, const float *ref, int32_t ref_rs, int64_t ref_ps,

@@ -9,44 +9,26 @@ kernels do not take is a ValueError, never a quiet torch implementation.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 from torch import nn
 
-from . import lib
-from .engine import _raw_stream
+from . import devargs, lib
+from .devargs import MAX_SIDE, planar
 
 MIN_SIDE = 161  # pytorch_msssim asserts min(H, W) > (11 - 1) * 2**4
 
 
 def _check(x, y):
     for t in (x, y):
-        if not torch.is_tensor(t) or t.dim() != 4:
-            raise ValueError("ms_ssim takes (N, C, H, W) tensors")
-        if not t.is_cuda:
-            raise ValueError("ms_ssim runs on the GPU only (no CPU fallback exists)")
-        if t.dtype != torch.float32:
-            raise ValueError(f"ms_ssim takes float32 tensors, got {t.dtype}")
+        devargs.on_gpu(t, "ms_ssim", noun="operand")
+        if t.dtype != torch.float32 or t.dim() != 4:
+            raise ValueError(f"ms_ssim: expected (N, C, H, W) float32 operands, got {tuple(t.shape)} {t.dtype}")
     if x.shape != y.shape or x.device != y.device:
         raise ValueError(f"operands differ: {tuple(x.shape)} on {x.device} and {tuple(y.shape)} on {y.device}")
     if min(x.shape[-2:]) < MIN_SIDE:
         raise ValueError(f"image sides must exceed 160 for the five levels of MS-SSIM, got {tuple(x.shape[-2:])}")
-    if x.shape[0] < 1 or x.shape[1] < 1 or x.shape[0] * x.shape[1] > 65535 or max(x.shape[-2:]) > 32768:
+    if x.shape[0] < 1 or x.shape[1] < 1 or x.shape[0] * x.shape[1] > 65535 or max(x.shape[-2:]) > MAX_SIDE:
         raise ValueError(f"unsupported shape {tuple(x.shape)}")
-
-
-def _planar(t):
-    """(tensor, row stride, plane stride): `t` itself when it is dense planar rows inside a contiguous NCHW buffer (a
-    spatial crop), else a contiguous copy."""
-    N, C_, H, W = t.shape
-    sn, sc, sh, sw = t.stride()
-    if C_ == 1:  # (the stride of a size-1 dimension means nothing: planes are then one sample apart)
-        sc = sn if N > 1 else H * sh
-    if not (sw == 1 and sh >= W and sc >= (H - 1) * sh + W and (N == 1 or sn == C_ * sc)):
-        t = t.contiguous()
-        sh, sc = W, H * W
-    return t, sh, sc
 
 
 def _workspace(N, C_, H, W, want_grad, device):
@@ -62,33 +44,28 @@ def measure(x, y, data_range=1.0, clamp01=False, want_levels=False, want_sse=Tru
     _check(x, y)
     x, y = x.detach(), y.detach()
     N, C_, H, W = x.shape
-    with torch.cuda.device(x.device):
-        xs, xr, xp = _planar(x)
-        ys, yr, yp = _planar(y)
-        ws = _workspace(N, C_, H, W, False, x.device)
-        ms = torch.empty(N, dtype=torch.float32, device=x.device)
-        levels = torch.empty((5, N, C_), dtype=torch.float32, device=x.device) if want_levels else None
-        sse = torch.empty(N, dtype=torch.float32, device=x.device) if want_sse else None
-        lib.check(lib.hip().dcvc_ms_ssim(xs.data_ptr(), ys.data_ptr(), N, C_, H, W, xr, xp, yr, yp, float(data_range),
-                                         int(bool(clamp01)), ws.data_ptr(), ms.data_ptr(),
-                                         None if levels is None else levels.data_ptr(),
-                                         None if sse is None else sse.data_ptr(),
-                                         C.c_void_p(_raw_stream(x.device.index))), "ms_ssim")
+    xs, xr, xp = planar(x)
+    ys, yr, yp = planar(y)
+    ws = _workspace(N, C_, H, W, False, x.device)
+    ms = torch.empty(N, dtype=torch.float32, device=x.device)
+    levels = torch.empty((5, N, C_), dtype=torch.float32, device=x.device) if want_levels else None
+    sse = torch.empty(N, dtype=torch.float32, device=x.device) if want_sse else None
+    devargs.launch("dcvc_ms_ssim", x.device, xs.data_ptr(), ys.data_ptr(), N, C_, H, W, xr, xp, yr, yp, float(data_range),
+                   int(bool(clamp01)), ws.data_ptr(), ms.data_ptr(), None if levels is None else levels.data_ptr(),
+                   None if sse is None else sse.data_ptr())
     return ms, levels, sse
 
 
 def _grad(x, y, g_ms, data_range):
     """d/dx of sum_n g_ms[n] * ms_ssim(x, y)[n]"""
     N, C_, H, W = x.shape
-    with torch.cuda.device(x.device):
-        xs, xr, xp = _planar(x)
-        ys, yr, yp = _planar(y)
-        ws = _workspace(N, C_, H, W, True, x.device)
-        gx = torch.empty((N, C_, H, W), dtype=torch.float32, device=x.device)
-        g_ms = g_ms.detach().to(torch.float32).contiguous()
-        lib.check(lib.hip().dcvc_ms_ssim_grad(xs.data_ptr(), ys.data_ptr(), N, C_, H, W, xr, xp, yr, yp, float(data_range),
-                                              0, ws.data_ptr(), g_ms.data_ptr(), gx.data_ptr(),
-                                              C.c_void_p(_raw_stream(x.device.index))), "ms_ssim_grad")
+    xs, xr, xp = planar(x)
+    ys, yr, yp = planar(y)
+    ws = _workspace(N, C_, H, W, True, x.device)
+    gx = torch.empty((N, C_, H, W), dtype=torch.float32, device=x.device)
+    g_ms = g_ms.detach().to(torch.float32).contiguous()
+    devargs.launch("dcvc_ms_ssim_grad", x.device, xs.data_ptr(), ys.data_ptr(), N, C_, H, W, xr, xp, yr, yp, float(data_range),
+                   0, ws.data_ptr(), g_ms.data_ptr(), gx.data_ptr())
     return gx
 
 

@@ -18,24 +18,18 @@ ValueError.
 """
 from __future__ import annotations
 
-import json
 import os
 import pickle
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import lib
-from .roi import CELL, MAX_BOXES, MAX_SIDE, grid_of
+from . import devargs
+from .devargs import MAX_SIDE, whole
+from .roi import CELL, MAX_BOXES, grid_of
 
 MOTION_JSON, COORDS, VERSION = "motion.json", "motion_coords", 1
 MAX_T, MAX_K, MAX_GROW_CELLS = 254, 16, 8
-
-
-def _whole(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-        raise ValueError(f"{name} must be an integer within {lo}..{hi}, got {v!r}")
-    return int(v)
 
 
 @dataclass(frozen=True)
@@ -54,16 +48,16 @@ class MotionParams:
     max_boxes: int = 64
 
     def __post_init__(self):
-        object.__setattr__(self, "threshold", _whole("threshold", self.threshold, 1, MAX_T))
+        object.__setattr__(self, "threshold", whole("threshold", self.threshold, 1, MAX_T))
         try:
             k_bg, k_fg = self.learn
         except (TypeError, ValueError):
             raise ValueError(f"learn must be a pair (k_bg, k_fg), got {self.learn!r}") from None
-        object.__setattr__(self, "learn", (_whole("learn[0] (k_bg)", k_bg, 0, MAX_K), _whole("learn[1] (k_fg)", k_fg, 0, MAX_K)))
-        object.__setattr__(self, "min_pixels", _whole("min_pixels", self.min_pixels, 1, CELL * CELL))
-        object.__setattr__(self, "grow", _whole("grow", self.grow, 0, MAX_GROW_CELLS))
-        object.__setattr__(self, "min_cells", _whole("min_cells", self.min_cells, 1, 65535))
-        object.__setattr__(self, "max_boxes", _whole("max_boxes", self.max_boxes, 1, MAX_BOXES))
+        object.__setattr__(self, "learn", (whole("learn[0] (k_bg)", k_bg, 0, MAX_K), whole("learn[1] (k_fg)", k_fg, 0, MAX_K)))
+        object.__setattr__(self, "min_pixels", whole("min_pixels", self.min_pixels, 1, CELL * CELL))
+        object.__setattr__(self, "grow", whole("grow", self.grow, 0, MAX_GROW_CELLS))
+        object.__setattr__(self, "min_cells", whole("min_cells", self.min_cells, 1, 65535))
+        object.__setattr__(self, "max_boxes", whole("max_boxes", self.max_boxes, 1, MAX_BOXES))
 
     def to_json(self):
         return {"threshold": self.threshold, "learn": list(self.learn), "min_pixels": self.min_pixels, "grow": self.grow,
@@ -90,11 +84,7 @@ class MotionScan:
     def __init__(self, device, height, width, capacity, params):
         import torch
 
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("MotionScan: pictures live on the GPU (no CPU fallback exists)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = devargs.cuda_device(device, "MotionScan")
         if not (0 < int(height) <= MAX_SIDE and 0 < int(width) <= MAX_SIDE):
             raise ValueError(f"picture sides must be within 1..{MAX_SIDE}, got {width}x{height}")
         if int(capacity) < 1:
@@ -110,35 +100,20 @@ class MotionScan:
     def add(self, picture):
         """One step on the height x width crop of a (1, 3, Hp, Wp) float32 picture, read in place, on the current stream;
         its counts land in the next row.  The first picture initialises the model (all counts 0)."""
-        import ctypes as C
-
         import torch
 
-        from .engine import _raw_stream
-        from .metrics import _planar
-
-        if not torch.is_tensor(picture) or not picture.is_cuda:
-            raise ValueError("MotionScan.add: pictures live on the GPU (no CPU fallback exists)")
-        if picture.device != self.device:
-            raise ValueError(f"MotionScan.add: the picture is on {picture.device}, the scan on {self.device}")
-        if picture.dtype != torch.float32 or picture.dim() != 4 or picture.shape[0] != 1 or picture.shape[1] != 3 or \
-                picture.shape[2] < self.height or picture.shape[3] < self.width:
-            raise ValueError(f"MotionScan.add: expected a (1, 3, >={self.height}, >={self.width}) float32 picture, got "
-                             f"{tuple(picture.shape)} {picture.dtype}")
+        crop = devargs.checked(picture, "MotionScan.add", device=self.device, at_least=(self.height, self.width), owner="scan")
         if self.n >= self.capacity:
             raise ValueError(f"MotionScan.add: picture {self.n} of a scan of {self.capacity} pictures")
-        x, rs, ps = _planar(picture.detach()[..., :self.height, :self.width])
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream(self.device)
-            if self._last is not None and cur != self._last[0]:
-                cur.wait_event(self._last[1])  # (the model is a recursion: a device-side dependency, the host waits for nothing)
-            lib.check(lib.hip().dcvc_motion_step(x.data_ptr(), rs, ps, self.height, self.width, self.bg.data_ptr(),
-                                                 int(self.n == 0), self.params.threshold, *self.params.learn,
-                                                 self.cells[self.n].data_ptr(), C.c_void_p(_raw_stream(self.device.index))),
-                      "motion_step")
-            done = torch.cuda.Event()
-            done.record(cur)
-            self._last = (cur, done)
+        x, rs, ps = devargs.planar(crop)
+        cur = torch.cuda.current_stream(self.device)
+        if self._last is not None and cur != self._last[0]:
+            cur.wait_event(self._last[1])  # (the model is a recursion: a device-side dependency, the host waits for nothing)
+        devargs.launch("dcvc_motion_step", self.device, x.data_ptr(), rs, ps, self.height, self.width, self.bg.data_ptr(),
+                       int(self.n == 0), self.params.threshold, *self.params.learn, self.cells[self.n].data_ptr())
+        done = torch.cuda.Event()
+        done.record(cur)
+        self._last = (cur, done)
         self.n += 1
 
     def counts(self):
@@ -255,18 +230,19 @@ def scan(pictures, n_frames, size, device, params):
 # -------------------------------------------------------------------------------------------------------------- files
 def read_info(root):
     """motion.json of `root` as (MotionParams, height, width, frames), or None without the file."""
-    path = os.path.join(root, MOTION_JSON)
-    if not os.path.exists(path):
+    from .stream import read_sidecar
+
+    found = read_sidecar(root, MOTION_JSON)
+    if found is None:
         return None
-    with open(path) as f:
-        info = json.load(f)
+    path, info = found
     try:
         if not isinstance(info, dict) or set(info) != {"version", "height", "width", "frames", "params"}:
             raise ValueError("expected the keys version, height, width, frames and params")
         if info["version"] != VERSION:
             raise ValueError(f"format version {info['version']!r}, this code reads {VERSION}")
-        size = tuple(_whole(k, info[k], 1, MAX_SIDE) for k in ("height", "width"))
-        return MotionParams.from_json(info["params"]), size[0], size[1], _whole("frames", info["frames"], 1, 2 ** 31 - 1)
+        size = tuple(whole(k, info[k], 1, MAX_SIDE) for k in ("height", "width"))
+        return MotionParams.from_json(info["params"]), size[0], size[1], whole("frames", info["frames"], 1, 2 ** 31 - 1)
     except ValueError as ex:
         raise ValueError(f"{path}: {ex}") from None
 
@@ -276,8 +252,10 @@ def write_boxes(root, per_frame_boxes, params, height, width):
     ones included (the reference's coordinate format: roi.PickleBoxes reads the folder as class "motion"), and
     `root`/motion.json with the parameters, the size, the frame count and a format version.  Refused: a motion_coords
     that already holds the files of a run with another frame count or size (or of unknown origin) -- nothing is mixed."""
+    from .stream import write_sidecar
+
     p = _params(params)
-    H, W = _whole("height", height, 1, MAX_SIDE), _whole("width", width, 1, MAX_SIDE)
+    H, W = whole("height", height, 1, MAX_SIDE), whole("width", width, 1, MAX_SIDE)
     arrays = []
     for t, b in enumerate(per_frame_boxes):
         a = np.asarray(b)
@@ -304,5 +282,4 @@ def write_boxes(root, per_frame_boxes, params, height, width):
     for t, a in enumerate(arrays):
         with open(os.path.join(folder, "%05d" % (t + 1)), "wb") as f:
             pickle.dump(a, f)
-    with open(os.path.join(root, MOTION_JSON), "w") as f:
-        json.dump({"version": VERSION, "height": H, "width": W, "frames": len(arrays), "params": p.to_json()}, f, indent=2)
+    write_sidecar(root, MOTION_JSON, {"version": VERSION, "height": H, "width": W, "frames": len(arrays), "params": p.to_json()})

@@ -15,18 +15,17 @@ asynchronous copy behind its last picture.  There is no torch fallback: a CPU te
 """
 from __future__ import annotations
 
-import json
 import os
 import re
 import warnings
 import zlib
 
-from . import lib
-from .stream import write_sidecar
+from . import devargs, lib
+from .devargs import MAX_SIDE
+from .stream import read_sidecar, write_sidecar
 
 HASHES_JSON = "hashes.json"
 VERSION, ALGORITHM = 1, "crc32"
-MAX_SIDE = 32768
 MODES = ("strict", "pixels", "warn", "off")
 _DIGEST = re.compile(r"^[0-9a-f]{8}$")
 
@@ -49,20 +48,14 @@ def _slot(out, device, what):
     return out
 
 
-def _launch(name, x, args, out, scratch, what):
-    import ctypes as C
-
-    import torch
-
-    from .engine import _raw_stream
-
-    dev = x.device
+def _launch(name, t, args, out, scratch, what):
+    """`t`: the checked tensor, read in place where devargs.planar allows; args: what follows its strides."""
+    dev = t.device
     out = _slot(out, dev, what)
-    with torch.cuda.device(dev):
-        if scratch is None:
-            scratch = new_scratch(dev)  # (the caching allocator hands it back to this stream only)
-        lib.check(getattr(lib.hip(), name)(x.data_ptr(), *args, out.data_ptr(), scratch.data_ptr(),
-                                           C.c_void_p(_raw_stream(dev.index))), what)
+    x, rs, ps = devargs.planar(t)
+    if scratch is None:
+        scratch = new_scratch(dev)  # (the caching allocator hands it back to this stream only)
+    devargs.launch(name, dev, x.data_ptr(), rs, ps, *args, out.data_ptr(), scratch.data_ptr(), what=what)
     return out
 
 
@@ -70,20 +63,8 @@ def crc32_pixels(picture, size=None, out=None, scratch=None):
     """The `pixels` digest of the size = (height, width) crop (default: all) of a (1, 3, H, W) float32 picture on the
     GPU, read in place: a 1-element uint32 device tensor (`out`, when given: one uint32 element, written).  Enqueued on
     the current stream; nothing is synchronised."""
-    import torch
-
-    from .metrics import _planar
-
-    what = "crc32_pixels"
-    if not torch.is_tensor(picture) or not picture.is_cuda:
-        raise ValueError(f"{what}: pictures live on the GPU (no CPU fallback exists)")
-    if picture.dtype != torch.float32 or picture.dim() != 4 or picture.shape[0] != 1 or picture.shape[1] != 3:
-        raise ValueError(f"{what}: expected a (1, 3, H, W) float32 picture, got {tuple(picture.shape)} {picture.dtype}")
-    h, w = (picture.shape[2], picture.shape[3]) if size is None else (int(size[0]), int(size[1]))
-    if not (0 < h <= min(MAX_SIDE, picture.shape[2]) and 0 < w <= min(MAX_SIDE, picture.shape[3])):
-        raise ValueError(f"{what}: a {h}x{w} crop of a {tuple(picture.shape)} picture (sides within 1..{MAX_SIDE})")
-    x, rs, ps = _planar(picture.detach()[..., :h, :w])
-    return _launch("dcvc_hash_pixels", x, (rs, ps, h, w), out, scratch, what)
+    crop = devargs.checked(picture, "crc32_pixels", at_least=size)
+    return _launch("dcvc_hash_pixels", crop, crop.shape[2:], out, scratch, "crc32_pixels")
 
 
 def crc32_f32(tensor, out=None, scratch=None):
@@ -91,11 +72,8 @@ def crc32_f32(tensor, out=None, scratch=None):
     tensor on the GPU, a view read in place.  Returns as crc32_pixels does."""
     import torch
 
-    from .metrics import _planar
-
     what = "crc32_f32"
-    if not torch.is_tensor(tensor) or not tensor.is_cuda:
-        raise ValueError(f"{what}: tensors live on the GPU (no CPU fallback exists)")
+    devargs.on_gpu(tensor, what, noun="tensor")
     t = tensor.detach()
     if t.dim() == 3:
         t = t[None]
@@ -103,8 +81,7 @@ def crc32_f32(tensor, out=None, scratch=None):
             4 * t.numel() >= 1 << 32:
         raise ValueError(f"{what}: expected a non-empty float32 (1, C, H, W) or (C, H, W) tensor with sides within "
                          f"1..{MAX_SIDE} and less than 4 GiB, got {tuple(tensor.shape)} {tensor.dtype}")
-    x, rs, ps = _planar(t)
-    return _launch("dcvc_hash_f32", x, (rs, ps, t.shape[1], t.shape[2], t.shape[3]), out, scratch, what)
+    return _launch("dcvc_hash_f32", t, t.shape[1:], out, scratch, what)
 
 
 # ---------------------------------------------------------------------------------------------------------- the log
@@ -213,15 +190,8 @@ def parse_hashes(info, where=HASHES_JSON):
 
 def read_hashes(bin_dir):
     """parse_hashes of the folder's hashes.json, or None without the file."""
-    path = os.path.join(bin_dir, HASHES_JSON)
-    if not os.path.exists(path):
-        return None
-    with open(path) as f:
-        try:
-            info = json.load(f)
-        except ValueError as ex:
-            raise ValueError(f"{path}: not JSON ({ex})") from None
-    return parse_hashes(info, path)
+    found = read_sidecar(bin_dir, HASHES_JSON)
+    return None if found is None else parse_hashes(found[1], found[0])
 
 
 # ------------------------------------------------------------------------------------------------------ verification

@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes as C
 from fractions import Fraction
 
-from . import lib
+from . import devargs
 
 LADDER = (50, 63, 79, 100, 126, 159, 200, 252)
 MAX_LADDER = 8          # DCVC_BITS_MAX_LADDER
@@ -113,8 +113,6 @@ class RateSweep:
         one asynchronous copy on the current stream; nothing synchronised."""
         import torch
 
-        from .bitmap import _stream
-
         lad = check_ladder(ladder)
         fac = ladder_factors(lad)
         K, dev = len(lad), y_res.device
@@ -124,10 +122,9 @@ class RateSweep:
         row = torch.empty(N * K + 1, dtype=torch.int64, device=dev)  # (the last slot holds the status word)
         status = row[N * K:].view(torch.int32)
         status.zero_()
-        lib.check(lib.hip().dcvc_bits_sweep_scale(y_res.data_ptr(), scales_hat.data_ptr(), edges.data_ptr(),
-                                                  fac.ctypes.data_as(C.c_void_p), K, cost.data_ptr(), rows, stride,
-                                                  sizes.data_ptr(), offsets.data_ptr(), row.data_ptr(), N, C_, H, W,
-                                                  status.data_ptr(), _stream(dev)), "bits_sweep_scale")
+        devargs.launch("dcvc_bits_sweep_scale", dev, y_res.data_ptr(), scales_hat.data_ptr(), edges.data_ptr(),
+                       fac.ctypes.data_as(C.c_void_p), K, cost.data_ptr(), rows, stride, sizes.data_ptr(), offsets.data_ptr(),
+                       row.data_ptr(), N, C_, H, W, status.data_ptr())
         host = torch.empty(N * K + 1, dtype=torch.int64, pin_memory=True)
         host.copy_(row, non_blocking=True)
         ev = torch.cuda.Event()

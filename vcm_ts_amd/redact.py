@@ -18,14 +18,14 @@ ValueError.
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import lib
+from . import devargs
+from .devargs import whole
 from .roi import MAX_BOXES, MAX_CLASSES, MAX_GROW, FrameBoxes, as_boxes, grid_of
-from .tnr import StreamFilter, _whole
+from .tnr import StreamFilter
 
 TILES, MAX_FILL, MAX_HOLD = (2, 4, 8, 16, 32, 64), 255, 32
 
@@ -61,9 +61,9 @@ class Redact:
         if self.tile is not None and (isinstance(self.tile, bool) or not isinstance(self.tile, (int, np.integer)) or self.tile not in TILES):
             raise ValueError(f"tile must be one of {list(TILES)}, got {self.tile!r}")
         object.__setattr__(self, "tile", None if self.tile is None else int(self.tile))
-        object.__setattr__(self, "fill", None if self.fill is None else _whole("fill", self.fill, 0, MAX_FILL))
-        object.__setattr__(self, "grow", _whole("grow", self.grow, 0, MAX_GROW))
-        object.__setattr__(self, "hold", _whole("hold", self.hold, 0, MAX_HOLD))
+        object.__setattr__(self, "fill", None if self.fill is None else whole("fill", self.fill, 0, MAX_FILL))
+        object.__setattr__(self, "grow", whole("grow", self.grow, 0, MAX_GROW))
+        object.__setattr__(self, "hold", whole("hold", self.hold, 0, MAX_HOLD))
         if not isinstance(self.restorable, (bool, np.bool_)):
             raise ValueError(f"restorable must be True or False, got {self.restorable!r}")
         object.__setattr__(self, "restorable", bool(self.restorable))
@@ -102,15 +102,12 @@ def held_boxes(frames, g, mask, hold):
 
 def _launch(src, out, out_rs, out_ps, h, w, boxes, mask, redact, count, device):
     """One dcvc_redact on the current stream of `device`: src a (1, 3, h, w) view, out the base of the result's crop."""
-    from .engine import _raw_stream
-    from .metrics import _planar
-
-    s, srs, sps = _planar(src)
+    s, srs, sps = devargs.planar(src)
     tile, fill = redact.mode()
     n = len(boxes)
-    lib.check(lib.hip().dcvc_redact(s.data_ptr(), srs, sps, out.data_ptr(), out_rs, out_ps, h, w,
-                                    boxes.array.ctypes.data if n else None, boxes.on_device(device).data_ptr() if n else None, n,
-                                    mask, redact.grow, tile, fill, count.data_ptr(), C.c_void_p(_raw_stream(device.index))), "redact")
+    devargs.launch("dcvc_redact", device, s.data_ptr(), srs, sps, out.data_ptr(), out_rs, out_ps, h, w,
+                   boxes.array.ctypes.data if n else None, boxes.on_device(device).data_ptr() if n else None, n,
+                   mask, redact.grow, tile, fill, count.data_ptr())
 
 
 class Redactor(StreamFilter):
@@ -138,8 +135,6 @@ class Redactor(StreamFilter):
         whose list is empty launches nothing and is returned itself.  Any other is one dcvc_redact launch on the current
         stream from the crop of x_padded into the crop of one of the two buffers, which stays valid until the step after
         the next."""
-        import torch
-
         self._check(x_padded)
         boxes = as_boxes(boxes).validate(self.height, self.width, len(self.names))
         t, self.n = self.n, self.n + 1
@@ -147,8 +142,7 @@ class Redactor(StreamFilter):
             return x_padded
         out = self.bufs[self.launches & 1]
         (h, w), (Hp, Wp) = (self.height, self.width), self.padded
-        with torch.cuda.device(self.device):
-            _launch(x_padded.detach()[..., :h, :w], out, Wp, Hp * Wp, h, w, boxes, self.mask, self.redact, self.count, self.device)
+        _launch(x_padded.detach()[..., :h, :w], out, Wp, Hp * Wp, h, w, boxes, self.mask, self.redact, self.count, self.device)
         self.launches += 1
         self._keep(t, self.count)
         return out
@@ -160,18 +154,15 @@ def redact_picture(x, boxes, redact, names):
     on the current stream, nothing synchronised; an empty list still launches (the result is a copy)."""
     import torch
 
-    from .roi import _picture
-
     if not isinstance(redact, Redact):
         raise ValueError(f"redact: expected a redact.Redact, got {type(redact).__name__}")
     names = tuple(names)
     mask = redact.mask(names)
-    src, _, _ = _picture(x, "x")
+    src = devargs.checked(x, "redact_picture")
     h, w = src.shape[2:]
     boxes = as_boxes(boxes).validate(h, w, len(names))
     hc, wc = grid_of(h, w)
-    with torch.cuda.device(src.device):
-        out = torch.empty((1, 3, h, w), dtype=torch.float32, device=src.device)
-        count = torch.empty((hc, wc), dtype=torch.int16, device=src.device)
-        _launch(src, out, w, h * w, h, w, boxes, mask, redact, count, src.device)
+    out = torch.empty((1, 3, h, w), dtype=torch.float32, device=src.device)
+    count = torch.empty((hc, wc), dtype=torch.int16, device=src.device)
+    _launch(src, out, w, h * w, h, w, boxes, mask, redact, count, src.device)
     return out, count

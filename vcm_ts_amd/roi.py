@@ -11,7 +11,6 @@ current stream and synchronises nothing.  There is no torch fallback: anything t
 """
 from __future__ import annotations
 
-import ctypes as C
 import io
 import math
 import os
@@ -20,10 +19,11 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import lib
+from . import devargs, lib
+from .devargs import MAX_SIDE, whole
 from .yuv import _Indexed, _readinto, _writefrom
 
-MAX_BOXES, MAX_CLASSES, MAX_BORDER, MAX_SIDE = 1024, 4, 64, 32768
+MAX_BOXES, MAX_CLASSES, MAX_BORDER = 1024, 4, 64
 CELL, MAX_GROW, MIN_Q, MAX_Q = 16, 255, 10, 1000  # the q-scale map: cell side in pixels, factors in hundredths
 ORDERS = {"rgb": (0, 1, 2), "gbr": (1, 2, 0)}  # slot j of the 8-bit picture holds channel ORDERS[..][j]
 LAYOUTS = ("planar", "hwc")
@@ -170,11 +170,6 @@ class RoiQ:
         if len(classes) > MAX_CLASSES:
             raise ValueError(f"classes: at most {MAX_CLASSES} factors, got {len(classes)}")
 
-        def whole(name, v, lo, hi, unit):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-                raise ValueError(f"{name} must be an integer within {lo}..{hi} ({unit}), got {v!r}")
-            return int(v)
-
         object.__setattr__(self, "background", whole("background", self.background, MIN_Q, MAX_Q, "hundredths"))
         object.__setattr__(self, "classes", tuple(whole(f"classes[{i}]", v, MIN_Q, MAX_Q, "hundredths")
                                                   for i, v in enumerate(classes)))
@@ -183,9 +178,7 @@ class RoiQ:
     @staticmethod
     def hundredths(value, name="factor"):
         """A float factor snapped to hundredths (the command line's --plate-q 0.6 -> 60)."""
-        if not math.isfinite(value):
-            raise ValueError(f"{name} must be a finite number, got {value!r}")
-        return int(round(float(value) * 100.0))
+        return devargs.hundredths(value, name)
 
     def factors(self):
         """[background, class 0, ...] as the float32 values the kernels multiply with (the HOST's IEEE division)."""
@@ -224,7 +217,8 @@ def q_map(boxes, height, width, roiq, out=None, device=None):
     stream (nothing synchronised): what IntraNoAR / DMC .compress and .decompress take as q_map=.  height, width: the
     UNPADDED picture the boxes live in.  device: where, unless `out` (a contiguous float32 tensor of hc * wc elements) or
     boxes already on a device say so; default the current one."""
-    torch = _torch()
+    import torch
+
     if not isinstance(roiq, RoiQ):
         raise ValueError(f"roiq: expected a RoiQ, got {type(roiq).__name__}")
     H, W = int(height), int(width)
@@ -237,20 +231,15 @@ def q_map(boxes, height, width, roiq, out=None, device=None):
             raise ValueError(f"out: expected a contiguous float32 tensor of {hc} x {wc} elements on the GPU")
         dev = out.device
     elif device is not None:
-        dev = torch.device(device)
+        dev = device
     else:
-        dev = boxes._dev.device if boxes._dev is not None else torch.device("cuda", torch.cuda.current_device())
-    if dev.type != "cuda":
-        raise ValueError("q_map: the map is made on the GPU (no CPU fallback exists)")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+        dev = boxes._dev.device if boxes._dev is not None else "cuda"
+    dev = devargs.cuda_device(dev, "q_map")
     f = np.ascontiguousarray(roiq.factors())
-    with torch.cuda.device(dev):
-        keep, host, devp, n = _box_args(boxes, H, W, len(roiq.classes), dev)
-        if out is None:
-            out = torch.empty((1, 1, hc, wc), dtype=torch.float32, device=dev)
-        lib.check(lib.hip().dcvc_roi_qmap(H, W, host, devp, n, roiq.grow, f.ctypes.data, len(roiq.classes), out.data_ptr(),
-                                          _stream(dev)), "roi_qmap")
+    keep, host, devp, n = _box_args(boxes, H, W, len(roiq.classes), dev)
+    if out is None:
+        out = torch.empty((1, 1, hc, wc), dtype=torch.float32, device=dev)
+    devargs.launch("dcvc_roi_qmap", dev, H, W, host, devp, n, roiq.grow, f.ctypes.data, len(roiq.classes), out.data_ptr())
     return out.view(1, 1, hc, wc)
 
 
@@ -259,37 +248,10 @@ def as_roi(roi):
 
 
 # ------------------------------------------------------------------------------------------------------------ device
-def _torch():
-    import torch
-
-    return torch
-
-
-def _stream(device):
-    from .engine import _raw_stream
-
-    return C.c_void_p(_raw_stream(device.index))
-
-
-def _picture(t, what, like=None):
-    from .metrics import _planar
-
-    torch = _torch()
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise ValueError(f"{what}: pictures live on the GPU (no CPU fallback exists)")
-    if t.dtype != torch.float32 or t.dim() != 4 or t.shape[0] != 1 or t.shape[1] != 3:
-        raise ValueError(f"{what}: expected a (1, 3, H, W) float32 picture, got {tuple(t.shape)} {t.dtype}")
-    H, W = t.shape[2:]
-    if not (0 < H <= MAX_SIDE and 0 < W <= MAX_SIDE):
-        raise ValueError(f"{what}: picture sides must be within 1..{MAX_SIDE}, got {W}x{H}")
-    if like is not None and (t.shape != like.shape or t.device != like.device):
-        raise ValueError(f"{what}: {tuple(t.shape)} on {t.device} does not match {tuple(like.shape)} on {like.device}")
-    return _planar(t.detach())
-
-
 def _u8_strides(t, layout, H, W, what):
     """(chan stride, row stride, pixel stride) of an 8-bit picture: planar (3, H, W) or interleaved (H, W, 3)."""
-    torch = _torch()
+    import torch
+
     shape = (3, H, W) if layout == "planar" else (H, W, 3)
     if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8 or tuple(t.shape) != shape:
         raise ValueError(f"{what}: expected a {shape} uint8 tensor on the GPU for layout {layout!r}")
@@ -320,20 +282,20 @@ def _box_args(boxes, H, W, n_classes, device):
 def residual_layer(source, recon, boxes, layout="planar", order="rgb", out=None):
     """compute_residuals: clip(code(source) - code(recon) + 128, 0, 255) inside the boxes, 0 outside, as a uint8 tensor:
     (3, H, W) planes (layout "planar"; order "gbr" gives the planes of ffmpeg's gbrp) or an (H, W, 3) picture ("hwc")."""
-    torch = _torch()
+    import torch
+
     if layout not in LAYOUTS:
         raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
     o = _order(order)
-    s, s_rs, s_ps = _picture(source, "source")
-    r, r_rs, r_ps = _picture(recon, "recon", like=source)
+    s, s_rs, s_ps = devargs.picture(source, "source")
+    r, r_rs, r_ps = devargs.picture(recon, "recon", like=source)
     H, W = s.shape[2:]
-    with torch.cuda.device(s.device):
-        keep, host, dev, n = _box_args(boxes, H, W, MAX_CLASSES, s.device)
-        if out is None:
-            out = torch.empty((3, H, W) if layout == "planar" else (H, W, 3), dtype=torch.uint8, device=s.device)
-        cs, rs, px = _u8_strides(out, layout, H, W, "out")
-        lib.check(lib.hip().dcvc_roi_residual(s.data_ptr(), s_rs, s_ps, r.data_ptr(), r_rs, r_ps, H, W, host, dev, n,
-                                              out.data_ptr(), cs, rs, px, *o, _stream(s.device)), "roi_residual")
+    keep, host, dev, n = _box_args(boxes, H, W, MAX_CLASSES, s.device)
+    if out is None:
+        out = torch.empty((3, H, W) if layout == "planar" else (H, W, 3), dtype=torch.uint8, device=s.device)
+    cs, rs, px = _u8_strides(out, layout, H, W, "out")
+    devargs.launch("dcvc_roi_residual", s.device, s.data_ptr(), s_rs, s_ps, r.data_ptr(), r_rs, r_ps, H, W, host, dev, n,
+                   out.data_ptr(), cs, rs, px, *o)
     return out
 
 
@@ -342,9 +304,10 @@ def fuse(base, residual, boxes, classes, out=None, layout=None, order="rgb"):
     and truncated as the reference does, returned as the (1, 3, H, W) float32 picture of those codes / 255 -- what
     save_torch_image and yuv.rgb_to_yuv420 take.  `residual`: what residual_layer returned (layout taken from its
     shape unless given; `order` as it was written)."""
-    torch = _torch()
+    import torch
+
     o = _order(order)
-    b, b_rs, b_ps = _picture(base, "base")
+    b, b_rs, b_ps = devargs.picture(base, "base")
     H, W = b.shape[2:]
     if layout is None:
         shape = tuple(residual.shape) if torch.is_tensor(residual) else None
@@ -357,18 +320,17 @@ def fuse(base, residual, boxes, classes, out=None, layout=None, order="rgb"):
     if layout not in LAYOUTS:
         raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
     recs, n_classes = _class_records(classes)
-    with torch.cuda.device(b.device):
-        cs, rs, px = _u8_strides(residual, layout, H, W, "residual")
-        if residual.device != b.device:
-            raise ValueError("residual and base are on different devices")
-        keep, host, dev, n = _box_args(boxes, H, W, n_classes, b.device)
-        if out is None:
-            out = torch.empty((1, 3, H, W), dtype=torch.float32, device=b.device)
-        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (1, 3, H, W) and
-                  out.device == b.device and out.is_contiguous()):
-            raise ValueError(f"out: expected a contiguous (1, 3, {H}, {W}) float32 tensor on {b.device}")
-        lib.check(lib.hip().dcvc_roi_fuse(b.data_ptr(), b_rs, b_ps, residual.data_ptr(), cs, rs, px, *o, H, W, host, dev, n,
-                                          recs, n_classes, out.data_ptr(), W, H * W, _stream(b.device)), "roi_fuse")
+    cs, rs, px = _u8_strides(residual, layout, H, W, "residual")
+    if residual.device != b.device:
+        raise ValueError("residual and base are on different devices")
+    keep, host, dev, n = _box_args(boxes, H, W, n_classes, b.device)
+    if out is None:
+        out = torch.empty((1, 3, H, W), dtype=torch.float32, device=b.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (1, 3, H, W) and
+              out.device == b.device and out.is_contiguous()):
+        raise ValueError(f"out: expected a contiguous (1, 3, {H}, {W}) float32 tensor on {b.device}")
+    devargs.launch("dcvc_roi_fuse", b.device, b.data_ptr(), b_rs, b_ps, residual.data_ptr(), cs, rs, px, *o, H, W, host, dev, n,
+                   recs, n_classes, out.data_ptr(), W, H * W)
     return out
 
 
@@ -376,20 +338,20 @@ def region_sse(a, b, boxes, classes, sums=None):
     """calc_visual_metrics' sums on 8-bit codes: a (3,) int64 device tensor of (squared error inside the boxes shrunk by
     their class's shrink, squared error outside, pixels inside), each error summed over the 3 channels.  `sums`: add
     onto these instead of onto zeros."""
-    torch = _torch()
-    x, x_rs, x_ps = _picture(a, "a")
-    y, y_rs, y_ps = _picture(b, "b", like=a)
+    import torch
+
+    x, x_rs, x_ps = devargs.picture(a, "a")
+    y, y_rs, y_ps = devargs.picture(b, "b", like=a)
     H, W = x.shape[2:]
     recs, n_classes = _class_records(classes)
-    with torch.cuda.device(x.device):
-        keep, host, dev, n = _box_args(boxes, H, W, n_classes, x.device)
-        if sums is None:
-            sums = torch.zeros(3, dtype=torch.int64, device=x.device)
-        elif not (torch.is_tensor(sums) and sums.dtype == torch.int64 and tuple(sums.shape) == (3,) and
-                  sums.device == x.device and sums.is_contiguous()):
-            raise ValueError("sums: expected a contiguous (3,) int64 tensor on the pictures' device")
-        lib.check(lib.hip().dcvc_roi_sse(x.data_ptr(), x_rs, x_ps, y.data_ptr(), y_rs, y_ps, H, W, host, dev, n, recs,
-                                         n_classes, sums.data_ptr(), _stream(x.device)), "roi_sse")
+    keep, host, dev, n = _box_args(boxes, H, W, n_classes, x.device)
+    if sums is None:
+        sums = torch.zeros(3, dtype=torch.int64, device=x.device)
+    elif not (torch.is_tensor(sums) and sums.dtype == torch.int64 and tuple(sums.shape) == (3,) and
+              sums.device == x.device and sums.is_contiguous()):
+        raise ValueError("sums: expected a contiguous (3,) int64 tensor on the pictures' device")
+    devargs.launch("dcvc_roi_sse", x.device, x.data_ptr(), x_rs, x_ps, y.data_ptr(), y_rs, y_ps, H, W, host, dev, n, recs,
+                   n_classes, sums.data_ptr())
     return sums
 
 

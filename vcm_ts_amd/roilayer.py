@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import lib
+from . import devargs, lib
 from . import roi as X
 
 MAX_STEP, HEADER, SLOT, CELL_MAX, VERSION, BAD_STREAM = 64, 8, 768, 774, 1, 1
@@ -28,9 +28,7 @@ _REFUSALS = {-16: "truncated record", -17: "bad magic", -18: "unknown version", 
 
 
 def check_step(step):
-    if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 1 <= step <= MAX_STEP:
-        raise ValueError(f"residual step must be an integer within 1..{MAX_STEP}, got {step!r}")
-    return int(step)
+    return devargs.whole("residual step", step, 1, MAX_STEP)
 
 
 def _size(height, width):
@@ -162,24 +160,23 @@ def encode_layer(source, recon, boxes, step=1, pool=None):
     import torch
 
     step = check_step(step)
-    s, s_rs, s_ps = X._picture(source, "source")
-    r, r_rs, r_ps = X._picture(recon, "recon", like=source)
+    s, s_rs, s_ps = devargs.picture(source, "source")
+    r, r_rs, r_ps = devargs.picture(recon, "recon", like=source)
     H, W = s.shape[2:]
     cells, _ = active_cells(boxes, H, W)
     A = len(cells)
     capacity = HEADER + CELL_MAX * A
-    with torch.cuda.device(s.device):
-        keep, host_boxes, dev_boxes, n = X._box_args(boxes, H, W, X.MAX_CLASSES, s.device)
-        pin, table = _table(cells, np.zeros_like(cells), s.device)
-        out = torch.empty(4 + capacity, dtype=torch.uint8, device=s.device)  # the size word, then the record
-        staging = torch.empty(SLOT * A, dtype=torch.uint8, device=s.device) if A else None
-        lib.check(lib.hip().dcvc_roil_encode(s.data_ptr(), s_rs, s_ps, r.data_ptr(), r_rs, r_ps, H, W, host_boxes, dev_boxes, n,
-                                             step, table.data_ptr() if A else None, A, staging.data_ptr() if A else None,
-                                             out.data_ptr() + 4, capacity, out.data_ptr(), X._stream(s.device)), "roil_encode")
-        host = _pinned(4 + capacity, pool)
-        host[:4 + capacity].copy_(out, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(s.device))
+    keep, host_boxes, dev_boxes, n = X._box_args(boxes, H, W, X.MAX_CLASSES, s.device)
+    pin, table = _table(cells, np.zeros_like(cells), s.device)
+    out = torch.empty(4 + capacity, dtype=torch.uint8, device=s.device)  # the size word, then the record
+    staging = torch.empty(SLOT * A, dtype=torch.uint8, device=s.device) if A else None
+    devargs.launch("dcvc_roil_encode", s.device, s.data_ptr(), s_rs, s_ps, r.data_ptr(), r_rs, r_ps, H, W, host_boxes, dev_boxes, n,
+                   step, table.data_ptr() if A else None, A, staging.data_ptr() if A else None,
+                   out.data_ptr() + 4, capacity, out.data_ptr())
+    host = _pinned(4 + capacity, pool)
+    host[:4 + capacity].copy_(out, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(s.device))
     return PendingRecord(host, ev, A, (keep, pin))
 
 
@@ -197,14 +194,7 @@ def decode_layer(record, boxes, height, width, layout="planar", order="rgb", out
     b = bytes(record)
     cells, counts = active_cells(boxes, H, W)
     info = check_record(b, counts)
-    if out is not None:
-        dev = out.device
-    else:
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if dev.type != "cuda":
-        raise ValueError("decode_layer: the picture is made on the GPU (no CPU fallback exists)")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = devargs.cuda_device(out.device if out is not None else "cuda" if device is None else device, "decode_layer")
     A = len(cells)
     with torch.cuda.device(dev):
         keep, host_boxes, dev_boxes, n = X._box_args(boxes, H, W, X.MAX_CLASSES, dev)
@@ -217,7 +207,7 @@ def decode_layer(record, boxes, height, width, layout="planar", order="rgb", out
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         rc = lib.hip().dcvc_roil_decode(b, rec_dev.data_ptr(), len(b), H, W, host_boxes, dev_boxes, n,
                                         table.data_ptr() if A else None, out.data_ptr(), cs, rs, px, *o, status.data_ptr(),
-                                        X._stream(dev))
+                                        devargs.stream(dev))
         if rc in _REFUSALS:
             raise RoiLayerError(f"{_REFUSALS[rc]} (status {rc})")
         lib.check(rc, "roil_decode")

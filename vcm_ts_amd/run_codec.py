@@ -663,18 +663,15 @@ def _aq_args(aq):
 def read_roiq(bin_dir, roi=None):
     """The roi.RoiQ the .bin files of `bin_dir` were coded with, or None without a roiq.json.  Refused by name: the file
     without `roi` (the maps are rebuilt from the boxes), class names that are not the roi's, values out of range."""
-    import json
-
     from . import roi as X
 
-    path = os.path.join(bin_dir, ROIQ_JSON)
-    if not os.path.exists(path):
+    found = S.read_sidecar(bin_dir, ROIQ_JSON)
+    if found is None:
         return None
+    path, info = found
     if roi is None:
         raise ValueError(f"{path}: these pictures were coded with q-scale maps made from ROI boxes; decoding them needs the "
                          f"same boxes (roi=, --roi-root)")
-    with open(path) as f:
-        info = json.load(f)
     try:
         return X.RoiQ.from_json(info, X.as_roi(roi).names)
     except ValueError as ex:
@@ -692,13 +689,10 @@ def read_gop_plan(bin_dir, gop=None):
     """(GopPlan of the .bin files in `bin_dir`, its longest GOP): from gops.json when encode left one, else an I picture
     every `gop` (default 32) pictures.  Refused by name: a plan whose frame count is not the number of .bin files, and an
     explicit `gop` that is not the plan's."""
-    import json
-
-    n, path = _count_bins(bin_dir), os.path.join(bin_dir, GOPS_JSON)
-    if not os.path.exists(path):
+    n, found = _count_bins(bin_dir), S.read_sidecar(bin_dir, GOPS_JSON)
+    if found is None:
         return GopPlan.fixed(n, gop or 32), gop or 32
-    with open(path) as f:
-        info = json.load(f)
+    path, info = found
     try:
         plan = GopPlan.from_json(info)
     except ValueError as ex:
@@ -1333,15 +1327,12 @@ def write_sequence_info(bin_dir, width, height, frames, gop, fps, spec, containe
 
 def read_sequence_info(bin_dir):
     """The dictionary write_sequence_info stored (with "color" as a ColorSpec), or None without the file."""
-    import json
-
     from .yuv import ColorSpec
 
-    path = os.path.join(bin_dir, SEQUENCE_JSON)
-    if not os.path.exists(path):
+    found = S.read_sidecar(bin_dir, SEQUENCE_JSON)
+    if found is None:
         return None
-    with open(path) as f:
-        info = json.load(f)
+    info = found[1]
     info["color"] = ColorSpec.from_json(info["color"])
     info["fps"] = tuple(info["fps"]) if info.get("fps") else None
     return info

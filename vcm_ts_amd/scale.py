@@ -13,18 +13,16 @@ uploads).  There is no torch fallback: anything the kernel does not take is a Va
 """
 from __future__ import annotations
 
-import ctypes as C
-import json
-import os
 import zlib
 from fractions import Fraction
 
 import numpy as np
 
-from . import lib
+from . import devargs
+from .devargs import MAX_SIDE
 
 SCALE_JSON = "scale.json"
-VERSION, FILTER, UNIT, MAX_TAPS, MAX_SIDE = 1, "lanczos3", 16384, 32, 32768
+VERSION, FILTER, UNIT, MAX_TAPS = 1, "lanczos3", 16384, 32
 MIN_RATIO = Fraction(1, 4)
 TABLES = ("down_y", "down_x", "up_y", "up_x")
 
@@ -133,10 +131,7 @@ def _planes(t, what, out=False):
     ValueError)."""
     import torch
 
-    from .metrics import _planar
-
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise ValueError(f"{what}: pictures live on the GPU (no CPU fallback exists)")
+    devargs.on_gpu(t, what)
     if t.dtype != torch.float32 or t.dim() < 3 or t.shape[-3] != 3 or t.numel() == 0:
         raise ValueError(f"{what}: expected a (..., 3, H, W) float32 picture, got {tuple(t.shape)} {t.dtype}")
     H, W = t.shape[-2:]
@@ -151,7 +146,7 @@ def _planes(t, what, out=False):
             t4 = t.reshape(-1, 3, H, W)
     else:
         t4 = t
-    p, rs, ps = _planar(t4)
+    p, rs, ps = devargs.planar(t4)
     if out and p is not t4:
         raise ValueError(f"{what}: out= must hold evenly spaced planes of dense rows, got strides {t.stride()}")
     return p, rs, ps, 3 * p.shape[0]
@@ -161,8 +156,6 @@ def scale_planes(x, size, y_axis, x_axis, out=None, what="scale"):
     """One launch of dcvc_scale_planes on the current stream: `x` (..., 3, H_in, W_in) -> (..., 3, *size) through the
     two tables.  out: a float32 tensor of that shape on x's device, written in place (a strided view is fine)."""
     import torch
-
-    from .engine import _raw_stream
 
     src, s_rs, s_ps, planes = _planes(x, what)
     H_in, W_in = src.shape[-2:]
@@ -175,10 +168,8 @@ def scale_planes(x, size, y_axis, x_axis, out=None, what="scale"):
     dst, d_rs, d_ps, _ = _planes(out, f"{what}: out=", out=True)
     if len(y_axis.start) != H_out or len(x_axis.start) != W_out:
         raise ValueError(f"{what}: tables of {len(y_axis.start)}x{len(x_axis.start)} outputs for a {H_out}x{W_out} picture")
-    with torch.cuda.device(src.device):
-        lib.check(lib.hip().dcvc_scale_planes(src.data_ptr(), s_rs, s_ps, dst.data_ptr(), d_rs, d_ps, planes, H_in, W_in,
-                                              H_out, W_out, *x_axis.args(), *y_axis.args(),
-                                              C.c_void_p(_raw_stream(src.device.index))), what)
+    devargs.launch("dcvc_scale_planes", src.device, src.data_ptr(), s_rs, s_ps, dst.data_ptr(), d_rs, d_ps, planes, H_in, W_in,
+                   H_out, W_out, *x_axis.args(), *y_axis.args(), what=what)
     return out
 
 
@@ -192,11 +183,7 @@ class Scale:
 
         self.full, self.ratio = (int(full[0]), int(full[1])), as_ratio(ratio)
         self.base = base_size(self.full[0], self.full[1], self.ratio)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("Scale: the resampler runs on the GPU (no CPU fallback exists)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = devargs.cuda_device(device, "Scale")
         self.tables = _tables(self.full, self.base)
         self.axes = {name: _Axis(self.tables[name], self.device) for name in TABLES}
         torch.cuda.synchronize(self.device)
@@ -275,12 +262,7 @@ def parse_scale(info, where=SCALE_JSON):
 
 def read_scale(bin_dir):
     """parse_scale of the folder's scale.json, or None without the file."""
-    path = os.path.join(bin_dir, SCALE_JSON)
-    if not os.path.exists(path):
-        return None
-    with open(path) as f:
-        try:
-            info = json.load(f)
-        except ValueError as ex:
-            raise ValueError(f"{path}: not JSON ({ex})") from None
-    return parse_scale(info, path)
+    from .stream import read_sidecar
+
+    found = read_sidecar(bin_dir, SCALE_JSON)
+    return None if found is None else parse_scale(found[1], found[0])

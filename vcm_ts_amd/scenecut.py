@@ -20,9 +20,10 @@ import bisect
 
 import numpy as np
 
-from . import lib
+from . import devargs
+from .devargs import MAX_SIDE
 
-COUNTERS, MAX_SIDE = 512, 32768
+COUNTERS = 512
 
 
 class SceneScan:
@@ -32,11 +33,7 @@ class SceneScan:
     def __init__(self, device, height, width, capacity):
         import torch
 
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("SceneScan: pictures live on the GPU (no CPU fallback exists)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = devargs.cuda_device(device, "SceneScan")
         if not (0 < int(height) <= MAX_SIDE and 0 < int(width) <= MAX_SIDE):
             raise ValueError(f"picture sides must be within 1..{MAX_SIDE}, got {width}x{height}")
         if int(capacity) < 1:
@@ -50,32 +47,17 @@ class SceneScan:
     def add(self, picture, row=None):
         """Count the height x width crop of a (1, 3, Hp, Wp) float32 picture, read in place, into the next row (or ONTO
         row `row`, which then is not advanced) on the current stream."""
-        import ctypes as C
-
         import torch
 
-        from .engine import _raw_stream
-
-        if not torch.is_tensor(picture) or not picture.is_cuda:
-            raise ValueError("SceneScan.add: pictures live on the GPU (no CPU fallback exists)")
-        if picture.device != self.device:
-            raise ValueError(f"SceneScan.add: the picture is on {picture.device}, the scan on {self.device}")
-        if picture.dtype != torch.float32 or picture.dim() != 4 or picture.shape[0] != 1 or picture.shape[1] != 3 or \
-                picture.shape[2] < self.height or picture.shape[3] < self.width:
-            raise ValueError(f"SceneScan.add: expected a (1, 3, >={self.height}, >={self.width}) float32 picture, got "
-                             f"{tuple(picture.shape)} {picture.dtype}")
+        crop = devargs.checked(picture, "SceneScan.add", device=self.device, at_least=(self.height, self.width), owner="scan")
         at = self.n if row is None else int(row)
         if not 0 <= at < self.capacity:
             raise ValueError(f"SceneScan.add: row {at} of a scan of {self.capacity} pictures")
-        from .metrics import _planar
-
-        x, rs, ps = _planar(picture.detach()[..., :self.height, :self.width])
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream(self.device)
-            if cur != self._stream:
-                cur.wait_event(self._zeroed)  # (a device-side dependency: the host waits for nothing)
-            lib.check(lib.hip().dcvc_scene_hist(x.data_ptr(), rs, ps, self.height, self.width, self.hist[at].data_ptr(),
-                                                C.c_void_p(_raw_stream(self.device.index))), "scene_hist")
+        x, rs, ps = devargs.planar(crop)
+        cur = torch.cuda.current_stream(self.device)
+        if cur != self._stream:
+            cur.wait_event(self._zeroed)  # (a device-side dependency: the host waits for nothing)
+        devargs.launch("dcvc_scene_hist", self.device, x.data_ptr(), rs, ps, self.height, self.width, self.hist[at].data_ptr())
         if row is None:
             self.n += 1
 

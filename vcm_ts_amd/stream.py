@@ -67,6 +67,21 @@ def write_sidecar(bin_dir, name, info):
     return info
 
 
+def read_sidecar(bin_dir, name):
+    """(path, what it holds) of the JSON file `name` beside the .bin files of `bin_dir`, or None without the file.  A
+    file that does not parse is a ValueError that names its path."""
+    import json
+
+    path = os.path.join(bin_dir, name)
+    if not os.path.exists(path):
+        return None
+    with open(path) as f:
+        try:
+            return path, json.load(f)
+        except ValueError as ex:
+            raise ValueError(f"{path}: not JSON ({ex})") from None
+
+
 def encode_i(height, width, q_index, bit_stream, output):
     with open(output, "wb") as f:
         f.write(_I_HEAD.pack(height, width, q_index, len(bit_stream)))

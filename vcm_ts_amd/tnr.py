@@ -18,22 +18,16 @@ ValueError.
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import lib
-from .roi import MAX_SIDE, grid_of
+from . import devargs
+from .devargs import MAX_SIDE, whole
+from .roi import grid_of
 
 MAX_T, MAX_FLOOR, MAX_P, FULL = 64, 255, 255, 256
 ROWS = 64  # pictures' totals kept on the device between two copies to the host
-
-
-def _whole(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-        raise ValueError(f"{name} must be an integer within {lo}..{hi}, got {v!r}")
-    return int(v)
 
 
 @dataclass(frozen=True)
@@ -48,9 +42,9 @@ class TNR:
     pixel: int = None
 
     def __post_init__(self):
-        object.__setattr__(self, "threshold", _whole("threshold", self.threshold, 1, MAX_T))
-        object.__setattr__(self, "floor", _whole("floor", self.floor, 1, MAX_FLOOR))
-        object.__setattr__(self, "pixel", min(MAX_P, 3 * self.threshold) if self.pixel is None else _whole("pixel", self.pixel, 0, MAX_P))
+        object.__setattr__(self, "threshold", whole("threshold", self.threshold, 1, MAX_T))
+        object.__setattr__(self, "floor", whole("floor", self.floor, 1, MAX_FLOOR))
+        object.__setattr__(self, "pixel", min(MAX_P, 3 * self.threshold) if self.pixel is None else whole("pixel", self.pixel, 0, MAX_P))
 
     def table(self):
         """wtab of dcvc_tnr_step: the weight of the current picture by the window's mean difference a = 0 .. 255, as
@@ -77,12 +71,7 @@ class StreamFilter:
         from . import stream as S
         from .goplog import GopLog
 
-        name = type(self).__name__
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError(f"{name}: pictures live on the GPU (no CPU fallback exists)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = devargs.cuda_device(device, type(self).__name__)
         self.height, self.width = int(size[0]), int(size[1])
         if not (0 < self.height <= MAX_SIDE and 0 < self.width <= MAX_SIDE):
             raise ValueError(f"picture sides must be within 1..{MAX_SIDE}, got {self.width}x{self.height}")
@@ -102,16 +91,7 @@ class StreamFilter:
         return self._log.done
 
     def _check(self, x):
-        import torch
-
-        name = type(self).__name__
-        if not torch.is_tensor(x) or not x.is_cuda:
-            raise ValueError(f"{name}.step: pictures live on the GPU (no CPU fallback exists)")
-        if x.device != self.device:
-            raise ValueError(f"{name}.step: the picture is on {x.device}, the {self.noun} on {self.device}")
-        if x.dtype != torch.float32 or tuple(x.shape) != (1, 3) + self.padded:
-            raise ValueError(f"{name}.step: expected a (1, 3, {self.padded[0]}, {self.padded[1]}) float32 picture, got "
-                             f"{tuple(x.shape)} {x.dtype}")
+        devargs.checked(x, f"{type(self).__name__}.step", device=self.device, exact=self.padded, owner=self.noun)
 
     def _keep(self, t, *cells):
         """Step t's totals: one small reduction per tensor of `cells` behind the launch; the host looks at them per GOP."""
@@ -166,11 +146,6 @@ class TnrFilter(StreamFilter):
         itself; it becomes the next step's reference.  A P picture is one dcvc_tnr_step launch on the current stream from
         the crops of x_padded and of the previous step's result into the crop of one of the two buffers, which stays valid
         until the step after the next."""
-        import torch
-
-        from .engine import _raw_stream
-        from .metrics import _planar
-
         self._check(x_padded)
         t, self.n = self.n, self.n + 1
         if intra:
@@ -181,12 +156,10 @@ class TnrFilter(StreamFilter):
             raise ValueError("TnrFilter.step: the first picture of a stream is an I picture")
         out = self.bufs[0] if self.ref is not self.bufs[0] else self.bufs[1]
         (h, w), (Hp, Wp) = (self.height, self.width), self.padded
-        cur, crs, cps = _planar(x_padded.detach()[..., :h, :w])  # (the crops, read in place)
-        ref, rrs, rps = _planar(self.ref[..., :h, :w])
-        with torch.cuda.device(self.device):
-            lib.check(lib.hip().dcvc_tnr_step(cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, out.data_ptr(), Wp, Hp * Wp, h, w,
-                                              self.wtab.data_ptr(), self.tnr.pixel, self.sad.data_ptr(), self.held.data_ptr(),
-                                              C.c_void_p(_raw_stream(self.device.index))), "tnr_step")
+        cur, crs, cps = devargs.planar(x_padded.detach()[..., :h, :w])  # (the crops, read in place)
+        ref, rrs, rps = devargs.planar(self.ref[..., :h, :w])
+        devargs.launch("dcvc_tnr_step", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, out.data_ptr(), Wp, Hp * Wp,
+                       h, w, self.wtab.data_ptr(), self.tnr.pixel, self.sad.data_ptr(), self.held.data_ptr())
         self.launches += 1
         self._keep(t, self.held, self.sad)
         self.ref = out

@@ -17,11 +17,11 @@ import math
 import os
 from dataclasses import asdict, dataclass
 
-from . import lib
+from . import devargs, lib
+from .devargs import MAX_SIDE
 
 MATRICES = {"bt709": 0, "bt601": 1}
 SITINGS = {"left": 0, "center": 1}
-MAX_SIDE = 32768
 
 
 @dataclass(frozen=True)
@@ -74,27 +74,14 @@ def frame_bytes(height, width, bit_depth=8):
 
 
 # --------------------------------------------------------------------------------------------------- device conversion
-def _torch():
+def _sample_dtype(spec):
     import torch
 
-    return torch
-
-
-def _stream(device):
-    from .engine import _raw_stream
-
-    return C.c_void_p(_raw_stream(device.index))
-
-
-def _sample_dtype(spec):
-    torch = _torch()
     return torch.uint8 if spec.bit_depth == 8 else torch.int16
 
 
 def _check_plane(t, rows, cols, spec, what):
-    torch = _torch()
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise ValueError(f"{what}: sample planes live on the GPU (no CPU fallback exists)")
+    devargs.on_gpu(t, what, noun="sample plane")
     if t.dtype != _sample_dtype(spec):
         raise ValueError(f"{what}: {spec.bit_depth}-bit samples are {_sample_dtype(spec)}, got {t.dtype}")
     if t.dim() != 2 or tuple(t.shape) != (rows, cols) or t.stride(1) != 1 or t.stride(0) < cols:
@@ -111,7 +98,8 @@ def split_planes(frame, height, width):
 
 def planes_to_rgb(y, u, v, spec, out_size=None, quantize8=False):
     """Three device sample planes (rows may be strided) -> (1, 3, out_H, out_W) float32, zero beyond the picture."""
-    torch = _torch()
+    import torch
+
     if not torch.is_tensor(y) or y.dim() != 2:
         raise ValueError("planes_to_rgb takes 2-D sample planes")
     H, W = y.shape
@@ -125,11 +113,9 @@ def planes_to_rgb(y, u, v, spec, out_size=None, quantize8=False):
     if oh < H or ow < W or oh > MAX_SIDE or ow > MAX_SIDE:
         raise ValueError(f"output size {(oh, ow)} does not hold a {(H, W)} picture")
     cc = spec.coeffs()
-    with torch.cuda.device(y.device):
-        out = torch.empty((1, 3, oh, ow), dtype=torch.float32, device=y.device)
-        lib.check(lib.hip().dcvc_yuv420_to_rgb(y.data_ptr(), u.data_ptr(), v.data_ptr(), H, W, y.stride(0), u.stride(0),
-                                               C.byref(cc), out.data_ptr(), oh, ow, ow, oh * ow, int(bool(quantize8)),
-                                               _stream(y.device)), "yuv420_to_rgb")
+    out = torch.empty((1, 3, oh, ow), dtype=torch.float32, device=y.device)
+    devargs.launch("dcvc_yuv420_to_rgb", y.device, y.data_ptr(), u.data_ptr(), v.data_ptr(), H, W, y.stride(0), u.stride(0),
+                   C.byref(cc), out.data_ptr(), oh, ow, ow, oh * ow, int(bool(quantize8)))
     return out
 
 
@@ -140,10 +126,8 @@ def yuv420_to_rgb(frame, height, width, spec=ColorSpec(), pad=True, quantize8=Fa
     floats uint8 / 255.0 has on the host, i.e. the picture a PNG of the rounded pixels would give encode_folder."""
     from . import stream as S
 
-    torch = _torch()
     check_size(height, width)
-    if not torch.is_tensor(frame) or not frame.is_cuda:
-        raise ValueError("yuv420_to_rgb runs on the GPU only (no CPU fallback exists)")
+    devargs.on_gpu(frame, "yuv420_to_rgb", noun="I420 buffer")
     if frame.dtype != _sample_dtype(spec):
         raise ValueError(f"{spec.bit_depth}-bit samples are {_sample_dtype(spec)}, got {frame.dtype}")
     if not frame.is_contiguous() or frame.numel() != frame_samples(height, width):
@@ -159,30 +143,22 @@ def rgb_to_yuv420(rgb, height, width, spec=ColorSpec(), source=None):
     """(1, 3, >=height, >=width) float32 on the GPU (clamped to [0, 1] as it is loaded; the top-left height x width
     pixels are read in place) -> the I420 device buffer.  With `source` (the I420 buffer the picture came from): also a
     (3,) int64 device tensor, the sums of squared sample differences of the Y, U and V planes (psnr_yuv)."""
-    from .metrics import _planar
+    import torch
 
-    torch = _torch()
     check_size(height, width)
-    if not torch.is_tensor(rgb) or not rgb.is_cuda:
-        raise ValueError("rgb_to_yuv420 runs on the GPU only (no CPU fallback exists)")
-    if rgb.dtype != torch.float32 or rgb.dim() != 4 or rgb.shape[0] != 1 or rgb.shape[1] != 3:
-        raise ValueError(f"rgb_to_yuv420 takes a (1, 3, H, W) float32 picture, got {tuple(rgb.shape)} {rgb.dtype}")
-    if rgb.shape[2] < height or rgb.shape[3] < width:
-        raise ValueError(f"a {tuple(rgb.shape[2:])} picture does not hold {(height, width)}")
+    crop = devargs.checked(rgb, "rgb_to_yuv420", at_least=(height, width))
     if source is not None:
         if not torch.is_tensor(source) or source.device != rgb.device or source.dtype != _sample_dtype(spec) or \
                 not source.is_contiguous() or source.numel() != frame_samples(height, width):
             raise ValueError("source must be the contiguous I420 device buffer of the same size and depth")
     cc = spec.coeffs()
-    with torch.cuda.device(rgb.device):
-        crop, rs, ps = _planar(rgb.detach()[..., :height, :width])
-        out = torch.empty(frame_samples(height, width), dtype=_sample_dtype(spec), device=rgb.device)
-        y, u, v = split_planes(out, height, width)
-        src = (None, None, None) if source is None else tuple(t.data_ptr() for t in split_planes(source, height, width))
-        sums = None if source is None else torch.zeros(3, dtype=torch.int64, device=rgb.device)
-        lib.check(lib.hip().dcvc_rgb_to_yuv420(crop.data_ptr(), height, width, rs, ps, C.byref(cc), y.data_ptr(), u.data_ptr(),
-                                               v.data_ptr(), width, width // 2, *src, width, width // 2,
-                                               None if sums is None else sums.data_ptr(), _stream(rgb.device)), "rgb_to_yuv420")
+    crop, rs, ps = devargs.planar(crop)
+    out = torch.empty(frame_samples(height, width), dtype=_sample_dtype(spec), device=rgb.device)
+    y, u, v = split_planes(out, height, width)
+    src = (None, None, None) if source is None else tuple(t.data_ptr() for t in split_planes(source, height, width))
+    sums = None if source is None else torch.zeros(3, dtype=torch.int64, device=rgb.device)
+    devargs.launch("dcvc_rgb_to_yuv420", rgb.device, crop.data_ptr(), height, width, rs, ps, C.byref(cc), y.data_ptr(), u.data_ptr(),
+                   v.data_ptr(), width, width // 2, *src, width, width // 2, None if sums is None else sums.data_ptr())
     return out if source is None else (out, sums)
 
 
