@@ -1,5 +1,6 @@
 """Shared helpers for the test-suite (the only place, with bench.py's cpu_baseline leg and
 __graft_entry__.smoke(), that may touch oracle/)."""
+import importlib.util
 import os
 import sys
 
@@ -38,3 +39,11 @@ def stats(t):
 
 def crop(t):
     return t.detach()[..., :8, :8].contiguous().cpu().numpy().astype(np.float32)
+
+
+def load_tool(tool):
+    """tools/<tool>.py as a fresh module under a name of its own: it takes tools.timing.SIZE as it is now."""
+    spec = importlib.util.spec_from_file_location(f"fresh_{tool}", os.path.join(ROOT, "tools", f"{tool}.py"))
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    return module

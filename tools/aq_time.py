@@ -18,36 +18,21 @@ import ctypes as C
 import os
 import shutil
 import sys
-import tempfile
-import time
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import timing  # noqa: E402
 from vcm_ts_amd import aq as A  # noqa: E402
 from vcm_ts_amd import lib  # noqa: E402
 
-H, W, GOP, STREAMS = 1080, 1920, 32, 2
-HP, WP = 1088, 1920
+H, W = timing.SIZE
+HP, WP = timing.padded((H, W))
+GOP, STREAMS = 32, 2
 DEV = torch.device("cuda:0")
 YARDSTICK_TBS = 4.5  # the warp kernel's measured rate
 SETTING = A.AQ(100)
-
-
-def _event_us(fn, launches):
-    """microseconds per call of fn(i), i = 0 .. launches - 1, between two HIP events (after a warm-up of every call)"""
-    for i in range(min(launches, 32)):
-        fn(i)
-    torch.cuda.synchronize(DEV)
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for i in range(launches):
-        fn(i)
-    t1.record()
-    torch.cuda.synchronize(DEV)
-    return 1000.0 * t0.elapsed_time(t1) / launches
 
 
 def kernels(launches):
@@ -73,14 +58,15 @@ def kernels(launches):
         lib.check(hip.dcvc_aq_map(L.data_ptr(), total.data_ptr(), hc, wc, maps.ktab.data_ptr(), maps.ftab.data_ptr(), None,
                                   out.data_ptr(), st), "aq_map")
 
+    us = lambda fn: timing.event_us(fn, launches, warmup=min(launches, 32), sync="device")
     nbytes = 3 * HP * WP * 4
     floor_us = nbytes / (YARDSTICK_TBS * 1e12) * 1e6
-    one = _event_us(lambda i: activity(i, False), launches)
-    many = _event_us(lambda i: activity(i, True), launches)
+    one = us(lambda i: activity(i, False))
+    many = us(lambda i: activity(i, True))
     total.zero_()
     activity(0, False)
-    mapped = _event_us(to_map, launches)
-    whole = _event_us(lambda i: maps.map(base[i % 16:i % 16 + 1]), launches)
+    mapped = us(to_map)
+    whole = us(lambda i: maps.map(base[i % 16:i % 16 + 1]))
     print(f"# {WP}x{HP} padded picture, {nbytes} bytes read per launch, {hc * wc} cells; {launches} launches between two HIP events")
     print(f"# yardstick: {nbytes} bytes at {YARDSTICK_TBS} TB/s = {floor_us:.2f} us")
     print(f"  dcvc_aq_activity, one picture (cache-resident)     {one:7.2f} us   {nbytes / one / 1e6:6.2f} TB/s   x{one / floor_us:.2f} of the yardstick")
@@ -89,94 +75,45 @@ def kernels(launches):
     print(f"  AqMaps.map (memset + both launches, from Python)   {whole:7.2f} us   (host-bound: launches issued back to back)")
 
 
-def _source(tmp, n):
-    from vcm_ts_amd import yuv as V
-    from vcm_ts_amd.synthetic import frames
-
-    spec, y4m = V.ColorSpec(), os.path.join(tmp, "src.y4m")
-    rgb = frames(0, n, H, W)
-    with V.Y4MWriter(y4m, W, H, spec, fps=(30, 1)) as wr:
-        for t in range(n):
-            wr.write(t, V.rgb_to_yuv420(torch.from_numpy(rgb[t:t + 1]).to(DEV), H, W, spec).cpu().numpy())
-    return y4m
-
-
-def _report(title, variants, rates, repeats):
-    print(title)
-    print(f"# frames/s, {repeats} alternating repeats: mean (min .. max)")
-    base = np.mean(rates[variants[0]])
-    for v in variants:
-        a = np.array(rates[v])
-        print(f"  {v:28s} {a.mean():6.2f}  ({a.min():.2f} .. {a.max():.2f})   " + " ".join(f"{x:.2f}" for x in a) +
-              ("" if v == variants[0] else f"   {100 * (a.mean() / base - 1):+.1f} % against {variants[0]}"))
-
-
 def files(n, repeats, decode=False):
     from vcm_ts_amd import run_codec as RC
 
-    tmp = tempfile.mkdtemp(prefix="dcvc_aq_time_")
-    try:
-        y4m = _source(tmp, n)
-        nets = [RC._nets(DEV, "fp16x3") for _ in range(STREAMS)]
+    with timing.workdir("dcvc_aq_time_") as tmp:
+        y4m = timing.y4m_clip(tmp, n, (H, W))
+        nets = timing.codec_pairs(DEV, "fp16x3", STREAMS)
         common = dict(gop=GOP, gop_streams=STREAMS, nets=nets)
-        variants = ["without", f"aq=AQ({SETTING.strength})"]
-        setting = {variants[0]: None, variants[1]: SETTING}
+        setting = {"without": None, f"aq=AQ({SETTING.strength})": SETTING}
         totals = {}
 
         def encode(v, where, max_frames=None):
             shutil.rmtree(where, ignore_errors=True)
-            torch.cuda.synchronize(DEV)
-            t0 = time.time()
-            bits, _ = RC.encode_video(y4m, where, max_frames=max_frames, aq=setting[v], **common)
-            torch.cuda.synchronize(DEV)
-            totals[v] = sum(bits)
-            return len(bits) / (time.time() - t0)
+
+            def run():
+                totals[v] = sum(RC.encode_video(y4m, where, max_frames=max_frames, aq=setting[v], **common)[0])
+            return timing.fps(run, n, DEV)
 
         if not decode:
-            for v in variants:  # warm-up: every shape and every code path once
+            for v in setting:  # warm-up: every shape and every code path once
                 encode(v, os.path.join(tmp, "out"), max_frames=GOP + 2)
-            rates = {v: [] for v in variants}
-            for _ in range(repeats):
-                for v in variants:  # alternating
-                    rates[v].append(encode(v, os.path.join(tmp, "out")))
-            _report(f"# encode_video, {n} pictures {W}x{H} from a Y4M file, GOP {GOP}, {STREAMS} GOP streams, fp16x3; .bin totals "
-                    f"{totals} bits (name-seeded weights: no rate is claimed)", variants, rates, repeats)
-            return
-        for k, v in enumerate(variants):
-            encode(v, os.path.join(tmp, f"bins{k}"))
-        made = RC._nets
-        RC._nets = lambda *a, **kw: nets[0]  # (decode_video builds its codecs itself: hand it the pair every run shares)
-        try:
-            def run(k):
-                torch.cuda.synchronize(DEV)
-                t0 = time.time()
-                count = RC.decode_video(os.path.join(tmp, f"bins{k}"), os.path.join(tmp, "dec.y4m"), precision="fp16x3")
-                torch.cuda.synchronize(DEV)
-                return count / (time.time() - t0)
+            rates = timing.alternating({v: v for v in setting}, repeats, lambda v: encode(v, os.path.join(tmp, "out")))
+            print(f"# encode_video, {n} pictures {W}x{H} from a Y4M file, GOP {GOP}, {STREAMS} GOP streams, fp16x3; .bin totals "
+                  f"{totals} bits (name-seeded weights: no rate is claimed)")
+        else:
+            bins = {v: os.path.join(tmp, f"bins{k}") for k, v in enumerate(setting)}
+            for v in setting:
+                encode(v, bins[v])
+            with timing.shared_nets(nets[0]):
+                def run(where):
+                    return timing.fps(lambda: RC.decode_video(where, os.path.join(tmp, "dec.y4m"), precision="fp16x3"), n, DEV)
 
-            for k in range(2):
-                run(k)
-            rates = {v: [] for v in variants}
-            for _ in range(repeats):
-                for k, v in enumerate(variants):
-                    rates[v].append(run(k))
-        finally:
-            RC._nets = made
-        _report(f"# decode_video, {n} pictures {W}x{H} to a Y4M file, GOP {GOP}, one stream, fp16x3", variants, rates, repeats)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+                for where in bins.values():
+                    run(where)
+                rates = timing.alternating(bins, repeats, run)
+            print(f"# decode_video, {n} pictures {W}x{H} to a Y4M file, GOP {GOP}, one stream, fp16x3")
+        print(f"# frames/s, {repeats} alternating repeats: mean (min .. max)")
+        timing.rate_table(rates, baseline="without", width=28)
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1] if len(sys.argv) > 1 else "files"
-    if not torch.cuda.is_available():
-        sys.exit("aq_time.py measures on the GPU; none is visible")
-    arg = lambda k, d: int(sys.argv[k]) if len(sys.argv) > k else d
-    if mode == "kernels":
-        kernels(arg(2, 200))
-    elif mode == "files":
-        files(arg(2, 64), arg(3, 3))
-    elif mode == "decode":
-        files(arg(2, 32), arg(3, 2), decode=True)
-    else:
-        sys.exit(__doc__)
+    timing.main(__doc__, "aq_time.py", {"kernels": (kernels, (200,)), "files": (files, (64, 3)),
+                                        "decode": (lambda n, repeats: files(n, repeats, decode=True), (32, 2))}, default="files")

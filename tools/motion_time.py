@@ -16,28 +16,15 @@ import ctypes as C
 import os
 import shutil
 import sys
-import tempfile
-import time
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import timing  # noqa: E402
 
-H, W, HP, WP, POOL = 1080, 1920, 1088, 1920, 16
+H, W = timing.SIZE
+HP, WP = timing.padded((H, W))
+POOL = 16
 BYTES = {"motion_step": (12 + 4) * H * W, "aq_activity": 12 * HP * WP}
-
-
-def _event_us(torch, fn, launches):
-    for i in range(5):
-        fn(i)
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(launches):
-        fn(i)
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / launches
 
 
 def kernels(launches, rounds):
@@ -74,19 +61,12 @@ def kernels(launches, rounds):
                 "aq_activity, one picture (cache-resident)": lambda i: activity(i, False),
                 "motion_step, rotating over 16 pictures (HBM)": lambda i: motion(i, True),
                 "aq_activity, rotating over 16 pictures (HBM)": lambda i: activity(i, True)}
-    times = {name: [] for name in variants}
-    for _ in range(rounds):
-        for name, fn in variants.items():  # alternating
-            times[name].append(_event_us(torch, fn, launches))
+    times = timing.alternating(variants, rounds, lambda fn: timing.event_us(fn, launches, warmup=5, sync="event"))
     print(f"# {W}x{H} crop of a {WP}x{HP} padded picture; {rounds} alternating rounds of {launches} launches between two HIP "
           f"events, us per launch: median (min .. max), bytes/s at the median")
     print(f"# bytes per launch: motion_step {BYTES['motion_step']} (picture read, model read and written), aq_activity "
           f"{BYTES['aq_activity']}: x{BYTES['motion_step'] / BYTES['aq_activity']:.2f}")
-    med = {}
-    for name, t in times.items():
-        t = np.array(t)
-        med[name] = np.median(t)
-        print(f"  {name:46s} {np.median(t):7.2f}  ({t.min():.2f} .. {t.max():.2f})   {BYTES[name.split(',')[0]] / np.median(t) / 1e6:6.2f} TB/s")
+    med = timing.kernel_table(times, lambda name: BYTES[name.split(",")[0]], width=46)
     for where in ("one picture (cache-resident)", "rotating over 16 pictures (HBM)"):
         print(f"# {where}: motion_step / aq_activity = x{med['motion_step, ' + where] / med['aq_activity, ' + where]:.2f} in time")
 
@@ -96,56 +76,24 @@ def boxes(n, repeats):
 
     from vcm_ts_amd import motionroi as M
     from vcm_ts_amd import run_codec as RC
-    from vcm_ts_amd import yuv as Y
-    from vcm_ts_amd.synthetic import frames
 
     dev = torch.device("cuda:0")
-    tmp = tempfile.mkdtemp(prefix="dcvc_motion_time_")
-    try:
-        spec, y4m = Y.ColorSpec(), os.path.join(tmp, "src.y4m")
-        ground = frames(0, 1, H, W, noise=0)[0]
-        g = np.random.default_rng(1)
-        with Y.Y4MWriter(y4m, W, H, spec, fps=(30, 1)) as wr:  # a static camera and one moving rectangle
-            for t in range(n):
-                pic = np.clip(ground + np.float32(1 / 255) * g.standard_normal(ground.shape).astype(np.float32), 0, 1)
-                x = 64 + (16 * t) % (W - 512)
-                pic[:, 400:656, x:x + 384] = 1.0 if ground[:, 400:656, x:x + 384].mean() < 0.5 else 0.0
-                wr.write(t, Y.rgb_to_yuv420(torch.from_numpy(pic[None]).to(dev), H, W, spec).cpu().numpy())
+    with timing.workdir("dcvc_motion_time_") as tmp:
+        y4m, _ = timing.moving_box_clip(tmp, n, (H, W), noise=1)  # a static camera and one moving rectangle
         params = M.MotionParams(24)
 
         def run():
-            out = os.path.join(tmp, "root")
+            out = os.path.join(tmp, "found")
             shutil.rmtree(out, ignore_errors=True)
             return RC.motion_boxes_video(y4m, out, params, dev)
 
         found = run()  # warm-up
-        rates = []
-        for _ in range(repeats):
-            torch.cuda.synchronize(dev)
-            t0 = time.time()
-            run()
-            torch.cuda.synchronize(dev)
-            rates.append(n / (time.time() - t0))
-        a = np.array(rates)
+        rates = timing.alternating({"boxes pass (read, convert, scan, box rule, write)": run}, repeats, lambda fn: timing.fps(fn, n, dev))
         print(f"# run_codec boxes --video: {n} pictures {W}x{H} from a Y4M file, threshold 24, default parameters; "
               f"{sum(len(b) for b in found)} boxes in {sum(1 for b in found if len(b))} pictures")
         print(f"# frames/s, {repeats} repeats after one warm-up: mean (min .. max)")
-        print(f"  boxes pass (read, convert, scan, box rule, write)  {a.mean():7.2f}  ({a.min():.2f} .. {a.max():.2f})   "
-              + " ".join(f"{x:.2f}" for x in a))
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+        timing.rate_table(rates, width=50, fmt="7.2f")
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1] if len(sys.argv) > 1 else ""
-    arg = lambda k, d: int(sys.argv[k]) if len(sys.argv) > k else d
-    if mode not in ("kernels", "boxes"):
-        sys.exit(__doc__)
-    import torch
-
-    if not torch.cuda.is_available():
-        sys.exit("motion_time.py measures on the GPU; none is visible")
-    if mode == "kernels":
-        kernels(arg(2, 200), arg(3, 5))
-    else:
-        boxes(arg(2, 64), arg(3, 3))
+    timing.main(__doc__, "motion_time.py", {"kernels": (kernels, (200, 5)), "boxes": (boxes, (64, 3))})

@@ -17,8 +17,6 @@ import json
 import os
 import shutil
 import sys
-import tempfile
-import time
 import zlib
 
 import numpy as np
@@ -26,9 +24,12 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import timing  # noqa: E402
 from vcm_ts_amd import picturehash as PH  # noqa: E402
 
-H, W, HP, WP, GOP, STREAMS = 1080, 1920, 1088, 1920, 32, 2
+H, W = timing.SIZE
+HP, WP = timing.padded((H, W))
+GOP, STREAMS = 32, 2
 DEV = torch.device("cuda:0")
 
 
@@ -46,76 +47,42 @@ def kernels(launches):
     print(f"# one padded {HP}x{WP} picture, {launches} calls each (a call is two launches: the blocks, then the fold); "
           f"{PH.lib.hash_constant('dcvc_hash_block_bytes')} bytes per workgroup")
     for n, (what, call) in enumerate(calls.items()):
-        for _ in range(5):
-            call()
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(launches):
-            call()
-        stop.record()
-        stop.synchronize()
+        us = timing.event_us(lambda i: call(), launches, warmup=5, sync="event")
         assert int(out.cpu().numpy()[n]) == want[n], what  # (zlib on the host is the judge here too)
-        print(f"  {what:72s} {1000 * start.elapsed_time(stop) / launches:8.1f} us per call")
+        print(f"  {what:72s} {us:8.1f} us per call")
 
 
 def files(n, repeats):
     from vcm_ts_amd import run_codec as RC
-    from vcm_ts_amd import yuv as V
-    from vcm_ts_amd.synthetic import frames
 
-    tmp = tempfile.mkdtemp(prefix="dcvc_picturehash_time_")
-    try:
-        spec, y4m = V.ColorSpec(), os.path.join(tmp, "src.y4m")
-        rgb = frames(0, n, H, W)
-        with V.Y4MWriter(y4m, W, H, spec, fps=(30, 1)) as wr:
-            for t in range(n):
-                wr.write(t, V.rgb_to_yuv420(torch.from_numpy(rgb[t:t + 1]).to(DEV), H, W, spec).cpu().numpy())
-        nets = [RC._nets(DEV, "fp16x3") for _ in range(STREAMS)]
-        records = []
+    with timing.workdir("dcvc_picturehash_time_") as tmp:
+        y4m = timing.y4m_clip(tmp, n, (H, W))
+        nets = timing.codec_pairs(DEV, "fp16x3", STREAMS)
+        records, totals = [], set()
 
         def run(hashed, max_frames=None):
             out = os.path.join(tmp, "out")
             shutil.rmtree(out, ignore_errors=True)
-            torch.cuda.synchronize(DEV)
-            t0 = time.time()
-            bits, _ = RC.encode_video(y4m, out, max_frames=max_frames, gop=GOP, gop_streams=STREAMS, nets=nets, picture_hash=hashed)
-            torch.cuda.synchronize(DEV)
-            dt = time.time() - t0
+            rate = timing.fps(lambda: totals.add(sum(RC.encode_video(y4m, out, max_frames=max_frames, gop=GOP, gop_streams=STREAMS, nets=nets,
+                                                                     picture_hash=hashed)[0])), n, DEV)
             assert os.path.exists(os.path.join(out, PH.HASHES_JSON)) == hashed
-            if hashed and max_frames is None:
-                records.append(json.load(open(os.path.join(out, PH.HASHES_JSON))))
-            return len(bits) / dt, sum(bits)
+            if max_frames is None:
+                assert len(totals) == 1, totals  # the option changes no .bin byte
+                if hashed:
+                    records.append(json.load(open(os.path.join(out, PH.HASHES_JSON))))
+            return rate
 
-        for v in (False, True):  # warm-up: both code paths once
+        variants = {"without picture_hash": False, "picture_hash=True": True}
+        for v in variants.values():  # warm-up: both code paths once
             run(v, max_frames=GOP + 2)
-        rates, total = {False: [], True: []}, None
-        for _ in range(repeats):
-            for v in (False, True):  # alternating
-                fps, bits = run(v)
-                rates[v].append(fps)
-                total = bits if total is None else total
-                assert bits == total, (bits, total)  # the option changes no .bin byte
+        totals.clear()
+        rates = timing.alternating(variants, repeats, run)
         assert all(r == records[0] for r in records)  # the same digests every time
         print(f"# encode_video, {n} pictures {W}x{H} from a Y4M file, GOP {GOP}, {STREAMS} GOP streams, fp16x3; .bin total of every run "
-              f"{total} bits; {len(records)} identical hashes.json, pixels[0] {records[0]['pixels'][0]} state[0] {records[0]['state'][0]}")
+              f"{totals.pop()} bits; {len(records)} identical hashes.json, pixels[0] {records[0]['pixels'][0]} state[0] {records[0]['state'][0]}")
         print(f"# frames/s, {repeats} alternating repeats: mean (min .. max)")
-        base = np.mean(rates[False])
-        for v in (False, True):
-            a = np.array(rates[v])
-            print(f"  {'picture_hash=True' if v else 'without picture_hash':24s} {a.mean():6.2f}  ({a.min():.2f} .. {a.max():.2f})   " +
-                  " ".join(f"{x:.2f}" for x in a) + (f"   {100 * (a.mean() / base - 1):+.1f} % against without" if v else ""))
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+        timing.rate_table(rates, baseline="without", width=24)
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1] if len(sys.argv) > 1 else "files"
-    if not torch.cuda.is_available():
-        sys.exit("picturehash_time.py measures on the GPU; none is visible")
-    arg = lambda k, d: int(sys.argv[k]) if len(sys.argv) > k else d
-    if mode == "kernels":
-        kernels(arg(2, 200))
-    elif mode == "files":
-        files(arg(2, 64), arg(3, 3))
-    else:
-        sys.exit(__doc__)
+    timing.main(__doc__, "picturehash_time.py", {"kernels": (kernels, (200,)), "files": (files, (64, 3))}, default="files")

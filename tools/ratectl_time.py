@@ -11,8 +11,6 @@ Random (name-seeded) weights: the figures say how the controller behaves on this
 import os
 import shutil
 import sys
-import tempfile
-import time
 from fractions import Fraction
 
 import numpy as np
@@ -20,22 +18,20 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import timing  # noqa: E402
 from vcm_ts_amd import ratectl  # noqa: E402
 from vcm_ts_amd import run_codec as RC  # noqa: E402
-from vcm_ts_amd import yuv as Y  # noqa: E402
 from vcm_ts_amd.pipeline import GopEncoder, pad_frame  # noqa: E402
 from vcm_ts_amd.synthetic import frames  # noqa: E402
 
-H, W, GOP, STREAMS = 1080, 1920, 32, 2
+H, W = timing.SIZE
+GOP, STREAMS = 32, 2
 DEV = torch.device("cuda:0")
 
 
 def write_clip(path, n):
-    spec = Y.ColorSpec()
-    rgb = frames(0, n, H, W)
-    with Y.Y4MWriter(path, W, H, spec, fps=(30, 1)) as wr:
-        for t in range(n):
-            wr.write(t, Y.rgb_to_yuv420(torch.from_numpy(rgb[t:t + 1]).to(DEV), H, W, spec).cpu().numpy())
+    with timing.workdir("dcvc_ratectl_") as tmp:
+        shutil.move(timing.y4m_clip(tmp, n, (H, W)), path)
 
 
 def model(n):
@@ -72,47 +68,24 @@ def model(n):
 
 
 def files(n, repeats):
-    tmp = tempfile.mkdtemp(prefix="dcvc_ratectl_")
-    try:
-        y4m = os.path.join(tmp, "src.y4m")
-        write_clip(y4m, n)
-        nets = [RC._nets(DEV, "fp16x3") for _ in range(STREAMS)]
-        common = dict(gop=GOP, gop_streams=STREAMS, nets=nets)
+    with timing.workdir("dcvc_ratectl_") as tmp:
+        y4m = timing.y4m_clip(tmp, n, (H, W))
+        common = dict(gop=GOP, gop_streams=STREAMS, nets=timing.codec_pairs(DEV, "fp16x3", STREAMS))
+        totals = []
 
-        def run(target, max_frames=None):
+        def run(target):
             out = os.path.join(tmp, "out")
             shutil.rmtree(out, ignore_errors=True)
-            torch.cuda.synchronize(DEV)
-            t0 = time.time()
-            bits, _ = RC.encode_video(y4m, out, max_frames=max_frames, target_bpp=target, **common)
-            torch.cuda.synchronize(DEV)
-            return len(bits) / (time.time() - t0), sum(bits)
+            return timing.fps(lambda: totals.append(sum(RC.encode_video(y4m, out, target_bpp=target, **common)[0])), n, DEV)
 
-        _, total = run(None)
-        target = 0.75 * total / (n * H * W)
+        run(None)
+        target = 0.75 * totals[0] / (n * H * W)
         run(target)  # (warm-up of both variants done)
-        rates = {None: [], target: []}
-        for _ in range(repeats):
-            for v in (None, target):  # alternating
-                rates[v].append(run(v)[0])
+        rates = timing.alternating({"without target_bpp": None, f"target_bpp={target:.4f}": target}, repeats, run)
         print(f"# {n} pictures {W}x{H}, GOP {GOP}, {STREAMS} GOP streams, fp16x3, Y4M file -> .bin folder; frames/s, {repeats} "
               f"alternating repeats: mean (min .. max)")
-        for v, name in ((None, "without target_bpp"), (target, f"target_bpp={target:.4f}")):
-            a = np.array(rates[v])
-            print(f"  {name:24s} {a.mean():6.2f}  ({a.min():.2f} .. {a.max():.2f})   " + " ".join(f"{x:.2f}" for x in a))
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+        timing.rate_table(rates, width=24)
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1] if len(sys.argv) > 1 else ""
-    if mode not in ("model", "files", "clip"):
-        sys.exit(__doc__)
-    if not torch.cuda.is_available():
-        sys.exit("ratectl_time.py measures on the GPU; none is visible")
-    if mode == "model":
-        model(int(sys.argv[2]) if len(sys.argv) > 2 else 32)
-    elif mode == "files":
-        files(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 3)
-    else:
-        write_clip(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 64)
+    timing.main(__doc__, "ratectl_time.py", {"model": (model, (32,)), "files": (files, (64, 3)), "clip": (write_clip, (str, 64))})

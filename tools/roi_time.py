@@ -16,7 +16,6 @@ stream shared by every run, a warm-up pass of both variants first; the .bin tota
 import os
 import shutil
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -24,9 +23,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import timing  # noqa: E402
 from vcm_ts_amd import roi as X  # noqa: E402
 
-H, W, GOP, STREAMS = 1080, 1920, 32, 2
+H, W = timing.SIZE
+GOP, STREAMS = 32, 2
 DEV = torch.device("cuda:0")
 CLASSES = (X.RoiClass(10), X.RoiClass(25))
 BOX_COUNTS = (0, 8, 64)
@@ -118,18 +119,11 @@ def host(repeats):
 
 def files(n, repeats):
     from vcm_ts_amd import run_codec as RC
-    from vcm_ts_amd import yuv as Y
-    from vcm_ts_amd.synthetic import frames
 
-    tmp = tempfile.mkdtemp(prefix="dcvc_roi_time_")
-    try:
-        spec, y4m = Y.ColorSpec(), os.path.join(tmp, "src.y4m")
-        rgb = frames(0, n, H, W)
-        with Y.Y4MWriter(y4m, W, H, spec, fps=(30, 1)) as wr:
-            for t in range(n):
-                wr.write(t, Y.rgb_to_yuv420(torch.from_numpy(rgb[t:t + 1]).to(DEV), H, W, spec).cpu().numpy())
-        nets = [RC._nets(DEV, "fp16x3") for _ in range(STREAMS)]
-        common = dict(gop=GOP, gop_streams=STREAMS, nets=nets)
+    with timing.workdir("dcvc_roi_time_") as tmp:
+        y4m = timing.y4m_clip(tmp, n, (H, W))
+        common = dict(gop=GOP, gop_streams=STREAMS, nets=timing.codec_pairs(DEV, "fp16x3", STREAMS))
+        totals = set()
 
         def run(n_boxes, max_frames=None):
             out = os.path.join(tmp, "out")
@@ -139,45 +133,22 @@ def files(n, repeats):
             if n_boxes is not None:
                 lists = [make_boxes(n_boxes, seed=t) for t in range(n)]
                 extra = dict(roi=X.Roi(lambda t: lists[t], CLASSES), residuals=os.path.join(out, "res.gbrp"))
-            torch.cuda.synchronize(DEV)
-            t0 = time.time()
-            bits, _ = RC.encode_video(y4m, os.path.join(out, "bin"), max_frames=max_frames, **extra, **common)
-            torch.cuda.synchronize(DEV)
-            return len(bits) / (time.time() - t0), sum(bits)
+            rate = timing.fps(lambda: totals.add(sum(RC.encode_video(y4m, os.path.join(out, "bin"), max_frames=max_frames, **extra, **common)[0])),
+                              n, DEV)
+            if max_frames is None:
+                assert len(totals) == 1, totals  # the enhancement layer changes no .bin byte
+            return rate
 
-        variants = [None, 8, 64]
-        for v in variants:  # warm-up: every shape and every code path once
+        variants = {"without roi": None, **{f"roi, {v:2d} boxes a picture, residuals to .gbrp": v for v in (8, 64)}}
+        for v in variants.values():  # warm-up: every shape and every code path once
             run(v, max_frames=GOP + 2)
-        rates, total = {v: [] for v in variants}, None
-        for _ in range(repeats):
-            for v in variants:  # alternating
-                fps, bits = run(v)
-                rates[v].append(fps)
-                total = bits if total is None else total
-                assert bits == total, (bits, total)  # the enhancement layer changes no .bin byte
+        totals.clear()
+        rates = timing.alternating(variants, repeats, run)
         print(f"# encode_video, {n} pictures {W}x{H} from a Y4M file, GOP {GOP}, {STREAMS} GOP streams, bins only; .bin total of every "
-              f"run {total} bits")
+              f"run {totals.pop()} bits")
         print(f"# frames/s, {repeats} alternating repeats: mean (min .. max)")
-        base = np.mean(rates[None])
-        for v in variants:
-            a = np.array(rates[v])
-            what = "without roi" if v is None else f"roi, {v:2d} boxes a picture, residuals to .gbrp"
-            print(f"  {what:44s} {a.mean():6.2f}  ({a.min():.2f} .. {a.max():.2f})   " + " ".join(f"{x:.2f}" for x in a) +
-                  ("" if v is None else f"   {100 * (a.mean() / base - 1):+.1f} % against without"))
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+        timing.rate_table(rates, baseline="without", width=44)
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1] if len(sys.argv) > 1 else "files"
-    if not torch.cuda.is_available():
-        sys.exit("roi_time.py measures on the GPU; none is visible")
-    arg = lambda k, d: int(sys.argv[k]) if len(sys.argv) > k else d
-    if mode == "kernels":
-        kernels(arg(2, 20), arg(3, 8))
-    elif mode == "host":
-        host(arg(2, 5))
-    elif mode == "files":
-        files(arg(2, 64), arg(3, 3))
-    else:
-        sys.exit(__doc__)
+    timing.main(__doc__, "roi_time.py", {"kernels": (kernels, (20, 8)), "host": (host, (5,)), "files": (files, (64, 3))}, default="files")

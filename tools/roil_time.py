@@ -16,16 +16,14 @@ pool's +-3 % box spread.  Frames/s from a host clock around work that ends in a 
 import os
 import shutil
 import sys
-import tempfile
-import time
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from roi_time import BOX_COUNTS, CLASSES, DEV, GOP, STREAMS, H, W, make_boxes, pictures  # noqa: E402
+from tools import timing  # noqa: E402
+from tools.roi_time import BOX_COUNTS, CLASSES, DEV, GOP, STREAMS, H, W, make_boxes, pictures  # noqa: E402
 from vcm_ts_amd import roi as X  # noqa: E402
 from vcm_ts_amd import roilayer as Y  # noqa: E402
 
@@ -46,19 +44,11 @@ def kernels(launches, n, step):
 
 def files(n, repeats):
     from vcm_ts_amd import run_codec as RC
-    from vcm_ts_amd import yuv as V
-    from vcm_ts_amd.synthetic import frames
 
-    tmp = tempfile.mkdtemp(prefix="dcvc_roil_time_")
-    try:
-        spec, y4m = V.ColorSpec(), os.path.join(tmp, "src.y4m")
-        rgb = frames(0, n, H, W)
-        with V.Y4MWriter(y4m, W, H, spec, fps=(30, 1)) as wr:
-            for t in range(n):
-                wr.write(t, V.rgb_to_yuv420(torch.from_numpy(rgb[t:t + 1]).to(DEV), H, W, spec).cpu().numpy())
-        nets = [RC._nets(DEV, "fp16x3") for _ in range(STREAMS)]
-        common = dict(gop=GOP, gop_streams=STREAMS, nets=nets)
-        sizes = {}
+    with timing.workdir("dcvc_roil_time_") as tmp:
+        y4m = timing.y4m_clip(tmp, n, (H, W))
+        common = dict(gop=GOP, gop_streams=STREAMS, nets=timing.codec_pairs(DEV, "fp16x3", STREAMS))
+        sizes, totals = {}, set()
 
         def run(n_boxes, how, max_frames=None):
             out = os.path.join(tmp, "out")
@@ -69,47 +59,28 @@ def files(n, repeats):
                 lists = [make_boxes(n_boxes, seed=t) for t in range(n)]
                 extra = dict(roi=X.Roi(lambda t: lists[t], CLASSES))
                 extra.update(dict(residuals=os.path.join(out, "res.gbrp")) if how == "gbrp" else dict(residual_bins=os.path.join(out, "rl")))
-            torch.cuda.synchronize(DEV)
-            t0 = time.time()
-            bits, _ = RC.encode_video(y4m, os.path.join(out, "bin"), max_frames=max_frames, **extra, **common)
-            torch.cuda.synchronize(DEV)
-            dt = time.time() - t0
-            if how == "records" and max_frames is None:
-                sizes[n_boxes] = [os.path.getsize(os.path.join(out, "rl", f)) for f in sorted(os.listdir(os.path.join(out, "rl")))]
-            return len(bits) / dt, sum(bits)
+            rate = timing.fps(lambda: totals.add(sum(RC.encode_video(y4m, os.path.join(out, "bin"), max_frames=max_frames, **extra, **common)[0])),
+                              n, DEV)
+            if max_frames is None:
+                assert len(totals) == 1, totals  # the enhancement layer changes no .bin byte
+                if how == "records":
+                    sizes[n_boxes] = [os.path.getsize(os.path.join(out, "rl", f)) for f in sorted(os.listdir(os.path.join(out, "rl")))]
+            return rate
 
-        variants = [(None, "neither")] + [(b, how) for b in BOX_COUNTS for how in ("gbrp", "records")]
-        for v in variants:  # warm-up: every shape and every code path once
+        variants = {"without roi": (None, "neither")}
+        for b in BOX_COUNTS:
+            variants[f"{b:2d} boxes a picture, residuals to .gbrp"] = (b, "gbrp")
+            variants[f"{b:2d} boxes a picture, residual_bins (.rl)"] = (b, "records")
+        for v in variants.values():  # warm-up: every shape and every code path once
             run(*v, max_frames=GOP + 2)
-        rates, total = {v: [] for v in variants}, None
-        for _ in range(repeats):
-            for v in variants:  # alternating
-                fps, bits = run(*v)
-                rates[v].append(fps)
-                total = bits if total is None else total
-                assert bits == total, (bits, total)  # the enhancement layer changes no .bin byte
-        print(f"# encode_video, {n} pictures {W}x{H} from a Y4M file, GOP {GOP}, {STREAMS} GOP streams; .bin total of every run {total} bits")
+        totals.clear()
+        rates = timing.alternating(variants, repeats, lambda v: run(*v))
+        print(f"# encode_video, {n} pictures {W}x{H} from a Y4M file, GOP {GOP}, {STREAMS} GOP streams; .bin total of every run {totals.pop()} bits")
         print(f"# frames/s, {repeats} alternating repeats: mean (min .. max)")
-        base = np.mean(rates[(None, "neither")])
-        for v in variants:
-            a = np.array(rates[v])
-            what = "without roi" if v[1] == "neither" else f"{v[0]:2d} boxes a picture, " + ("residuals to .gbrp" if v[1] == "gbrp" else "residual_bins (.rl)")
-            print(f"  {what:44s} {a.mean():6.2f}  ({a.min():.2f} .. {a.max():.2f})   " + " ".join(f"{x:.2f}" for x in a) +
-                  ("" if v[1] == "neither" else f"   {100 * (a.mean() / base - 1):+.1f} % against without"))
+        timing.rate_table(rates, baseline="without", width=44)
         for b, s in sizes.items():
             print(f"# {b:2d} boxes: records of {np.mean(s):.0f} bytes a picture ({min(s)} .. {max(s)}) at step 1; a raw frame has {3 * H * W}")
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1] if len(sys.argv) > 1 else "files"
-    if not torch.cuda.is_available():
-        sys.exit("roil_time.py measures on the GPU; none is visible")
-    arg = lambda k, d: int(sys.argv[k]) if len(sys.argv) > k else d
-    if mode == "kernels":
-        kernels(arg(2, 20), arg(3, 8), arg(4, 1))
-    elif mode == "files":
-        files(arg(2, 64), arg(3, 3))
-    else:
-        sys.exit(__doc__)
+    timing.main(__doc__, "roil_time.py", {"kernels": (kernels, (20, 8, 1)), "files": (files, (64, 3))}, default="files")

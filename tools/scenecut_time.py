@@ -21,15 +21,15 @@ import csv
 import os
 import shutil
 import sys
-import tempfile
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import timing  # noqa: E402
 
-H, W, GOP, STREAMS, BATCH = 1080, 1920, 32, 2, 20
+H, W = timing.SIZE
+GOP, STREAMS, BATCH = 32, 2, 20
 VARIANTS = ("scene_hist random", "roi_sse random", "scene_hist constant", "roi_sse constant")
 BYTES = {"scene_hist": 12 * H * W, "roi_sse": 24 * H * W}
 
@@ -53,21 +53,11 @@ def kernels(rounds):
         for _ in range(3):
             step()
     torch.cuda.synchronize(dev)
-    times = [[] for _ in steps]
-    for _ in range(rounds):
-        for k, step in enumerate(steps):  # alternating; each variant BATCH launches back to back between two events
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(BATCH):
-                step()
-            b.record()
-            b.synchronize()
-            times[k].append(a.elapsed_time(b) * 1e3 / BATCH)
+    # each variant BATCH launches back to back between two events
+    times = timing.alternating(dict(zip(VARIANTS, steps)), rounds, lambda step: timing.event_us(lambda i: step(), BATCH, warmup=0, sync="event"))
     print(f"# {W}x{H}, {rounds} alternating rounds of {BATCH} launches per variant; device events around a batch, us per launch "
           f"(includes whatever gap the host leaves between launches): median (min .. max), bytes/s at the median")
-    for name, t in zip(VARIANTS, times):
-        t = np.array(t)
-        print(f"  {name:22s} {np.median(t):7.2f}  ({t.min():.2f} .. {t.max():.2f})   {BYTES[name.split()[0]] / np.median(t) / 1e6:6.2f} TB/s")
+    timing.kernel_table(times, lambda name: BYTES[name.split()[0]], width=22)
     print(f"# launch order for `trace`: {', '.join(VARIANTS)}; {3 * len(steps)} warm-up dispatches first")
 
 
@@ -77,18 +67,14 @@ def trace(path):
                     if "scene_hist_kernel" in r["Kernel_Name"] or "roi_kernel" in r["Kernel_Name"])
     picked = picked[12:]  # the warm-up: 3 dispatches of each of the 4 variants
     assert len(picked) % (4 * BATCH) == 0 and picked, len(picked)
-    times = [[] for _ in VARIANTS]
+    times = {v: [] for v in VARIANTS}
     for i, (t0, t1, name) in enumerate(picked):
         k = (i // BATCH) % 4
         assert ("scene_hist" in name) == (k % 2 == 0), (i, name)
-        times[k].append((t1 - t0) / 1e3)
-    print(f"# kernel times from a rocprofv3 kernel trace, {W}x{H}, {len(times[0])} dispatches per variant, us: "
+        times[VARIANTS[k]].append((t1 - t0) / 1e3)
+    print(f"# kernel times from a rocprofv3 kernel trace, {W}x{H}, {len(times[VARIANTS[0]])} dispatches per variant, us: "
           f"median (min .. max), bytes/s at the median")
-    med = []
-    for name, t in zip(VARIANTS, times):
-        t = np.array(t)
-        med.append(np.median(t))
-        print(f"  {name:22s} {np.median(t):7.2f}  ({t.min():.2f} .. {t.max():.2f})   {BYTES[name.split()[0]] / np.median(t) / 1e6:6.2f} TB/s")
+    med = list(timing.kernel_table(times, lambda name: BYTES[name.split()[0]], width=22).values())
     for k, what in ((0, "random"), (2, "constant")):
         print(f"# {what}: scene_hist / roi_sse = {med[k] / med[k + 1]:.2f}  ({'within' if med[k] <= med[k + 1] else 'ABOVE'} the yardstick)")
 
@@ -103,18 +89,16 @@ def scan(n, repeats):
     from vcm_ts_amd.synthetic import frames
 
     dev = torch.device("cuda:0")
-    tmp = tempfile.mkdtemp(prefix="dcvc_scenecut_time_")
-    try:
-        spec, y4m, png = Y.ColorSpec(), os.path.join(tmp, "src.y4m"), os.path.join(tmp, "png")
+    with timing.workdir("dcvc_scenecut_time_") as tmp:
+        spec, png = Y.ColorSpec(), os.path.join(tmp, "png")
         os.makedirs(png)
         # two scenes, the second from frame n // 2 + 3 on: one cut in the middle of a GOP
         cut = n // 2 + 3
         rgb = np.concatenate([0.5 + 0.5 * frames(0, cut, H, W), 0.35 * frames(1, n - cut, H, W)]).astype(np.float32)
-        with Y.Y4MWriter(y4m, W, H, spec, fps=(30, 1)) as wr:
-            for t in range(n):
-                wr.write(t, Y.rgb_to_yuv420(torch.from_numpy(rgb[t:t + 1]).to(dev), H, W, spec).cpu().numpy())
-                Image.fromarray(np.rint(rgb[t].transpose(1, 2, 0) * 255).astype(np.uint8)).save(os.path.join(png, f"im{t + 1:05d}.png"))
-        nets = [RC._nets(dev, "fp16x3") for _ in range(STREAMS)]
+        y4m = timing.y4m_clip(tmp, n, (H, W), frames=rgb)
+        for t in range(n):
+            Image.fromarray(np.rint(rgb[t].transpose(1, 2, 0) * 255).astype(np.uint8)).save(os.path.join(png, f"im{t + 1:05d}.png"))
+        nets = timing.codec_pairs(dev, "fp16x3", STREAMS)
         common = dict(gop=GOP, gop_streams=STREAMS, nets=nets)
 
         def scan_y4m():
@@ -141,42 +125,23 @@ def scan(n, repeats):
         variants = {"scan pass alone, Y4M file": scan_y4m, "scan pass alone, PNG folder, 8 readers": scan_png,
                     "encode (Y4M), plain": lambda: encode(None), "encode (Y4M), --scenecut 0.5": lambda: encode(0.5)}
         encode(None, GOP + 2), encode(0.5, GOP + 2), scan_y4m(), scan_png()  # warm-up: every shape and code path once
-        rates = {k: [] for k in variants}
         plans = set()
-        for _ in range(repeats):
-            for name, fn in variants.items():  # alternating
-                torch.cuda.synchronize(dev)
-                t0 = time.time()
-                r = fn()
-                torch.cuda.synchronize(dev)
-                rates[name].append(n / (time.time() - t0))
-                if isinstance(r, list):
-                    plans.add(tuple(r))
+
+        def noted(fn):
+            r = fn()
+            if isinstance(r, list):
+                plans.add(tuple(r))
+
+        rates = timing.alternating(variants, repeats, lambda fn: timing.fps(lambda: noted(fn), n, dev))
         print(f"# {n} pictures {W}x{H}, a scene change at frame {cut}, GOP {GOP}, {STREAMS} GOP streams, fp16x3, bins only; "
               f"plans found by the scans: {sorted(plans)}")
         print(f"# frames/s, {repeats} alternating repeats: mean (min .. max)")
-        for name, v in rates.items():
-            a = np.array(v)
-            print(f"  {name:42s} {a.mean():7.2f}  ({a.min():.2f} .. {a.max():.2f})   " + " ".join(f"{x:.2f}" for x in a))
+        timing.rate_table(rates, width=42, fmt="7.2f")
         base, cutr = np.mean(rates["encode (Y4M), plain"]), np.mean(rates["encode (Y4M), --scenecut 0.5"])
         print(f"# encode with --scenecut against plain: {100 * (cutr / base - 1):+.1f} % frames/s (the scan pass, plus one more I picture)")
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1] if len(sys.argv) > 1 else ""
-    arg = lambda k, d: int(sys.argv[k]) if len(sys.argv) > k else d
-    if mode == "trace" and len(sys.argv) > 2:
-        trace(sys.argv[2])
-        sys.exit(0)
-    if mode not in ("kernels", "scan"):
-        sys.exit(__doc__)
-    import torch
-
-    if not torch.cuda.is_available():
-        sys.exit("scenecut_time.py measures on the GPU; none is visible")
-    if mode == "kernels":
-        kernels(arg(2, 30))
-    else:
-        scan(arg(2, 64), arg(3, 3))
+    if sys.argv[1:2] == ["trace"] and len(sys.argv) > 2:  # (a path, and no GPU)
+        sys.exit(trace(sys.argv[2]))
+    timing.main(__doc__, "scenecut_time.py", {"kernels": (kernels, (30,)), "scan": (scan, (64, 3))})

@@ -14,7 +14,6 @@ Frames/s from a host clock around work that ends in a device synchronise.
 import os
 import shutil
 import sys
-import tempfile
 import time
 from concurrent.futures import ThreadPoolExecutor
 
@@ -23,28 +22,26 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import timing  # noqa: E402
 from vcm_ts_amd import run_codec as RC  # noqa: E402
 from vcm_ts_amd import yuv as Y  # noqa: E402
 
-H, W, GOP, STREAMS = 1080, 1920, 32, 2
+H, W = timing.SIZE
+GOP, STREAMS = 32, 2
 DEV = torch.device("cuda:0")
 
 
 def make_inputs(tmp, n):
     from PIL import Image
 
-    from vcm_ts_amd.synthetic import frames
-
-    spec = Y.ColorSpec()
-    y4m, png = os.path.join(tmp, "src.y4m"), os.path.join(tmp, "png")
+    spec, png = Y.ColorSpec(), os.path.join(tmp, "png")
     os.makedirs(png)
-    rgb = frames(0, n, H, W)
-    with Y.Y4MWriter(y4m, W, H, spec, fps=(30, 1)) as wr, ThreadPoolExecutor(8) as pool:
-        jobs = []
-        for t in range(n):
-            samples = Y.rgb_to_yuv420(torch.from_numpy(rgb[t:t + 1]).to(DEV), H, W, spec)
-            wr.write(t, samples.cpu().numpy())
-            x = Y.yuv420_to_rgb(samples, H, W, spec, pad=False, quantize8=True)
+    y4m = timing.y4m_clip(tmp, n, (H, W))
+    with Y.open_video(y4m, None, 8, None) as reader, ThreadPoolExecutor(8) as pool:
+        samples, jobs = np.empty(reader.frame_bytes, np.uint8), []
+        for t in range(n):  # the folder holds what encode_video(quantize8=True) makes of the file's samples
+            reader.read_into(t, samples)
+            x = Y.yuv420_to_rgb(torch.from_numpy(samples).to(DEV), H, W, spec, pad=False, quantize8=True)
             u8 = torch.round(x[0] * 255.0).to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
             jobs.append(pool.submit(lambda a, p: Image.fromarray(a).save(p), u8, os.path.join(png, f"im{t + 1:05d}.png")))
         for j in jobs:
@@ -53,55 +50,43 @@ def make_inputs(tmp, n):
 
 
 def files(n, repeats):
-    tmp = tempfile.mkdtemp(prefix="dcvc_yuv_io_")
-    try:
+    with timing.workdir("dcvc_yuv_io_") as tmp:
         t0 = time.time()
         y4m, png = make_inputs(tmp, n)
         print(f"# inputs: {n} pictures {W}x{H}; src.y4m {os.path.getsize(y4m) / 1e6:.1f} MB, PNG folder "
               f"{sum(os.path.getsize(os.path.join(png, f)) for f in os.listdir(png)) / 1e6:.1f} MB ({time.time() - t0:.0f} s to make)")
-        nets = [RC._nets(DEV, "fp16x3") for _ in range(STREAMS)]
-        common = dict(gop=GOP, gop_streams=STREAMS, nets=nets)
+        common = dict(gop=GOP, gop_streams=STREAMS, nets=timing.codec_pairs(DEV, "fp16x3", STREAMS))
+        totals = set()
 
         def run(path, recon, workers, max_frames=None):
             out = os.path.join(tmp, "out")
             shutil.rmtree(out, ignore_errors=True)
             os.makedirs(out)
-            torch.cuda.synchronize(DEV)
-            t0 = time.time()
             if path == "png":
-                bits, _ = RC.encode_folder(png, os.path.join(out, "bin"), os.path.join(out, "rec") if recon else None,
-                                           io_workers=workers, max_frames=max_frames, **common)
+                code = lambda: RC.encode_folder(png, os.path.join(out, "bin"), os.path.join(out, "rec") if recon else None,
+                                                io_workers=workers, max_frames=max_frames, **common)
             else:
-                bits, _ = RC.encode_video(y4m, os.path.join(out, "bin"), os.path.join(out, "rec.y4m") if recon else None,
-                                          quantize8=True, io_workers=workers, max_frames=max_frames, **common)
-            torch.cuda.synchronize(DEV)
-            return len(bits) / (time.time() - t0), sum(bits)
+                code = lambda: RC.encode_video(y4m, os.path.join(out, "bin"), os.path.join(out, "rec.y4m") if recon else None,
+                                               quantize8=True, io_workers=workers, max_frames=max_frames, **common)
+            rate = timing.fps(lambda: totals.add(sum(code()[0])), n, DEV)
+            assert max_frames is not None or len(totals) == 1, totals  # identical inputs, identical .bin totals
+            return rate
 
-        variants = [(p, r) for r in (False, True) for p in ("png", "y4m")]
-        for p, r in variants:  # warm-up: every shape and every code path once
+        what = {"png": "encode_folder, PNG folder, 8 I/O threads", "y4m": "encode_video,  Y4M file,  no helper threads"}
+        variants = {f"{what[p]:44s} {'+ reconstruction output' if r else '  bins only            '}": (p, r)
+                    for r in (False, True) for p in ("png", "y4m")}
+        for p, r in variants.values():  # warm-up: every shape and every code path once
             run(p, r, 8, max_frames=GOP + 2)
-        rates, totals = {v: [] for v in variants}, {}
-        for _ in range(repeats):
-            for v in variants:  # alternating
-                fps, total = run(v[0], v[1], 8)
-                rates[v].append(fps)
-                totals.setdefault(v[0], total)
-                assert totals[v[0]] == total
-        assert totals["png"] == totals["y4m"], totals  # identical inputs, identical .bin totals
-        print(f"# .bin total of every run: {totals['png']} bits ({totals['png'] / (n * H * W):.4f} bpp)")
+        totals.clear()
+        rates = timing.alternating(variants, repeats, lambda v: run(v[0], v[1], 8))
+        total = next(iter(totals))
+        print(f"# .bin total of every run: {total} bits ({total / (n * H * W):.4f} bpp)")
         print(f"# frames/s, {repeats} alternating repeats: mean (min .. max)")
-        for v in variants:
-            a = np.array(rates[v])
-            what = "encode_folder, PNG folder, 8 I/O threads" if v[0] == "png" else "encode_video,  Y4M file,  no helper threads"
-            print(f"  {what:44s} {'+ reconstruction output' if v[1] else '  bins only            '}  "
-                  f"{a.mean():6.2f}  ({a.min():.2f} .. {a.max():.2f})   " + " ".join(f"{x:.2f}" for x in a))
+        timing.rate_table(rates, width=69)
         print("# io_workers=0 (reading, decoding and writing inline on the encoding thread), one run each")
-        for v in variants:
-            fps, total = run(v[0], v[1], 0)
-            assert total == totals["png"]
-            print(f"  {'encode_folder' if v[0] == 'png' else 'encode_video '} io_workers=0 {'+ reconstruction output' if v[1] else '  bins only            '}  {fps:6.2f}")
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+        for p, r in variants.values():
+            print(f"  {'encode_folder' if p == 'png' else 'encode_video '} io_workers=0 {'+ reconstruction output' if r else '  bins only            '}  "
+                  f"{run(p, r, 0):6.2f}")
 
 
 def kernels(launches, variant):
@@ -115,19 +100,11 @@ def kernels(launches, variant):
     for _ in range(launches):
         Y.rgb_to_yuv420(rgb, H, W, spec, source=src if full else None)
     torch.cuda.synchronize(DEV)
-    to_rgb = H * W * 3 // 2 + 3 * 1088 * W * 4
+    to_rgb = H * W * 3 // 2 + 3 * timing.padded((H, W))[0] * W * 4
     from_rgb = H * W * 3 // 2 + 3 * H * W * 4 + (H * W * 3 // 2 if full else 0)
     print(f"# variant {variant}: {launches} launches each; bytes per launch from the shapes: yuv420_to_rgb {to_rgb / 1e6:.2f} MB "
           f"(1.5 read + 12 written per pixel, 8 padding rows included), rgb_to_yuv420 {from_rgb / 1e6:.2f} MB")
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1] if len(sys.argv) > 1 else "files"
-    if not torch.cuda.is_available():
-        sys.exit("yuv_io_time.py measures on the GPU; none is visible")
-    if mode == "files":
-        files(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 3)
-    elif mode == "kernels":
-        kernels(int(sys.argv[2]) if len(sys.argv) > 2 else 20, sys.argv[3] if len(sys.argv) > 3 else "plain")
-    else:
-        sys.exit(__doc__)
+    timing.main(__doc__, "yuv_io_time.py", {"files": (files, (64, 3)), "kernels": (kernels, (20, "plain"))}, default="files")
