@@ -3,22 +3,11 @@ float picture, the activity L of every 16x16 cell, the picture mean, the two hos
 the pictures the backward-adaptive quantisation tests share."""
 import numpy as np
 
+from tests.pixel_ref import code, luma  # noqa: F401 (the tests use them as R.code, R.luma)
+
 F32 = np.float32
 CELL, MAX_L = 16, 7935
 SIZES = [(64, 64), (64, 128), (128, 192), (192, 64)]  # (Hp, Wp)
-
-
-def code(v):
-    """(int) rint(255.0f * clamp01(v)) in float32; a NaN codes as 0 (fmaxf(NaN, 0) is 0)."""
-    v = np.asarray(v, dtype=F32)
-    c = np.minimum(np.maximum(np.where(np.isnan(v), F32(0), v), F32(0)), F32(1))
-    return np.rint(F32(255.0) * c).astype(np.int64)
-
-
-def luma(pic):
-    """Y of a (3, Hp, Wp) float32 picture, int64."""
-    r, g, b = code(pic[0]), code(pic[1]), code(pic[2])
-    return (54 * r + 183 * g + 19 * b + 128) >> 8
 
 
 def variance256(Y):

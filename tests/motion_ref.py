@@ -5,29 +5,13 @@ the static-camera clip the motion tests share."""
 import numpy as np
 from scipy import ndimage
 
+from tests.pixel_ref import code, grid, luma  # noqa: F401 (the tests use them as R.code, ...)
 from vcm_ts_amd.synthetic import frames
 
 F32 = np.float32
 CELL = 16
 SIZES = [(64, 64), (70, 100), (128, 192), (16, 16), (1, 1)]  # (H, W)
 SETTINGS = [(24, 4, 8), (1, 0, 16), (254, 16, 0)]  # (T, k_bg, k_fg)
-
-
-def code(v):
-    """(int) rint(255.0f * clamp01(v)) in float32; a NaN codes as 0."""
-    v = np.asarray(v, dtype=F32)
-    c = np.minimum(np.maximum(np.where(np.isnan(v), F32(0), v), F32(0)), F32(1))
-    return np.rint(F32(255.0) * c).astype(np.int64)
-
-
-def luma(pic):
-    """Y of a (3, H, W) float32 picture, int64."""
-    r, g, b = code(pic[0]), code(pic[1]), code(pic[2])
-    return (54 * r + 183 * g + 19 * b + 128) >> 8
-
-
-def grid(H, W):
-    return 4 * ((H + 63) // 64), 4 * ((W + 63) // 64)
 
 
 def cell_sums(mask):

@@ -6,6 +6,8 @@ import functools
 
 import numpy as np
 
+from tests.pixel_ref import code, grid  # noqa: F401 (the tests use them as R.code, R.grid)
+
 F32 = np.float32
 CELL, MAX_BOXES = 16, 1024
 T = np.arange(256, dtype=F32) / F32(255.0)  # T[k] = (float) k / 255.0f
@@ -17,17 +19,6 @@ SIZES = [(1, 1), (7, 5), (16, 16), (64, 64), (65, 67), (70, 100), (130, 200)]
 MODES = [(t, -1) for t in TILES] + [(0, 0), (0, 200)]
 NAMES = ("liplates", "faces", "motion")
 MASK, GROW = 0b101, 5  # what the box sets below are written for: classes 0 and 2 selected, class 1 not
-
-
-def code(v):
-    """(int) rint(255.0f * clamp01(v)) in float32; a NaN codes as 0."""
-    v = np.asarray(v, dtype=F32)
-    c = np.minimum(np.maximum(np.where(np.isnan(v), F32(0), v), F32(0)), F32(1))
-    return np.rint(F32(255.0) * c).astype(np.int64)
-
-
-def grid(H, W):
-    return 4 * ((H + 63) // 64), 4 * ((W + 63) // 64)
 
 
 def region(boxes, H, W, mask, grow):

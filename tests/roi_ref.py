@@ -3,14 +3,10 @@ pictures the ROI tests share.  The feather mask exists twice: `feather_mask_lite
 after box, slice assignment of a gradient mask built ring by ring), `feather_mask` the header's closed form."""
 import numpy as np
 
+from tests.pixel_ref import code  # noqa: F401 (the tests use it as R.code)
+
 F32 = np.float32
 T = np.arange(256).astype(F32) / F32(255.0)  # the host quotients k / 255
-
-
-def code(v):
-    """(int) rint(255.0f * clamp01(v)), every step in float32"""
-    v = np.asarray(v, dtype=F32)
-    return np.rint(F32(255.0) * np.minimum(np.maximum(v, F32(0.0)), F32(1.0))).astype(np.int64)
 
 
 def feather_table(border):

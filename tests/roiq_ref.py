@@ -4,6 +4,8 @@ is the literal procedure (paint a per-pixel factor image box by box with `minimu
 `min`), `q_map_touches` the header's closed-form "touches" rule."""
 import numpy as np
 
+from tests.pixel_ref import grid  # noqa: F401 (the tests use it as R.grid)
+
 F32 = np.float32
 CELL = 16
 SIZES = [(1, 1), (16, 16), (17, 33), (64, 64), (65, 63), (135, 241)]  # (H, W)
@@ -14,10 +16,6 @@ BACKGROUND, CLASSES = 100, (60, 140, 10, 1000)  # hundredths: a class above, two
 def factors(background=BACKGROUND, classes=CLASSES):
     """[background, class 0, ...]: float32(k) / float32(100)"""
     return np.array((background,) + tuple(classes), dtype=F32) / F32(100)
-
-
-def grid(H, W):
-    return 4 * ((H + 63) // 64), 4 * ((W + 63) // 64)
 
 
 def _grown(boxes, H, W, grow):

@@ -3,6 +3,8 @@ and the fold one tap at a time in float32, so that every product and every sum i
 has no fma; numpy float32 arithmetic never contracts).  fold64 is the same tables folded in float64."""
 import numpy as np
 
+from tests.pixel_ref import code  # noqa: F401 (the tests use it as R.code)
+
 UNIT = 16384
 
 
@@ -74,9 +76,3 @@ def up(a, full):
 def fold64(a, size):
     """The same tables folded in float64, unclamped."""
     return resize(np.asarray(a, dtype=np.float64), size, dtype=np.float64, clamp=False)
-
-
-def code(a):
-    """the 8-bit codes of dcvc_hip_roi.h: rint(255 * clamp01(v)) in float32"""
-    a = np.asarray(a, dtype=np.float32)
-    return np.rint(np.float32(255.0) * np.clip(a, np.float32(0.0), np.float32(1.0))).astype(np.int32)

@@ -5,19 +5,11 @@ Everything is integer arithmetic after one float32 multiply per sample, so compa
 """
 import numpy as np
 
+from tests.pixel_ref import code, luma_of_codes as luma  # noqa: F401 (the tests use them as R.code, R.luma)
+
 from vcm_ts_amd.synthetic import frames
 
 GRID, BINS = 4, 32
-
-
-def code(v):
-    """(int) rint(255.0f * clamp01(v)): one float32 multiply, round-half-to-even; clamp01 = min(max(v, 0), 1)."""
-    v = np.asarray(v, dtype=np.float32)
-    return np.rint(np.float32(255.0) * np.minimum(np.maximum(v, np.float32(0.0)), np.float32(1.0))).astype(np.int64)
-
-
-def luma(r, g, b):
-    return (54 * r + 183 * g + 19 * b + 128) >> 8
 
 
 def hist(rgb):

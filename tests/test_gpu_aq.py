@@ -1,7 +1,6 @@
 """Backward-adaptive quantisation on a real MI355X: the activity and map kernels bit for bit against the numpy
 restatement (tests/aq_ref.py), a flat reference against no map, the GOP loop with the decoder rebuilding every map from its
 own reference pictures, the refusals, and the file loops with their aq.json side file."""
-import ctypes as C
 import json
 import os
 
@@ -10,7 +9,9 @@ import pytest
 import torch
 
 from tests import aq_ref as R
+from tests import gpu_util as U
 from tests import roiq_ref as QR
+from tests.gpu_util import file_nets  # noqa: F401 (fixture)
 from vcm_ts_amd import aq as A
 from vcm_ts_amd import lib
 from vcm_ts_amd import roi as X
@@ -20,27 +21,7 @@ from vcm_ts_amd.synthetic import frames
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 F32 = np.float32
-GUARD = 64
-
-
-def _bits(t):
-    return t.detach().cpu().numpy().view(np.uint32)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _strided(pic, row_pad, plane_pad, offset):
-    """`pic` (3, Hp, Wp) as a view with row stride Wp + row_pad and plane stride Hp * rs + plane_pad, `offset` elements into
-    a buffer of NaN: (the buffer, the view, row stride, plane stride)."""
-    _, Hp, Wp = pic.shape
-    rs = Wp + row_pad
-    ps = Hp * rs + plane_pad
-    buf = torch.full((offset + 3 * ps + GUARD,), float("nan"), device=DEV)
-    view = buf.as_strided((3, Hp, Wp), (ps, rs, 1), offset)
-    view.copy_(torch.from_numpy(pic))
-    return buf, view, rs, ps
+GUARD = U.GUARD
 
 
 # ------------------------------------------------------------------------------------------------ the activity kernel
@@ -53,10 +34,10 @@ def test_activity_kernel_equals_the_restatement_bit_for_bit(size):
     for n, (name, pic) in enumerate(R.pictures(Hp, Wp).items()):
         want_L, want_sum = R.activity(pic)
         for row_pad, plane_pad, offset in (layouts if n < 2 else [layouts[0], layouts[1 + n % 3]]):
-            buf, view, rs, ps = _strided(pic, row_pad, plane_pad, offset)
+            buf, view, rs, ps = U.strided(pic, Hp, Wp, row_pad, plane_pad, offset, DEV)[:4]
             L = torch.full((hc * wc + 2 * GUARD,), -7, dtype=torch.int32, device=DEV)
             total = torch.tensor([12345, -1], dtype=torch.int64, device=DEV)  # pre-loaded: the kernel ADDS
-            lib.check(lib.hip().dcvc_aq_activity(view.data_ptr(), rs, ps, Hp, Wp, L[GUARD:].data_ptr(), total.data_ptr(), _stream()),
+            lib.check(lib.hip().dcvc_aq_activity(view.data_ptr(), rs, ps, Hp, Wp, L[GUARD:].data_ptr(), total.data_ptr(), U.stream(DEV)),
                       "aq_activity")
             got = L.cpu().numpy()
             where = (name, row_pad, plane_pad, offset)
@@ -96,7 +77,7 @@ def test_map_kernel_equals_the_restatement_bit_for_bit(size):
     rois = {name: X.q_map(lists[name], Hp, Wp, roiq) for name in ("random-7", "random-40", "edges", "whole")}
     roi_host = {name: QR.q_map(lists[name], Hp, Wp, 0, QR.factors()) for name in rois}
     for name in rois:  # (the maps the products below are formed with are the restatement's)
-        assert np.array_equal(_bits(rois[name]).reshape(hc, wc), roi_host[name].view(np.uint32))
+        assert np.array_equal(U.f32_bits(rois[name]).reshape(hc, wc), roi_host[name].view(np.uint32))
     pics = R.pictures(Hp, Wp)
     seen = set()
     for strength, lo, hi in SETTINGS:
@@ -106,12 +87,12 @@ def test_map_kernel_equals_the_restatement_bit_for_bit(size):
             got = maps.map(x)
             want = R.picture_map(pics[pname], strength, lo, hi)
             assert got.shape == (hc, wc) and got.dtype == torch.float32 and got.device == DEV
-            assert np.array_equal(_bits(got), want.view(np.uint32)), (strength, lo, hi, pname)
+            assert np.array_equal(U.f32_bits(got), want.view(np.uint32)), (strength, lo, hi, pname)
             seen.update(np.unique(want).tolist())
             for rname, roi in rois.items():
                 got = maps.map(x, roi if pname != "random" else roi[0, 0])  # (both accepted shapes)
                 want = R.picture_map(pics[pname], strength, lo, hi, roi_host[rname])
-                assert np.array_equal(_bits(got), want.view(np.uint32)), (strength, lo, hi, pname, rname)
+                assert np.array_equal(U.f32_bits(got), want.view(np.uint32)), (strength, lo, hi, pname, rname)
     assert min(seen) < 0.9 and max(seen) > 2.0 and 1.0 in seen
     # one busy cell among flat ones at full strength: both clamps' neighbourhood
     lone = R.picture_map(pics["lone-busy"], 400)
@@ -142,8 +123,8 @@ def test_map_kernel_at_both_ends_of_the_table():
                 out = torch.full((hc * wc + 2 * GUARD,), float("nan"), device=DEV)
                 rd = None if r is None else torch.from_numpy(r).to(DEV)
                 lib.check(lib.hip().dcvc_aq_map(Ld.data_ptr(), sd.data_ptr(), hc, wc, maps.ktab.data_ptr(), maps.ftab.data_ptr(),
-                                                None if rd is None else rd.data_ptr(), out[GUARD:].data_ptr(), _stream()), "aq_map")
-                got = _bits(out)
+                                                None if rd is None else rd.data_ptr(), out[GUARD:].data_ptr(), U.stream(DEV)), "aq_map")
+                got = U.f32_bits(out)
                 want = R.q_map(L, total, strength, lo, hi, r)
                 assert np.array_equal(got[GUARD:GUARD + hc * wc].reshape(hc, wc), want.view(np.uint32)), (strength, lo, hi, total)
                 assert np.isnan(out[:GUARD].cpu().numpy()).all() and np.isnan(out[GUARD + hc * wc:].cpu().numpy()).all()
@@ -157,13 +138,7 @@ def test_map_kernel_at_both_ends_of_the_table():
 def nets(request):
     """Both arithmetic modes of the convolution kernels, as in tests/test_gpu_codec.py; the name-seeded weights of
     tests.util.oracle_weights."""
-    from vcm_ts_amd.dmc import DMC
-    from vcm_ts_amd.intra import IntraNoAR
-
-    d, i = DMC(precision=request.param).to(DEV).eval(), IntraNoAR(precision=request.param).to(DEV).eval()
-    d.update()
-    i.update()
-    return d, i
+    return U.seeded_pair(DEV, request.param)
 
 
 def test_a_flat_reference_gives_no_map(nets):
@@ -174,7 +149,7 @@ def test_a_flat_reference_gives_no_map(nets):
     for level in (0.0, 0.3, 1.0):
         ref = torch.full((1, 3, h, w), level, device=DEV)
         m = maps.map(ref)
-        assert np.array_equal(_bits(m), np.full((4, 8), F32(1.0)).view(np.uint32))
+        assert np.array_equal(U.f32_bits(m), np.full((4, 8), F32(1.0)).view(np.uint32))
         a = d.compress(x, intra_dpb(ref), 1.0, 1.0)
         keep = (a["bit_stream"], {k: v.clone() for k, v in a["dpb"].items()})
         b = d.compress(x, intra_dpb(ref), 1.0, 1.0, q_map=m)
@@ -215,7 +190,7 @@ def test_gop_round_trip_rebuilds_every_map(nets, size, seed):
         host = {t: recon[t].cpu().numpy()[0] for t in range(4)}
         for t in (1, 2, 3):  # the map of picture t is the restatement's on the reconstruction of t - 1
             want = R.picture_map(host[t - 1], STRENGTH)
-            assert np.array_equal(_bits(spy.seen[t - 1]), want.view(np.uint32)), t
+            assert np.array_equal(U.f32_bits(spy.seen[t - 1]), want.view(np.uint32)), t
         assert any(not bool((m == 1).all()) for m in spy.seen)
         print("maps:", [(float(m.min()), float(m.max())) for m in spy.seen])
         # the decoder, given the setting alone, rebuilds every reference picture bit for bit
@@ -278,35 +253,14 @@ def _roi():
     return X.Roi(lambda t: X.FrameBoxes(BOX), (X.RoiClass(0),), ("plate",))
 
 
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
-
-
-def _same_pngs(a, b, n=N_FRAMES):
-    for t in range(n):
-        name = f"im{t + 1:05d}.png"
-        assert (a / name).read_bytes() == (b / name).read_bytes(), t
-
-
-@pytest.fixture(scope="module")
-def file_nets():
-    from vcm_ts_amd import run_codec as RC
-
-    return [RC._nets(DEV, None) for _ in range(2)]
-
-
 @pytest.fixture(scope="module")
 def e2e(tmp_path_factory, file_nets):
     """the clip as PNGs; a plain encode and the encode with backward-adaptive quantisation"""
-    from PIL import Image
-
     from vcm_ts_amd import run_codec as RC
 
     tmp = tmp_path_factory.mktemp("aq_e2e")
     clip = np.rint(frames(11, N_FRAMES, FH, FW) * 255).astype(np.uint8).transpose(0, 2, 3, 1)
-    os.makedirs(tmp / "png")
-    for t, a in enumerate(clip):
-        Image.fromarray(a).save(tmp / "png" / f"im{t + 1:05d}.png")
+    U.write_pngs(tmp / "png", clip)
     RC.encode_folder(str(tmp / "png"), str(tmp / "plain"), gop=GOP, nets=file_nets)
     bits, size = RC.encode_folder(str(tmp / "png"), str(tmp / "aq"), str(tmp / "aq_rec"), gop=GOP, nets=file_nets, aq=AQ_FILE)
     assert size == (FH, FW) and len(bits) == N_FRAMES
@@ -319,13 +273,13 @@ def test_folder_side_file_and_decoder_output(e2e):
     tmp = e2e["tmp"]
     assert json.loads((tmp / "aq" / "aq.json").read_text()) == AQ_FILE.to_json()
     assert sorted(n for n in os.listdir(tmp / "aq") if not n.endswith(".bin")) == ["aq.json"]
-    aq, plain = _bins(tmp / "aq"), _bins(tmp / "plain")
+    aq, plain = U.bins(tmp / "aq"), U.bins(tmp / "plain")
     assert list(aq) == list(plain) and aq != plain
     for t in range(N_FRAMES):  # I pictures are not adapted; the first P picture of each GOP already is
         name = f"im{t + 1:05d}.bin"
         assert (aq[name] == plain[name]) == (t % GOP == 0), t
     assert RC.decode_folder(str(tmp / "aq"), str(tmp / "aq_dec"), FH, FW, gop=GOP) == N_FRAMES
-    _same_pngs(tmp / "aq_dec", tmp / "aq_rec")
+    U.same_pngs(tmp / "aq_dec", tmp / "aq_rec", N_FRAMES)
     # a record this host would build differently is refused by name, before anything is decoded
     info = AQ_FILE.to_json()
     info["tables"]["ktab"] = "%08x" % (int(info["tables"]["ktab"], 16) ^ 1)
@@ -345,14 +299,14 @@ def test_command_line(e2e, capsys):
     tmp = e2e["tmp"]
     RC.main(["encode", "--frames", str(tmp / "png"), "--bins", str(tmp / "cli"), "--recon", str(tmp / "cli_rec"), "--gop", str(GOP),
              "--aq-strength", str(STRENGTH)])
-    assert _bins(tmp / "cli") == _bins(tmp / "aq") and (tmp / "cli" / "aq.json").read_text() == (tmp / "aq" / "aq.json").read_text()
+    assert U.bins(tmp / "cli") == U.bins(tmp / "aq") and (tmp / "cli" / "aq.json").read_text() == (tmp / "aq" / "aq.json").read_text()
     RC.main(["decode", "--bins", str(tmp / "cli"), "--recon", str(tmp / "cli_dec"), "--height", str(FH), "--width", str(FW),
              "--gop", str(GOP)])
-    _same_pngs(tmp / "cli_dec", tmp / "cli_rec")
+    U.same_pngs(tmp / "cli_dec", tmp / "cli_rec", N_FRAMES)
     RC.main(["encode", "--frames", str(tmp / "png"), "--bins", str(tmp / "cli"), "--gop", str(GOP), "--aq-strength", "100",
              "--aq-clamp", "50", "200"])
     assert json.loads((tmp / "cli" / "aq.json").read_text())["clamp"] == [50, 200]
-    assert _bins(tmp / "cli") != _bins(tmp / "aq")
+    assert U.bins(tmp / "cli") != U.bins(tmp / "aq")
 
 
 def test_two_gop_streams_write_the_same_bins(e2e, file_nets):
@@ -360,7 +314,7 @@ def test_two_gop_streams_write_the_same_bins(e2e, file_nets):
 
     tmp = e2e["tmp"]
     RC.encode_folder(str(tmp / "png"), str(tmp / "aq2"), gop=GOP, nets=file_nets, gop_streams=2, aq=AQ_FILE)
-    assert _bins(tmp / "aq2") == _bins(tmp / "aq")
+    assert U.bins(tmp / "aq2") == U.bins(tmp / "aq")
     assert (tmp / "aq2" / "aq.json").read_text() == (tmp / "aq" / "aq.json").read_text()
 
 
@@ -370,7 +324,7 @@ def test_feature_off_gives_the_plain_bins_and_no_file(e2e, file_nets):
     from vcm_ts_amd.pipeline import pad_frame
 
     tmp = e2e["tmp"]
-    plain = _bins(tmp / "plain")
+    plain = U.bins(tmp / "plain")
     assert sorted(os.listdir(tmp / "plain")) == sorted(plain)  # no aq.json, nothing but the .bin files
     # the bytes of the GOP loop called directly, without the argument
     xs = [pad_frame(RC.u8_to_unit_float(torch.from_numpy(a).to(DEV))) for a in e2e["clip"]]
@@ -383,10 +337,10 @@ def test_feature_off_gives_the_plain_bins_and_no_file(e2e, file_nets):
     RC.encode_folder(str(tmp / "png"), str(tmp / "stale"), gop=GOP, nets=file_nets, aq=A.AQ(100, 50, 200))
     assert (tmp / "stale" / "aq.json").exists()
     RC.encode_folder(str(tmp / "png"), str(tmp / "stale"), gop=GOP, nets=file_nets)
-    assert _bins(tmp / "stale") == plain and sorted(os.listdir(tmp / "stale")) == sorted(plain)
+    assert U.bins(tmp / "stale") == plain and sorted(os.listdir(tmp / "stale")) == sorted(plain)
     # a clamp of 100 .. 100 adapts nothing: the plain bins, with the file
     RC.encode_folder(str(tmp / "png"), str(tmp / "stale"), gop=GOP, nets=file_nets, aq=A.AQ(STRENGTH, 100, 100))
-    assert _bins(tmp / "stale") == plain and (tmp / "stale" / "aq.json").exists()
+    assert U.bins(tmp / "stale") == plain and (tmp / "stale" / "aq.json").exists()
 
 
 def test_y4m_round_trip(e2e, file_nets):
@@ -405,7 +359,7 @@ def test_y4m_round_trip(e2e, file_nets):
     assert (tmp / "dec.y4m").read_bytes() == (tmp / "enc.y4m").read_bytes()
     assert (tmp / "dec.y4m").stat().st_size > N_FRAMES * FH * FW * 3 // 2
     RC.encode_video(str(tmp / "src.y4m"), str(tmp / "vplain"), gop=GOP, nets=file_nets)
-    assert _bins(tmp / "vplain") != _bins(tmp / "vbins") and not (tmp / "vplain" / "aq.json").exists()
+    assert U.bins(tmp / "vplain") != U.bins(tmp / "vbins") and not (tmp / "vplain" / "aq.json").exists()
 
 
 def test_with_roi_weighted_quantisation(e2e, file_nets):
@@ -417,24 +371,22 @@ def test_with_roi_weighted_quantisation(e2e, file_nets):
                      aq=AQ_FILE)
     assert sorted(n for n in os.listdir(tmp / "both") if not n.endswith(".bin")) == ["aq.json", "roiq.json"]
     RC.encode_folder(str(tmp / "png"), str(tmp / "roiq"), gop=GOP, nets=file_nets, roi=_roi(), roi_q=roi_q)
-    both, roiq, aq = _bins(tmp / "both"), _bins(tmp / "roiq"), _bins(tmp / "aq")
+    both, roiq, aq = U.bins(tmp / "both"), U.bins(tmp / "roiq"), U.bins(tmp / "aq")
     for t in range(N_FRAMES):  # an I picture keeps its ROI map; a P picture is coded under the product
         name = f"im{t + 1:05d}.bin"
         assert (both[name] == roiq[name]) == (t % GOP == 0) and both[name] != aq[name], t
     assert RC.decode_folder(str(tmp / "both"), str(tmp / "both_dec"), FH, FW, gop=GOP, roi=_roi()) == N_FRAMES
-    _same_pngs(tmp / "both_dec", tmp / "both_rec")
+    U.same_pngs(tmp / "both_dec", tmp / "both_rec", N_FRAMES)
 
 
 def test_with_rate_control(e2e, file_nets):
     """At 128x192 no report exists (MS-SSIM needs sides above 160, and frame_q_y is a key of the report): there the run, the
     decode and the q indexes in the P headers are checked; frame_q_y itself on a 176x192 clip, the smallest that reports."""
-    from PIL import Image
-
     from vcm_ts_amd import run_codec as RC
     from vcm_ts_amd import stream as S
 
     tmp = e2e["tmp"]
-    bpp = 0.5 * 8 * sum(len(v) for v in _bins(tmp / "aq").values()) / (N_FRAMES * FH * FW)
+    bpp = 0.5 * 8 * sum(len(v) for v in U.bins(tmp / "aq").values()) / (N_FRAMES * FH * FW)
     bits, size = RC.encode_folder(str(tmp / "png"), str(tmp / "rate"), str(tmp / "rate_rec"), gop=GOP, nets=file_nets,
                                   target_bpp=bpp, q_range=(0.5, 3.0), aq=AQ_FILE)
     assert len(bits) == N_FRAMES and (tmp / "rate" / "aq.json").exists()
@@ -442,20 +394,18 @@ def test_with_rate_control(e2e, file_nets):
     print("q_y indexes in the P headers", q_y)
     assert all(50 <= q <= 300 for q in q_y) and any(q != 100 for q in q_y)
     assert RC.decode_folder(str(tmp / "rate"), str(tmp / "rate_dec"), FH, FW, gop=GOP) == N_FRAMES
-    _same_pngs(tmp / "rate_dec", tmp / "rate_rec")
+    U.same_pngs(tmp / "rate_dec", tmp / "rate_rec", N_FRAMES)
     # with a report
     h, w = 176, 192
     clip = np.rint(frames(12, N_FRAMES, h, w) * 255).astype(np.uint8).transpose(0, 2, 3, 1)
-    os.makedirs(tmp / "png176")
-    for t, a in enumerate(clip):
-        Image.fromarray(a).save(tmp / "png176" / f"im{t + 1:05d}.png")
+    U.write_pngs(tmp / "png176", clip)
     plain, _ = RC.encode_folder(str(tmp / "png176"), str(tmp / "plain176"), gop=GOP, nets=file_nets, aq=AQ_FILE)
     bits, size, rd = RC.encode_folder(str(tmp / "png176"), str(tmp / "rate176"), str(tmp / "rate176_rec"), gop=GOP, nets=file_nets,
                                       report=True, target_bpp=0.5 * sum(plain) / (N_FRAMES * h * w), q_range=(0.5, 3.0), aq=AQ_FILE)
     print("frame_q_y", rd["frame_q_y"])
     assert len(rd["frame_q_y"]) == N_FRAMES and all(0.5 <= q <= 3.0 for q in rd["frame_q_y"]) and any(q != 1.0 for q in rd["frame_q_y"])
     assert RC.decode_folder(str(tmp / "rate176"), str(tmp / "rate176_dec"), h, w, gop=GOP) == N_FRAMES
-    _same_pngs(tmp / "rate176_dec", tmp / "rate176_rec")
+    U.same_pngs(tmp / "rate176_dec", tmp / "rate176_rec", N_FRAMES)
 
 
 def test_with_a_base_scale(e2e, file_nets):
@@ -465,9 +415,9 @@ def test_with_a_base_scale(e2e, file_nets):
     RC.encode_folder(str(tmp / "png"), str(tmp / "half"), str(tmp / "half_rec"), gop=GOP, nets=file_nets, base_scale="1/2", aq=AQ_FILE)
     assert sorted(n for n in os.listdir(tmp / "half") if not n.endswith(".bin")) == ["aq.json", "scale.json"]
     RC.encode_folder(str(tmp / "png"), str(tmp / "half_plain"), gop=GOP, nets=file_nets, base_scale="1/2")
-    assert _bins(tmp / "half") != _bins(tmp / "half_plain")  # (the map is taken from the base-size reference)
+    assert U.bins(tmp / "half") != U.bins(tmp / "half_plain")  # (the map is taken from the base-size reference)
     assert RC.decode_folder(str(tmp / "half"), str(tmp / "half_dec"), FH, FW, gop=GOP) == N_FRAMES
-    _same_pngs(tmp / "half_dec", tmp / "half_rec")
+    U.same_pngs(tmp / "half_dec", tmp / "half_rec", N_FRAMES)
     assert RC.decode_folder(str(tmp / "half"), str(tmp / "half_base"), FH, FW, gop=GOP, base_scale=None) == N_FRAMES  # --base-only
     with pytest.raises(NotImplementedError, match="base_scale= with roi_q="):
         RC.encode_folder(str(tmp / "png"), str(tmp / "never2"), gop=GOP, nets=file_nets, base_scale="1/2", roi=_roi(),

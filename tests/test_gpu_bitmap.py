@@ -10,6 +10,8 @@ import pytest
 import torch
 
 from tests import bitmap_ref as R
+from tests import gpu_util as U
+from tests.gpu_util import seeded_nets  # noqa: F401 (fixture: the name-seeded weights the CPU oracle's tests use)
 from vcm_ts_amd import bitmap as B
 from vcm_ts_amd import lib
 from vcm_ts_amd import roi as X
@@ -18,30 +20,21 @@ from vcm_ts_amd.synthetic import frames
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-GUARD, FILL = 64, 0x5A5A5A5A
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+FILL = 0x5A5A5A5A
 
 
 def _table_on_device(table):
     cdf, sizes, offsets = table
-    return _dev(B.cost_array(cdf, sizes, offsets)), _dev(sizes), _dev(offsets), cdf.shape[0], cdf.shape[1]
+    return U.to_dev(B.cost_array(cdf, sizes, offsets), DEV), U.to_dev(sizes, DEV), U.to_dev(offsets, DEV), cdf.shape[0], cdf.shape[1]
 
 
-def _guarded(n, dtype=torch.int32):
-    buf = torch.full((n + 2 * GUARD,), FILL, dtype=dtype, device=DEV)
-    return buf, buf[GUARD:GUARD + n]
+def _guarded(n, dtype=np.uint32):
+    buf, at = U.guarded(n, 0, dtype, FILL, DEV)
+    return buf, buf[at:at + n]
 
 
 def _guards_intact(buf, n):
-    h = buf.cpu().numpy()
-    return bool((h[:GUARD] == FILL).all() and (h[GUARD + n:] == FILL).all())
+    return U.guards_intact(buf, U.GUARD, n, FILL)
 
 
 # ----------------------------------------------------------------------------------------------------- the map kernels
@@ -59,12 +52,12 @@ def _scale_case(seed, N, Cc, H, W, rows=9):
 
 def _run_scale(table, planes, N, Cc, H, W):
     cost, sizes, offsets, rows, stride = _table_on_device(table)
-    (s0, i0), (s1, i1) = [(_dev(s), _dev(i)) for s, i in planes]
+    (s0, i0), (s1, i1) = [(U.to_dev(s, DEV), U.to_dev(i, DEV)) for s, i in planes]
     buf, view = _guarded(N * H * W)
     status = torch.zeros(1, dtype=torch.int32, device=DEV)
     lib.check(lib.hip().dcvc_bits_map_scale(s0.data_ptr(), i0.data_ptr(), s1.data_ptr(), i1.data_ptr(), cost.data_ptr(), rows,
                                             stride, sizes.data_ptr(), offsets.data_ptr(), view.data_ptr(), N, Cc, H, W,
-                                            status.data_ptr(), _stream()), "bits_map_scale")
+                                            status.data_ptr(), U.stream(DEV)), "bits_map_scale")
     return buf, view.cpu().numpy().reshape(N, H, W), int(status.item())
 
 
@@ -88,12 +81,12 @@ def test_factorized_map_kernel_equals_the_restatement_bit_for_bit():
     chan = np.broadcast_to(np.arange(Cc)[None, :, None, None], (N, Cc, H, W)).reshape(-1)
     sym, _ = R.random_symbols(rng, table, chan.size, rows=chan, escapes=0.2)
     cost, sizes, offsets, rows, stride = _table_on_device(table)
-    s = _dev(sym)
+    s = U.to_dev(sym, DEV)
     buf, view = _guarded(N * H * W)
     status = torch.zeros(1, dtype=torch.int32, device=DEV)
     lib.check(lib.hip().dcvc_bits_map_factorized(s.data_ptr(), cost.data_ptr(), rows, stride, sizes.data_ptr(),
                                                  offsets.data_ptr(), view.data_ptr(), N, Cc, H, W, status.data_ptr(),
-                                                 _stream()), "bits_map_factorized")
+                                                 U.stream(DEV)), "bits_map_factorized")
     want = R.map_factorized(sym, table, N, Cc, H, W)
     assert int(status.item()) == 0 and np.array_equal(view.cpu().numpy().reshape(N, H, W).astype(np.int64), want)
     assert _guards_intact(buf, N * H * W)
@@ -135,15 +128,15 @@ def test_region_kernel_equals_the_restatement_bit_for_bit(grid, K):
     maps = [m.astype(np.int32) for m in maps]
     labels = np.zeros((N, hc, wc), dtype=np.uint8)
     labels[:, :used_h, :used_w] = rng.integers(0, K, (N, used_h, used_w))
-    lab = _dev(labels)
+    lab = U.to_dev(labels, DEV)
     for absent in ((), (0, 1), (2,), (0, 1, 2)):
         present = [None if c in absent else m for c, m in enumerate(maps)]
-        on_dev = [None if m is None else _dev(m) for m in present]
+        on_dev = [None if m is None else U.to_dev(m, DEV) for m in present]
         ptrs = (C.c_void_p * 4)(*[None if m is None else m.data_ptr() for m in on_dev])
-        buf, view = _guarded(N * K * 4, torch.int64)
+        buf, view = _guarded(N * K * 4, np.uint64)
         status = torch.zeros(1, dtype=torch.int32, device=DEV)
         lib.check(lib.hip().dcvc_bits_regions(ptrs, lab.data_ptr(), K, view.data_ptr(), N, hc, wc, status.data_ptr(),
-                                              _stream()), "bits_regions")
+                                              U.stream(DEV)), "bits_regions")
         want = R.region_sums(present, labels, K)
         assert int(status.item()) == 0
         assert np.array_equal(view.cpu().numpy().reshape(N, K, 4), want), absent
@@ -162,8 +155,8 @@ def test_a_label_out_of_range_adds_nothing_and_sets_the_status():
     y = np.full((1, hc, wc), 5, dtype=np.int32)
     labels = np.zeros((1, hc, wc), dtype=np.uint8)
     labels[0, 1, 2] = 2
-    bm = B.BitMap({"y": _dev(y)}, torch.zeros(2, dtype=torch.int32, device=DEV), 1, hc, wc)
-    row = bm.regions_enqueue(_dev(labels), 2).cpu().numpy()
+    bm = B.BitMap({"y": U.to_dev(y, DEV)}, torch.zeros(2, dtype=torch.int32, device=DEV), 1, hc, wc)
+    row = bm.regions_enqueue(U.to_dev(labels, DEV), 2).cpu().numpy()
     assert row[:8].tolist() == [0, 0, 0, 15 * 16 * 5, 0, 0, 0, 0] and int(row[8:].view(np.int32)[0]) == B.BAD_LABEL
     with pytest.raises(B.BitMapError, match="label"):
         B.BitMap.decode(row, 1, 2)
@@ -189,22 +182,6 @@ def test_labels_from_boxes_follow_the_touch_rule():
 
 
 # ---------------------------------------------------------------------------------------------------------- the codecs
-@pytest.fixture(scope="module")
-def nets():
-    """The name-seeded weights the CPU oracle's tests use (tests/util.py oracle_weights are the same seeded state dicts)."""
-    from vcm_ts_amd.dmc import DMC
-    from vcm_ts_amd.intra import IntraNoAR
-
-    d, i = DMC().to(DEV).eval(), IntraNoAR().to(DEV).eval()
-    d.update()
-    i.update()
-    return d, i
-
-
-def _intra_dpb(x_hat):
-    return {"ref_frame": x_hat, "ref_feature": None, "ref_y": None, "ref_mv_y": None}
-
-
 def _np(t):
     return t.detach().cpu().numpy()
 
@@ -268,11 +245,11 @@ def _q(batch, a, b):
 
 
 @pytest.mark.parametrize("case", ["64x64", "72x104", "72x104-qmap", "64x64-batch2"])
-def test_codecs_bit_maps_equal_the_restatement_and_leave_the_bytes_alone(nets, case):
+def test_codecs_bit_maps_equal_the_restatement_and_leave_the_bytes_alone(seeded_nets, case):
     """I + 2 P: compress(bit_map=True) returns the bytes and the DPB of bit_map=False; the six maps are the restatement
     applied to the staged symbol planes; 8 * len(bit_stream) - totals.sum() / 65536 lies in the coder's bound.  With a
     q-scale map; with a batch of two rate points: one stream and one total per element."""
-    d, i = nets
+    d, i = seeded_nets
     size, *opt = case.split("-")
     h, w = (int(v) for v in size.split("x"))
     batch = 2 if "batch2" in opt else 1
@@ -293,7 +270,7 @@ def test_codecs_bit_maps_equal_the_restatement_and_leave_the_bytes_alone(nets, c
     assert (tot[:, :2] == 0).all() and res["bit_map"].maps["mv_y"] is None  # an I picture has no mv maps
     if batch == 2:
         assert tot[0].sum() != tot[1].sum()
-    dpb = _intra_dpb(keep[1])
+    dpb = U.intra_dpb(keep[1])
     for t in (1, 2):
         plain = d.compress(xs[t], dpb, qm, qy, q_map=q_map)
         assert "bit_map" not in plain
@@ -306,17 +283,17 @@ def test_codecs_bit_maps_equal_the_restatement_and_leave_the_bytes_alone(nets, c
         dpb = keep[1]
 
 
-def test_bit_maps_with_defer_and_the_device_coder(nets):
+def test_bit_maps_with_defer_and_the_device_coder(seeded_nets):
     """defer=True carries the map beside the pending stream; coder="device" codes other bytes from the same planes, so
     the maps are the host coder's."""
-    d, i = nets
+    d, i = seeded_nets
     xs = _clip(64, 64, 1)
     ref = i.compress(xs[0], 1.0, bit_map=True)
     want_i, x_hat = ref["bit_map"].totals(), ref["x_hat"].clone()
     r = i.compress(xs[0], 1.0, defer=True, bit_map=True)
     assert "bit_stream" not in r and np.array_equal(r["bit_map"].totals(), want_i)
     assert r["pending"].finish() == ref["bit_stream"]
-    dpb = _intra_dpb(x_hat)
+    dpb = U.intra_dpb(x_hat)
     ref = d.compress(xs[1], dpb, 1.0, 1.0, bit_map=True)
     want_p = {k: v.clone() for k, v in ref["bit_map"].maps.items()}
     r = d.compress(xs[1], dpb, 1.0, 1.0, defer=True, bit_map=True)
@@ -328,14 +305,14 @@ def test_bit_maps_with_defer_and_the_device_coder(nets):
     assert np.array_equal(r["bit_map"].totals(), want_i)
 
 
-def test_graph_replay_with_a_bit_map_is_refused(nets):
-    d, _ = nets
+def test_graph_replay_with_a_bit_map_is_refused(seeded_nets):
+    d, _ = seeded_nets
     x = torch.zeros((1, 3, 64, 64), device=DEV)
     with pytest.raises(NotImplementedError, match="bit_map.*graph"):
-        d.compress(x, _intra_dpb(x), 1.0, 1.0, graph=True, bit_map=True)
+        d.compress(x, U.intra_dpb(x), 1.0, 1.0, graph=True, bit_map=True)
     from vcm_ts_amd.pipeline import GopEncoder
 
-    enc = GopEncoder(nets[1], nets[0], gop_size=2, graphs=True)
+    enc = GopEncoder(seeded_nets[1], seeded_nets[0], gop_size=2, graphs=True)
     with pytest.raises(NotImplementedError, match="bit_maps"):
         enc.encode_gop([x, x], 1.0, 1.0, 1.0, bit_maps=lambda t, b: None)
 
@@ -355,16 +332,8 @@ def _roi():
     return X.Roi(lambda t: X.FrameBoxes(BOX), (X.RoiClass(0),), ("plate",))
 
 
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
-
-
 def _write_clip(folder, h, w):
-    from PIL import Image
-
-    os.makedirs(folder)
-    for t, a in enumerate(np.rint(frames(21, N_FRAMES, h, w) * 255).astype(np.uint8).transpose(0, 2, 3, 1)):
-        Image.fromarray(a).save(folder / f"im{t + 1:05d}.png")
+    U.write_pngs(folder, np.rint(frames(21, N_FRAMES, h, w) * 255).astype(np.uint8).transpose(0, 2, 3, 1))
 
 
 def test_file_loop_reports_regional_bits_and_writes_the_same_bins(tmp_path):
@@ -378,7 +347,7 @@ def test_file_loop_reports_regional_bits_and_writes_the_same_bins(tmp_path):
     small = dict(gop=GOP, nets=file_nets, roi=_roi(), roi_q=ROIQ)
     sbits, ssize = RC.encode_folder(str(tmp_path / "small"), str(tmp_path / "sbins"), bit_map=str(tmp_path / "smaps"), **small)
     RC.encode_folder(str(tmp_path / "small"), str(tmp_path / "splain"), **small)
-    assert _bins(tmp_path / "sbins") == _bins(tmp_path / "splain") and ssize == (SH, SW)
+    assert U.bins(tmp_path / "sbins") == U.bins(tmp_path / "splain") and ssize == (SH, SW)
     for g in range(N_FRAMES):
         cells = np.load(tmp_path / "smaps" / f"im{g + 1:05d}.npy")
         assert cells.shape == (1,) + X.grid_of(SH, SW) and float(cells.min()) > 0
@@ -392,7 +361,7 @@ def test_file_loop_reports_regional_bits_and_writes_the_same_bins(tmp_path):
     report = str(tmp_path / "report.json")
     bits, size, rd = RC.encode_folder(str(tmp_path / "png"), str(tmp_path / "bins"), report=report,
                                       bit_map=str(tmp_path / "maps"), **common)
-    assert _bins(tmp_path / "bins") == _bins(tmp_path / "plain") and len(bits) == N_FRAMES and size == (FH, FW)
+    assert U.bins(tmp_path / "bins") == U.bins(tmp_path / "plain") and len(bits) == N_FRAMES and size == (FH, FW)
     assert set(rd) == TODAY | NEW | {"frame_bits_roi", "frame_bits_bg", "frame_roi_cells"}
     assert json.loads(open(report).read()) == rd
     assert all(rd[k] == plain[k] for k in ("frame_bpp", "frame_type", "frame_roi_pixels", "frame_pixel_num"))
@@ -426,7 +395,7 @@ def test_file_loop_reports_regional_bits_and_writes_the_same_bins(tmp_path):
     assert len(out) == 2
     _, _, rd2 = RC.encode_folder(str(tmp_path / "png"), str(tmp_path / "bins3"), gop=GOP, nets=file_nets, report=True, bit_map=True)
     assert set(rd2) == (TODAY - {"frame_psnr_roi", "frame_psnr_bg", "frame_roi_pixels"}) | NEW
-    assert _bins(tmp_path / "bins2") == _bins(tmp_path / "bins3")
+    assert U.bins(tmp_path / "bins2") == U.bins(tmp_path / "bins3")
     for g in range(N_FRAMES):
         cells = np.load(tmp_path / "maps2" / f"im{g + 1:05d}.npy")
         assert float(cells.sum()) == sum(rd2[k][g] for k in NEW)

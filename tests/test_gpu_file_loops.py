@@ -14,8 +14,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_util as U
 from tests import scenecut_ref as SR
 from tests import yuv_ref as YR
+from tests.gpu_util import file_nets  # noqa: F401 (fixture)
 from vcm_ts_amd import yuv as Y
 
 pytestmark = pytest.mark.gpu
@@ -51,13 +53,6 @@ def _options(case, tmp, side):
 
 
 @pytest.fixture(scope="module")
-def file_nets():
-    from vcm_ts_amd import run_codec as RC
-
-    return [RC._nets(DEV, None) for _ in range(2)]
-
-
-@pytest.fixture(scope="module")
 def clip(tmp_path_factory):
     """src.y4m, and png/: the device's own 8-bit conversion of its pictures (what quantize8=True hands the codec)"""
     from PIL import Image
@@ -75,12 +70,6 @@ def clip(tmp_path_factory):
 
 def _files(folder, keep):
     return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if keep(n)}
-
-
-def _png(path):
-    from PIL import Image
-
-    return np.asarray(Image.open(path).convert("RGB"))
 
 
 @pytest.mark.parametrize("case", ["maps", "base", "base-roi"])
@@ -123,8 +112,8 @@ def test_both_sources_code_and_decode_alike(clip, file_nets, case):
     assert (tmp / f"{case}_v_dec.y4m").stat().st_size > N * H * W * 3 // 2
     for t in range(N):
         name = f"im{t + 1:05d}.png"
-        got = _png(tmp / f"{case}_f_dec" / name)
-        assert got.shape == (H, W, 3) and np.array_equal(got, _png(tmp / f"{case}_f_rec" / name)), t
+        got = U.png(tmp / f"{case}_f_dec" / name)
+        assert got.shape == (H, W, 3) and np.array_equal(got, U.png(tmp / f"{case}_f_rec" / name)), t
 
 
 def test_base_scale_with_bit_map_and_roi_stays_refused(clip, file_nets):

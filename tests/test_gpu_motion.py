@@ -1,7 +1,6 @@
 """Motion ROI boxes on a real MI355X: the background-model kernel bit for bit against the numpy restatement
 (tests/motion_ref.py) in strided, offset, NaN-surrounded layouts with guarded outputs, its refusals, MotionScan, a
 static-camera clip end to end, and the command line: `boxes`, then encode and decode with the third box class."""
-import ctypes as C
 import json
 import os
 import pickle
@@ -10,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_util as U
 from tests import motion_ref as R
 from vcm_ts_amd import lib
 from vcm_ts_amd import motionroi as M
@@ -18,29 +18,7 @@ from vcm_ts_amd import roi as X
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 F32 = np.float32
-GUARD, SENTINEL = 64, 0xABCD
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _strided(pic, row_pad, plane_pad, offset):
-    """`pic` (3, H, W) as a view with row stride W + row_pad and plane stride H * rs + plane_pad, `offset` elements into a
-    buffer of NaN (the layouts of test_gpu_aq.py): (the buffer, the view, row stride, plane stride)."""
-    _, H, W = pic.shape
-    rs = W + row_pad
-    ps = H * rs + plane_pad
-    buf = torch.full((offset + 3 * ps + GUARD,), float("nan"), device=DEV)
-    view = buf.as_strided((3, H, W), (ps, rs, 1), offset)
-    view.copy_(torch.from_numpy(pic))
-    return buf, view, rs, ps
-
-
-def _guarded(n, shift):
-    """n uint16 words of SENTINEL with GUARD (+ shift) words before and GUARD after: (the buffer, the first word's index)."""
-    buf = torch.from_numpy(np.full(2 * GUARD + shift + n, SENTINEL, dtype=np.uint16)).to(DEV)
-    return buf, GUARD + shift
+SENTINEL = 0xABCD
 
 
 def _ptr(buf, at):
@@ -48,9 +26,9 @@ def _ptr(buf, at):
 
 
 def _check(buf, at, n, want, where):
-    got = buf.cpu().numpy().astype(np.int64)
+    got = U.words(buf)
     assert np.array_equal(got[at:at + n], np.asarray(want, dtype=np.int64).reshape(-1)), where
-    assert (got[:at] == SENTINEL).all() and (got[at + n:] == SENTINEL).all(), where
+    assert U.guards_intact(buf, at, n, SENTINEL), where
 
 
 # (row pad, plane pad, picture offset, model / counts shift): 16-byte picture loads and 8-byte model accesses; an odd
@@ -75,22 +53,22 @@ def test_kernel_equals_the_restatement_bit_for_bit(size):
             for n, (row_pad, plane_pad, offset, shift) in enumerate(LAYOUTS):
                 if name != "random" and n not in (0, 1 + (T + len(name)) % 3):  # (every layout on one sequence, two on the others)
                     continue
-                bg, b0 = _guarded(H * W, shift)
+                bg, b0 = U.guarded(H * W, shift, np.uint16, SENTINEL, DEV)
                 for t, pic in enumerate(pics):
                     where = (name, T, k_bg, k_fg, row_pad, plane_pad, offset, shift, t)
-                    keep, view, rs, ps = _strided(pic, row_pad, plane_pad, offset)
-                    counts, c0 = _guarded(hc * wc, shift)  # (fresh sentinels every step: every cell is WRITTEN)
+                    keep, view, rs, ps = U.strided(pic, H, W, row_pad, plane_pad, offset, DEV)[:4]
+                    counts, c0 = U.guarded(hc * wc, shift, np.uint16, SENTINEL, DEV)  # (fresh sentinels every step: every cell is WRITTEN)
                     lib.check(L.dcvc_motion_step(view.data_ptr(), rs, ps, H, W, _ptr(bg, b0), int(t == 0), T, k_bg, k_fg,
-                                                 _ptr(counts, c0), _stream()), "motion_step")
+                                                 _ptr(counts, c0), U.stream(DEV)), "motion_step")
                     _check(bg, b0, H * W, want[t][0], where)
                     _check(counts, c0, hc * wc, want[t][1], where)
                     assert not want[t][1][(H + 15) // 16:].any() and not want[t][1][:, (W + 15) // 16:].any()  # the padding cells
                 # one more step from a model written by the host: |delta| on both sides of the threshold, side by side
-                bg[b0:b0 + H * W] = torch.from_numpy(edge_bg.astype(np.uint16).reshape(-1)).to(DEV)
-                keep, view, rs, ps = _strided(edge_pic, row_pad, plane_pad, offset)
-                counts, c0 = _guarded(hc * wc, shift)
+                bg[b0:b0 + H * W] = torch.from_numpy(edge_bg.astype(np.uint16).view(np.int16).reshape(-1)).to(DEV)
+                keep, view, rs, ps = U.strided(edge_pic, H, W, row_pad, plane_pad, offset, DEV)[:4]
+                counts, c0 = U.guarded(hc * wc, shift, np.uint16, SENTINEL, DEV)
                 lib.check(L.dcvc_motion_step(view.data_ptr(), rs, ps, H, W, _ptr(bg, b0), 0, T, k_bg, k_fg, _ptr(counts, c0),
-                                             _stream()), "motion_step")
+                                             U.stream(DEV)), "motion_step")
                 _check(bg, b0, H * W, edge_want[0], ("edge", T, n))
                 _check(counts, c0, hc * wc, edge_want[1], ("edge", T, n))
         assert int(edge_want[1].sum()) == H * (W // 2)  # exactly the odd columns are foreground
@@ -100,9 +78,9 @@ def test_kernel_equals_the_restatement_bit_for_bit(size):
 def test_entry_point_refusals_leave_the_outputs_alone():
     H, W = 70, 100
     hc, wc = R.grid(H, W)
-    keep, view, rs, ps = _strided(R.pictures(H, W)["random0"], 8, 24, 12)
-    bg, b0 = _guarded(H * W, 0)
-    counts, c0 = _guarded(hc * wc, 0)
+    keep, view, rs, ps = U.strided(R.pictures(H, W)["random0"], H, W, 8, 24, 12, DEV)[:4]
+    bg, b0 = U.guarded(H * W, 0, np.uint16, SENTINEL, DEV)
+    counts, c0 = U.guarded(hc * wc, 0, np.uint16, SENTINEL, DEV)
     good = dict(rgb=view.data_ptr(), rs=rs, ps=ps, H=H, W=W, bg=_ptr(bg, b0), init=1, T=24, k_bg=4, k_fg=8, counts=_ptr(counts, c0))
     order = ("rgb", "rs", "ps", "H", "W", "bg", "init", "T", "k_bg", "k_fg", "counts")
     for bad in ({"rgb": None}, {"bg": None}, {"counts": None}, {"H": 0}, {"W": 0}, {"H": 32769}, {"W": 32769},
@@ -110,10 +88,10 @@ def test_entry_point_refusals_leave_the_outputs_alone():
                 {"k_fg": 17}, {"rgb": view.data_ptr() + 2}, {"bg": _ptr(bg, b0) + 1}, {"counts": _ptr(counts, c0) + 1},
                 {"init": 0, "T": 0}, {"init": 0, "k_fg": 17}):
         v = dict(good, **bad)
-        assert lib.hip().dcvc_motion_step(*[v[k] for k in order], _stream()) == -1, bad
+        assert lib.hip().dcvc_motion_step(*[v[k] for k in order], U.stream(DEV)) == -1, bad
     torch.cuda.synchronize(DEV)
-    assert (bg.cpu().numpy() == SENTINEL).all() and (counts.cpu().numpy() == SENTINEL).all()
-    assert lib.hip().dcvc_motion_step(*[good[k] for k in order], _stream()) == 0  # (and the arguments were good ones)
+    assert (U.words(bg) == SENTINEL).all() and (U.words(counts) == SENTINEL).all()
+    assert lib.hip().dcvc_motion_step(*[good[k] for k in order], U.stream(DEV)) == 0  # (and the arguments were good ones)
     _check(bg, b0, H * W, R.init(R.pictures(H, W)["random0"])[0], "init")
 
 
@@ -181,10 +159,6 @@ def test_static_camera_clip_end_to_end(size):
 
 # ------------------------------------------------------------------------------------------------------- command line
 CH, CW, GOP = 70, 100, 3
-
-
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
 
 
 def _coords(folder, per_frame):
@@ -261,7 +235,7 @@ def test_encode_and_decode_with_the_motion_class(cli, capsys):
     _coords(tmp / "empty" / "motion_coords", [[]] * R.CLIP_FRAMES)
     RC.main(["encode", "--frames", str(tmp / "png"), "--bins", str(tmp / "flat"), "--motion-q", "0.5", "--background-q", "2.0",
              "--gop", str(GOP), "--roi-root", str(tmp / "empty")])
-    assert list(_bins(tmp / "flat")) == list(_bins(tmp / "bins")) and _bins(tmp / "flat") != _bins(tmp / "bins")
+    assert list(U.bins(tmp / "flat")) == list(U.bins(tmp / "bins")) and U.bins(tmp / "flat") != U.bins(tmp / "bins")
 
 
 def test_a_root_without_motion_coords_codes_the_bytes_it_did(cli, capsys):
@@ -275,7 +249,7 @@ def test_a_root_without_motion_coords_codes_the_bytes_it_did(cli, capsys):
     base = ["encode", "--frames", str(tmp / "png"), "--gop", str(GOP), "--plate-q", "0.6"]
     RC.main(base + ["--bins", str(tmp / "old_bins"), "--roi-root", str(tmp / "old")])
     RC.main(base + ["--bins", str(tmp / "new_bins"), "--roi-root", str(tmp / "new"), "--motion-q", "1.0"])
-    assert _bins(tmp / "old_bins") == _bins(tmp / "new_bins") and len(_bins(tmp / "old_bins")) == R.CLIP_FRAMES
+    assert U.bins(tmp / "old_bins") == U.bins(tmp / "new_bins") and len(U.bins(tmp / "old_bins")) == R.CLIP_FRAMES
     assert json.loads((tmp / "old_bins" / "roiq.json").read_text())["classes"] == {"liplates": 60, "faces": 100}
     assert json.loads((tmp / "new_bins" / "roiq.json").read_text())["classes"] == {"liplates": 60, "faces": 100, "motion": 100}
     assert sorted(os.listdir(tmp / "old_bins")) == sorted(os.listdir(tmp / "new_bins"))

@@ -19,8 +19,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_util as U
 from tests import picturehash_ref as R
 from tests import scenecut_ref as SR
+from tests.gpu_util import file_nets  # noqa: F401 (fixture)
 from vcm_ts_amd import lib
 from vcm_ts_amd import picturehash as PH
 
@@ -190,41 +192,20 @@ def test_wrong_inputs_are_value_errors():
 GOP, N, H, W = 8, 16, 64, 64
 
 
-def _png(path):
-    from PIL import Image
-
-    return np.asarray(Image.open(path).convert("RGB"))
-
-
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
-
-
 def _record(folder):
     return json.loads((folder / "hashes.json").read_text())
 
 
 @pytest.fixture(scope="module")
-def nets():
-    from vcm_ts_amd import run_codec as RC
-
-    return [RC._nets(DEV, None) for _ in range(2)]
-
-
-@pytest.fixture(scope="module")
-def e2e(tmp_path_factory, nets):
+def e2e(tmp_path_factory, file_nets):
     """the clip as PNGs; a plain encode, and the hashed encode with its reconstructions and every ref_frame its on_recon
     hook was handed (kept as host copies: the reference all tests share)"""
-    from PIL import Image
-
     from vcm_ts_amd import run_codec as RC
 
     tmp = tmp_path_factory.mktemp("picturehash_e2e")
     clip = SR.cut_clip(H, W)
-    os.makedirs(tmp / "png")
-    for t, a in enumerate(clip):
-        Image.fromarray(a).save(tmp / "png" / f"im{t + 1:05d}.png")
-    RC.encode_folder(str(tmp / "png"), str(tmp / "plain"), str(tmp / "plain_rec"), gop=GOP, nets=nets)
+    U.write_pngs(tmp / "png", clip)
+    RC.encode_folder(str(tmp / "png"), str(tmp / "plain"), str(tmp / "plain_rec"), gop=GOP, nets=file_nets)
     seen, add = {}, PH.HashLog.add
 
     def spy(self, g, ref_frame, size):
@@ -233,7 +214,7 @@ def e2e(tmp_path_factory, nets):
 
     with pytest.MonkeyPatch.context() as mp:
         mp.setattr(PH.HashLog, "add", spy)
-        RC.encode_folder(str(tmp / "png"), str(tmp / "hashed"), str(tmp / "hashed_rec"), gop=GOP, nets=nets, picture_hash=True)
+        RC.encode_folder(str(tmp / "png"), str(tmp / "hashed"), str(tmp / "hashed_rec"), gop=GOP, nets=file_nets, picture_hash=True)
     assert sorted(seen) == list(range(N))
     return dict(tmp=tmp, clip=clip, ref_frames=seen, bins=tmp / "hashed")
 
@@ -242,7 +223,7 @@ def _edited(e2e, name, key=None, t=5):
     """a copy of the hashed folder with one hex digit of key[t] changed (no .bin file is touched)"""
     dst = e2e["tmp"] / name
     os.makedirs(dst)
-    for n, data in _bins(e2e["bins"]).items():
+    for n, data in U.bins(e2e["bins"]).items():
         (dst / n).write_bytes(data)
     info = _record(e2e["bins"])
     if key:
@@ -254,14 +235,14 @@ def _edited(e2e, name, key=None, t=5):
 
 def test_encode_records_the_digests_of_its_own_reconstruction(e2e):
     tmp = e2e["tmp"]
-    assert _bins(tmp / "hashed") == _bins(tmp / "plain") and len(_bins(tmp / "plain")) == N
+    assert U.bins(tmp / "hashed") == U.bins(tmp / "plain") and len(U.bins(tmp / "plain")) == N
     assert sorted(n for n in os.listdir(tmp / "hashed") if not n.endswith(".bin")) == ["hashes.json"]
     info = _record(tmp / "hashed")
     assert (info["version"], info["algorithm"], info["frames"], info["height"], info["width"], info["padded"]) == \
         (1, "crc32", N, H, W, [64, 64])
     assert info["precision"] == os.environ.get("DCVC_PRECISION", "fp32")
     for t in range(N):
-        assert int(info["pixels"][t], 16) == zlib.crc32(_png(tmp / "hashed_rec" / f"im{t + 1:05d}.png").tobytes()), t
+        assert int(info["pixels"][t], 16) == zlib.crc32(U.png(tmp / "hashed_rec" / f"im{t + 1:05d}.png").tobytes()), t
         assert int(info["state"][t], 16) == R.crc32_f32(e2e["ref_frames"][t]), t
         assert int(info["pixels"][t], 16) == R.crc32_pixels(e2e["ref_frames"][t][:, :H, :W]), t
     assert len(set(info["pixels"])) == N and len(set(info["state"])) == N
@@ -269,20 +250,20 @@ def test_encode_records_the_digests_of_its_own_reconstruction(e2e):
     assert PH.verify_pngs(str(tmp / "hashed"), str(tmp / "plain_rec")) is None
 
 
-def test_feature_off_is_free_and_removes_a_stale_record(e2e, nets):
+def test_feature_off_is_free_and_removes_a_stale_record(e2e, file_nets):
     from vcm_ts_amd import run_codec as RC
 
     tmp = e2e["tmp"]
-    assert sorted(os.listdir(tmp / "plain")) == sorted(_bins(tmp / "plain"))  # nothing but the .bin files
+    assert sorted(os.listdir(tmp / "plain")) == sorted(U.bins(tmp / "plain"))  # nothing but the .bin files
     launches = []
     with pytest.MonkeyPatch.context() as mp:
         mp.setattr(PH, "_launch", lambda *a, **k: launches.append(a[0]))
         assert RC.decode_folder(str(tmp / "plain"), str(tmp / "plain_dec"), H, W, gop=GOP) == N
         stale, _ = _edited(e2e, "stale")
-        RC.encode_folder(str(tmp / "png"), str(stale), gop=GOP, nets=nets)
+        RC.encode_folder(str(tmp / "png"), str(stale), gop=GOP, nets=file_nets)
     assert launches == []
     assert sorted(os.listdir(tmp / "plain_dec")) == [f"im{t + 1:05d}.png" for t in range(N)]
-    assert sorted(os.listdir(stale)) == sorted(_bins(tmp / "plain")) and _bins(stale) == _bins(tmp / "plain")
+    assert sorted(os.listdir(stale)) == sorted(U.bins(tmp / "plain")) and U.bins(stale) == U.bins(tmp / "plain")
     for mode in ("strict", "pixels", "warn"):
         with pytest.raises(ValueError, match="there is no hashes.json"):
             RC.decode_folder(str(tmp / "plain"), str(tmp / "never"), H, W, gop=GOP, verify=mode)
@@ -290,27 +271,27 @@ def test_feature_off_is_free_and_removes_a_stale_record(e2e, nets):
     assert RC.decode_folder(str(tmp / "plain"), str(tmp / "plain_off"), H, W, gop=GOP, verify="off") == N
 
 
-def test_two_gop_streams_and_scenecut_record_the_same_digests(e2e, nets):
+def test_two_gop_streams_and_scenecut_record_the_same_digests(e2e, file_nets):
     from vcm_ts_amd import run_codec as RC
 
     tmp = e2e["tmp"]
-    RC.encode_folder(str(tmp / "png"), str(tmp / "two"), gop=GOP, nets=nets, gop_streams=2, picture_hash=True)
+    RC.encode_folder(str(tmp / "png"), str(tmp / "two"), gop=GOP, nets=file_nets, gop_streams=2, picture_hash=True)
     assert (tmp / "two" / "hashes.json").read_text() == (tmp / "hashed" / "hashes.json").read_text()
-    assert _bins(tmp / "two") == _bins(tmp / "hashed")
+    assert U.bins(tmp / "two") == U.bins(tmp / "hashed")
     # scene-cut I pictures at [0, 5, 13] (tests/test_gpu_scenecut.py): the first GOP is the same pictures, and every
     # digest is of the encode's own reconstruction
-    RC.encode_folder(str(tmp / "png"), str(tmp / "cut"), str(tmp / "cut_rec"), gop=GOP, nets=nets, gop_streams=2, scenecut=0.5,
+    RC.encode_folder(str(tmp / "png"), str(tmp / "cut"), str(tmp / "cut_rec"), gop=GOP, nets=file_nets, gop_streams=2, scenecut=0.5,
                      min_gop=2, picture_hash=True)
     cut, base = _record(tmp / "cut"), _record(tmp / "hashed")
     assert json.loads((tmp / "cut" / "gops.json").read_text())["i_pictures"] == [0, 5, 13]
     assert cut["pixels"][:5] == base["pixels"][:5] and cut["state"][:5] == base["state"][:5]
     assert cut["pixels"][5] != base["pixels"][5]
     for t in range(N):
-        assert int(cut["pixels"][t], 16) == zlib.crc32(_png(tmp / "cut_rec" / f"im{t + 1:05d}.png").tobytes()), t
+        assert int(cut["pixels"][t], 16) == zlib.crc32(U.png(tmp / "cut_rec" / f"im{t + 1:05d}.png").tobytes()), t
     assert RC.decode_folder(str(tmp / "cut"), str(tmp / "cut_dec"), H, W, verify="strict") == N
 
 
-def test_y4m_path_records_and_verifies(e2e, nets):
+def test_y4m_path_records_and_verifies(e2e, file_nets):
     from tests import yuv_ref as YR
     from vcm_ts_amd import run_codec as RC
 
@@ -318,11 +299,11 @@ def test_y4m_path_records_and_verifies(e2e, nets):
     planes = [tuple(p.astype(np.uint8) for p in YR.from_rgb(a.transpose(2, 0, 1).astype(np.float32) / np.float32(255.0), dtype=np.float64))
               for a in e2e["clip"]]
     YR.write_y4m(str(tmp / "src.y4m"), planes, W, H, fps="30:1")
-    RC.encode_video(str(tmp / "src.y4m"), str(tmp / "v1"), gop=GOP, nets=nets, picture_hash=True)
-    RC.encode_video(str(tmp / "src.y4m"), str(tmp / "v2"), gop=GOP, nets=nets, gop_streams=2, picture_hash=True)
-    RC.encode_video(str(tmp / "src.y4m"), str(tmp / "v0"), gop=GOP, nets=nets)
+    RC.encode_video(str(tmp / "src.y4m"), str(tmp / "v1"), gop=GOP, nets=file_nets, picture_hash=True)
+    RC.encode_video(str(tmp / "src.y4m"), str(tmp / "v2"), gop=GOP, nets=file_nets, gop_streams=2, picture_hash=True)
+    RC.encode_video(str(tmp / "src.y4m"), str(tmp / "v0"), gop=GOP, nets=file_nets)
     assert (tmp / "v1" / "hashes.json").read_text() == (tmp / "v2" / "hashes.json").read_text()
-    assert _bins(tmp / "v1") == _bins(tmp / "v0") == _bins(tmp / "v2")
+    assert U.bins(tmp / "v1") == U.bins(tmp / "v0") == U.bins(tmp / "v2")
     assert sorted(n for n in os.listdir(tmp / "v0") if not n.endswith(".bin")) == ["sequence.json"]
     assert sorted(n for n in os.listdir(tmp / "v1") if not n.endswith(".bin")) == ["hashes.json", "sequence.json"]
     assert RC.decode_video(str(tmp / "v1"), str(tmp / "v1.y4m"), verify="strict") == N
@@ -387,7 +368,7 @@ def test_an_edited_state_digest_is_a_warning_unless_strict(e2e):
         assert sorted(set(launches)) == ["dcvc_hash_f32", "dcvc_hash_pixels"]  # (the counter does see them)
 
 
-def test_decoding_with_another_precision_stops_where_the_pictures_part(e2e, nets):
+def test_decoding_with_another_precision_stops_where_the_pictures_part(e2e, file_nets):
     """The judge is independent of the hashes: both precisions decode the folder through _decode_bins, every ref_frame is
     kept, t* is the first picture whose fp32 bits differ and p* the first whose 8-bit codes differ."""
     from vcm_ts_amd import run_codec as RC
@@ -397,7 +378,7 @@ def test_decoding_with_another_precision_stops_where_the_pictures_part(e2e, nets
     coded = _record(e2e["bins"])["precision"]
     other = "fp16x3" if coded == "fp32" else "fp32"
     plan, frames = GopPlan.fixed(N, GOP), {}
-    for precision, pair in ((coded, nets[0]), (other, RC._nets(DEV, other))):
+    for precision, pair in ((coded, file_nets[0]), (other, RC._nets(DEV, other))):
         kept = frames[precision] = []
         RC._decode_bins(pair, str(e2e["bins"]), H, W, plan, lambda t, ref_frame: kept.append(ref_frame.detach().clone()))
     assert all(np.array_equal(a.cpu().numpy()[0].view(np.uint32), e2e["ref_frames"][t].view(np.uint32))

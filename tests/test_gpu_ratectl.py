@@ -4,7 +4,6 @@ and the DPB left alone; a rate-controlled GOP against the restated controller re
 the decoder; the direction of the control; GOP streams; the file loop; the refusals."""
 import ctypes as C
 import json
-import os
 from fractions import Fraction
 
 import numpy as np
@@ -12,7 +11,9 @@ import pytest
 import torch
 
 from tests import bitmap_ref as B
+from tests import gpu_util as U
 from tests import ratectl_ref as R
+from tests.gpu_util import seeded_nets  # noqa: F401 (fixture)
 from vcm_ts_amd import bitmap as BM
 from vcm_ts_amd import lib
 from vcm_ts_amd import ratectl as RC
@@ -26,18 +27,10 @@ LADDERS = {1: (100,), 3: (63, 100, 159), 8: RC.LADDER}
 I100 = RC.LADDER.index(100)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
 def _offset(a, lead):
     """`a` on the device as a view that starts `lead` elements into its buffer."""
     buf = torch.zeros(a.size + lead + 5, dtype=torch.from_numpy(a[:0]).dtype, device=DEV)
-    buf[lead:lead + a.size] = _dev(a.reshape(-1))
+    buf[lead:lead + a.size] = U.to_dev(a.reshape(-1), DEV)
     return buf[lead:lead + a.size]
 
 
@@ -85,7 +78,7 @@ def _reference(shape):
 def _run_kernel(table, edges, res, sc, ladder, shape):
     N, Cc, H, W = shape
     K = len(ladder)
-    cost, sizes, offsets = _dev(BM.cost_array(*table)), _dev(table[1]), _dev(table[2])
+    cost, sizes, offsets = U.to_dev(BM.cost_array(*table), DEV), U.to_dev(table[1], DEV), U.to_dev(table[2], DEV)
     r, s, e = _offset(res, 3), _offset(sc, 1), _offset(edges, 5)
     buf = torch.full((N * K + 2 * GUARD,), FILL, dtype=torch.int64, device=DEV)
     view = buf[GUARD:GUARD + N * K]
@@ -93,7 +86,7 @@ def _run_kernel(table, edges, res, sc, ladder, shape):
     fac = np.array([R.factor(h) for h in ladder], dtype=np.float32)
     lib.check(lib.hip().dcvc_bits_sweep_scale(r.data_ptr(), s.data_ptr(), e.data_ptr(), fac.ctypes.data_as(C.c_void_p), K,
                                               cost.data_ptr(), table[0].shape[0], table[0].shape[1], sizes.data_ptr(),
-                                              offsets.data_ptr(), view.data_ptr(), N, Cc, H, W, status.data_ptr(), _stream()),
+                                              offsets.data_ptr(), view.data_ptr(), N, Cc, H, W, status.data_ptr(), U.stream(DEV)),
               "bits_sweep_scale")
     h = buf.cpu().numpy()
     intact = bool((h[:GUARD] == FILL).all() and (h[GUARD + N * K:] == FILL).all())
@@ -141,21 +134,6 @@ def test_a_row_outside_the_table_costs_nothing_and_sets_the_status():
 
 
 # ------------------------------------------------------------------------------------------------------------ the codec
-@pytest.fixture(scope="module")
-def nets():
-    from vcm_ts_amd.dmc import DMC
-    from vcm_ts_amd.intra import IntraNoAR
-
-    d, i = DMC().to(DEV).eval(), IntraNoAR().to(DEV).eval()
-    d.update()
-    i.update()
-    return d, i
-
-
-def _intra_dpb(x_hat):
-    return {"ref_frame": x_hat, "ref_feature": None, "ref_y": None, "ref_mv_y": None}
-
-
 def _clip(h, w, batch, n=3, seed=31):
     fr = frames(seed, n, h, w)
     xs = [pad_frame(torch.from_numpy(fr[t:t + 1]).to(DEV)) for t in range(n)]
@@ -167,13 +145,13 @@ def _q(batch, a, b):
 
 
 @pytest.mark.parametrize("case", ["64x64", "72x104", "72x104-qmap", "64x64-batch2"])
-def test_compress_with_a_sweep_prices_the_coded_symbols_and_leaves_the_bytes_alone(nets, case):
+def test_compress_with_a_sweep_prices_the_coded_symbols_and_leaves_the_bytes_alone(seeded_nets, case):
     """I + 2 P: compress(sweep=LADDER) returns the bytes and every DPB tensor of the call without it; the column of 100
     hundredths is the y total of the picture's bit map, exactly; the whole row is the restatement applied to the residual
     and scale planes the picture left on the device."""
     from vcm_ts_amd.entropy import scale_index_edges
 
-    d, i = nets
+    d, i = seeded_nets
     size, *opt = case.split("-")
     h, w = (int(v) for v in size.split("x"))
     batch = 2 if "batch2" in opt else 1
@@ -184,7 +162,7 @@ def test_compress_with_a_sweep_prices_the_coded_symbols_and_leaves_the_bytes_alo
         q_map = torch.full((1, 1, Hp // 16, Wp // 16), 1.4, device=DEV)
         q_map[:, :, 1:4, 2:6] = 0.6
     qm, qy = _q(batch, 1.0, 1.3), _q(batch, 1.0, 0.7)
-    dpb = _intra_dpb(i.compress(xs[0], _q(batch, 1.0, 0.6), q_map=q_map)["x_hat"].clone())
+    dpb = U.intra_dpb(i.compress(xs[0], _q(batch, 1.0, 0.6), q_map=q_map)["x_hat"].clone())
     edges = scale_index_edges("laplace").numpy()
     for t in (1, 2):
         plain = d.compress(xs[t], dpb, qm, qy, q_map=q_map)
@@ -230,28 +208,28 @@ def _coded_bits(coded):
 
 
 @pytest.fixture(scope="module")
-def free_run(nets, clip8):
+def free_run(seeded_nets, clip8):
     """The 8 pictures coded without rate control: (coded, bits per picture)."""
-    coded, bits, _ = GopEncoder(nets[1], nets[0], gop_size=GOP).encode_gop(clip8, *START)
+    coded, bits, _ = GopEncoder(seeded_nets[1], seeded_nets[0], gop_size=GOP).encode_gop(clip8, *START)
     per = _coded_bits(coded)
     assert sum(per) == bits
     return coded, per
 
 
-def _controlled(nets, clip8, target_bits, q_range=(1, 65500)):
+def _controlled(seeded_nets, clip8, target_bits, q_range=(1, 65500)):
     recons, res = [], {}
-    enc = GopEncoder(nets[1], nets[0], gop_size=GOP)
+    enc = GopEncoder(seeded_nets[1], seeded_nets[0], gop_size=GOP)
     coded, bits, _ = enc.encode_gop(clip8, *START, on_recon=lambda t, x: recons.append(x.clone()), res=res,
                                     rate=RC.factory(target_bits, GOP, q_range))
     assert sum(_coded_bits(coded)) == bits
     return enc, coded, recons, res["rate_log"]
 
 
-def test_a_controlled_gop_follows_the_restated_controller_and_decodes(nets, clip8, free_run):
+def test_a_controlled_gop_follows_the_restated_controller_and_decodes(seeded_nets, clip8, free_run):
     """8 pictures at 64x64, target 0.7 of the free run's average: the q indexes in the headers are what the restated
     controller decides when replayed on the run's own log, and the decoder reproduces the encoder's reconstructions."""
     target = Fraction(7 * sum(free_run[1]), 10 * GOP)
-    enc, coded, recons, log = _controlled(nets, clip8, target)
+    enc, coded, recons, log = _controlled(seeded_nets, clip8, target)
     assert [k for k, _, _ in coded] == ["I"] + ["P"] * 7 and len(log) == GOP
     assert [e[1] for e in log] == _coded_bits(coded)
     assert log[0][0] == 100 and log[0][2] is None and log[0][3] is None
@@ -266,34 +244,34 @@ def test_a_controlled_gop_follows_the_restated_controller_and_decodes(nets, clip
 
 
 @pytest.mark.parametrize("factor,sign", [(Fraction(1, 2), -1), (2, 1)], ids=["half", "twice"])
-def test_direction_of_the_control(nets, clip8, free_run, factor, sign):
+def test_direction_of_the_control(seeded_nets, clip8, free_run, factor, sign):
     """A target of half the free run's average bits per picture must cost fewer bits from the third P picture on than
     the free run's same pictures, a target of twice must cost more.  The sign only: how close a GOP lands to its target
     is measured (profiles/ratectl_1080p.txt), not asserted."""
     free = free_run[1]
     target = factor * Fraction(sum(free), GOP)
-    _, coded, _, log = _controlled(nets, clip8, target)
+    _, coded, _, log = _controlled(seeded_nets, clip8, target)
     got = _coded_bits(coded)
     print("target", float(target), "free", free, "controlled", got, "q_y", [q[-1] for _, q, _ in coded])
     assert got[:3] == free[:3]  # (the I picture and the first two P pictures are not controlled)
     assert (sum(got[3:]) - sum(free[3:])) * sign > 0
 
 
-def test_q_range_bounds_every_decision(nets, clip8, free_run):
+def test_q_range_bounds_every_decision(seeded_nets, clip8, free_run):
     target = Fraction(sum(free_run[1]), 4 * GOP)
-    _, coded, _, _ = _controlled(nets, clip8, target, q_range=(90, 130))
+    _, coded, _, _ = _controlled(seeded_nets, clip8, target, q_range=(90, 130))
     qs = [q[1] for _, q, _ in coded[1:]]
     assert qs[:2] == [100, 100] and all(90 <= q <= 130 for q in qs) and 130 in qs
 
 
-def test_two_gops_on_two_streams_give_the_bytes_of_sequential_coding(nets, clip8, free_run):
+def test_two_gops_on_two_streams_give_the_bytes_of_sequential_coding(seeded_nets, clip8, free_run):
     from vcm_ts_amd.dmc import DMC
     from vcm_ts_amd.intra import IntraNoAR
 
     target = Fraction(6 * sum(free_run[1]), 10 * GOP)
     rate = RC.factory(target, 4)
     res = {}
-    seq, _, _ = GopEncoder(nets[1], nets[0], gop_size=4).encode_gop(clip8, *START, rate=rate, res=res)
+    seq, _, _ = GopEncoder(seeded_nets[1], seeded_nets[0], gop_size=4).encode_gop(clip8, *START, rate=rate, res=res)
     assert [k for k, _, _ in seq] == ["I", "P", "P", "P"] * 2 and len(R.split_gops(res["rate_log"])) == 2
     assert any(q[1] != 100 for _, q, _ in seq[3::4])
 
@@ -311,16 +289,8 @@ def test_two_gops_on_two_streams_give_the_bytes_of_sequential_coding(nets, clip8
 N_FRAMES, FGOP, FH, FW = 6, 5, 176, 192  # (a report takes MS-SSIM, whose five levels need sides above 160)
 
 
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
-
-
 def _write_clip(folder, h, w):
-    from PIL import Image
-
-    os.makedirs(folder)
-    for t, a in enumerate(np.rint(frames(21, N_FRAMES, h, w) * 255).astype(np.uint8).transpose(0, 2, 3, 1)):
-        Image.fromarray(a).save(folder / f"im{t + 1:05d}.png")
+    U.write_pngs(folder, np.rint(frames(21, N_FRAMES, h, w) * 255).astype(np.uint8).transpose(0, 2, 3, 1))
 
 
 def test_file_loop_with_a_target(tmp_path):
@@ -361,21 +331,21 @@ def test_file_loop_with_a_target(tmp_path):
     # two GOP streams: the same bytes
     F.encode_folder(str(tmp_path / "png"), str(tmp_path / "bins2"), gop=FGOP, nets=[file_nets, F._nets(DEV, None)], gop_streams=2,
                     target_bpp=bpp, q_range=(0.5, 3.0))
-    assert _bins(tmp_path / "bins2") == _bins(tmp_path / "bins")
+    assert U.bins(tmp_path / "bins2") == U.bins(tmp_path / "bins")
 
 
 # ------------------------------------------------------------------------------------------------------------- refusals
-def test_refusals(nets, tmp_path, monkeypatch, capsys):
-    d, i = nets
+def test_refusals(seeded_nets, tmp_path, monkeypatch, capsys):
+    d, i = seeded_nets
     x = torch.zeros((1, 3, 64, 64), device=DEV)
     with pytest.raises(NotImplementedError, match="sweep.*graph"):
-        d.compress(x, _intra_dpb(x), 1.0, 1.0, graph=True, sweep=RC.LADDER)
+        d.compress(x, U.intra_dpb(x), 1.0, 1.0, graph=True, sweep=RC.LADDER)
     with pytest.raises(ValueError, match="ladder.*must contain 100"):
-        d.compress(x, _intra_dpb(x), 1.0, 1.0, sweep=(50, 200))
+        d.compress(x, U.intra_dpb(x), 1.0, 1.0, sweep=(50, 200))
     d.train()
     try:
         with pytest.raises(ValueError, match="sweep.*eval"):
-            d.compress(x, _intra_dpb(x), 1.0, 1.0, sweep=RC.LADDER)
+            d.compress(x, U.intra_dpb(x), 1.0, 1.0, sweep=RC.LADDER)
     finally:
         d.eval()
     enc = GopEncoder(i, d, gop_size=2, graphs=True)

@@ -3,7 +3,6 @@ offset, NaN-surrounded layouts with guarded outputs, its refusals, Redactor, and
 the codec is handed, the bytes of a plain encode of those pictures, an unchanged decoder, the report, two GOP streams, a
 Y4M file, a reduced base layer, the prefilter before it, the residual layer beside it, the command line."""
 import contextlib
-import ctypes as C
 import json
 import os
 import pickle
@@ -12,60 +11,17 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_util as U
 from tests import redact_ref as R
+from tests.gpu_util import file_nets, no_garbage_left_behind  # noqa: F401 (fixtures)
 from vcm_ts_amd import lib
 from vcm_ts_amd import redact as D
 from vcm_ts_amd import roi as X
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("no_garbage_left_behind")]
 DEV = torch.device("cuda:0")
 F32 = np.float32
-GUARD, SENT16 = 64, 0xABCD
-
-
-@pytest.fixture(autouse=True)
-def _no_garbage_left_behind():
-    """As in test_gpu_tnr.py: the file loops keep pinned buffers and events, and whatever of them ends up in a reference
-    cycle is collected here, at a known point between tests with the device idle."""
-    import gc
-
-    yield
-    torch.cuda.synchronize(DEV)
-    gc.collect()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _strided(pic, H, W, row_pad, plane_pad, offset):
-    """A (3, H, W) view with row stride W + row_pad and plane stride H * rs + plane_pad, `offset` elements into a buffer of
-    NaN (the layouts of test_gpu_tnr.py), holding `pic` when one is given: (the buffer, the view, row stride, plane
-    stride, the buffer's mask of the view's words)."""
-    rs = W + row_pad
-    ps = H * rs + plane_pad
-    buf = torch.full((offset + 3 * ps + GUARD,), float("nan"), device=DEV)
-    view = buf.as_strided((3, H, W), (ps, rs, 1), offset)
-    if pic is not None:
-        view.copy_(torch.from_numpy(np.array(pic)))
-    mask = np.zeros(buf.numel(), dtype=bool)
-    mask[offset + np.add.outer(np.add.outer(ps * np.arange(3), rs * np.arange(H)), np.arange(W))] = True
-    return buf, view, rs, ps, mask
-
-
-def _guarded(n, shift):
-    """n uint16 words of SENT16 with GUARD (+ shift) words before and GUARD after, as an int16 tensor: (the buffer, the
-    first word's index)."""
-    buf = torch.from_numpy(np.full(2 * GUARD + shift + n, SENT16, dtype=np.uint16).view(np.int16)).to(DEV)
-    return buf, GUARD + shift
-
-
-def _words(buf):
-    return buf.cpu().numpy().view(np.uint16).astype(np.int64)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+SENT16 = 0xABCD
 
 
 def _box_pair(boxes):
@@ -86,19 +42,19 @@ def _run(pic, boxes, mask, grow, tile, fill, H, W, layout, want, where):
     """One dcvc_redact in `layout`, held against want = (out, count)."""
     row_pad, plane_pad, offset, shift = layout
     hc, wc = R.grid(H, W)
-    ks, vs, srs, sps, smask = _strided(pic, H, W, row_pad, plane_pad, offset)
+    ks, vs, srs, sps, smask = U.strided(pic, H, W, row_pad, plane_pad, offset, DEV)
     before = ks.cpu().numpy().view(np.uint32).copy()
-    ko, vo, ors, ops, omask = _strided(None, H, W, row_pad, plane_pad, offset)
-    count, c0 = _guarded(hc * wc, shift)  # (fresh sentinels every run: every cell is WRITTEN)
+    ko, vo, ors, ops, omask = U.strided(None, H, W, row_pad, plane_pad, offset, DEV)
+    count, c0 = U.guarded(hc * wc, shift, np.uint16, SENT16, DEV)  # (fresh sentinels every run: every cell is WRITTEN)
     keep, host, dev, devp, n = _box_pair(boxes)
     lib.check(lib.hip().dcvc_redact(vs.data_ptr(), srs, sps, vo.data_ptr(), ors, ops, H, W, host, devp, n, mask, grow, tile, fill,
-                                    count.data_ptr() + 2 * c0, _stream()), "redact")
+                                    count.data_ptr() + 2 * c0, U.stream(DEV)), "redact")
     got = ko.cpu().numpy()
-    assert np.array_equal(_bits(got[omask]), _bits(want[0].reshape(-1))), where
+    assert np.array_equal(U.f32_bits(got[omask]), U.f32_bits(want[0].reshape(-1))), where
     assert np.isnan(got[~omask]).all(), where  # nothing outside the crop of out is touched
-    words = _words(count)
+    words = U.words(count)
     assert np.array_equal(words[c0:c0 + hc * wc], np.asarray(want[1]).reshape(-1)), where
-    assert (words[:c0] == SENT16).all() and (words[c0 + hc * wc:] == SENT16).all(), where
+    assert U.guards_intact(count, c0, hc * wc, SENT16), where
     assert np.array_equal(ks.cpu().numpy().view(np.uint32), before), where  # the input is only read
     if dev is not None:
         assert np.array_equal(dev.cpu().numpy(), keep.reshape(-1)), where
@@ -140,9 +96,9 @@ def test_entry_point_refusals_leave_the_outputs_alone():
     H, W = 70, 100
     hc, wc = R.grid(H, W)
     pic, boxes = R.picture(H, W), R.box_sets(H, W)["classes"]
-    ks, vs, srs, sps, _ = _strided(pic, H, W, 8, 24, 12)
-    ko, vo, ors, ops, omask = _strided(None, H, W, 8, 24, 12)
-    count, c0 = _guarded(hc * wc, 0)
+    ks, vs, srs, sps, _ = U.strided(pic, H, W, 8, 24, 12, DEV)
+    ko, vo, ors, ops, omask = U.strided(None, H, W, 8, 24, 12, DEV)
+    count, c0 = U.guarded(hc * wc, 0, np.uint16, SENT16, DEV)
     keep, host, dev, devp, n = _box_pair(boxes)
     good = dict(src=vs.data_ptr(), srs=srs, sps=sps, out=vo.data_ptr(), ors=ors, ops=ops, H=H, W=W, host=host, dev=devp, n=n,
                 mask=R.MASK, grow=R.GROW, tile=8, fill=-1, count=count.data_ptr() + 2 * c0)
@@ -166,16 +122,16 @@ def test_entry_point_refusals_leave_the_outputs_alone():
           [{"host": a.ctypes.data} for a in bad_lists]
     for b in bad:
         v = dict(good, **b)
-        assert lib.hip().dcvc_redact(*[v[k] for k in order], _stream()) == -1, b
+        assert lib.hip().dcvc_redact(*[v[k] for k in order], U.stream(DEV)) == -1, b
     torch.cuda.synchronize(DEV)
-    assert (_words(count) == SENT16).all() and np.isnan(ko.cpu().numpy()).all()
-    assert lib.hip().dcvc_redact(*[good[k] for k in order], _stream()) == 0  # (and the arguments were good ones)
+    assert (U.words(count) == SENT16).all() and np.isnan(ko.cpu().numpy()).all()
+    assert lib.hip().dcvc_redact(*[good[k] for k in order], U.stream(DEV)) == 0  # (and the arguments were good ones)
     want = R.expected(H, W, "classes", R.GROW, 8, -1)
-    assert np.array_equal(_bits(ko.cpu().numpy()[omask]), _bits(want[0].reshape(-1)))
-    assert np.array_equal(_words(count)[c0:c0 + hc * wc], want[1].reshape(-1))
+    assert np.array_equal(U.f32_bits(ko.cpu().numpy()[omask]), U.f32_bits(want[0].reshape(-1)))
+    assert np.array_equal(U.words(count)[c0:c0 + hc * wc], want[1].reshape(-1))
     # n == 0 needs no lists
-    assert lib.hip().dcvc_redact(*[dict(good, host=None, dev=None, n=0)[k] for k in order], _stream()) == 0
-    assert np.array_equal(_bits(ko.cpu().numpy()[omask]), _bits(pic.reshape(-1))) and not _words(count)[c0:c0 + hc * wc].any()
+    assert lib.hip().dcvc_redact(*[dict(good, host=None, dev=None, n=0)[k] for k in order], U.stream(DEV)) == 0
+    assert np.array_equal(U.f32_bits(ko.cpu().numpy()[omask]), U.f32_bits(pic.reshape(-1))) and not U.words(count)[c0:c0 + hc * wc].any()
 
 
 def _padded(pic, Hp, Wp):
@@ -208,12 +164,12 @@ def test_redactor_launches_nothing_without_boxes_and_keeps_the_padding_zero():
         launches.append(f.launches)
         got.append(y.cpu().numpy())  # (a buffer of the redactor is valid until the step after the next: copy now)
         want, count = R.redact(pic, boxes, R.MASK, R.GROW, 8, -1)
-        assert np.array_equal(_bits(got[-1]), _bits(_padded(want, Hp, Wp))), s  # (the padding: zeros)
+        assert np.array_equal(U.f32_bits(got[-1]), U.f32_bits(_padded(want, Hp, Wp))), s  # (the padding: zeros)
         want_totals.append(int(count.sum()))
     assert launches == [1, 1, 2, 3, 4, 5]  # an empty list launches nothing ...
     assert results[1] is x and results[0] is not x  # ... and the picture is returned itself
     # a list of unselected classes only is not empty: it launches and copies (the file loops drop such boxes before)
-    assert np.array_equal(_bits(got[3]), _bits(_padded(pic, Hp, Wp))) and want_totals[3] == 0
+    assert np.array_equal(U.f32_bits(got[3]), U.f32_bits(_padded(pic, Hp, Wp))) and want_totals[3] == 0
     assert results[0] is f.bufs[0] and results[2] is f.bufs[1] and results[3] is f.bufs[0] and results[4] is f.bufs[1]  # alternately
     assert torch.equal(x.view(torch.int32), source.view(torch.int32))  # the source is only read
     assert f.totals() == want_totals and want_totals[1] == 0 and want_totals[4] == H * W and not f._done
@@ -221,7 +177,7 @@ def test_redactor_launches_nothing_without_boxes_and_keeps_the_padding_zero():
     assert f.totals() == want_totals
     bare = D.Redactor(D.Redact(["liplates", "motion"], fill=17, grow=R.GROW), _roi(), (H, W), DEV, totals=False)
     y = bare.step(x, sets["classes"])
-    assert np.array_equal(_bits(y.cpu().numpy()), _bits(_padded(R.redact(pic, sets["classes"], R.MASK, R.GROW, 0, 17)[0], Hp, Wp)))
+    assert np.array_equal(U.f32_bits(y.cpu().numpy()), U.f32_bits(_padded(R.redact(pic, sets["classes"], R.MASK, R.GROW, 0, 17)[0], Hp, Wp)))
     assert bare.launches == 1 and bare._rows is None and not bare._done
     with pytest.raises(ValueError, match="totals=False"):
         bare.totals()
@@ -237,7 +193,7 @@ def test_redactor_launches_nothing_without_boxes_and_keeps_the_padding_zero():
     # one picture, for library use
     out, count = D.redact_picture(x[..., :H, :W], sets["classes"], setting, R.NAMES)
     want = R.expected(H, W, "classes", R.GROW, 8, -1)
-    assert np.array_equal(_bits(out.cpu().numpy()[0]), _bits(want[0])) and np.array_equal(count.cpu().numpy(), want[1])
+    assert np.array_equal(U.f32_bits(out.cpu().numpy()[0]), U.f32_bits(want[0])) and np.array_equal(count.cpu().numpy(), want[1])
     with pytest.raises(ValueError, match="no CPU fallback"):
         D.redact_picture(x.cpu()[..., :H, :W], sets["classes"], setting, R.NAMES)
 
@@ -248,33 +204,6 @@ def test_redactor_launches_nothing_without_boxes_and_keeps_the_padding_zero():
 GOP, N_FRAMES, FH, FW, RH = 4, 8, 128, 192, 176
 SETTING = D.Redact(("liplates", "motion"), tile=8, grow=3, hold=2)
 RESTORABLE = D.Redact(("liplates", "motion"), tile=8, grow=3, hold=2, restorable=True)
-
-
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
-
-
-def _png(path):
-    from PIL import Image
-
-    return np.asarray(Image.open(path).convert("RGB")).transpose(2, 0, 1)
-
-
-def _same_pngs(a, b):
-    for t in range(N_FRAMES):
-        name = f"im{t + 1:05d}.png"
-        assert (a / name).read_bytes() == (b / name).read_bytes(), t
-
-
-def _write_pngs(folder, pics):
-    """float pictures of exact 8-bit samples as PNGs"""
-    from PIL import Image
-
-    os.makedirs(folder)
-    for t, a in enumerate(pics):
-        u8 = R.code(a).astype(np.uint8)
-        assert np.array_equal(_bits(R.T[u8]), _bits(a)), t  # exactly 8-bit representable
-        Image.fromarray(u8.transpose(1, 2, 0)).save(folder / f"im{t + 1:05d}.png")
 
 
 def _write_root(path, frames):
@@ -302,7 +231,7 @@ def _handed(seen, want, H, W):
     for t in range(N_FRAMES):
         Hp, Wp = seen[t].shape[2:]
         assert (Hp, Wp) == ((H + 63) // 64 * 64, (W + 63) // 64 * 64)
-        assert np.array_equal(_bits(seen[t]), _bits(_padded(want[t][0], Hp, Wp))), t
+        assert np.array_equal(U.f32_bits(seen[t]), U.f32_bits(_padded(want[t][0], Hp, Wp))), t
 
 
 @contextlib.contextmanager
@@ -337,13 +266,6 @@ def _spies():
 
 
 @pytest.fixture(scope="module")
-def file_nets():
-    from vcm_ts_amd import run_codec as RC
-
-    return [RC._nets(DEV, None) for _ in range(2)]
-
-
-@pytest.fixture(scope="module")
 def e2e(tmp_path_factory, file_nets):
     """the clip as PNGs and its boxes as a root; the redacted encode -- the pictures its codec was handed captured on the
     way -- and a PLAIN encode of a folder holding the restatement's pictures"""
@@ -351,10 +273,10 @@ def e2e(tmp_path_factory, file_nets):
 
     tmp = tmp_path_factory.mktemp("redact_e2e")
     pics, frames = list(R.clip(FH, FW)), R.clip_boxes(FH, FW)
-    _write_pngs(tmp / "png", pics)
+    U.write_pngs(tmp / "png", pics)
     roi = _write_root(tmp / "root", frames)
     want = _want(pics, frames, SETTING)
-    _write_pngs(tmp / "want_png", [w[0] for w in want])
+    U.write_pngs(tmp / "want_png", [w[0] for w in want])
     RC.encode_folder(str(tmp / "want_png"), str(tmp / "plain_of_want"), gop=GOP, nets=file_nets)
     with _spies() as (seen, _):
         bits, size = RC.encode_folder(str(tmp / "png"), str(tmp / "red"), str(tmp / "red_rec"), gop=GOP, nets=file_nets,
@@ -376,7 +298,7 @@ def test_the_codec_is_handed_the_restatements_pictures_and_writes_their_bytes(e2
     # the face (not selected) is untouched everywhere
     for t in range(N_FRAMES):
         assert np.array_equal(want[t][0][:, FH - 40:FH - 28, FW - 50:FW - 20], pics[t][:, FH - 40:FH - 28, FW - 50:FW - 20]), t
-    assert _bins(tmp / "red") == _bins(tmp / "plain_of_want") and len(_bins(tmp / "red")) == N_FRAMES
+    assert U.bins(tmp / "red") == U.bins(tmp / "plain_of_want") and len(U.bins(tmp / "red")) == N_FRAMES
     assert sorted(n for n in os.listdir(tmp / "red") if not n.endswith(".bin")) == ["hashes.json", "redact.json"]
     assert json.loads((tmp / "red" / "redact.json").read_text()) == SETTING.to_json()
 
@@ -386,7 +308,7 @@ def test_an_unchanged_decoder_decodes_and_verifies(e2e):
 
     tmp = e2e["tmp"]
     assert RC.decode_folder(str(tmp / "red"), str(tmp / "red_dec"), FH, FW, gop=GOP, verify="strict") == N_FRAMES
-    _same_pngs(tmp / "red_dec", tmp / "red_rec")
+    U.same_pngs(tmp / "red_dec", tmp / "red_rec", N_FRAMES)
 
 
 def test_two_gop_streams_write_the_same_bins(e2e, file_nets):
@@ -395,7 +317,7 @@ def test_two_gop_streams_write_the_same_bins(e2e, file_nets):
     tmp = e2e["tmp"]
     with _spies() as (seen, _):
         RC.encode_folder(str(tmp / "png"), str(tmp / "red2"), gop=GOP, nets=file_nets, gop_streams=2, roi=e2e["roi"], redact=SETTING)
-    assert _bins(tmp / "red2") == _bins(tmp / "red")
+    assert U.bins(tmp / "red2") == U.bins(tmp / "red")
     _handed(seen, e2e["want"], FH, FW)
 
 
@@ -405,7 +327,7 @@ def test_base_scale_codes_the_scaled_redacted_picture(e2e, file_nets):
     tmp = e2e["tmp"]
     RC.encode_folder(str(tmp / "want_png"), str(tmp / "half_of_want"), gop=GOP, nets=file_nets, base_scale="1/2")
     RC.encode_folder(str(tmp / "png"), str(tmp / "half"), gop=GOP, nets=file_nets, base_scale="1/2", roi=e2e["roi"], redact=SETTING)
-    assert _bins(tmp / "half") == _bins(tmp / "half_of_want") and _bins(tmp / "half") != _bins(tmp / "red")
+    assert U.bins(tmp / "half") == U.bins(tmp / "half_of_want") and U.bins(tmp / "half") != U.bins(tmp / "red")
     assert (tmp / "half" / "scale.json").read_text() == (tmp / "half_of_want" / "scale.json").read_text()
 
 
@@ -425,9 +347,9 @@ def test_y4m_file(e2e, file_nets):
         RC.encode_video(str(tmp / "src.y4m"), str(tmp / "vbins"), str(tmp / "enc.y4m"), quantize8=True, gop=GOP, nets=file_nets,
                         gop_streams=2, roi=e2e["roi"], redact=SETTING)
     _handed(seen, want, FH, FW)
-    _write_pngs(tmp / "vwant_png", [w[0] for w in want])
+    U.write_pngs(tmp / "vwant_png", [w[0] for w in want])
     RC.encode_folder(str(tmp / "vwant_png"), str(tmp / "plain_of_vwant"), gop=GOP, nets=file_nets)
-    assert _bins(tmp / "vbins") == _bins(tmp / "plain_of_vwant")
+    assert U.bins(tmp / "vbins") == U.bins(tmp / "plain_of_vwant")
     assert sorted(n for n in os.listdir(tmp / "vbins") if not n.endswith(".bin")) == ["redact.json", "sequence.json"]
     assert "redact" not in RC.read_sequence_info(str(tmp / "vbins"))
     assert RC.decode_video(str(tmp / "vbins"), str(tmp / "dec.y4m")) == N_FRAMES
@@ -446,7 +368,7 @@ def test_after_the_prefilter(e2e, file_nets):
         RC.encode_folder(str(tmp / "png"), str(tmp / "tnr_red"), gop=GOP, nets=file_nets, roi=e2e["roi"], redact=SETTING,
                          tnr=N.TNR(12, 64, 36))
     _handed(seen, want, FH, FW)
-    assert _bins(tmp / "tnr_red") != _bins(tmp / "red")
+    assert U.bins(tmp / "tnr_red") != U.bins(tmp / "red")
 
 
 def test_feature_off_and_refusals(e2e, file_nets):
@@ -454,18 +376,18 @@ def test_feature_off_and_refusals(e2e, file_nets):
 
     tmp, roi = e2e["tmp"], e2e["roi"]
     RC.encode_folder(str(tmp / "png"), str(tmp / "plain"), gop=GOP, nets=file_nets)
-    plain = _bins(tmp / "plain")
+    plain = U.bins(tmp / "plain")
     os.makedirs(tmp / "none")
     (tmp / "none" / "redact.json").write_text("{}")  # a stale file of an earlier encode into the same folder
     RC.encode_folder(str(tmp / "png"), str(tmp / "none"), gop=GOP, nets=file_nets, roi=roi, redact=None)
-    assert _bins(tmp / "none") == plain and sorted(os.listdir(tmp / "none")) == sorted(plain) and plain != _bins(tmp / "red")
+    assert U.bins(tmp / "none") == plain and sorted(os.listdir(tmp / "none")) == sorted(plain) and plain != U.bins(tmp / "red")
     # a class no picture has a box of: nothing is launched, the plain bytes, but the file says what was asked for
     empty = _write_root(tmp / "root_faces_only", [f[f[:, 4] == 1] for f in e2e["frames"]])
     with _spies() as (seen, _):
         RC.encode_folder(str(tmp / "png"), str(tmp / "untouched"), gop=GOP, nets=file_nets, roi=empty, redact=SETTING)
-    assert _bins(tmp / "untouched") == plain and (tmp / "untouched" / "redact.json").exists()
+    assert U.bins(tmp / "untouched") == plain and (tmp / "untouched" / "redact.json").exists()
     for t in range(N_FRAMES):
-        assert np.array_equal(_bits(seen[t][0, :, :FH, :FW]), _bits(e2e["pics"][t])), t
+        assert np.array_equal(U.f32_bits(seen[t][0, :, :FH, :FW]), U.f32_bits(e2e["pics"][t])), t
     for kw, name in ((dict(redact=SETTING), "needs roi="), (dict(redact=("motion", 8), roi=roi), "redact.Redact"),
                      (dict(redact=SETTING, roi=roi, residual_bins=str(tmp / "never_rl")), "restorable=True"),
                      (dict(redact=SETTING, roi=roi, residuals=str(tmp / "never.gbrp")), "restorable=True"),
@@ -488,19 +410,19 @@ def test_restorable_residual_layer_holds_what_was_removed(e2e, file_nets):
     tmp, roi, pics = e2e["tmp"], e2e["roi"], e2e["pics"]
     RC.encode_folder(str(tmp / "png"), str(tmp / "rest"), str(tmp / "rest_rec"), gop=GOP, nets=file_nets, gop_streams=2, roi=roi,
                      redact=RESTORABLE, residuals=str(tmp / "res.gbrp"), residual_bins=str(tmp / "rest"))
-    assert _bins(tmp / "rest") == _bins(tmp / "red")  # the base layer is the redacted one, with or without the layer
+    assert U.bins(tmp / "rest") == U.bins(tmp / "red")  # the base layer is the redacted one, with or without the layer
     assert json.loads((tmp / "rest" / "redact.json").read_text())["restorable"] is True
     raw = np.frombuffer((tmp / "res.gbrp").read_bytes(), np.uint8).reshape(N_FRAMES, 3, FH, FW)
     assert RC.decode_folder(str(tmp / "rest"), str(tmp / "fused"), FH, FW, gop=GOP, roi=roi, residual_bins=str(tmp / "rest")) == N_FRAMES
     for t in range(N_FRAMES):
         boxes = roi.boxes(t).array  # the picture's OWN boxes, all classes: no grow, nothing held
-        rec = _png(tmp / "rest_rec" / f"im{t + 1:05d}.png")
+        rec = U.png(tmp / "rest_rec" / f"im{t + 1:05d}.png", planar=True)
         want = RR.residual(pics[t], RR.T[rec], boxes)  # against the UNREDACTED source
         assert np.array_equal(raw[t], want[[1, 2, 0]]), t  # G, B, R planes
         record = (tmp / "rest" / f"im{t + 1:05d}{Y.FILE_EXT}").read_bytes()
         assert record == RL.encode_record(want, boxes, 1)[0], t
         # decode puts the content back wherever the residual was not clipped
-        inside, fused = RR.binary_mask(boxes, FH, FW), _png(tmp / "fused" / f"im{t + 1:05d}.png")
+        inside, fused = RR.binary_mask(boxes, FH, FW), U.png(tmp / "fused" / f"im{t + 1:05d}.png", planar=True)
         ok = inside[None] & (want > 0) & (want < 255)
         assert np.array_equal(fused[ok], R.code(pics[t])[ok]) and ok.any(), t
         assert np.array_equal(fused[:, ~inside], rec[:, ~inside]), t
@@ -513,7 +435,7 @@ def reported(tmp_path_factory, file_nets):
 
     tmp = tmp_path_factory.mktemp("redact_report")
     pics, frames = list(R.clip(RH, FW)), R.clip_boxes(RH, FW)
-    _write_pngs(tmp / "png", pics)
+    U.write_pngs(tmp / "png", pics)
     roi = _write_root(tmp / "root", frames)
     _, _, plain_rd = RC.encode_folder(str(tmp / "png"), str(tmp / "plain"), gop=GOP, nets=file_nets, report=True, roi=roi)
     with _spies() as (seen, measured):
@@ -538,20 +460,20 @@ def test_report_speaks_of_the_redaction_and_measures_against_the_source(reported
     assert sorted(n for n in os.listdir(tmp / "red") if not n.endswith(".bin")) == ["redact.json"]
     # PSNR, MS-SSIM and the ROI figures are measured against the UNREDACTED source, which is not what the codec was handed
     for t in range(N_FRAMES):
-        assert np.array_equal(_bits(reported["measured"][t][0, :, :RH, :FW]), _bits(pics[t])), t
+        assert np.array_equal(U.f32_bits(reported["measured"][t][0, :, :RH, :FW]), U.f32_bits(pics[t])), t
         assert not np.array_equal(reported["measured"][t], reported["seen"][t]), t
     assert len(rd["frame_psnr"]) == N_FRAMES and all(np.isfinite(rd["frame_psnr"]))
     assert len(rd["frame_psnr_roi"]) == N_FRAMES and rd["frame_roi_pixels"] == reported["plain_rd"]["frame_roi_pixels"]
     # two GOP streams: the same bytes and the same figures
     _, _, rd2 = RC.encode_folder(str(tmp / "png"), str(tmp / "red2"), gop=GOP, nets=file_nets, gop_streams=2, report=True, roi=roi,
                                  redact=SETTING)
-    assert _bins(tmp / "red2") == _bins(tmp / "red")
+    assert U.bins(tmp / "red2") == U.bins(tmp / "red")
     for key in ("redact", "frame_redacted", "frame_bpp", "frame_psnr_roi"):
         assert rd2[key] == rd[key], key
     # redact=None: the bytes and the report keys of a run without the argument, and no file
     _, _, rd0 = RC.encode_folder(str(tmp / "png"), str(tmp / "none"), gop=GOP, nets=file_nets, report=True, roi=roi, redact=None)
-    assert _bins(tmp / "none") == _bins(tmp / "plain") and list(rd0) == list(reported["plain_rd"])
-    assert rd0["frame_bpp"] == reported["plain_rd"]["frame_bpp"] and sorted(os.listdir(tmp / "none")) == sorted(_bins(tmp / "plain"))
+    assert U.bins(tmp / "none") == U.bins(tmp / "plain") and list(rd0) == list(reported["plain_rd"])
+    assert rd0["frame_bpp"] == reported["plain_rd"]["frame_bpp"] and sorted(os.listdir(tmp / "none")) == sorted(U.bins(tmp / "plain"))
 
 
 def test_command_line(e2e, file_nets, capsys):
@@ -560,17 +482,17 @@ def test_command_line(e2e, file_nets, capsys):
     tmp = e2e["tmp"]
     RC.main(["encode", "--frames", str(tmp / "png"), "--bins", str(tmp / "cli"), "--gop", str(GOP), "--picture-hash", "--roi-root",
              str(tmp / "root"), "--redact", "liplates", "motion", "--redact-tile", "8", "--redact-grow", "3", "--redact-hold", "2"])
-    assert _bins(tmp / "cli") == _bins(tmp / "red")
+    assert U.bins(tmp / "cli") == U.bins(tmp / "red")
     assert (tmp / "cli" / "redact.json").read_text() == (tmp / "red" / "redact.json").read_text()
     RC.main(["decode", "--bins", str(tmp / "cli"), "--recon", str(tmp / "cli_dec"), "--height", str(FH), "--width", str(FW),
              "--gop", str(GOP), "--verify", "strict"])
-    _same_pngs(tmp / "cli_dec", tmp / "red_rec")
+    U.same_pngs(tmp / "cli_dec", tmp / "red_rec", N_FRAMES)
     RC.main(["encode", "--frames", str(tmp / "png"), "--bins", str(tmp / "cli2"), "--gop", str(GOP), "--roi-root", str(tmp / "root"),
              "--redact", "faces", "--redact-fill", "16", "--redact-restorable", "--residual-bins", str(tmp / "cli2")])
     fill = D.Redact(("faces",), fill=16, restorable=True)
     with _spies() as (seen, _):
         RC.encode_folder(str(tmp / "png"), str(tmp / "api2"), gop=GOP, nets=file_nets, roi=e2e["roi"], redact=fill)
-    assert _bins(tmp / "cli2") == _bins(tmp / "api2") and _bins(tmp / "cli2") != _bins(tmp / "red")
+    assert U.bins(tmp / "cli2") == U.bins(tmp / "api2") and U.bins(tmp / "cli2") != U.bins(tmp / "red")
     assert json.loads((tmp / "cli2" / "redact.json").read_text()) == fill.to_json()
     assert len([n for n in os.listdir(tmp / "cli2") if n.endswith(".rl")]) == N_FRAMES
     want = _want(e2e["pics"], e2e["frames"], fill)

@@ -14,7 +14,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_util as U
 from tests import roi_ref as R
+from tests.gpu_util import file_nets  # noqa: F401 (fixture)
 from vcm_ts_amd import roi as X
 
 pytestmark = pytest.mark.gpu
@@ -23,18 +25,6 @@ CLASSES = tuple(X.RoiClass(b) for b in R.BORDERS)
 CASES = [(seed, H, W, False) for seed, (H, W) in enumerate(R.SIZES)] + [(9, 40, 130, True)]
 IDS = [f"{H}x{W}" + ("-crop" if crop else "") for _, H, W, crop in CASES]
 SLOTS = {"rgb": [0, 1, 2], "gbr": [1, 2, 0]}
-
-
-def _dev(a, crop):
-    """(1, 3, H, W) on the device; crop: a view at a one-pixel offset inside a 64 x 192 buffer (rows unaligned, strides
-    beyond the width)"""
-    t = torch.from_numpy(np.ascontiguousarray(a))[None].to(DEV)
-    if not crop:
-        return t
-    H, W = a.shape[1:]
-    big = torch.full((1, 3, 64, 192), 0.77, device=DEV)
-    big[..., 1:1 + H, 1:1 + W] = t
-    return big[..., 1:1 + H, 1:1 + W]
 
 
 def _dev_u8(a, layout, crop):
@@ -75,7 +65,7 @@ def refs():
 def test_residual_in_both_layouts_and_orders(case, refs):
     _, H, W, crop = case
     ref = refs[(H, W)]
-    src, rec = _dev(ref["src"], crop), _dev(ref["rec"], crop)
+    src, rec = U.picture(ref["src"], crop, DEV), U.picture(ref["rec"], crop, DEV)
     for name, boxes in ref["lists"].items():
         for layout in X.LAYOUTS:
             for order, slots in SLOTS.items():
@@ -98,7 +88,7 @@ def test_residual_in_both_layouts_and_orders(case, refs):
 def test_fuse_from_both_residual_layouts(case, refs):
     _, H, W, crop = case
     ref = refs[(H, W)]
-    base = _dev(ref["rec"], crop)
+    base = U.picture(ref["rec"], crop, DEV)
     table = R.T.view(np.uint32)
     for name, boxes in ref["lists"].items():
         want = ref["fuse"][name].view(np.uint32)
@@ -116,7 +106,7 @@ def test_fuse_from_both_residual_layouts(case, refs):
     # outside every box the result is T[code(base)]
     assert np.array_equal(ref["fuse"]["none"].view(np.uint32), R.T[R.code(ref["rec"])].view(np.uint32))
     # the layout is taken from the residual's shape; fusing a residual_layer output in place of a file
-    r = X.residual_layer(_dev(ref["src"], crop), base, X.FrameBoxes(ref["lists"]["whole"]), layout="hwc")
+    r = X.residual_layer(U.picture(ref["src"], crop, DEV), base, X.FrameBoxes(ref["lists"]["whole"]), layout="hwc")
     if (H, W, 3) != (3, H, W):
         got = X.fuse(base, r, X.FrameBoxes(ref["lists"]["whole"]), CLASSES)
         want = R.fuse(ref["rec"], R.residual(ref["src"], ref["rec"], ref["lists"]["whole"]), ref["lists"]["whole"], R.BORDERS)
@@ -127,7 +117,7 @@ def test_fuse_from_both_residual_layouts(case, refs):
 def test_region_sums_added_onto_starting_values(case, refs):
     _, H, W, crop = case
     ref = refs[(H, W)]
-    a, b = _dev(ref["src"], crop), _dev(ref["rec"], crop)
+    a, b = U.picture(ref["src"], crop, DEV), U.picture(ref["rec"], crop, DEV)
     start = [7, 2 ** 40 + 11, 13]
     for name, boxes in ref["lists"].items():
         for sname, shrinks in R.SHRINKS.items():
@@ -169,7 +159,7 @@ def test_run_to_run_identical_also_beside_convolutions_on_another_stream(refs):
 
     H, W = 38, 518
     ref = refs[(H, W)]
-    src, rec = _dev(ref["src"], False), _dev(ref["rec"], False)
+    src, rec = U.picture(ref["src"], False, DEV), U.picture(ref["rec"], False, DEV)
     res = _dev_u8(ref["res"], "planar", False)
     boxes = X.FrameBoxes(ref["lists"]["many150"])
     boxes.on_device(DEV)
@@ -212,16 +202,6 @@ def _e2e_boxes(h, w):
     return boxes
 
 
-def _png(path):
-    from PIL import Image
-
-    return np.asarray(Image.open(path).convert("RGB")).transpose(2, 0, 1)
-
-
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
-
-
 def _source(path, seed, n, h, w):
     """a seeded Y4M; returns the float32 RGB pictures the encoder is given (the restatement of the colour conversion,
     which tests/test_gpu_yuv.py holds the device to bit for bit)"""
@@ -233,26 +213,19 @@ def _source(path, seed, n, h, w):
 
 
 @pytest.fixture(scope="module")
-def nets():
-    from vcm_ts_amd import run_codec as RC
-
-    return [RC._nets(DEV, None) for _ in range(2)]
-
-
-@pytest.fixture(scope="module")
-def e2e(tmp_path_factory, nets):
+def e2e(tmp_path_factory, file_nets):
     from vcm_ts_amd import run_codec as RC
 
     tmp = tmp_path_factory.mktemp("roi_e2e")
     n, h, w, gop = 6, 64, 96, 3
     src = _source(tmp / "src.y4m", 51, n, h, w)
     roi = X.Roi(_e2e_boxes(h, w), tuple(X.RoiClass(b) for b in E2E_BORDERS), ("liplates", "faces"))
-    kw = dict(gop=gop, gop_streams=2, nets=nets)
+    kw = dict(gop=gop, gop_streams=2, nets=file_nets)
     RC.encode_video(str(tmp / "src.y4m"), str(tmp / "plain"), **kw)
     bits, size = RC.encode_video(str(tmp / "src.y4m"), str(tmp / "bins"), roi=roi, residuals=str(tmp / "res.gbrp"), **kw)
     assert size == (h, w) and len(bits) == n
     assert RC.decode_folder(str(tmp / "plain"), str(tmp / "rec"), h, w, gop=gop) == n
-    rec = [_png(tmp / "rec" / f"im{t + 1:05d}.png") for t in range(n)]  # code(reconstruction), as save_torch_image rounds it
+    rec = [U.png(tmp / "rec" / f"im{t + 1:05d}.png", planar=True) for t in range(n)]  # code(reconstruction), as save_torch_image rounds it
     raw = np.frombuffer((tmp / "res.gbrp").read_bytes(), np.uint8).reshape(n, 3, h, w)
     return dict(tmp=tmp, n=n, h=h, w=w, gop=gop, src=src, rec=rec, roi=roi, raw=raw, kw=kw)
 
@@ -261,7 +234,7 @@ def test_end_to_end_same_bins_and_residual_file_in_display_order(e2e):
     from vcm_ts_amd import run_codec as RC
 
     tmp, n, h, w = e2e["tmp"], e2e["n"], e2e["h"], e2e["w"]
-    assert _bins(tmp / "bins") == _bins(tmp / "plain") and len(_bins(tmp / "bins")) == n
+    assert U.bins(tmp / "bins") == U.bins(tmp / "plain") and len(U.bins(tmp / "bins")) == n
     assert sorted(os.listdir(tmp / "bins")) == sorted(os.listdir(tmp / "plain"))
     info = RC.read_sequence_info(str(tmp / "bins"))
     assert info["roi"] == {"classes": [{"name": "liplates", "border": 3, "shrink": 3}, {"name": "faces", "border": 10, "shrink": 10}]}
@@ -287,7 +260,7 @@ def test_end_to_end_decoders_write_the_fused_picture(e2e):
     for t in range(n):
         want = R.fuse(R.T[e2e["rec"][t]], e2e["raw"][t][[2, 0, 1]], roi.boxes(t).array, E2E_BORDERS)
         codes = np.rint(want * np.float32(255.0)).astype(np.uint8)
-        assert np.array_equal(_png(tmp / "fused" / f"im{t + 1:05d}.png"), codes), t
+        assert np.array_equal(U.png(tmp / "fused" / f"im{t + 1:05d}.png", planar=True), codes), t
         changed += int((codes != e2e["rec"][t]).sum())
         samples = Y.rgb_to_yuv420(torch.from_numpy(want)[None].to(DEV), h, w)
         assert np.array_equal(samples.cpu().numpy(), np.asarray(frames[t]).reshape(-1)), t
@@ -308,36 +281,36 @@ def test_end_to_end_png_residuals_agree_with_the_raw_file(e2e):
 
     tmp, n, h, w, gop, roi = (e2e[k] for k in ("tmp", "n", "h", "w", "gop", "roi"))
     RC.encode_video(str(tmp / "src.y4m"), str(tmp / "bins_png"), roi=roi, residuals=str(tmp / "res_png"), **e2e["kw"])
-    assert _bins(tmp / "bins_png") == _bins(tmp / "plain")
+    assert U.bins(tmp / "bins_png") == U.bins(tmp / "plain")
     assert sorted(os.listdir(tmp / "res_png")) == [f"im{t + 1:05d}.png" for t in range(n)]
     for t in range(n):
-        assert np.array_equal(_png(tmp / "res_png" / f"im{t + 1:05d}.png"), e2e["raw"][t][[2, 0, 1]]), t
+        assert np.array_equal(U.png(tmp / "res_png" / f"im{t + 1:05d}.png", planar=True), e2e["raw"][t][[2, 0, 1]]), t
     assert RC.decode_folder(str(tmp / "bins"), str(tmp / "fused_png"), h, w, gop=gop, roi=roi, residuals=str(tmp / "res_png")) == n
     if (tmp / "fused").exists():
         for t in range(n):
             name = f"im{t + 1:05d}.png"
-            assert np.array_equal(_png(tmp / "fused_png" / name), _png(tmp / "fused" / name)), t
+            assert np.array_equal(U.png(tmp / "fused_png" / name, planar=True), U.png(tmp / "fused" / name, planar=True)), t
 
 
-def test_report_gains_region_psnr(tmp_path, nets):
+def test_report_gains_region_psnr(tmp_path, file_nets):
     """At 192x320 (see the module's docstring), otherwise the end-to-end setting."""
     from vcm_ts_amd import run_codec as RC
 
     n, h, w, gop = 6, 192, 320, 3
     src = _source(tmp_path / "src.y4m", 53, n, h, w)
     roi = X.Roi(_e2e_boxes(h, w), tuple(X.RoiClass(b) for b in E2E_BORDERS))
-    kw = dict(gop=gop, gop_streams=2, nets=nets)
+    kw = dict(gop=gop, gop_streams=2, nets=file_nets)
     _, _, plain = RC.encode_video(str(tmp_path / "src.y4m"), str(tmp_path / "plain"), report=True, **kw)
     _, _, rd = RC.encode_video(str(tmp_path / "src.y4m"), str(tmp_path / "bins"), report=str(tmp_path / "rd.json"), roi=roi,
                                residuals=str(tmp_path / "res.gbrp"), **kw)
-    assert _bins(tmp_path / "bins") == _bins(tmp_path / "plain")
+    assert U.bins(tmp_path / "bins") == U.bins(tmp_path / "plain")
     new = {"frame_psnr_roi", "frame_psnr_bg", "frame_roi_pixels"}
     assert set(rd) - set(plain) == new and not new & set(plain)
     for key in plain:  # what was there is what it was
         assert rd[key] == plain[key], key
     assert RC.decode_folder(str(tmp_path / "plain"), str(tmp_path / "rec"), h, w, gop=gop) == n
     for t in range(n):
-        rec = R.T[_png(tmp_path / "rec" / f"im{t + 1:05d}.png")]
+        rec = R.T[U.png(tmp_path / "rec" / f"im{t + 1:05d}.png", planar=True)]
         sums = R.sse(rec, src[t], roi.boxes(t).array, E2E_BORDERS)
         total, bg, inside = R.psnr(sums, h, w, "samples")
         assert rd["frame_roi_pixels"][t] == sums[2] and (sums[2] > 0) == (t != 4)

@@ -15,8 +15,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_util as U
 from tests import roi_ref as R
 from tests import roil_ref as RL
+from tests.gpu_util import file_nets  # noqa: F401 (fixture)
 from vcm_ts_amd import roi as X
 from vcm_ts_amd import roilayer as Y
 
@@ -26,18 +28,6 @@ CASES = [(seed, H, W, False) for seed, (H, W) in enumerate(R.SIZES)] + [(9, 40, 
 IDS = [f"{H}x{W}" + ("-crop" if crop else "") for _, H, W, crop in CASES]
 SLOTS = {"rgb": [0, 1, 2], "gbr": [1, 2, 0]}
 STEPS = (1, 7)
-
-
-def _dev(a, crop):
-    """(1, 3, H, W) on the device; crop: a view at a one-pixel offset inside a 64 x 192 buffer (rows unaligned, strides
-    beyond the width, foreign values around it)"""
-    t = torch.from_numpy(np.ascontiguousarray(a))[None].to(DEV)
-    if not crop:
-        return t
-    H, W = a.shape[1:]
-    big = torch.full((1, 3, 64, 192), 0.77, device=DEV)
-    big[..., 1:1 + H, 1:1 + W] = t
-    return big[..., 1:1 + H, 1:1 + W]
 
 
 def _guarded(layout, H, W):
@@ -77,7 +67,7 @@ def refs():
 def test_device_record_is_the_restatements_bytes(case, refs):
     _, H, W, crop = case
     ref = refs[(H, W)]
-    src, rec = _dev(ref["src"], crop), _dev(ref["rec"], crop)
+    src, rec = U.picture(ref["src"], crop, DEV), U.picture(ref["rec"], crop, DEV)
     pending = {(n, S): Y.encode_layer(src, rec, X.FrameBoxes(b), step=S) for n, b in ref["lists"].items() for S in STEPS}
     seen = set()
     for key, p in pending.items():
@@ -117,7 +107,7 @@ def test_device_decodes_the_restatements_record_in_both_layouts_and_orders(case,
 def test_decode_of_the_devices_own_record_is_the_quantised_residual(case, refs):
     _, H, W, crop = case
     ref = refs[(H, W)]
-    src, rec = _dev(ref["src"], crop), _dev(ref["rec"], crop)
+    src, rec = U.picture(ref["src"], crop, DEV), U.picture(ref["rec"], crop, DEV)
     for name in ("edges", "overlap", "whole", "max1024"):
         boxes = X.FrameBoxes(ref["lists"][name])
         for S in STEPS:
@@ -169,18 +159,11 @@ def test_python_layer_refuses_by_name(refs):
 
 
 # ------------------------------------------------------------------------------------------------------- end to end
-from tests import test_gpu_roi as G  # noqa: E402  (its seeded source, boxes and file helpers: the same loop setting)
+from tests import test_gpu_roi as G  # noqa: E402  (its seeded source and boxes: the same loop setting)
 
 
 @pytest.fixture(scope="module")
-def nets():
-    from vcm_ts_amd import run_codec as RC
-
-    return [RC._nets(DEV, None) for _ in range(2)]
-
-
-@pytest.fixture(scope="module")
-def e2e(tmp_path_factory, nets):
+def e2e(tmp_path_factory, file_nets):
     """encode without the layer, and with --residuals x.gbrp and --residual-bins (into the --bins folder) together"""
     from vcm_ts_amd import run_codec as RC
 
@@ -188,7 +171,7 @@ def e2e(tmp_path_factory, nets):
     n, h, w, gop = 6, 64, 96, 3
     G._source(tmp / "src.y4m", 51, n, h, w)
     roi = X.Roi(G._e2e_boxes(h, w), tuple(X.RoiClass(b) for b in G.E2E_BORDERS), ("liplates", "faces"))
-    kw = dict(gop=gop, gop_streams=2, nets=nets)
+    kw = dict(gop=gop, gop_streams=2, nets=file_nets)
     RC.encode_video(str(tmp / "src.y4m"), str(tmp / "plain"), **kw)
     bits, size = RC.encode_video(str(tmp / "src.y4m"), str(tmp / "bins"), roi=roi, residuals=str(tmp / "res.gbrp"),
                                  residual_bins=str(tmp / "bins"), **kw)
@@ -205,7 +188,7 @@ def test_end_to_end_same_bins_and_records_of_the_raw_residual(e2e):
     from vcm_ts_amd import run_codec as RC
 
     tmp, n, h, w, roi = (e2e[k] for k in ("tmp", "n", "h", "w", "roi"))
-    assert G._bins(tmp / "bins") == G._bins(tmp / "plain") and len(G._bins(tmp / "bins")) == n
+    assert U.bins(tmp / "bins") == U.bins(tmp / "plain") and len(U.bins(tmp / "bins")) == n
     assert sorted(set(os.listdir(tmp / "bins")) - set(os.listdir(tmp / "plain"))) == [f"im{t + 1:05d}.rl" for t in range(n)]
     assert RC.read_sequence_info(str(tmp / "bins"))["residual_step"] == 1
     assert "residual_step" not in RC.read_sequence_info(str(tmp / "plain"))
@@ -230,7 +213,8 @@ def test_end_to_end_decoding_the_records_writes_the_pngs_of_the_raw_file(e2e):
         assert (tmp / "fused_rl" / name).read_bytes() == (tmp / "fused_raw" / name).read_bytes(), t
     assert RC.decode_folder(str(tmp / "plain"), str(tmp / "rec"), h, w, gop=gop) == n
     for t in range(n):
-        changed += int((G._png(tmp / "fused_rl" / f"im{t + 1:05d}.png") != G._png(tmp / "rec" / f"im{t + 1:05d}.png")).sum())
+        name = f"im{t + 1:05d}.png"
+        changed += int((U.png(tmp / "fused_rl" / name, planar=True) != U.png(tmp / "rec" / name, planar=True)).sum())
     assert changed > 100  # the enhancement layer did something
     assert RC.decode_video(str(tmp / "bins"), str(tmp / "fused_rl.y4m"), roi=roi, residual_bins=str(tmp / "bins")) == n
     assert RC.decode_video(str(tmp / "bins"), str(tmp / "fused_raw.y4m"), roi=roi, residuals=str(tmp / "res.gbrp")) == n
@@ -258,7 +242,7 @@ def test_end_to_end_step_seven_is_recorded_and_coded(e2e):
 
     tmp, n, h, w, roi = (e2e[k] for k in ("tmp", "n", "h", "w", "roi"))
     RC.encode_video(str(tmp / "src.y4m"), str(tmp / "bins7"), roi=roi, residual_bins=str(tmp / "rl7"), residual_step=7, **e2e["kw"])
-    assert G._bins(tmp / "bins7") == G._bins(tmp / "plain")
+    assert U.bins(tmp / "bins7") == U.bins(tmp / "plain")
     assert RC.read_sequence_info(str(tmp / "bins7"))["residual_step"] == 7
     assert sorted(os.listdir(tmp / "rl7")) == [f"im{t + 1:05d}.rl" for t in range(n)]
     for t, record in enumerate(_records(tmp / "rl7", n)):
@@ -271,18 +255,18 @@ def test_end_to_end_step_seven_is_recorded_and_coded(e2e):
         RC.encode_video(str(tmp / "src.y4m"), str(tmp / "x"), residual_bins=str(tmp / "x"), **e2e["kw"])
 
 
-def test_report_gains_the_enhancement_layers_bits(tmp_path, nets):
+def test_report_gains_the_enhancement_layers_bits(tmp_path, file_nets):
     """At 192x320, the smallest size MS-SSIM admits; otherwise the end-to-end setting."""
     from vcm_ts_amd import run_codec as RC
 
     n, h, w, gop = 6, 192, 320, 3
     G._source(tmp_path / "src.y4m", 53, n, h, w)
     roi = X.Roi(G._e2e_boxes(h, w), tuple(X.RoiClass(b) for b in G.E2E_BORDERS))
-    kw = dict(gop=gop, gop_streams=2, nets=nets, roi=roi)
+    kw = dict(gop=gop, gop_streams=2, nets=file_nets, roi=roi)
     _, _, base = RC.encode_video(str(tmp_path / "src.y4m"), str(tmp_path / "base"), report=True, **kw)
     _, _, rd = RC.encode_video(str(tmp_path / "src.y4m"), str(tmp_path / "bins"), report=str(tmp_path / "rd.json"),
                                residual_bins=str(tmp_path / "bins"), **kw)
-    assert G._bins(tmp_path / "bins") == G._bins(tmp_path / "base")
+    assert U.bins(tmp_path / "bins") == U.bins(tmp_path / "base")
     new = {"frame_bits_enh", "frame_bpp_enh", "ave_all_frame_bpp_enh", "ave_all_frame_bpp_total"}
     assert set(rd) - set(base) == new and not new & set(base)
     for key in base:  # what was there is what it was

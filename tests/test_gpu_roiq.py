@@ -11,7 +11,9 @@ import pytest
 import torch
 
 from oracle import dcvc_ref as OR
+from tests import gpu_util as U
 from tests import roiq_ref as R
+from tests.gpu_util import file_nets  # noqa: F401 (fixture)
 from tests.util import oracle_weights
 from vcm_ts_amd import lib
 from vcm_ts_amd import roi as X
@@ -20,10 +22,6 @@ from vcm_ts_amd.synthetic import frames
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 F32 = np.float32
-
-
-def _bits(t):
-    return t.detach().cpu().numpy().view(np.uint32)
 
 
 # -------------------------------------------------------------------------------------------------- the map kernel
@@ -38,16 +36,16 @@ def test_q_map_kernel_equals_the_restatement_bit_for_bit(size):
         fb = X.FrameBoxes(boxes)
         for grow in R.GROWS:
             buf = torch.full((hc * wc + 2 * guard,), float("nan"), device=DEV)
-            before = _bits(buf).copy()
+            before = U.f32_bits(buf).copy()
             got = X.q_map(fb, H, W, roiq[grow], out=buf[guard:guard + hc * wc])
             assert got.shape == (1, 1, hc, wc) and got.data_ptr() == buf[guard:].data_ptr()
-            after = _bits(buf)
+            after = U.f32_bits(buf)
             want = R.q_map(boxes, H, W, grow, f)
             assert np.array_equal(after[guard:guard + hc * wc].reshape(hc, wc), want.view(np.uint32)), (name, grow)
             assert np.array_equal(after[:guard], before[:guard]) and np.array_equal(after[-guard:], before[-guard:]), (name, grow)
     # without `out`: a fresh tensor on the current device; two classes only -> a box of class 2 is refused by name
     got = X.q_map(boxes, H, W, roiq[0])
-    assert got.device == DEV and np.array_equal(_bits(got).reshape(hc, wc), R.q_map(boxes, H, W, 0, f).view(np.uint32))
+    assert got.device == DEV and np.array_equal(U.f32_bits(got).reshape(hc, wc), R.q_map(boxes, H, W, 0, f).view(np.uint32))
     with pytest.raises(ValueError, match="unknown class"):
         X.q_map(np.array([[0, 0, W, H, 2]]), H, W, X.RoiQ(100, (60, 140)))
 
@@ -79,7 +77,7 @@ def test_scale_channels_map_bit_for_bit(multiply):
                                                 N, H * W, Cc, None if q_map is None else q_map.data_ptr(), H, W, st),
                       "scale_channels_map")
         assert bool(torch.isnan(out[..., Cc:]).all())  # the stride's padding is not written
-        return _bits(out[..., :Cc].contiguous())
+        return U.f32_bits(out[..., :Cc].contiguous())
 
     assert np.array_equal(run(md), want.view(np.uint32))
     plain = run(None, plain=True)
@@ -91,13 +89,7 @@ def test_scale_channels_map_bit_for_bit(multiply):
 @pytest.fixture(scope="module", params=["fp32", "fp16x3"])
 def nets(request):
     """Both arithmetic modes of the convolution kernels, as in tests/test_gpu_codec.py."""
-    from vcm_ts_amd.dmc import DMC
-    from vcm_ts_amd.intra import IntraNoAR
-
-    d, i = DMC(precision=request.param).to(DEV).eval(), IntraNoAR(precision=request.param).to(DEV).eval()
-    d.update()
-    i.update()
-    return d, i
+    return U.seeded_pair(DEV, request.param)
 
 
 def _i_planes(v):
@@ -106,10 +98,6 @@ def _i_planes(v):
 
 def _p_planes(v):
     return [v["sym_mv_z"], v["sym_z"]] + [v[r][k][j] for r in ("r_mv", "r_y") for k in ("sym", "idx") for j in (0, 1)]
-
-
-def _intra_dpb(x_hat):
-    return {"ref_frame": x_hat, "ref_feature": None, "ref_y": None, "ref_mv_y": None}
 
 
 def test_a_map_of_ones_is_no_map(nets):
@@ -123,7 +111,7 @@ def test_a_map_of_ones_is_no_map(nets):
     b = i.compress(xs[0], 1.0, q_map=ones)
     assert torch.equal(b["x_hat"], keep[0]) and b["bit_stream"] == keep[2]
     assert all(torch.equal(p, q) for p, q in zip(_i_planes(b["_views"]), keep[1]))
-    dpb = _intra_dpb(keep[0])
+    dpb = U.intra_dpb(keep[0])
     for t, shape in ((1, ones), (2, ones[0, 0])):  # (both accepted shapes of a one-picture map)
         a = d.compress(xs[t], dpb, 1.0, 1.0)
         keep = ({k: v.clone() for k, v in a["dpb"].items()}, [p.clone() for p in _p_planes(a["_views"])], a["bit_stream"])
@@ -150,7 +138,7 @@ def _oracle_with_a_map(xs, m):
         wd, wi = oracle_weights("dmc"), oracle_weights("intra")
         with torch.no_grad():
             ro = OR.intra_forward(wi, xs[0], 0.8 * m)
-            dpb_o, ps = _intra_dpb(ro["x_hat"].clamp(0, 1)), []
+            dpb_o, ps = U.intra_dpb(ro["x_hat"].clamp(0, 1)), []
             for t in (1, 2):
                 po = OR.dmc_forward_one_frame(wd, xs[t], dpb_o, 1.1, 0.9 * m)
                 ps.append(po)
@@ -177,8 +165,8 @@ def test_intermediates_and_symbols_match_oracle_with_a_map(nets):
             share = (got != sym.numpy()).mean()
             print("I", tag, "symbol mismatch share", share)
             assert share < 1e-4, tag
-        dpb_o = _intra_dpb(ro["x_hat"].clamp(0, 1))
-        dpb_g = _intra_dpb(rg["x_hat"])
+        dpb_o = U.intra_dpb(ro["x_hat"].clamp(0, 1))
+        dpb_g = U.intra_dpb(rg["x_hat"])
         print("I x_hat max abs diff", float((rg["x_hat"].cpu() - dpb_o["ref_frame"]).abs().max()))
         np.testing.assert_allclose(rg["x_hat"].cpu().numpy(), dpb_o["ref_frame"].numpy(), atol=2e-5)
         for t in (1, 2):
@@ -215,7 +203,7 @@ def test_round_trip_needs_the_encoders_map(nets):
     assert torch.equal(i.decompress(ci["bit_stream"], h, w, 1.0, q_map=m)["x_hat"], x_hat)
     assert not torch.equal(i.decompress(ci["bit_stream"], h, w, 1.0, q_map=ones)["x_hat"], x_hat)
     assert not torch.equal(i.decompress(ci["bit_stream"], h, w, 1.0)["x_hat"], x_hat)
-    dpb = _intra_dpb(x_hat)
+    dpb = U.intra_dpb(x_hat)
     for t in (1, 2):
         c = d.compress(xs[t], dpb, 1.0, 1.0, q_map=m)
         enc = {k: v.clone() for k, v in c["dpb"].items()}
@@ -231,7 +219,7 @@ def test_round_trip_needs_the_encoders_map(nets):
 def test_codecs_refuse_by_name(nets):
     d, i = nets
     x = torch.zeros((1, 3, 64, 128), device=DEV)
-    dpb = _intra_dpb(x)
+    dpb = U.intra_dpb(x)
     good = torch.ones((4, 8), device=DEV)
     for bad, match in ((torch.ones((8, 4), device=DEV), "shape"), (torch.ones((2, 1, 4, 8), device=DEV), "shape"),
                        (torch.ones((4, 8), device=DEV, dtype=torch.float64), "float32"), (torch.ones((4, 8)), "cpu"),
@@ -262,33 +250,18 @@ def _roi():
     return X.Roi(lambda t: X.FrameBoxes(BOX), (X.RoiClass(0),), ("plate",))
 
 
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
-
-
 def _size(folder):
-    return sum(len(v) for v in _bins(folder).values())
-
-
-@pytest.fixture(scope="module")
-def file_nets():
-    from vcm_ts_amd import run_codec as RC
-
-    return [RC._nets(DEV, None) for _ in range(2)]
+    return sum(len(v) for v in U.bins(folder).values())
 
 
 @pytest.fixture(scope="module")
 def e2e(tmp_path_factory, file_nets):
     """the clip as PNGs; a plain encode (the parent's bins) and the encode with 0.6 inside / 1.4 outside the box"""
-    from PIL import Image
-
     from vcm_ts_amd import run_codec as RC
 
     tmp = tmp_path_factory.mktemp("roiq_e2e")
     clip = np.rint(frames(21, N_FRAMES, SIDE, SIDE) * 255).astype(np.uint8).transpose(0, 2, 3, 1)
-    os.makedirs(tmp / "png")
-    for t, a in enumerate(clip):
-        Image.fromarray(a).save(tmp / "png" / f"im{t + 1:05d}.png")
+    U.write_pngs(tmp / "png", clip)
     RC.encode_folder(str(tmp / "png"), str(tmp / "plain"), gop=GOP, nets=file_nets)
     bits, size = RC.encode_folder(str(tmp / "png"), str(tmp / "in"), str(tmp / "in_rec"), gop=GOP, nets=file_nets, roi=_roi(),
                                   roi_q=Q_IN)
@@ -302,7 +275,7 @@ def test_folder_side_file_and_decoder_output(e2e):
     tmp = e2e["tmp"]
     assert json.loads((tmp / "in" / "roiq.json").read_text()) == {"cell": 16, "background": 140, "classes": {"plate": 60}, "grow": 0}
     assert sorted(n for n in os.listdir(tmp / "in") if not n.endswith(".bin")) == ["roiq.json"]
-    assert _bins(tmp / "in") != _bins(tmp / "plain") and list(_bins(tmp / "in")) == list(_bins(tmp / "plain"))
+    assert U.bins(tmp / "in") != U.bins(tmp / "plain") and list(U.bins(tmp / "in")) == list(U.bins(tmp / "plain"))
     assert RC.decode_folder(str(tmp / "in"), str(tmp / "in_dec"), SIDE, SIDE, gop=GOP, roi=_roi()) == N_FRAMES
     for t in range(N_FRAMES):
         name = f"im{t + 1:05d}.png"
@@ -316,7 +289,7 @@ def test_two_gop_streams_write_the_same_bins(e2e, file_nets):
 
     tmp = e2e["tmp"]
     RC.encode_folder(str(tmp / "png"), str(tmp / "in2"), gop=GOP, nets=file_nets, gop_streams=2, roi=_roi(), roi_q=Q_IN)
-    assert _bins(tmp / "in2") == _bins(tmp / "in")
+    assert U.bins(tmp / "in2") == U.bins(tmp / "in")
     assert (tmp / "in2" / "roiq.json").read_text() == (tmp / "in" / "roiq.json").read_text()
 
 
@@ -324,13 +297,13 @@ def test_neutral_factors_and_feature_off_give_the_plain_bins(e2e, file_nets):
     from vcm_ts_amd import run_codec as RC
 
     tmp = e2e["tmp"]
-    plain = _bins(tmp / "plain")
+    plain = U.bins(tmp / "plain")
     assert sorted(os.listdir(tmp / "plain")) == sorted(plain)  # no roiq.json, nothing but the .bin files
     RC.encode_folder(str(tmp / "png"), str(tmp / "neutral"), gop=GOP, nets=file_nets, roi=_roi(), roi_q=X.RoiQ(100, (100,), 7))
-    assert _bins(tmp / "neutral") == plain and (tmp / "neutral" / "roiq.json").exists()
+    assert U.bins(tmp / "neutral") == plain and (tmp / "neutral" / "roiq.json").exists()
     # the feature off, with the boxes and into a folder that holds a stale side file: the parent's bins, the file gone
     RC.encode_folder(str(tmp / "png"), str(tmp / "neutral"), gop=GOP, nets=file_nets, roi=_roi())
-    assert _bins(tmp / "neutral") == plain and sorted(os.listdir(tmp / "neutral")) == sorted(plain)
+    assert U.bins(tmp / "neutral") == plain and sorted(os.listdir(tmp / "neutral")) == sorted(plain)
 
 
 def test_y4m_round_trip_with_a_map(e2e, file_nets):

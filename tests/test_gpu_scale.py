@@ -15,15 +15,17 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_util as U
 from tests import roi_ref as XR
 from tests import scale_ref as R
+from tests.gpu_util import file_nets, no_garbage_left_behind  # noqa: F401 (fixtures)
 from tests.test_scale_host import _HostScale
 from vcm_ts_amd import picturehash as PH
 from vcm_ts_amd import roi as X
 from vcm_ts_amd import scale as SC
 from vcm_ts_amd import synthetic
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("no_garbage_left_behind")]
 DEV = torch.device("cuda:0")
 NAN = float("nan")
 
@@ -40,10 +42,6 @@ def _data(seed, shape):
     flat = a.reshape(-1)
     flat[rng.integers(0, flat.size, 5)] = np.nan
     return a
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def _view(shape, off=3, pad_w=5, pad_h=2):
@@ -91,7 +89,7 @@ def test_kernel_equals_the_restatement_bit_for_bit(case, layout, refs):
             assert x.data_ptr() % 16 and got.data_ptr() % 16
             assert fn(x, out=got) is got
             assert torch.isnan(buf[~inside]).all() and not torch.isnan(buf[inside]).any()  # the surroundings are intact
-        np.testing.assert_array_equal(_bits(got.cpu().numpy()), _bits(want), err_msg=which)
+        np.testing.assert_array_equal(U.f32_bits(got.cpu().numpy()), U.f32_bits(want), err_msg=which)
         assert not np.isnan(want).any() and want.min() >= 0 and want.max() <= 1 and (want == 0).any()  # (clamped; NaN -> 0)
         assert which == "down" or (want == 1).any()
 
@@ -105,17 +103,17 @@ def test_aligned_padded_interior_and_batches(refs):
     hb, wb = s.base
     padded = torch.zeros((1, 3, 128, 128), device=DEV)
     s.down(torch.from_numpy(ref["src"]).to(DEV), out=padded[..., :hb, :wb])
-    np.testing.assert_array_equal(_bits(padded[..., :hb, :wb].cpu().numpy()), _bits(ref["down"]))
+    np.testing.assert_array_equal(U.f32_bits(padded[..., :hb, :wb].cpu().numpy()), U.f32_bits(ref["down"]))
     assert float(padded[..., hb:, :].abs().sum()) == 0 and float(padded[..., :, wb:].abs().sum()) == 0
     padded[..., :hb, :wb] = torch.from_numpy(ref["low"]).to(DEV)
     padded[..., hb:, :] = NAN
     padded[..., :, wb:] = NAN
-    np.testing.assert_array_equal(_bits(s.up(padded[..., :hb, :wb]).cpu().numpy()), _bits(ref["up"]))
+    np.testing.assert_array_equal(U.f32_bits(s.up(padded[..., :hb, :wb]).cpu().numpy()), U.f32_bits(ref["up"]))
     both = torch.from_numpy(np.stack([ref["src"][0], ref["src"][0, ::-1].copy()])).to(DEV)  # (2, 3, H, W)
     got = s.down(both).cpu().numpy()
-    np.testing.assert_array_equal(_bits(got[0]), _bits(ref["down"][0]))
-    np.testing.assert_array_equal(_bits(got[1]), _bits(ref["down"][0, ::-1]))
-    np.testing.assert_array_equal(_bits(s.down(both[0]).cpu().numpy()), _bits(ref["down"][0]))  # (3, H, W) too
+    np.testing.assert_array_equal(U.f32_bits(got[0]), U.f32_bits(ref["down"][0]))
+    np.testing.assert_array_equal(U.f32_bits(got[1]), U.f32_bits(ref["down"][0, ::-1]))
+    np.testing.assert_array_equal(U.f32_bits(s.down(both[0]).cpu().numpy()), U.f32_bits(ref["down"][0]))  # (3, H, W) too
 
 
 def test_wrong_inputs_are_value_errors():
@@ -154,7 +152,7 @@ def test_down_up_residual_fuse_returns_the_source_inside_the_boxes(case, worst):
     for t in range(2):
         src = torch.from_numpy(fr[t:t + 1]).to(DEV)
         up = s.up(s.down(src))
-        np.testing.assert_array_equal(_bits(up.cpu().numpy()), _bits(R.up(R.down(fr[t:t + 1], n, d), (h, w))))
+        np.testing.assert_array_equal(U.f32_bits(up.cpu().numpy()), U.f32_bits(R.up(R.down(fr[t:t + 1], n, d), (h, w))))
         diff = np.abs(R.code(fr[t]) - R.code(up.cpu().numpy()[0]))
         largest = max(largest, int(diff.max()))
         res = X.residual_layer(src, up, boxes)
@@ -170,30 +168,7 @@ def test_down_up_residual_fuse_returns_the_source_inside_the_boxes(case, worst):
 GOP, N = 8, 16
 
 
-@pytest.fixture(autouse=True)
-def _no_garbage_left_behind():
-    """The file loops keep pinned buffers, and a caught exception keeps their frames alive in a reference cycle: collect
-    them here, at a known point between tests, instead of whenever the collector next runs in a later test."""
-    import gc
-
-    yield
-    torch.cuda.synchronize(DEV)
-    gc.collect()
 E2E = {"128at1of2": ((128, 128), (1, 2)), "96at2of3": ((96, 96), (2, 3))}
-
-
-def _png(path):
-    from PIL import Image
-
-    return np.asarray(Image.open(path).convert("RGB"))
-
-
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
-
-
-def _others(folder):
-    return sorted(n for n in os.listdir(folder) if not n.endswith(".bin"))
 
 
 def _hwc(a):
@@ -201,20 +176,11 @@ def _hwc(a):
     return R.code(a).transpose(1, 2, 0).astype(np.uint8)
 
 
-@pytest.fixture(scope="module")
-def nets():
-    from vcm_ts_amd import run_codec as RC
-
-    return [RC._nets(DEV, None) for _ in range(2)]
-
-
 @pytest.fixture(scope="module", params=sorted(E2E))
-def e2e(request, tmp_path_factory, nets):
+def e2e(request, tmp_path_factory, file_nets):
     """One clip per full size, as PNGs.  `direct`: the down() pictures coded through the API that exists without the option
     (an _EncodeRun fed by a generator), with every base reconstruction kept; `want`: those scaled up by the restatement --
     the reference all tests share.  `scaled`: the encode with base_scale, one stream, everything switched on."""
-    from PIL import Image
-
     from vcm_ts_amd import run_codec as RC
     from vcm_ts_amd.pipeline import pad_frame
     from vcm_ts_amd.scenecut import GopPlan
@@ -222,13 +188,11 @@ def e2e(request, tmp_path_factory, nets):
     (h, w), ratio = E2E[request.param]
     tmp = tmp_path_factory.mktemp("scale_" + request.param)
     clip = np.rint(synthetic.frames(5, N, h, w).transpose(0, 2, 3, 1) * 255.0).astype(np.uint8)
-    os.makedirs(tmp / "png")
-    for t, a in enumerate(clip):
-        Image.fromarray(a).save(tmp / "png" / f"im{t + 1:05d}.png")
+    U.write_pngs(tmp / "png", clip)
     s = SC.Scale((h, w), ratio, DEV)
     hb, wb = s.base
     assert (hb, wb) == (64, 64)
-    run = RC._EncodeRun(str(tmp / "direct"), GopPlan.fixed(N, GOP), (hb, wb), GOP, DEV, None, None, None, "host", nets, 1, None)
+    run = RC._EncodeRun(str(tmp / "direct"), GopPlan.fixed(N, GOP), (hb, wb), GOP, DEV, None, None, None, "host", file_nets, 1, None)
     kept = {}
 
     def frames(k):
@@ -238,38 +202,36 @@ def e2e(request, tmp_path_factory, nets):
     run.encode(frames, (1.0, 1.0, 1.0), lambda k, g, ref: kept.__setitem__(g, ref[0, :, :hb, :wb].cpu().numpy().copy()))
     direct_bits, _ = run.results(None)
     want = [R.up(kept[g][None], (h, w))[0] for g in range(N)]
-    bits, size = RC.encode_folder(str(tmp / "png"), str(tmp / "scaled"), str(tmp / "scaled_rec"), gop=GOP, nets=nets,
+    bits, size = RC.encode_folder(str(tmp / "png"), str(tmp / "scaled"), str(tmp / "scaled_rec"), gop=GOP, nets=file_nets,
                                   picture_hash=True, base_scale=ratio)
     return dict(tmp=tmp, h=h, w=w, ratio=ratio, clip=clip, base=kept, want=want, direct_bits=direct_bits, bits=bits, size=size,
                 scale=s)
 
 
-def test_bins_are_those_of_the_down_scaled_pictures_and_recon_is_the_up_scaled_one(e2e, nets):
+def test_bins_are_those_of_the_down_scaled_pictures_and_recon_is_the_up_scaled_one(e2e, file_nets):
     from vcm_ts_amd import run_codec as RC
 
     tmp, h, w = e2e["tmp"], e2e["h"], e2e["w"]
-    assert _bins(tmp / "scaled") == _bins(tmp / "direct") and len(_bins(tmp / "direct")) == N
-    assert _others(tmp / "direct") == [] and _others(tmp / "scaled") == ["hashes.json", "scale.json"]
+    assert U.bins(tmp / "scaled") == U.bins(tmp / "direct") and len(U.bins(tmp / "direct")) == N
+    assert U.others(tmp / "direct") == [] and U.others(tmp / "scaled") == ["hashes.json", "scale.json"]
     assert e2e["size"] == (h, w) and e2e["bits"] == e2e["direct_bits"]
     info = json.loads((tmp / "scaled" / "scale.json").read_text())
     assert info == _HostScale((h, w), e2e["ratio"]).to_json() and info["base"] == [64, 64] and info["full"] == [h, w]
     for t in range(N):
-        assert np.array_equal(_png(tmp / "scaled_rec" / f"im{t + 1:05d}.png"), _hwc(e2e["want"][t])), t
+        assert np.array_equal(U.png(tmp / "scaled_rec" / f"im{t + 1:05d}.png"), _hwc(e2e["want"][t])), t
     # two GOP streams: the same bytes and the same records
-    RC.encode_folder(str(tmp / "png"), str(tmp / "two"), gop=GOP, nets=nets, gop_streams=2, picture_hash=True, base_scale=e2e["ratio"])
-    assert _bins(tmp / "two") == _bins(tmp / "direct")
+    RC.encode_folder(str(tmp / "png"), str(tmp / "two"), gop=GOP, nets=file_nets, gop_streams=2, picture_hash=True, base_scale=e2e["ratio"])
+    assert U.bins(tmp / "two") == U.bins(tmp / "direct")
     for name in ("hashes.json", "scale.json"):
         assert (tmp / "two" / name).read_text() == (tmp / "scaled" / name).read_text()
 
 
-def test_report_speaks_of_the_full_size(tmp_path, nets):
+def test_report_speaks_of_the_full_size(tmp_path, file_nets):
     """At 192x192 coded at 1/2 (a 96x96 base layer, padded to 128x128), 4 pictures: --report measures MS-SSIM, which refuses
     sides of 160 or less, so the report cannot be asked for at the 128x128 and 96x96 full sizes of the other tests.  What is
     asserted is the same: every bpp key divides by the FULL-size pixels, PSNR and the ROI figures compare the full-size
     source with the up-scaled picture (the restatement applied to the base reconstructions the encoder held)."""
     import math
-
-    from PIL import Image
 
     from tests import test_gpu_roi as G
     from vcm_ts_amd import run_codec as RC
@@ -278,9 +240,7 @@ def test_report_speaks_of_the_full_size(tmp_path, nets):
     h = w = 192
     n, gop = 4, 4
     clip = np.rint(synthetic.frames(7, n, h, w).transpose(0, 2, 3, 1) * 255.0).astype(np.uint8)
-    os.makedirs(tmp_path / "png")
-    for t, a in enumerate(clip):
-        Image.fromarray(a).save(tmp_path / "png" / f"im{t + 1:05d}.png")
+    U.write_pngs(tmp_path / "png", clip)
     roi = X.Roi(G._e2e_boxes(h, w), tuple(X.RoiClass(b) for b in G.E2E_BORDERS), ("liplates", "faces"))
     seen, shown = {}, RC._BaseLayer.shown
 
@@ -294,7 +254,7 @@ def test_report_speaks_of_the_full_size(tmp_path, nets):
     with pytest.MonkeyPatch.context() as mp:
         mp.setattr(RC._BaseLayer, "shown", spy)
         mp.setattr(ratectl, "target_bits_of", lambda bpp, hh, ww: budgets.append((bpp, hh, ww)) or target_bits_of(bpp, hh, ww))
-        bits, size, rd = RC.encode_folder(str(tmp_path / "png"), str(tmp_path / "bins"), gop=gop, nets=nets, roi=roi, report=True,
+        bits, size, rd = RC.encode_folder(str(tmp_path / "png"), str(tmp_path / "bins"), gop=gop, nets=file_nets, roi=roi, report=True,
                                           residual_bins=str(tmp_path / "bins"), target_bpp=2.0, base_scale="1/2")
     assert size == (h, w) and S.decode_i(str(tmp_path / "bins" / "im00001.bin"))[:2] == (96, 96)
     assert rd["frame_pixel_num"] == h * w
@@ -323,7 +283,7 @@ def test_decode_follows_scale_json_and_base_only_ignores_it(e2e):
     for t in range(N):
         name = f"im{t + 1:05d}.png"
         assert (tmp / "dec" / name).read_bytes() == (tmp / "scaled_rec" / name).read_bytes(), t
-        assert np.array_equal(_png(tmp / "dec" / name), _hwc(e2e["want"][t])), t
+        assert np.array_equal(U.png(tmp / "dec" / name), _hwc(e2e["want"][t])), t
     # run_codec verify checks the folder decode --recon writes
     assert PH.verify_pngs(str(tmp / "scaled"), str(tmp / "dec")) is None
     RC.main(["verify", "--bins", str(tmp / "scaled"), "--recon", str(tmp / "dec")])
@@ -333,10 +293,10 @@ def test_decode_follows_scale_json_and_base_only_ignores_it(e2e):
     for t in range(N):
         name = f"im{t + 1:05d}.png"
         assert (tmp / "base_only" / name).read_bytes() == (tmp / "direct_dec" / name).read_bytes(), t
-        assert np.array_equal(_png(tmp / "base_only" / name), _hwc(e2e["base"][t])), t
+        assert np.array_equal(U.png(tmp / "base_only" / name), _hwc(e2e["base"][t])), t
     RC.main(["decode", "--bins", str(tmp / "scaled"), "--recon", str(tmp / "cli_base"), "--height", str(h), "--width", str(w),
              "--gop", str(GOP), "--base-only"])
-    assert _png(tmp / "cli_base" / "im00003.png").shape == (64, 64, 3)
+    assert U.png(tmp / "cli_base" / "im00003.png").shape == (64, 64, 3)
     # a drifting scaler is caught: 8 units of 16384 moved from one tap of the decoder's up table to the next (rows still sum)
     with pytest.MonkeyPatch.context() as mp:
         real = SC._tables
@@ -365,7 +325,7 @@ def test_a_scale_json_that_does_not_fit_is_refused_before_any_launch(e2e):
     def folder(name, info):
         dst = tmp / name
         os.makedirs(dst)
-        for n, data in _bins(tmp / "scaled").items():
+        for n, data in U.bins(tmp / "scaled").items():
             (dst / n).write_bytes(data)
         (dst / "hashes.json").write_text((tmp / "scaled" / "hashes.json").read_text())
         (dst / "scale.json").write_text(json.dumps(info))
@@ -393,15 +353,15 @@ def test_a_scale_json_that_does_not_fit_is_refused_before_any_launch(e2e):
     assert not (tmp / "never").exists()
 
 
-def test_residual_bins_at_step_one_return_the_source_in_the_boxes(e2e, nets):
+def test_residual_bins_at_step_one_return_the_source_in_the_boxes(e2e, file_nets):
     from tests import test_gpu_roi as G
     from vcm_ts_amd import run_codec as RC
 
     tmp, h, w = e2e["tmp"], e2e["h"], e2e["w"]
     roi = X.Roi(G._e2e_boxes(h, w), tuple(X.RoiClass(b) for b in G.E2E_BORDERS), ("liplates", "faces"))
-    bits, size = RC.encode_folder(str(tmp / "png"), str(tmp / "roi"), gop=GOP, nets=nets, gop_streams=2, roi=roi,
+    bits, size = RC.encode_folder(str(tmp / "png"), str(tmp / "roi"), gop=GOP, nets=file_nets, gop_streams=2, roi=roi,
                                   residuals=str(tmp / "res.gbrp"), residual_bins=str(tmp / "roi"), base_scale=e2e["ratio"])
-    assert _bins(tmp / "roi") == _bins(tmp / "direct") and size == (h, w)
+    assert U.bins(tmp / "roi") == U.bins(tmp / "direct") and size == (h, w)
     raw = np.frombuffer((tmp / "res.gbrp").read_bytes(), np.uint8).reshape(N, 3, h, w)
     assert RC.decode_folder(str(tmp / "roi"), str(tmp / "fused"), h, w, gop=GOP, roi=roi, residual_bins=str(tmp / "roi")) == N
     changed = 0
@@ -409,7 +369,7 @@ def test_residual_bins_at_step_one_return_the_source_in_the_boxes(e2e, nets):
         src, up, boxes = XR.T[e2e["clip"][t].transpose(2, 0, 1)], e2e["want"][t], roi.boxes(t).array
         res = XR.residual(src, up, boxes)  # (against the up-scaled picture, boxes in full-size coordinates)
         assert np.array_equal(raw[t][[2, 0, 1]], res), t
-        got = _png(tmp / "fused" / f"im{t + 1:05d}.png")
+        got = U.png(tmp / "fused" / f"im{t + 1:05d}.png")
         assert np.array_equal(got, _hwc(XR.fuse(up, res, boxes, G.E2E_BORDERS))), t
         changed += int((got != _hwc(up)).sum())
         # (the name-seeded weights of the suite reconstruct poorly: |code(src) - code(up)| reaches 254 here, the residual
@@ -419,7 +379,7 @@ def test_residual_bins_at_step_one_return_the_source_in_the_boxes(e2e, nets):
         RC.decode_folder(str(tmp / "roi"), str(tmp / "never"), h, w, gop=GOP, roi=roi, residual_bins=str(tmp / "roi"), base_scale=None)
 
 
-def test_y4m_round_trip(e2e, nets):
+def test_y4m_round_trip(e2e, file_nets):
     from tests import yuv_ref as YR
     from vcm_ts_amd import run_codec as RC
 
@@ -435,28 +395,28 @@ def test_y4m_round_trip(e2e, nets):
 
     with pytest.MonkeyPatch.context() as mp:
         mp.setattr(RC._BaseLayer, "shown", spy)
-        bits, size = RC.encode_video(str(tmp / "src.y4m"), str(tmp / "v"), str(tmp / "v_enc.y4m"), gop=GOP, nets=nets, gop_streams=2,
+        bits, size = RC.encode_video(str(tmp / "src.y4m"), str(tmp / "v"), str(tmp / "v_enc.y4m"), gop=GOP, nets=file_nets, gop_streams=2,
                                      picture_hash=True, base_scale=e2e["ratio"])
     assert size == (h, w) and sorted(seen) == list(range(N))
-    assert _others(tmp / "v") == ["hashes.json", "scale.json", "sequence.json"]
+    assert U.others(tmp / "v") == ["hashes.json", "scale.json", "sequence.json"]
     info = json.loads((tmp / "v" / "sequence.json").read_text())
     assert (info["height"], info["width"]) == (h, w)
     assert RC.decode_video(str(tmp / "v"), str(tmp / "v_dec.y4m"), verify="strict") == N
     assert (tmp / "v_dec.y4m").read_bytes() == (tmp / "v_enc.y4m").read_bytes()
     assert RC.decode_folder(str(tmp / "v"), str(tmp / "v_png"), h, w, gop=GOP) == N
     for t in range(N):
-        assert np.array_equal(_png(tmp / "v_png" / f"im{t + 1:05d}.png"), _hwc(R.up(seen[t][None], (h, w))[0])), t
+        assert np.array_equal(U.png(tmp / "v_png" / f"im{t + 1:05d}.png"), _hwc(R.up(seen[t][None], (h, w))[0])), t
     assert RC.decode_video(str(tmp / "v"), str(tmp / "v_base.y4m"), base_scale=None) == N
     assert os.path.getsize(tmp / "v_base.y4m") < os.path.getsize(tmp / "v_dec.y4m") * (64 * 64) / (h * w) + 4096
 
 
-def test_refused_combinations_and_the_option_left_out(e2e, nets):
+def test_refused_combinations_and_the_option_left_out(e2e, file_nets):
     from tests import test_gpu_roi as G
     from vcm_ts_amd import run_codec as RC
 
     tmp, h, w = e2e["tmp"], e2e["h"], e2e["w"]
     roi = X.Roi(G._e2e_boxes(h, w), tuple(X.RoiClass(b) for b in G.E2E_BORDERS))
-    kw = dict(gop=GOP, nets=nets, base_scale=e2e["ratio"])
+    kw = dict(gop=GOP, nets=file_nets, base_scale=e2e["ratio"])
     with pytest.raises(NotImplementedError, match="roi_q="):
         RC.encode_folder(str(tmp / "png"), str(tmp / "no"), roi=roi, roi_q=X.RoiQ(100, (60, 60)), **kw)
     with pytest.raises(NotImplementedError, match="bit_map= and roi="):
@@ -464,11 +424,11 @@ def test_refused_combinations_and_the_option_left_out(e2e, nets):
     with pytest.raises(NotImplementedError, match="bit_map= and roi="):
         RC.encode_folder(str(tmp / "png"), str(tmp / "no"), roi=roi, bit_map=str(tmp / "maps"), **kw)
     with pytest.raises(ValueError, match="1/4 <= n/d < 1"):
-        RC.encode_folder(str(tmp / "png"), str(tmp / "no"), gop=GOP, nets=nets, base_scale="1/8")
+        RC.encode_folder(str(tmp / "png"), str(tmp / "no"), gop=GOP, nets=file_nets, base_scale="1/8")
     assert not (tmp / "no").exists()
     # bit_map without roi is unchanged: the cells of the base grid
     RC.encode_folder(str(tmp / "png"), str(tmp / "maps_bins"), bit_map=str(tmp / "maps"), **kw)
-    assert np.load(tmp / "maps" / "im00001.npy").shape == (1, 4, 4) and _bins(tmp / "maps_bins") == _bins(tmp / "direct")
+    assert np.load(tmp / "maps" / "im00001.npy").shape == (1, 4, 4) and U.bins(tmp / "maps_bins") == U.bins(tmp / "direct")
     # without the option: no launch, no file (a stale one is removed), and the bytes are those of the layers below the file
     # loops, which the option does not reach (pipeline.ConcurrentGopEncoder and the stream.py containers, fed by hand)
     stale = tmp / "stale"
@@ -477,10 +437,10 @@ def test_refused_combinations_and_the_option_left_out(e2e, nets):
     launches = []
     with pytest.MonkeyPatch.context() as mp:
         mp.setattr(SC, "scale_planes", lambda *a, **k: launches.append(a))
-        RC.encode_folder(str(tmp / "scaled_rec"), str(stale), gop=GOP, nets=nets)
-        RC.encode_folder(str(tmp / "scaled_rec"), str(tmp / "plain"), gop=GOP, nets=nets)
+        RC.encode_folder(str(tmp / "scaled_rec"), str(stale), gop=GOP, nets=file_nets)
+        RC.encode_folder(str(tmp / "scaled_rec"), str(tmp / "plain"), gop=GOP, nets=file_nets)
         assert RC.decode_folder(str(stale), str(tmp / "stale_dec"), h, w, gop=GOP) == N
-    assert launches == [] and _others(stale) == [] and _others(tmp / "plain") == [] and _bins(stale) == _bins(tmp / "plain")
+    assert launches == [] and U.others(stale) == [] and U.others(tmp / "plain") == [] and U.bins(stale) == U.bins(tmp / "plain")
     from vcm_ts_amd import stream as S
     from vcm_ts_amd.pipeline import ConcurrentGopEncoder, pad_frame
 
@@ -493,8 +453,8 @@ def test_refused_combinations_and_the_option_left_out(e2e, nets):
         else:
             S.encode_p(payload, qidx[0], qidx[1], path)
 
-    pictures = (pad_frame(RC.u8_to_unit_float(torch.from_numpy(_png(tmp / "scaled_rec" / f"im{t + 1:05d}.png").copy()).to(DEV)))
+    pictures = (pad_frame(RC.u8_to_unit_float(torch.from_numpy(U.png(tmp / "scaled_rec" / f"im{t + 1:05d}.png").copy()).to(DEV)))
                 for t in range(N))
     with torch.no_grad():
-        ConcurrentGopEncoder(lambda: nets[0], gop_size=GOP, streams=1).encode_gops([pictures], 1.0, 1.0, 1.0, sinks=[sink])
-    assert _bins(tmp / "by_hand") == _bins(tmp / "plain") and len(_bins(tmp / "plain")) == N
+        ConcurrentGopEncoder(lambda: file_nets[0], gop_size=GOP, streams=1).encode_gops([pictures], 1.0, 1.0, 1.0, sinks=[sink])
+    assert U.bins(tmp / "by_hand") == U.bins(tmp / "plain") and len(U.bins(tmp / "plain")) == N

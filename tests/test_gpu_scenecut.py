@@ -7,7 +7,6 @@ The end-to-end tests run at 64x64, 16 pictures (five of a bright scene, eleven o
 0.5, min_gop 2: the plan is [0, 5, 13] (tests/test_scenecut_host.py holds the margins of that threshold).  The report test
 alone runs at 192x192: a report carries MS-SSIM, which takes no picture side below 161 (vcm_ts_amd/metrics.py).
 """
-import ctypes as C
 import json
 import os
 
@@ -15,7 +14,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_util as U
 from tests import scenecut_ref as R
+from tests.gpu_util import file_nets  # noqa: F401 (fixture)
 from vcm_ts_amd import lib
 from vcm_ts_amd import scenecut as SC
 
@@ -45,18 +46,12 @@ def _view(a, layout):
     return v, rs, ps
 
 
-def _stream():
-    from vcm_ts_amd.engine import _raw_stream
-
-    return C.c_void_p(_raw_stream(DEV.index))
-
-
 def _kernel(v, rs, ps, hist=None):
     """dcvc_scene_hist itself, on the view's own strides"""
     H, W = v.shape[2:]
     if hist is None:
         hist = torch.zeros(512, dtype=torch.int32, device=DEV)
-    lib.check(lib.hip().dcvc_scene_hist(v.data_ptr(), rs, ps, H, W, hist.data_ptr(), _stream()), "scene_hist")
+    lib.check(lib.hip().dcvc_scene_hist(v.data_ptr(), rs, ps, H, W, hist.data_ptr(), U.stream(DEV)), "scene_hist")
     return hist
 
 
@@ -135,49 +130,24 @@ def test_scan_on_another_stream_through_padded_pictures():
 GOP, T, MIN_GOP, PLAN = 8, 0.5, 2, [0, 5, 13]
 
 
-def _png(path):
-    from PIL import Image
-
-    return np.asarray(Image.open(path).convert("RGB"))
-
-
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
-
-
-def _write_pngs(folder, clip):
-    from PIL import Image
-
-    os.makedirs(folder)
-    for t, a in enumerate(clip):
-        Image.fromarray(a).save(os.path.join(folder, f"im{t + 1:05d}.png"))
-
-
 @pytest.fixture(scope="module")
-def nets():
-    from vcm_ts_amd import run_codec as RC
-
-    return [RC._nets(DEV, None) for _ in range(2)]
-
-
-@pytest.fixture(scope="module")
-def e2e(tmp_path_factory, nets):
+def e2e(tmp_path_factory, file_nets):
     """the clip as PNGs; a plain encode (the baseline) and the scene-cut encode with its reconstructions"""
     from vcm_ts_amd import run_codec as RC
 
     tmp = tmp_path_factory.mktemp("scenecut_e2e")
     clip = R.cut_clip(64, 64)
-    _write_pngs(tmp / "png", clip)
-    RC.encode_folder(str(tmp / "png"), str(tmp / "plain"), gop=GOP, nets=nets)
+    U.write_pngs(tmp / "png", clip)
+    RC.encode_folder(str(tmp / "png"), str(tmp / "plain"), gop=GOP, nets=file_nets)
     return dict(tmp=tmp, clip=clip, n=len(clip))
 
 
 @pytest.fixture(scope="module")
-def cut(e2e, nets):
+def cut(e2e, file_nets):
     from vcm_ts_amd import run_codec as RC
 
     tmp = e2e["tmp"]
-    bits, size = RC.encode_folder(str(tmp / "png"), str(tmp / "cut"), str(tmp / "cut_rec"), gop=GOP, nets=nets, scenecut=T,
+    bits, size = RC.encode_folder(str(tmp / "png"), str(tmp / "cut"), str(tmp / "cut_rec"), gop=GOP, nets=file_nets, scenecut=T,
                                   min_gop=MIN_GOP)
     assert size == (64, 64) and len(bits) == e2e["n"]
     return tmp / "cut"
@@ -194,8 +164,8 @@ def test_folder_plan_is_recorded_and_the_cut_pictures_are_i_files(e2e, cut):
     for g in PLAN:
         h, w, _, payload = S.decode_i(str(cut / f"im{g + 1:05d}.bin"))
         assert (h, w) == (64, 64) and len(payload) > 0
-    plain = _bins(e2e["tmp"] / "plain")
-    ours = _bins(cut)
+    plain = U.bins(e2e["tmp"] / "plain")
+    ours = U.bins(cut)
     assert list(ours) == list(plain) and len(ours) == 16
     assert all(ours[f"im{t + 1:05d}.bin"] == plain[f"im{t + 1:05d}.bin"] for t in range(5))  # the first GOP is the same
     assert ours["im00006.bin"] != plain["im00006.bin"]
@@ -216,40 +186,40 @@ def test_folder_decodes_to_the_encoders_reconstruction(e2e, cut):
         RC.decode_folder(str(cut), str(tmp / "x"), 64, 64, gop=4)
 
 
-def test_two_gop_streams_write_the_same_bins(e2e, cut, nets):
+def test_two_gop_streams_write_the_same_bins(e2e, cut, file_nets):
     from vcm_ts_amd import run_codec as RC
 
     tmp = e2e["tmp"]
-    RC.encode_folder(str(tmp / "png"), str(tmp / "cut2"), gop=GOP, nets=nets, gop_streams=2, scenecut=T, min_gop=MIN_GOP)
-    assert _bins(tmp / "cut2") == _bins(cut)
+    RC.encode_folder(str(tmp / "png"), str(tmp / "cut2"), gop=GOP, nets=file_nets, gop_streams=2, scenecut=T, min_gop=MIN_GOP)
+    assert U.bins(tmp / "cut2") == U.bins(cut)
     assert (tmp / "cut2" / "gops.json").read_text() == (cut / "gops.json").read_text()
 
 
-def test_feature_off_is_free(e2e, nets):
+def test_feature_off_is_free(e2e, file_nets):
     from vcm_ts_amd import run_codec as RC
 
     tmp = e2e["tmp"]
-    plain = _bins(tmp / "plain")
+    plain = U.bins(tmp / "plain")
     assert sorted(os.listdir(tmp / "plain")) == sorted(plain)  # no gops.json, nothing but the .bin files
-    RC.encode_folder(str(tmp / "png"), str(tmp / "never"), gop=GOP, nets=nets, scenecut=1.0)  # d > 1.0 cannot happen
-    assert _bins(tmp / "never") == plain
+    RC.encode_folder(str(tmp / "png"), str(tmp / "never"), gop=GOP, nets=file_nets, scenecut=1.0)  # d > 1.0 cannot happen
+    assert U.bins(tmp / "never") == plain
     info = json.loads((tmp / "never" / "gops.json").read_text())
     assert SC.GopPlan.from_json(info) == SC.GopPlan.fixed(16, GOP) and info["scenecut"] == 1.0 and info["min_gop"] == 1
     for bad in (dict(scenecut=0.0), dict(scenecut=1.5), dict(scenecut=0.5, min_gop=9), dict(scenecut=0.5, min_gop=0)):
         with pytest.raises(ValueError, match="threshold|min_gop"):
-            RC.encode_folder(str(tmp / "png"), str(tmp / "bad"), gop=GOP, nets=nets, **bad)
+            RC.encode_folder(str(tmp / "png"), str(tmp / "bad"), gop=GOP, nets=file_nets, **bad)
     assert not (tmp / "bad").exists()
 
 
-def test_report_marks_the_i_pictures(tmp_path, nets):
+def test_report_marks_the_i_pictures(tmp_path, file_nets):
     """At 192x192 (see the module's docstring), otherwise the end-to-end clip and options."""
     from vcm_ts_amd import run_codec as RC
 
     clip = R.cut_clip(192, 192)
     floats = [a.transpose(2, 0, 1).astype(np.float32) / np.float32(255.0) for a in clip]
     assert R.plan(R.distances(floats), GOP, T, MIN_GOP) == PLAN
-    _write_pngs(tmp_path / "png", clip)
-    _, _, rd = RC.encode_folder(str(tmp_path / "png"), str(tmp_path / "bins"), gop=GOP, nets=nets, gop_streams=2, report=True,
+    U.write_pngs(tmp_path / "png", clip)
+    _, _, rd = RC.encode_folder(str(tmp_path / "png"), str(tmp_path / "bins"), gop=GOP, nets=file_nets, gop_streams=2, report=True,
                                 scenecut=T, min_gop=MIN_GOP)
     assert [t for t, k in enumerate(rd["frame_type"]) if k == 0] == PLAN and len(rd["frame_type"]) == 16
     assert rd["i_frame_num"] == 3 and rd["p_frame_num"] == 13
@@ -257,7 +227,7 @@ def test_report_marks_the_i_pictures(tmp_path, nets):
     assert json.loads((tmp_path / "bins" / "gops.json").read_text())["i_pictures"] == PLAN
 
 
-def test_y4m_plan_and_decoder_output(e2e, nets):
+def test_y4m_plan_and_decoder_output(e2e, file_nets):
     from tests import yuv_ref as YR
     from vcm_ts_amd import run_codec as RC
 
@@ -268,7 +238,7 @@ def test_y4m_plan_and_decoder_output(e2e, nets):
     # the restatement on the CONVERTED pictures is the judge of what the scan sees
     converted = [YR.to_rgb(*p, dtype=np.float32) for p in planes]
     assert R.plan(R.distances(converted), GOP, T, MIN_GOP) == PLAN
-    RC.encode_video(str(tmp / "src.y4m"), str(tmp / "vbins"), str(tmp / "enc.y4m"), gop=GOP, nets=nets, gop_streams=2,
+    RC.encode_video(str(tmp / "src.y4m"), str(tmp / "vbins"), str(tmp / "enc.y4m"), gop=GOP, nets=file_nets, gop_streams=2,
                     scenecut=T, min_gop=MIN_GOP)
     assert json.loads((tmp / "vbins" / "gops.json").read_text())["i_pictures"] == PLAN
     info = RC.read_sequence_info(str(tmp / "vbins"))
@@ -278,7 +248,7 @@ def test_y4m_plan_and_decoder_output(e2e, nets):
     assert (tmp / "dec.y4m").stat().st_size > 16 * 64 * 64 * 3 // 2
 
 
-def test_roi_layer_either_side_of_the_cut(e2e, nets):
+def test_roi_layer_either_side_of_the_cut(e2e, file_nets):
     """Boxes on frames 4, 5 and 6 (the cut is at 5; with two GOP streams frames 4 and 5 are coded on different streams):
     the residual file and the decoder's fused pictures are what tests/test_gpu_roi.py checks for fixed GOPs."""
     from tests import roi_ref as RR
@@ -295,7 +265,7 @@ def test_roi_layer_either_side_of_the_cut(e2e, nets):
 
     roi = X.Roi(boxes, tuple(X.RoiClass(b) for b in borders), ("liplates", "faces"))
     res = str(tmp / "res.gbrp")
-    RC.encode_folder(str(tmp / "png"), str(tmp / "rbins"), gop=GOP, nets=nets, gop_streams=2, roi=roi, residuals=res,
+    RC.encode_folder(str(tmp / "png"), str(tmp / "rbins"), gop=GOP, nets=file_nets, gop_streams=2, roi=roi, residuals=res,
                      scenecut=T, min_gop=MIN_GOP)
     assert json.loads((tmp / "rbins" / "gops.json").read_text())["i_pictures"] == PLAN
     assert RC.decode_folder(str(tmp / "rbins"), str(tmp / "rrec"), h, w) == n
@@ -303,13 +273,13 @@ def test_roi_layer_either_side_of_the_cut(e2e, nets):
     raw = np.frombuffer(open(res, "rb").read(), np.uint8).reshape(n, 3, h, w)
     changed = 0
     for t in range(n):
-        rec = _png(tmp / "rrec" / f"im{t + 1:05d}.png").transpose(2, 0, 1)
+        rec = U.png(tmp / "rrec" / f"im{t + 1:05d}.png", planar=True)
         src = RR.T[e2e["clip"][t].transpose(2, 0, 1)]
         want_res = RR.residual(src, RR.T[rec], boxes(t).array)
         assert np.array_equal(raw[t], want_res[[1, 2, 0]]), t  # G, B, R planes
         assert want_res.any() == (t in (4, 5, 6))
         want = RR.fuse(RR.T[rec], raw[t][[2, 0, 1]], boxes(t).array, borders)
         codes = np.rint(want * np.float32(255.0)).astype(np.uint8)
-        assert np.array_equal(_png(tmp / "rfused" / f"im{t + 1:05d}.png").transpose(2, 0, 1), codes), t
+        assert np.array_equal(U.png(tmp / "rfused" / f"im{t + 1:05d}.png", planar=True), codes), t
         changed += int((codes != rec).sum())
     assert changed > 100

@@ -2,7 +2,6 @@
 in strided, offset, NaN-surrounded layouts with guarded outputs, its refusals, TnrFilter, and the file loops end to end:
 the pictures the codec is handed, an unchanged decoder, the report, two GOP streams, a Y4M file, the command line."""
 import contextlib
-import ctypes as C
 import json
 import os
 
@@ -10,64 +9,23 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_util as U
 from tests import tnr_ref as R
+from tests.gpu_util import file_nets, no_garbage_left_behind  # noqa: F401 (fixtures)
 from vcm_ts_amd import lib
 from vcm_ts_amd import roi as X
 from vcm_ts_amd import tnr as N
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("no_garbage_left_behind")]
 DEV = torch.device("cuda:0")
 F32 = np.float32
-GUARD, SENT16, SENT32 = 64, 0xABCD, 0xABCD1234
+SENT16, SENT32 = 0xABCD, 0xABCD1234
 
 
-@pytest.fixture(autouse=True)
-def _no_garbage_left_behind():
-    """As in test_gpu_scale.py: the file loops keep pinned buffers and events, and whatever of them ends up in a reference
-    cycle is collected here, at a known point between tests with the device idle, instead of whenever the collector next
-    runs in a later test -- inside a graph capture, for instance."""
-    import gc
-
-    yield
-    torch.cuda.synchronize(DEV)
-    gc.collect()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _strided(pic, H, W, row_pad, plane_pad, offset):
-    """A (3, H, W) view with row stride W + row_pad and plane stride H * rs + plane_pad, `offset` elements into a buffer of
-    NaN (the layouts of test_gpu_motion.py), holding `pic` when one is given: (the buffer, the view, row stride, plane
-    stride, the buffer's mask of the view's words)."""
-    rs = W + row_pad
-    ps = H * rs + plane_pad
-    buf = torch.full((offset + 3 * ps + GUARD,), float("nan"), device=DEV)
-    view = buf.as_strided((3, H, W), (ps, rs, 1), offset)
-    if pic is not None:
-        view.copy_(torch.from_numpy(pic))
-    mask = np.zeros(buf.numel(), dtype=bool)
-    mask[offset + np.add.outer(np.add.outer(ps * np.arange(3), rs * np.arange(H)), np.arange(W))] = True
-    return buf, view, rs, ps, mask
-
-
-def _guarded(n, shift, dtype, sentinel):
-    """n words of `sentinel` with GUARD (+ shift) words before and GUARD after, as a tensor of the signed type of the same
-    width: (the buffer, the first word's index)."""
-    signed = {np.uint16: np.int16, np.uint32: np.int32}[dtype]
-    buf = torch.from_numpy(np.full(2 * GUARD + shift + n, sentinel, dtype=dtype).view(signed)).to(DEV)
-    return buf, GUARD + shift
-
-
-def _words(buf, dtype):
-    return buf.cpu().numpy().view(dtype).astype(np.int64)
-
-
-def _check_cells(buf, at, n, want, dtype, sentinel, where):
-    got = _words(buf, dtype)
+def _check_cells(buf, at, n, want, sentinel, where):
+    got = U.words(buf)
     assert np.array_equal(got[at:at + n], np.asarray(want, dtype=np.int64).reshape(-1)), where
-    assert (got[:at] == sentinel).all() and (got[at + n:] == sentinel).all(), where
+    assert U.guards_intact(buf, at, n, sentinel), where
 
 
 # (row pad, plane pad, offset of cur / ref / out, shift of sad / held): 16-byte accesses; an odd offset, an odd row
@@ -79,18 +37,18 @@ def _step(cur, ref, tab_dev, P, H, W, layout, want, where):
     """One dcvc_tnr_step in `layout`, held against want = (out, sad, held)."""
     row_pad, plane_pad, offset, shift = layout
     hc, wc = R.grid(H, W)
-    kc, vc, crs, cps, _ = _strided(cur, H, W, row_pad, plane_pad, offset)
-    kr, vr, rrs, rps, _ = _strided(ref, H, W, row_pad, plane_pad, offset)
-    ko, vo, ors, ops, mask = _strided(None, H, W, row_pad, plane_pad, offset)
-    sad, s0 = _guarded(hc * wc, shift, np.uint32, SENT32)  # (fresh sentinels every step: every cell is WRITTEN)
-    held, h0 = _guarded(hc * wc, shift, np.uint16, SENT16)
+    kc, vc, crs, cps, _ = U.strided(cur, H, W, row_pad, plane_pad, offset, DEV)
+    kr, vr, rrs, rps, _ = U.strided(ref, H, W, row_pad, plane_pad, offset, DEV)
+    ko, vo, ors, ops, mask = U.strided(None, H, W, row_pad, plane_pad, offset, DEV)
+    sad, s0 = U.guarded(hc * wc, shift, np.uint32, SENT32, DEV)  # (fresh sentinels every step: every cell is WRITTEN)
+    held, h0 = U.guarded(hc * wc, shift, np.uint16, SENT16, DEV)
     lib.check(lib.hip().dcvc_tnr_step(vc.data_ptr(), crs, cps, vr.data_ptr(), rrs, rps, vo.data_ptr(), ors, ops, H, W,
-                                      tab_dev.data_ptr(), P, sad.data_ptr() + 4 * s0, held.data_ptr() + 2 * h0, _stream()), "tnr_step")
+                                      tab_dev.data_ptr(), P, sad.data_ptr() + 4 * s0, held.data_ptr() + 2 * h0, U.stream(DEV)), "tnr_step")
     got = ko.cpu().numpy()
     assert np.array_equal(got[mask].view(np.uint32), want[0].reshape(-1).view(np.uint32)), where
     assert np.isnan(got[~mask]).all(), where  # nothing outside the crop of out is touched
-    _check_cells(sad, s0, hc * wc, want[1], np.uint32, SENT32, where)
-    _check_cells(held, h0, hc * wc, want[2], np.uint16, SENT16, where)
+    _check_cells(sad, s0, hc * wc, want[1], SENT32, where)
+    _check_cells(held, h0, hc * wc, want[2], SENT16, where)
     for k, pic in ((kc, cur), (kr, ref)):  # the inputs are only read
         assert np.array_equal(k.cpu().numpy()[mask].view(np.uint32), pic.reshape(-1).view(np.uint32)), where
 
@@ -148,11 +106,11 @@ def test_entry_point_refusals_leave_the_outputs_alone():
     H, W = 70, 100
     hc, wc = R.grid(H, W)
     pics = R.sequences(H, W)["clip"]
-    kc, vc, crs, cps, _ = _strided(pics[1], H, W, 8, 24, 12)
-    kr, vr, rrs, rps, _ = _strided(pics[0], H, W, 8, 24, 12)
-    ko, vo, ors, ops, mask = _strided(None, H, W, 8, 24, 12)
-    sad, s0 = _guarded(hc * wc, 0, np.uint32, SENT32)
-    held, h0 = _guarded(hc * wc, 0, np.uint16, SENT16)
+    kc, vc, crs, cps, _ = U.strided(pics[1], H, W, 8, 24, 12, DEV)
+    kr, vr, rrs, rps, _ = U.strided(pics[0], H, W, 8, 24, 12, DEV)
+    ko, vo, ors, ops, mask = U.strided(None, H, W, 8, 24, 12, DEV)
+    sad, s0 = U.guarded(hc * wc, 0, np.uint32, SENT32, DEV)
+    held, h0 = U.guarded(hc * wc, 0, np.uint16, SENT16, DEV)
     tab = torch.from_numpy(R.table(12, 64).view(np.int16)).to(DEV)
     good = dict(cur=vc.data_ptr(), crs=crs, cps=cps, ref=vr.data_ptr(), rrs=rrs, rps=rps, out=vo.data_ptr(), ors=ors, ops=ops, H=H, W=W,
                 wtab=tab.data_ptr(), P=36, sad=sad.data_ptr() + 4 * s0, held=held.data_ptr() + 2 * h0)
@@ -166,18 +124,18 @@ def test_entry_point_refusals_leave_the_outputs_alone():
            {"cur": good["out"] + 4 * ops}, {"ref": good["out"] + 4 * (H - 1) * ors}]
     for b in bad:
         v = dict(good, **b)
-        assert lib.hip().dcvc_tnr_step(*[v[k] for k in order], _stream()) == -1, b
+        assert lib.hip().dcvc_tnr_step(*[v[k] for k in order], U.stream(DEV)) == -1, b
     torch.cuda.synchronize(DEV)
-    assert (_words(sad, np.uint32) == SENT32).all() and (_words(held, np.uint16) == SENT16).all()
+    assert (U.words(sad) == SENT32).all() and (U.words(held) == SENT16).all()
     assert np.isnan(ko.cpu().numpy()).all()
-    assert lib.hip().dcvc_tnr_step(*[good[k] for k in order], _stream()) == 0  # (and the arguments were good ones)
+    assert lib.hip().dcvc_tnr_step(*[good[k] for k in order], U.stream(DEV)) == 0  # (and the arguments were good ones)
     want = R.step(pics[1], pics[0], R.table(12, 64), 36)
     assert np.array_equal(ko.cpu().numpy()[mask].view(np.uint32), want[0].reshape(-1).view(np.uint32))
-    _check_cells(sad, s0, hc * wc, want[1], np.uint32, SENT32, "good")
-    _check_cells(held, h0, hc * wc, want[2], np.uint16, SENT16, "good")
+    _check_cells(sad, s0, hc * wc, want[1], SENT32, "good")
+    _check_cells(held, h0, hc * wc, want[2], SENT16, "good")
     # cur and ref may be the same picture: only out must stand apart
-    assert lib.hip().dcvc_tnr_step(*[dict(good, ref=good["cur"])[k] for k in order], _stream()) == 0
-    _check_cells(sad, s0, hc * wc, np.zeros(hc * wc), np.uint32, SENT32, "cur is ref")
+    assert lib.hip().dcvc_tnr_step(*[dict(good, ref=good["cur"])[k] for k in order], U.stream(DEV)) == 0
+    _check_cells(sad, s0, hc * wc, np.zeros(hc * wc), SENT32, "cur is ref")
 
 
 def _padded(pic, Hp, Wp):
@@ -232,24 +190,10 @@ SETTING = N.TNR(12, 64, 36)
 INTRA = {0, 4}
 
 
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
-
-
-def _same_pngs(a, b):
-    for t in range(N_FRAMES):
-        name = f"im{t + 1:05d}.png"
-        assert (a / name).read_bytes() == (b / name).read_bytes(), t
-
-
 def _write_pngs(folder, H, W):
     """The first pictures of the noisy clip as PNGs -> what u8_to_unit_float uploads of them, (3, H, W) float32 each."""
-    from PIL import Image
-
     u8 = np.rint(R.clip(H, W)[0][:N_FRAMES] * 255).astype(np.uint8)
-    os.makedirs(folder)
-    for t, a in enumerate(u8):
-        Image.fromarray(a.transpose(1, 2, 0)).save(folder / f"im{t + 1:05d}.png")
+    U.write_pngs(folder, u8.transpose(0, 2, 3, 1))
     return [a.astype(F32) / F32(255.0) for a in u8]
 
 
@@ -294,13 +238,6 @@ def _spies():
 
 
 @pytest.fixture(scope="module")
-def file_nets():
-    from vcm_ts_amd import run_codec as RC
-
-    return [RC._nets(DEV, None) for _ in range(2)]
-
-
-@pytest.fixture(scope="module")
 def e2e(tmp_path_factory, file_nets):
     """the noisy clip as PNGs; a plain encode, and the encode with the prefilter -- the pictures its codec was handed
     captured on the way"""
@@ -327,13 +264,13 @@ def test_an_unchanged_decoder_decodes_and_verifies(e2e):
 
     tmp = e2e["tmp"]
     assert sorted(n for n in os.listdir(tmp / "tnr") if not n.endswith(".bin")) == ["hashes.json"]  # no side file of the filter
-    tnr, plain = _bins(tmp / "tnr"), _bins(tmp / "plain")
+    tnr, plain = U.bins(tmp / "tnr"), U.bins(tmp / "plain")
     assert list(tnr) == list(plain)
     for t in range(N_FRAMES):  # I pictures are handed over as they are; every P picture is another picture
         name = f"im{t + 1:05d}.bin"
         assert (tnr[name] == plain[name]) == (t in INTRA), t
     assert RC.decode_folder(str(tmp / "tnr"), str(tmp / "tnr_dec"), FH, FW, gop=GOP, verify="strict") == N_FRAMES
-    _same_pngs(tmp / "tnr_dec", tmp / "tnr_rec")
+    U.same_pngs(tmp / "tnr_dec", tmp / "tnr_rec", N_FRAMES)
 
 
 def test_two_gop_streams_write_the_same_bins(e2e, file_nets):
@@ -342,7 +279,7 @@ def test_two_gop_streams_write_the_same_bins(e2e, file_nets):
     tmp = e2e["tmp"]
     with _spies() as (seen, _):
         RC.encode_folder(str(tmp / "png"), str(tmp / "tnr2"), gop=GOP, nets=file_nets, gop_streams=2, tnr=SETTING)
-    assert _bins(tmp / "tnr2") == _bins(tmp / "tnr")
+    assert U.bins(tmp / "tnr2") == U.bins(tmp / "tnr")
     _handed(seen, e2e["want"], FH, FW)
 
 
@@ -350,10 +287,10 @@ def test_feature_off_gives_the_plain_bins(e2e, file_nets):
     from vcm_ts_amd import run_codec as RC
 
     tmp = e2e["tmp"]
-    plain = _bins(tmp / "plain")
+    plain = U.bins(tmp / "plain")
     assert sorted(os.listdir(tmp / "plain")) == sorted(plain)
     RC.encode_folder(str(tmp / "png"), str(tmp / "none"), gop=GOP, nets=file_nets, tnr=None)
-    assert _bins(tmp / "none") == plain and sorted(os.listdir(tmp / "none")) == sorted(plain)
+    assert U.bins(tmp / "none") == plain and sorted(os.listdir(tmp / "none")) == sorted(plain)
     with pytest.raises(ValueError, match="tnr.TNR"):
         RC.encode_folder(str(tmp / "png"), str(tmp / "never"), gop=GOP, nets=file_nets, tnr=12)
     assert not (tmp / "never").exists()
@@ -364,15 +301,15 @@ def test_command_line(e2e, file_nets, capsys):
 
     tmp = e2e["tmp"]
     RC.main(["encode", "--frames", str(tmp / "png"), "--bins", str(tmp / "cli"), "--gop", str(GOP), "--tnr", "12", "--picture-hash"])
-    assert _bins(tmp / "cli") == _bins(tmp / "tnr")
+    assert U.bins(tmp / "cli") == U.bins(tmp / "tnr")
     RC.main(["decode", "--bins", str(tmp / "cli"), "--recon", str(tmp / "cli_dec"), "--height", str(FH), "--width", str(FW),
              "--gop", str(GOP), "--verify", "strict"])
-    _same_pngs(tmp / "cli_dec", tmp / "tnr_rec")
+    U.same_pngs(tmp / "cli_dec", tmp / "tnr_rec", N_FRAMES)
     RC.main(["encode", "--frames", str(tmp / "png"), "--bins", str(tmp / "cli2"), "--gop", str(GOP), "--tnr", "6", "--tnr-floor", "32",
              "--tnr-pixel", "255"])
     with _spies() as (seen, _):
         RC.encode_folder(str(tmp / "png"), str(tmp / "api2"), gop=GOP, nets=file_nets, tnr=N.TNR(6, 32, 255))
-    assert _bins(tmp / "cli2") == _bins(tmp / "api2") and _bins(tmp / "cli2") != _bins(tmp / "tnr")
+    assert U.bins(tmp / "cli2") == U.bins(tmp / "api2") and U.bins(tmp / "cli2") != U.bins(tmp / "tnr")
     _handed(seen, R.run(e2e["pics"], (6, 32, 255), INTRA), FH, FW)
 
 
@@ -403,7 +340,7 @@ def test_report_speaks_of_the_filter_and_measures_against_the_source(reported, f
     assert all((rd["frame_tnr_mad"][t] == 0.0) == (t in INTRA) for t in range(N_FRAMES))
     assert json.loads((tmp / "tnr.json").read_text()) == rd
     assert set(rd) - set(reported["plain_rd"]) == {"tnr", "frame_tnr_held", "frame_tnr_mad"}
-    assert set(reported["plain_rd"]) <= set(rd) and sorted(os.listdir(tmp / "tnr")) == sorted(_bins(tmp / "tnr"))
+    assert set(reported["plain_rd"]) <= set(rd) and sorted(os.listdir(tmp / "tnr")) == sorted(U.bins(tmp / "tnr"))
     # PSNR and MS-SSIM are measured against the UNFILTERED source, which is not what the codec was handed
     for t in range(N_FRAMES):
         assert np.array_equal(reported["measured"][t][0, :, :RH, :FW].view(np.uint32), pics[t].view(np.uint32)), t
@@ -411,12 +348,12 @@ def test_report_speaks_of_the_filter_and_measures_against_the_source(reported, f
     assert len(rd["frame_psnr"]) == N_FRAMES and all(np.isfinite(rd["frame_psnr"]))
     # two GOP streams: the same bytes and the same figures of the filter
     _, _, rd2 = RC.encode_folder(str(tmp / "png"), str(tmp / "tnr2"), gop=GOP, nets=file_nets, gop_streams=2, report=True, tnr=SETTING)
-    assert _bins(tmp / "tnr2") == _bins(tmp / "tnr")
+    assert U.bins(tmp / "tnr2") == U.bins(tmp / "tnr")
     for key in ("tnr", "frame_tnr_held", "frame_tnr_mad", "frame_bpp"):
         assert rd2[key] == rd[key], key
     # tnr=None: the bytes and the report keys of a run without the argument
     _, _, rd0 = RC.encode_folder(str(tmp / "png"), str(tmp / "none"), gop=GOP, nets=file_nets, report=True, tnr=None)
-    assert _bins(tmp / "none") == _bins(tmp / "plain") and list(rd0) == list(reported["plain_rd"])
+    assert U.bins(tmp / "none") == U.bins(tmp / "plain") and list(rd0) == list(reported["plain_rd"])
     assert rd0["frame_bpp"] == reported["plain_rd"]["frame_bpp"]
 
 
@@ -445,5 +382,5 @@ def test_y4m_file(reported, file_nets):
     assert RC.decode_video(str(tmp / "vbins"), str(tmp / "dec.y4m")) == N_FRAMES
     assert (tmp / "dec.y4m").read_bytes() == (tmp / "enc.y4m").read_bytes()
     RC.encode_video(str(tmp / "src.y4m"), str(tmp / "vplain"), gop=GOP, nets=file_nets)
-    assert _bins(tmp / "vplain") != _bins(tmp / "vbins")
+    assert U.bins(tmp / "vplain") != U.bins(tmp / "vbins")
     assert (tmp / "vplain" / "sequence.json").read_text() == (tmp / "vbins" / "sequence.json").read_text()

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_util as U
 from tests import yuv_ref as R
 from vcm_ts_amd import yuv as Y
 
@@ -41,10 +42,6 @@ def _host_planes(frame, h, w):
     return R.from_i420(a.view(np.uint16) if a.dtype == np.int16 else a, h, w)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
 # ------------------------------------------------------------------------------------------------------------ K1, K2
 @pytest.mark.parametrize("kind", ["gamut", "random"])
 @pytest.mark.parametrize("case", CASES, ids=IDS)
@@ -59,14 +56,14 @@ def test_k1_yuv420_to_rgb_unrounded(case, kind):
     want32, want64 = R.to_rgb(*planes, dtype=np.float32, **col), R.to_rgb(*planes, dtype=np.float64, **col)
     err = float(np.abs(got[:, :h, :w].astype(np.float64) - want64).max())
     print(name, kind, "max |gpu - fp64|", err, " fp32 restatement", float(np.abs(want32.astype(np.float64) - want64).max()),
-          " bit mismatches", int((_bits(got[:, :h, :w]) != _bits(want32)).sum()))
-    assert np.array_equal(_bits(got[:, :h, :w]), _bits(want32))
+          " bit mismatches", int((U.f32_bits(got[:, :h, :w]) != U.f32_bits(want32)).sum()))
+    assert np.array_equal(U.f32_bits(got[:, :h, :w]), U.f32_bits(want32))
     assert err <= CAP_RGB
     pad = got.copy()
     pad[:, :h, :w] = 0
-    assert not _bits(pad).any()  # the padding is exactly +0.0
+    assert not U.f32_bits(pad).any()  # the padding is exactly +0.0
     plain = Y.yuv420_to_rgb(_dev_frame(planes, col["depth"]), h, w, _spec(col), pad=False)
-    assert tuple(plain.shape) == (1, 3, h, w) and np.array_equal(_bits(plain.cpu().numpy()[0]), _bits(want32))
+    assert tuple(plain.shape) == (1, 3, h, w) and np.array_equal(U.f32_bits(plain.cpu().numpy()[0]), U.f32_bits(want32))
 
 
 @pytest.mark.parametrize("kind", ["gamut", "random"])
@@ -76,11 +73,11 @@ def test_k2_quantize8(case, kind):
     planes = R.case_planes(name, h, w, col, kind)
     got = Y.yuv420_to_rgb(_dev_frame(planes, col["depth"]), h, w, _spec(col), quantize8=True).cpu().numpy()[0]
     want32 = R.to_rgb(*planes, dtype=np.float32, quantize8=True, **col)
-    assert np.array_equal(_bits(got[:, :h, :w]), _bits(want32))
+    assert np.array_equal(U.f32_bits(got[:, :h, :w]), U.f32_bits(want32))
     table = np.arange(256, dtype=np.float32) / 255.0
-    assert np.isin(_bits(got), _bits(table)).all()  # padding included: 0.0 is T[0]
+    assert np.isin(U.f32_bits(got), U.f32_bits(table)).all()  # padding included: 0.0 is T[0]
     codes = np.rint(got[:, :h, :w].astype(np.float64) * 255.0)
-    assert np.array_equal(_bits(table[codes.astype(np.int64)]), _bits(got[:, :h, :w]))
+    assert np.array_equal(U.f32_bits(table[codes.astype(np.int64)]), U.f32_bits(got[:, :h, :w]))
     d = np.abs(codes - R.to_rgb(*planes, dtype=np.float64, quantize8=True, **col))
     print(name, kind, "codes differing from fp64", int((d != 0).sum()), "of", d.size)
     assert d.max() <= 1 and (d != 0).sum() <= CAP_CODES * d.size
@@ -99,9 +96,9 @@ def test_k1_strided_planes_and_odd_output_sizes():
     for size in (None, (67, 131), (70, 133), (128, 192)):
         got = Y.planes_to_rgb(*views, Y.ColorSpec(), size).cpu().numpy()[0]
         assert got.shape[1:] == (size or (h, w))
-        assert np.array_equal(_bits(got[:, :h, :w]), _bits(want))
+        assert np.array_equal(U.f32_bits(got[:, :h, :w]), U.f32_bits(want))
         got[:, :h, :w] = 0
-        assert not _bits(got).any()
+        assert not U.f32_bits(got).any()
     with pytest.raises(ValueError):
         Y.planes_to_rgb(views[0], views[1], views[2][:, ::2], Y.ColorSpec())
     with pytest.raises(ValueError):
@@ -225,10 +222,6 @@ def _write_source(path, seed, n, h, w, depth=8, chroma=None, **col):
     return frames
 
 
-def _bins(folder):
-    return {n: open(os.path.join(folder, n), "rb").read() for n in sorted(os.listdir(folder)) if n.endswith(".bin")}
-
-
 def test_e1_video_path_codes_the_same_bytes_as_the_png_path(tmp_path):
     from PIL import Image
 
@@ -243,17 +236,17 @@ def test_e1_video_path_codes_the_same_bytes_as_the_png_path(tmp_path):
     for t, p in enumerate(planes):
         x = Y.yuv420_to_rgb(_dev_frame(p, 8), h, w, Y.ColorSpec(), pad=False, quantize8=True)
         u8 = torch.round(x[0] * 255.0).to(torch.uint8).permute(1, 2, 0).cpu().numpy()
-        assert np.array_equal(_bits(u8.astype(np.float32) / 255.0), _bits(x[0].permute(1, 2, 0).cpu().numpy()))
+        assert np.array_equal(U.f32_bits(u8.astype(np.float32) / 255.0), U.f32_bits(x[0].permute(1, 2, 0).cpu().numpy()))
         Image.fromarray(u8).save(png / f"im{t + 1:05d}.png")
     bits_f, size_f = RC.encode_folder(str(png), str(tmp_path / "bf"), gop=gop, gop_streams=2)
     assert size_v == size_f == (h, w) and bits_v == bits_f and len(bits_v) == n
-    a, b = _bins(tmp_path / "bv"), _bins(tmp_path / "bf")
+    a, b = U.bins(tmp_path / "bv"), U.bins(tmp_path / "bf")
     assert sorted(a) == sorted(b) == [f"im{t + 1:05d}.bin" for t in range(n)]
     for name in a:
         assert a[name] == b[name], name
     # without quantize8 the codec sees the unrounded floats: other pictures, other bytes
     bits_u, _ = RC.encode_video(str(tmp_path / "src.y4m"), str(tmp_path / "bu"), gop=gop, gop_streams=2)
-    assert _bins(tmp_path / "bu") != a and len(bits_u) == n
+    assert U.bins(tmp_path / "bu") != a and len(bits_u) == n
 
 
 def _round_trip(tmp_path, h, w, n=6, gop=4, depth=8, chroma=None, coder="host", **col):
@@ -329,7 +322,7 @@ def test_e4_report_has_sample_domain_psnr(tmp_path):
     plain_bits, _ = RC.encode_video(str(src), str(tmp_path / "plain"), gop=gop, gop_streams=2)
     bits, size, rd = RC.encode_video(str(src), str(tmp_path / "rep"), recon_video=str(tmp_path / "r.y4m"), gop=gop, gop_streams=2,
                                      report=str(tmp_path / "rd.json"))
-    assert bits == plain_bits and _bins(tmp_path / "rep") == _bins(tmp_path / "plain")
+    assert bits == plain_bits and U.bins(tmp_path / "rep") == U.bins(tmp_path / "plain")
     assert json.loads((tmp_path / "rd.json").read_text()) == json.loads(json.dumps(rd))
     _, fr_src = R.read_y4m(str(src))
     _, fr_rec = R.read_y4m(str(tmp_path / "r.y4m"))
@@ -376,4 +369,4 @@ def test_command_line_round_trip_without_pil(tmp_path):
     r = run("encode", "--video", str(tmp_path / "x.yuv"), "--size", f"{w}x{h}", "--fps", "30", "--bins", str(tmp_path / "B2"),
             "--gop", "4")
     assert r.returncode == 0, r.stdout + r.stderr
-    assert _bins(tmp_path / "B2") == _bins(tmp_path / "B")
+    assert U.bins(tmp_path / "B2") == U.bins(tmp_path / "B")

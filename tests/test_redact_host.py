@@ -8,15 +8,12 @@ import pickle
 import numpy as np
 import pytest
 
+from tests import gpu_util as U
 from tests import redact_ref as R
 from vcm_ts_amd import redact as D
 from vcm_ts_amd import roi as X
 
 F32 = np.float32
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_table_is_the_hosts_division_and_codes_back():
@@ -35,10 +32,10 @@ def test_restatement_properties(size):
         for tile, fill in R.MODES:
             out, count = R.expected(H, W, name, grow, tile, fill)
             assert out.dtype == F32 and count.shape == R.grid(H, W)
-            assert np.array_equal(_bits(out)[:, ~Rg], _bits(pic)[:, ~Rg])  # outside R: the bits, NaN payloads included
+            assert np.array_equal(U.f32_bits(out)[:, ~Rg], U.f32_bits(pic)[:, ~Rg])  # outside R: the bits, NaN payloads included
             inside = out[:, Rg]
             k = R.code(inside)
-            assert np.array_equal(_bits(inside), _bits(R.T[k])) and np.array_equal(np.rint(F32(255.0) * R.T[k]).astype(np.int64), k)
+            assert np.array_equal(U.f32_bits(inside), U.f32_bits(R.T[k])) and np.array_equal(np.rint(F32(255.0) * R.T[k]).astype(np.int64), k)
             assert int(count.sum()) == int(Rg.sum()) and count.max(initial=0) <= 256
             assert not count[(H + 15) // 16:].any() and not count[:, (W + 15) // 16:].any()
             if tile == 0:
@@ -85,7 +82,7 @@ def test_the_grid_does_not_move_with_the_boxes():
     for box in ([3, 5, 40, 33, 0], [17, 1, 99, 70, 2], [50, 50, 51, 51, 0]):
         out, _ = R.redact(pic, [box], R.MASK, 0, 16, -1)
         Rg = R.region([box], H, W, R.MASK, 0)
-        assert np.array_equal(_bits(out)[:, Rg], _bits(whole)[:, Rg])  # a tile's value comes from ALL its pixels, in R or not
+        assert np.array_equal(U.f32_bits(out)[:, Rg], U.f32_bits(whole)[:, Rg])  # a tile's value comes from ALL its pixels, in R or not
 
 
 def test_grow_clips_and_empty_or_unselected_boxes_change_nothing():
@@ -99,11 +96,11 @@ def test_grow_clips_and_empty_or_unselected_boxes_change_nothing():
     for boxes in ([[5, 5, 5, 40, 0]], [[5, 40, 30, 40, 2]], [[30, 30, 10, 10, 0]], [[5, 5, 60, 60, 1]], [[5, 5, 60, 60, 3]]):
         for grow in (0, 200):
             out, count = R.redact(pic, boxes, R.MASK, grow, 8, -1)
-            assert np.array_equal(_bits(out), _bits(pic)) and not count.any(), (boxes, grow)
+            assert np.array_equal(U.f32_bits(out), U.f32_bits(pic)) and not count.any(), (boxes, grow)
     # an unselected box neither adds to R nor shields what a selected one covers
     a = R.redact(pic, [[10, 10, 50, 50, 0]], R.MASK, 2, 0, 9)
     b = R.redact(pic, [[0, 0, 100, 70, 1], [10, 10, 50, 50, 0], [20, 20, 30, 30, 1]], R.MASK, 2, 0, 9)
-    assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(a[1], b[1]) and int(a[1].sum()) == 44 * 44
+    assert np.array_equal(U.f32_bits(a[0]), U.f32_bits(b[0])) and np.array_equal(a[1], b[1]) and int(a[1].sum()) == 44 * 44
 
 
 def test_list_order_does_not_matter():
@@ -115,7 +112,7 @@ def test_list_order_does_not_matter():
         want = R.redact(pic, boxes, R.MASK, 3, tile, fill)
         for _ in range(3):
             got = R.redact(pic, boxes[g.permutation(len(boxes))], R.MASK, 3, tile, fill)
-            assert np.array_equal(_bits(got[0]), _bits(want[0])) and np.array_equal(got[1], want[1])
+            assert np.array_equal(U.f32_bits(got[0]), U.f32_bits(want[0])) and np.array_equal(got[1], want[1])
 
 
 def test_held_boxes_at_the_ends_and_across_gops():
@@ -212,7 +209,6 @@ def test_entry_point_refuses_on_the_host():
     for b in bad:
         v = dict(good, **b)
         assert lib.hip().dcvc_redact(*[v[k] for k in order], None) == -1, b
-    assert "dcvc_redact" in lib.REDACT_SYMBOLS and "dcvc_redact" not in lib.HIP_SYMBOLS and "dcvc_redact" in lib._SIGS
 
 
 def _root(path, frames, names=R.NAMES):

@@ -195,15 +195,6 @@ def test_video_path_does_not_import_pil():
 
 
 # ------------------------------------------------------------------------------------------------- the C entry points
-def test_library_exports_what_the_colour_header_declares():
-    text = open(os.path.join(ROOT, "include", "dcvc_hip_color.h")).read()
-    assert set(re.findall(r"\b(dcvc_[a-z0-9_]+)\s*\(", text)) == set(lib.COLOR_SYMBOLS)
-    for name in lib.COLOR_SYMBOLS:
-        assert hasattr(lib.hip(), name), name
-    assert set(lib.COLOR_SYMBOLS) <= set(lib._SIGS)  # walked by test_build's NULL / empty-argument test
-    assert not set(lib.COLOR_SYMBOLS) & set(lib.HIP_SYMBOLS)
-
-
 @pytest.mark.parametrize("matrix", ["bt709", "bt601"])
 @pytest.mark.parametrize("full", [False, True])
 @pytest.mark.parametrize("depth", [8, 10])

@@ -4,6 +4,8 @@ in float32 operation by operation, the cells' sad / held -- and the pictures and
 share.  Integer work is int64."""
 import numpy as np
 
+from tests.pixel_ref import code, grid, luma  # noqa: F401 (the tests use them as R.code, ...)
+
 F32 = np.float32
 CELL, WINDOW, FULL = 16, 5, 256
 STRIP_H, STRIP_W = 16, 256  # what one workgroup of csrc/tnr.hip owns: windows across these lines read the halo
@@ -16,23 +18,6 @@ SETTINGS = [(12, 64, 36), (6, 32, 255), (24, 128, 12)]  # (T, floor, P)
 def table(T, floor):
     """256 uint16: 256 from T on, floor + ((256 - floor) a) // T below."""
     return np.array([FULL if a >= T else floor + ((FULL - floor) * a) // T for a in range(256)], dtype=np.uint16)
-
-
-def code(v):
-    """(int) rint(255.0f * clamp01(v)) in float32; a NaN codes as 0."""
-    v = np.asarray(v, dtype=F32)
-    c = np.minimum(np.maximum(np.where(np.isnan(v), F32(0), v), F32(0)), F32(1))
-    return np.rint(F32(255.0) * c).astype(np.int64)
-
-
-def luma(pic):
-    """Y of a (3, H, W) float32 picture, int64."""
-    r, g, b = code(pic[0]), code(pic[1]), code(pic[2])
-    return (54 * r + 183 * g + 19 * b + 128) >> 8
-
-
-def grid(H, W):
-    return 4 * ((H + 63) // 64), 4 * ((W + 63) // 64)
 
 
 def cell_sums(values):

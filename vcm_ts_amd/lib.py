@@ -7,6 +7,7 @@ There is no fallback: if a library is missing the import of the product path fai
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -31,30 +32,25 @@ def _load(name):
 
 
 # ----------------------------------------------------------------------------- rans (host)
-_rans = None
-
-
+@functools.lru_cache(maxsize=None)
 def rans():
-    global _rans
-    if _rans is None:
-        L = _load("libdcvc_rans.so")
-        L.dcvc_rans_encoder_create.restype = C.c_void_p
-        L.dcvc_rans_encoder_destroy.argtypes = [C.c_void_p]
-        L.dcvc_rans_encoder_reset.argtypes = [C.c_void_p]
-        L.dcvc_rans_encoder_encode_with_indexes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-        L.dcvc_rans_encoder_flush_bound.argtypes = [C.c_void_p]
-        L.dcvc_rans_encoder_flush_bound.restype = C.c_int64
-        L.dcvc_rans_encoder_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-        L.dcvc_rans_encoder_flush.restype = C.c_int64
-        L.dcvc_rans_decoder_create.restype = C.c_void_p
-        L.dcvc_rans_decoder_destroy.argtypes = [C.c_void_p]
-        L.dcvc_rans_decoder_set_stream.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-        L.dcvc_rans_decoder_decode_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
-                                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.dcvc_pmf_to_quantized_cdf.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-        _rans = L
-    return _rans
+    L = _load("libdcvc_rans.so")
+    L.dcvc_rans_encoder_create.restype = C.c_void_p
+    L.dcvc_rans_encoder_destroy.argtypes = [C.c_void_p]
+    L.dcvc_rans_encoder_reset.argtypes = [C.c_void_p]
+    L.dcvc_rans_encoder_encode_with_indexes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dcvc_rans_encoder_flush_bound.argtypes = [C.c_void_p]
+    L.dcvc_rans_encoder_flush_bound.restype = C.c_int64
+    L.dcvc_rans_encoder_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.dcvc_rans_encoder_flush.restype = C.c_int64
+    L.dcvc_rans_decoder_create.restype = C.c_void_p
+    L.dcvc_rans_decoder_destroy.argtypes = [C.c_void_p]
+    L.dcvc_rans_decoder_set_stream.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+    L.dcvc_rans_decoder_decode_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dcvc_pmf_to_quantized_cdf.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    return L
 
 
 # ----------------------------------------------------------------------------- hip kernels
@@ -144,127 +140,143 @@ class RoiClassRec(C.Structure):  # dcvc_roi_class_t
 
 PRECISIONS = {"fp32": 0, "fp16x3": 1}
 
-_hip = None
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
-_SIGS = {
-    "dcvc_conv2d": [C.POINTER(ConvArgs), vp],
-    "dcvc_conv_pack_weights": [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp],
-    "dcvc_conv_pack_weights_paired": [vp, vp, i32, i32, vp, vp],
-    "dcvc_conv_set_lookahead": [i32],
-    "dcvc_conv2d_small": [C.POINTER(ConvArgs), vp],
-    "dcvc_conv_small_pack_weights": [vp, vp, i32, i32, i32, vp, vp, vp],
-    "dcvc_conv2d_k32": [C.POINTER(ConvArgs), vp],
-    "dcvc_conv_k32_pack_weights": [vp, vp, i32, i32, i32, vp, i32, vp, vp],
-    "dcvc_conv_k32_set_waves": [i32],
-    "dcvc_warp": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp],
-    "dcvc_up2": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp],
-    "dcvc_down2": [vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, vp],
-    "dcvc_maxpool2": [vp, i32, vp, i32, i32, i32, i32, i32, vp],
-    "dcvc_copy_channels": [vp, i32, vp, i32, i64, i32, vp],
-    "dcvc_nchw_to_nhwc": [vp, vp, i32, i32, i32, i32, i32, vp],
-    "dcvc_nhwc_to_nchw": [vp, i32, vp, i32, i32, i32, i32, i32, vp],
-    "dcvc_channel_mean": [vp, i32, vp, vp, i32, i32, i32, vp],
-    "dcvc_se_gate": [vp, vp, vp, vp, i32, i32, i32, vp],
-    "dcvc_channel_mean_finish": [vp, i32, i32, vp, i32, i32, i32, vp],
-    "dcvc_scale_channels": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp],
-    "dcvc_scale_channels_map": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp],
-    "dcvc_round_symbols": [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp],
-    "dcvc_symbols_to_nhwc": [vp, vp, i32, i32, i32, i32, i32, vp],
-    "dcvc_scale_indexes": [vp, vp, i64, vp, vp],
-    "dcvc_dual_prior_enc": [C.POINTER(DualPriorArgs), vp],
-    "dcvc_dual_prior_dec_index": [C.POINTER(DualPriorArgs), vp],
-    "dcvc_dual_prior_dec_apply": [C.POINTER(DualPriorArgs), vp],
-    "dcvc_build_scale_cdfs": [vp, i32, i32, vp, vp, vp, vp],
-    "dcvc_build_factorized_cdfs": [vp, i32, vp, vp, vp, vp],
-    "dcvc_scale_bits": [vp, vp, vp, vp, i32, i32, i64, vp],
-    "dcvc_factorized_bits": [vp, i32, vp, vp, vp, i32, i32, i32, vp],
-    "dcvc_sq_err": [vp, i32, vp, i32, vp, vp, i32, i32, i32, vp],
-    # include/dcvc_hip_grad.h
-    "dcvc_conv_pack_weights_dev": [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp],
-    "dcvc_pack_plan_create": [C.POINTER(PackJob), i32, C.POINTER(C.c_void_p)],
-    "dcvc_pack_plan_run": [vp, vp],
-    "dcvc_pack_plan_destroy": [vp],
-    "dcvc_conv_bwd_prologue": [C.POINTER(ConvBwdArgs), vp],
-    "dcvc_conv_wgrad": [C.POINTER(WgradArgs), vp],
-    "dcvc_channel_dot": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp],
-    "dcvc_mask_accumulate": [vp, i32, vp, i32, f32, vp, i32, i64, i32, vp],
-    "dcvc_add_planes": [vp, i32, vp, i32, vp, i32, i64, i32, vp],
-    "dcvc_warp_bwd": [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp],
-    "dcvc_up2_bwd": [vp, i32, vp, i32, i32, i32, i32, i32, f32, vp],
-    "dcvc_down2_bwd": [vp, i32, vp, i32, i32, i32, i32, i32, f32, vp],
-    "dcvc_maxpool2_bwd": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp],
-    "dcvc_se_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
-    "dcvc_add_channel_vec": [vp, i32, vp, f32, i32, i32, i32, vp],
-    "dcvc_scale_channels_bwd": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp],
-    "dcvc_q_finish": [vp, vp, vp, vp, vp, vp, i32, i32, vp],
-    "dcvc_dual_prior_bwd": [C.POINTER(DualPriorBwdArgs), vp],
-    "dcvc_scale_bits_bwd": [vp, vp, vp, vp, vp, i32, i32, i64, vp],
-    "dcvc_factorized_bits_bwd": [vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, vp],
-    "dcvc_sq_err_bwd": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp],
-    # include/dcvc_hip_rans.h
-    "dcvc_drans_encode": [vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp, vp],
-    "dcvc_drans_decode": [vp, i64, vp, vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp],
-    "dcvc_drans_build_lut": [vp, i32, i32, vp, vp],
-    # include/dcvc_hip_metrics.h
-    "dcvc_ms_ssim": [vp, vp, i32, i32, i32, i32, i32, i64, i32, i64, f32, i32, vp, vp, vp, vp, vp],
-    "dcvc_ms_ssim_grad": [vp, vp, i32, i32, i32, i32, i32, i64, i32, i64, f32, i32, vp, vp, vp, vp],
-    # include/dcvc_hip_color.h
-    "dcvc_color_coeffs": [i32, i32, i32, i32, vp],
-    "dcvc_yuv420_to_rgb": [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i64, i32, vp],
-    "dcvc_rgb_to_yuv420": [vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp],
-    # include/dcvc_hip_roi.h
-    "dcvc_roi_residual": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, vp, i64, i64, i32, i32, i32, i32, vp],
-    "dcvc_roi_fuse": [vp, i32, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i64, vp],
-    "dcvc_roi_sse": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, vp, i32, vp, vp],
-    "dcvc_roi_qmap": [i32, i32, vp, vp, i32, i32, vp, i32, vp, vp],
-    # include/dcvc_hip_roil.h
-    "dcvc_roil_cells": [i32, i32, vp, i32, vp, vp, i32],
-    "dcvc_roil_check": [vp, i64, vp, i32],
-    "dcvc_roil_encode": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, i64, vp, vp],
-    "dcvc_roil_decode": [vp, vp, i64, i32, i32, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32, i32, vp, vp],
-    # include/dcvc_hip_scene.h
-    "dcvc_scene_hist": [vp, i32, i64, i32, i32, vp, vp],
-    # include/dcvc_hip_bits.h
-    "dcvc_bits_map_scale": [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp],
-    "dcvc_bits_map_factorized": [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp],
-    "dcvc_bits_regions": [vp, vp, i32, vp, i32, i32, i32, vp, vp],
-    "dcvc_bits_sweep_scale": [vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp],
-    # include/dcvc_hip_hash.h
-    "dcvc_hash_pixels": [vp, i32, i64, i32, i32, vp, vp, vp],
-    "dcvc_hash_f32": [vp, i32, i64, i32, i32, i32, vp, vp, vp],
-    # include/dcvc_hip_scale.h
-    "dcvc_scale_planes": [vp, i32, i64, vp, i32, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp],
-    # include/dcvc_hip_aq.h
-    "dcvc_aq_activity": [vp, i32, i64, i32, i32, vp, vp, vp],
-    "dcvc_aq_map": [vp, vp, i32, i32, vp, vp, vp, vp, vp],
-    # include/dcvc_hip_motion.h
-    "dcvc_motion_step": [vp, i32, i64, i32, i32, vp, i32, i32, i32, i32, vp, vp],
-    # include/dcvc_hip_tnr.h
-    "dcvc_tnr_step": [vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp, i32, vp, vp, vp],
-    # include/dcvc_hip_redact.h
-    "dcvc_redact": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp],
+# One table per header of include/, in the headers' order.  A function that answers the int status is bound as the list of
+# its argtypes; the size queries and the void destructor as a tuple (restype, argtype, ...).  Everything below is derived
+# from this table, and tests/test_bindings_host.py holds it against the headers' own declarations.
+HEADERS = {
+    "dcvc_hip.h": {
+        "dcvc_conv_tile_rows": (i32, i32, i32),
+        "dcvc_conv_chan_partial_parts": (i32, i32, i32, i32, i32),
+        "dcvc_channel_mean_finish": [vp, i32, i32, vp, i32, i32, i32, vp],
+        "dcvc_conv_pack_size": (i64, i32, i32, i32, vp, C.POINTER(i32)),
+        "dcvc_conv_pack_weights": [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp],
+        "dcvc_conv_pack_size_paired": (i64, i32, i32, C.POINTER(i32)),
+        "dcvc_conv_pack_weights_paired": [vp, vp, i32, i32, vp, vp],
+        "dcvc_conv2d": [C.POINTER(ConvArgs), vp],
+        "dcvc_conv_set_lookahead": [i32],
+        "dcvc_conv_small_pack_bytes": (i64, i32, i32, i32, vp),
+        "dcvc_conv_small_pack_weights": [vp, vp, i32, i32, i32, vp, vp, vp],
+        "dcvc_conv2d_small": [C.POINTER(ConvArgs), vp],
+        "dcvc_conv_k32_pack_bytes": (i64, i32, i32, i32, vp, C.POINTER(i32)),
+        "dcvc_conv_k32_pack_weights": [vp, vp, i32, i32, i32, vp, i32, vp, vp],
+        "dcvc_conv2d_k32": [C.POINTER(ConvArgs), vp],
+        "dcvc_conv_k32_set_waves": [i32],
+        "dcvc_warp": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp],
+        "dcvc_up2": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp],
+        "dcvc_down2": [vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, vp],
+        "dcvc_maxpool2": [vp, i32, vp, i32, i32, i32, i32, i32, vp],
+        "dcvc_copy_channels": [vp, i32, vp, i32, i64, i32, vp],
+        "dcvc_nchw_to_nhwc": [vp, vp, i32, i32, i32, i32, i32, vp],
+        "dcvc_nhwc_to_nchw": [vp, i32, vp, i32, i32, i32, i32, i32, vp],
+        "dcvc_channel_mean": [vp, i32, vp, vp, i32, i32, i32, vp],
+        "dcvc_se_gate": [vp, vp, vp, vp, i32, i32, i32, vp],
+        "dcvc_scale_channels": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp],
+        "dcvc_scale_channels_map": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp],
+        "dcvc_round_symbols": [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp],
+        "dcvc_symbols_to_nhwc": [vp, vp, i32, i32, i32, i32, i32, vp],
+        "dcvc_scale_indexes": [vp, vp, i64, vp, vp],
+        "dcvc_dual_prior_enc": [C.POINTER(DualPriorArgs), vp],
+        "dcvc_dual_prior_dec_index": [C.POINTER(DualPriorArgs), vp],
+        "dcvc_dual_prior_dec_apply": [C.POINTER(DualPriorArgs), vp],
+        "dcvc_scale_bits": [vp, vp, vp, vp, i32, i32, i64, vp],
+        "dcvc_factorized_bits": [vp, i32, vp, vp, vp, i32, i32, i32, vp],
+        "dcvc_sq_err": [vp, i32, vp, i32, vp, vp, i32, i32, i32, vp],
+        "dcvc_cdf_table_cols": (i32,),
+        "dcvc_build_scale_cdfs": [vp, i32, i32, vp, vp, vp, vp],
+        "dcvc_build_factorized_cdfs": [vp, i32, vp, vp, vp, vp],
+        "dcvc_hip_version": (C.c_char_p,),
+    },
+    "dcvc_hip_grad.h": {
+        "dcvc_conv_pack_weights_dev": [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp],
+        "dcvc_pack_plan_create": [C.POINTER(PackJob), i32, C.POINTER(C.c_void_p)],
+        "dcvc_pack_plan_run": [vp, vp],
+        "dcvc_pack_plan_destroy": (None, vp),
+        "dcvc_conv_bwd_prologue": [C.POINTER(ConvBwdArgs), vp],
+        "dcvc_conv_wgrad_scratch_min": (i64, i32, i32, i32),
+        "dcvc_conv_wgrad": [C.POINTER(WgradArgs), vp],
+        "dcvc_channel_dot": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp],
+        "dcvc_mask_accumulate": [vp, i32, vp, i32, f32, vp, i32, i64, i32, vp],
+        "dcvc_add_planes": [vp, i32, vp, i32, vp, i32, i64, i32, vp],
+        "dcvc_warp_bwd": [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp],
+        "dcvc_up2_bwd": [vp, i32, vp, i32, i32, i32, i32, i32, f32, vp],
+        "dcvc_down2_bwd": [vp, i32, vp, i32, i32, i32, i32, i32, f32, vp],
+        "dcvc_maxpool2_bwd": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp],
+        "dcvc_se_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+        "dcvc_add_channel_vec": [vp, i32, vp, f32, i32, i32, i32, vp],
+        "dcvc_scale_channels_bwd": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp],
+        "dcvc_q_finish": [vp, vp, vp, vp, vp, vp, i32, i32, vp],
+        "dcvc_dual_prior_bwd": [C.POINTER(DualPriorBwdArgs), vp],
+        "dcvc_scale_bits_bwd": [vp, vp, vp, vp, vp, i32, i32, i64, vp],
+        "dcvc_factorized_bits_bwd": [vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, vp],
+        "dcvc_sq_err_bwd": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp],
+    },
+    "dcvc_hip_rans.h": {
+        "dcvc_drans_default_lanes": (i32, i64),
+        "dcvc_drans_scratch_words": (i64, i64, i32),
+        "dcvc_drans_build_lut": [vp, i32, i32, vp, vp],
+        "dcvc_drans_encode": [vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp, vp],
+        "dcvc_drans_decode": [vp, i64, vp, vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp],
+    },
+    "dcvc_hip_metrics.h": {
+        "dcvc_ms_ssim": [vp, vp, i32, i32, i32, i32, i32, i64, i32, i64, f32, i32, vp, vp, vp, vp, vp],
+        "dcvc_ms_ssim_grad": [vp, vp, i32, i32, i32, i32, i32, i64, i32, i64, f32, i32, vp, vp, vp, vp],
+        "dcvc_ms_ssim_workspace_bytes": (i64, i32, i32, i32, i32, i32),
+    },
+    "dcvc_hip_color.h": {
+        "dcvc_color_coeffs": [i32, i32, i32, i32, vp],
+        "dcvc_yuv420_to_rgb": [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i64, i32, vp],
+        "dcvc_rgb_to_yuv420": [vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp],
+    },
+    "dcvc_hip_roi.h": {
+        "dcvc_roi_residual": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, vp, i64, i64, i32, i32, i32, i32, vp],
+        "dcvc_roi_fuse": [vp, i32, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i64, vp],
+        "dcvc_roi_sse": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, vp, i32, vp, vp],
+        "dcvc_roi_qmap": [i32, i32, vp, vp, i32, i32, vp, i32, vp, vp],
+    },
+    "dcvc_hip_roil.h": {
+        "dcvc_roil_cells": [i32, i32, vp, i32, vp, vp, i32],
+        "dcvc_roil_check": [vp, i64, vp, i32],
+        "dcvc_roil_encode": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, i64, vp, vp],
+        "dcvc_roil_decode": [vp, vp, i64, i32, i32, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32, i32, vp, vp],
+    },
+    "dcvc_hip_scene.h": {"dcvc_scene_hist": [vp, i32, i64, i32, i32, vp, vp]},
+    "dcvc_hip_bits.h": {
+        "dcvc_bits_map_scale": [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp],
+        "dcvc_bits_map_factorized": [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp],
+        "dcvc_bits_regions": [vp, vp, i32, vp, i32, i32, i32, vp, vp],
+        "dcvc_bits_sweep_scale": [vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp],
+    },
+    "dcvc_hip_hash.h": {
+        "dcvc_hash_pixels": [vp, i32, i64, i32, i32, vp, vp, vp],
+        "dcvc_hash_f32": [vp, i32, i64, i32, i32, i32, vp, vp, vp],
+    },
+    "dcvc_hip_scale.h": {"dcvc_scale_planes": [vp, i32, i64, vp, i32, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]},
+    "dcvc_hip_aq.h": {
+        "dcvc_aq_activity": [vp, i32, i64, i32, i32, vp, vp, vp],
+        "dcvc_aq_map": [vp, vp, i32, i32, vp, vp, vp, vp, vp],
+    },
+    "dcvc_hip_motion.h": {"dcvc_motion_step": [vp, i32, i64, i32, i32, vp, i32, i32, i32, i32, vp, vp]},
+    "dcvc_hip_tnr.h": {"dcvc_tnr_step": [vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp, i32, vp, vp, vp]},
+    "dcvc_hip_redact.h": {"dcvc_redact": [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp]},
 }
 
-# include/dcvc_hip_metrics.h (same library; listed apart because HIP_SYMBOLS is what the three kernel headers declare)
-METRICS_SYMBOLS = ["dcvc_ms_ssim", "dcvc_ms_ssim_grad", "dcvc_ms_ssim_workspace_bytes"]
-COLOR_SYMBOLS = ["dcvc_color_coeffs", "dcvc_yuv420_to_rgb", "dcvc_rgb_to_yuv420"]  # include/dcvc_hip_color.h
-ROI_SYMBOLS = ["dcvc_roi_residual", "dcvc_roi_fuse", "dcvc_roi_sse", "dcvc_roi_qmap"]  # include/dcvc_hip_roi.h
-ROIL_SYMBOLS = ["dcvc_roil_cells", "dcvc_roil_check", "dcvc_roil_encode", "dcvc_roil_decode"]  # include/dcvc_hip_roil.h
-SCENE_SYMBOLS = ["dcvc_scene_hist"]  # include/dcvc_hip_scene.h
-BITS_SYMBOLS = ["dcvc_bits_map_scale", "dcvc_bits_map_factorized", "dcvc_bits_regions",
-                "dcvc_bits_sweep_scale"]  # include/dcvc_hip_bits.h
-HASH_SYMBOLS = ["dcvc_hash_pixels", "dcvc_hash_f32"]  # include/dcvc_hip_hash.h
+
+def _signature(entry):  # (restype, argtypes) of a table entry
+    return (entry[0], list(entry[1:])) if isinstance(entry, tuple) else (C.c_int, entry)
+
+
+# every function of libdcvc_hip.so, and the argtypes of those that answer a status (or nothing: the void destructor)
+ALL_HIP_SYMBOLS = [name for funcs in HEADERS.values() for name in funcs]
+_SIGS = {name: _signature(e)[1] for funcs in HEADERS.values() for name, e in funcs.items() if isinstance(e, list) or e[0] is None}
+# the three kernel headers share HIP_SYMBOLS; every feature header has a list of its own, in the table's order
+_CORE = ("dcvc_hip.h", "dcvc_hip_grad.h", "dcvc_hip_rans.h")
+HIP_SYMBOLS = sorted(name for h in _CORE for name in HEADERS[h])
+(METRICS_SYMBOLS, COLOR_SYMBOLS, ROI_SYMBOLS, ROIL_SYMBOLS, SCENE_SYMBOLS, BITS_SYMBOLS, HASH_SYMBOLS, SCALE_SYMBOLS, AQ_SYMBOLS,
+ MOTION_SYMBOLS, TNR_SYMBOLS, REDACT_SYMBOLS) = (list(funcs) for h, funcs in HEADERS.items() if h not in _CORE)
 HASH_CONSTANTS = ["dcvc_hash_chunk_bytes", "dcvc_hash_block_bytes", "dcvc_hash_scratch_bytes"]  # (int32 data symbols)
-SCALE_SYMBOLS = ["dcvc_scale_planes"]  # include/dcvc_hip_scale.h
-AQ_SYMBOLS = ["dcvc_aq_activity", "dcvc_aq_map"]  # include/dcvc_hip_aq.h
-MOTION_SYMBOLS = ["dcvc_motion_step"]  # include/dcvc_hip_motion.h
-TNR_SYMBOLS = ["dcvc_tnr_step"]  # include/dcvc_hip_tnr.h
-REDACT_SYMBOLS = ["dcvc_redact"]  # include/dcvc_hip_redact.h
-HIP_SYMBOLS = sorted([s for s in _SIGS if s not in METRICS_SYMBOLS + COLOR_SYMBOLS + ROI_SYMBOLS + ROIL_SYMBOLS + SCENE_SYMBOLS + BITS_SYMBOLS + HASH_SYMBOLS + SCALE_SYMBOLS + AQ_SYMBOLS + MOTION_SYMBOLS + TNR_SYMBOLS + REDACT_SYMBOLS] +
-                     ["dcvc_cdf_table_cols", "dcvc_conv_pack_size", "dcvc_conv_pack_size_paired", "dcvc_conv_small_pack_bytes", "dcvc_conv_k32_pack_bytes", "dcvc_conv_tile_rows", "dcvc_conv_chan_partial_parts", "dcvc_hip_version", "dcvc_conv_wgrad_scratch_min",
-                      "dcvc_drans_default_lanes", "dcvc_drans_scratch_words"])
-RANS_SYMBOLS = [
+RANS_SYMBOLS = [  # include/dcvc_rans.h (libdcvc_rans.so, bound in rans() above)
     "dcvc_rans_encoder_create", "dcvc_rans_encoder_destroy", "dcvc_rans_encoder_reset",
     "dcvc_rans_encoder_encode_with_indexes", "dcvc_rans_encoder_flush_bound", "dcvc_rans_encoder_flush",
     "dcvc_rans_decoder_create", "dcvc_rans_decoder_destroy", "dcvc_rans_decoder_set_stream",
@@ -272,40 +284,14 @@ RANS_SYMBOLS = [
 ]
 
 
+@functools.lru_cache(maxsize=None)
 def hip():
-    global _hip
-    if _hip is None:
-        L = _load("libdcvc_hip.so")
-        for name, sig in _SIGS.items():
+    L = _load("libdcvc_hip.so")
+    for funcs in HEADERS.values():
+        for name, entry in funcs.items():
             fn = getattr(L, name)
-            fn.argtypes = sig
-            fn.restype = C.c_int
-        L.dcvc_pack_plan_destroy.restype = None
-        L.dcvc_conv_pack_size.argtypes = [i32, i32, i32, vp, C.POINTER(i32)]
-        L.dcvc_conv_pack_size.restype = i64
-        L.dcvc_conv_pack_size_paired.argtypes = [i32, i32, C.POINTER(i32)]
-        L.dcvc_conv_pack_size_paired.restype = i64
-        L.dcvc_cdf_table_cols.argtypes = []
-        L.dcvc_cdf_table_cols.restype = i32
-        L.dcvc_conv_chan_partial_parts.argtypes = [i32, i32, i32, i32]
-        L.dcvc_conv_chan_partial_parts.restype = i32
-        L.dcvc_conv_small_pack_bytes.argtypes = [i32, i32, i32, vp]
-        L.dcvc_conv_small_pack_bytes.restype = i64
-        L.dcvc_conv_tile_rows.argtypes = [i32, i32]
-        L.dcvc_conv_tile_rows.restype = i32
-        L.dcvc_conv_k32_pack_bytes.argtypes = [i32, i32, i32, vp, C.POINTER(i32)]
-        L.dcvc_conv_k32_pack_bytes.restype = i64
-        L.dcvc_hip_version.restype = C.c_char_p
-        L.dcvc_conv_wgrad_scratch_min.argtypes = [i32, i32, i32]
-        L.dcvc_conv_wgrad_scratch_min.restype = i64
-        L.dcvc_drans_default_lanes.argtypes = [i64]
-        L.dcvc_drans_default_lanes.restype = i32
-        L.dcvc_drans_scratch_words.argtypes = [i64, i32]
-        L.dcvc_drans_scratch_words.restype = i64
-        L.dcvc_ms_ssim_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
-        L.dcvc_ms_ssim_workspace_bytes.restype = i64
-        _hip = L
-    return _hip
+            fn.restype, fn.argtypes = _signature(entry)
+    return L
 
 
 def hash_constant(name):
