@@ -23,7 +23,7 @@
     python -m vcm_ts_amd.run_codec boxes (--frames DIR | --video FILE [--size WxH]) --out ROOT --threshold T [--learn KB KF]
                                          [--min-pixels P] [--grow G] [--min-cells C] [--max-boxes N]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT [--motion-border N] [--motion-q F]
-    python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P]
+    python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P] [--tnr-search R [--tnr-penalty L]]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT --redact NAME [NAME ...] (--redact-tile N | --redact-fill K)
                                               [--redact-grow G] [--redact-hold N] [--redact-restorable]
 
@@ -84,8 +84,11 @@ With --tnr T (1 .. 64 luma codes) the codec is handed a temporally filtered pict
 blended with the previous filtered picture wherever their luma differs by fewer than T codes on average over a 5x5 window, the
 source itself wherever something moves.  The filter restarts at every I picture.  It is encoder side only: the .bin format is
 unchanged, no file is written and `decode` needs nothing; --report keeps measuring against the unfiltered source and gains
-`tnr`, `frame_tnr_held` and `frame_tnr_mad`.  There is no default T, --tnr-floor and --tnr-pixel are untuned placeholders, there
-is no motion compensation, and nothing is claimed about rate or quality.
+`tnr`, `frame_tnr_held` and `frame_tnr_mad`.  There is no default T, --tnr-floor and --tnr-pixel are untuned placeholders, and
+nothing is claimed about rate or quality.  Motion compensation is opt-in: with --tnr-search R (1 .. 32 pixels) every 16x16 cell
+of a P picture is searched for in the previous filtered picture (whole-pixel full search on luma SAD plus --tnr-penalty codes
+per pixel of vector length, default 4, untuned), that picture is moved cell by cell and the blend runs against the moved
+picture: three kernels per P picture.  --report then also gains `frame_tnr_moved` and `frame_tnr_mad_zero`.
 
 With --redact NAME ... (and a ROI) the codec is handed every picture with the boxes of the named classes made unreadable
 (vcm_ts_amd/redact.py: one kernel per picture that has such a box): a mosaic of N x N tiles on a picture-aligned grid
@@ -1153,7 +1156,10 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     looking at the UNFILTERED source; aq, target_bpp, roi_q, bit_map, picture_hash and base_scale simply code the filtered
     picture.  With report the dictionary gains tnr (the setting), frame_tnr_held (the fraction of the picture's pixels that
     were blended) and frame_tnr_mad (the mean absolute luma difference to the previous filtered picture, in codes), both 0.0
-    for an I picture.  None: no launch, allocation, key or byte changes.
+    for an I picture.  With tnr.search (motion compensation, opt-in) that previous picture is moved cell by cell by the
+    vectors of a block search first, and the report also gains frame_tnr_moved (the cells with a nonzero vector among the
+    cells that hold a pixel) and frame_tnr_mad_zero (frame_tnr_mad against the picture as it stood), 0.0 for an I picture.
+    None: no launch, allocation, key or byte changes.
     redact (with roi): a redact.Redact -- ROI redaction (vcm_ts_amd/redact.py).  Inside the boxes of the named
     classes (grown by redact.grow; with redact.hold also the boxes of that many pictures before and after) the picture the
     codec is handed is a mosaic of the source on a picture-aligned grid, or a solid fill: one launch per picture that has
@@ -1622,13 +1628,20 @@ def _stream_totals(steps, run):
 
 def _tnr_report_keys(tnr, filters, run, h, w):
     """--report's keys of the temporal noise prefilter: the setting, and per picture the fraction of its pixels that were
-    blended and the mean absolute luma difference to the previous filtered picture, both 0.0 for an I picture."""
+    blended and the mean absolute luma difference to the previous filtered picture, both 0.0 for an I picture.  With
+    tnr.search that picture is the motion-compensated one, and two more keys speak of the search: frame_tnr_moved, the
+    cells with a nonzero vector among the cells that hold a pixel, and frame_tnr_mad_zero, what frame_tnr_mad would have
+    been against the uncompensated picture; 0.0 for an I picture too."""
     def keys(rd, types, values):
         totals = _stream_totals(filters, run)
         order = sorted(totals)
         rd["tnr"] = tnr.to_json()
         rd["frame_tnr_held"] = [totals[g][0] / (h * w) for g in order]
         rd["frame_tnr_mad"] = [totals[g][1] / (h * w) for g in order]
+        if tnr.search is not None:  # (the totals' rows are then (held, sad, moved, zero))
+            cells = -(-h // 16) * -(-w // 16)  # the cells that hold a pixel
+            rd["frame_tnr_moved"] = [totals[g][2] / cells for g in order]
+            rd["frame_tnr_mad_zero"] = [totals[g][3] / (h * w) for g in order]
 
     return keys
 
@@ -1971,14 +1984,23 @@ def _parser():
                         "codes on average over a 5x5 window, and untouched wherever something moves; T, 1 .. 64 (no default "
                         "exists -- the right value depends on the noise).  Encoder side only: the .bin format is unchanged, no "
                         "file is written and decode needs nothing; --report keeps measuring against the unfiltered source and "
-                        "gains tnr, frame_tnr_held and frame_tnr_mad.  No motion compensation; nothing is claimed about rate or "
-                        "quality")
+                        "gains tnr, frame_tnr_held and frame_tnr_mad.  Motion compensation is opt-in (--tnr-search); nothing is "
+                        "claimed about rate or quality")
     e.add_argument("--tnr-floor", type=int, default=None, metavar="W",
                    help="with --tnr: the weight of the current picture, in 1/256ths, where nothing differs, 1 .. 255 (default 64, "
                         "an untuned placeholder)")
     e.add_argument("--tnr-pixel", type=int, default=None, metavar="P",
                    help="with --tnr: a pixel whose own luma differs by more than P codes is passed through whatever its window "
                         "says, 0 .. 255 (default min(255, 3 T), an untuned placeholder)")
+    e.add_argument("--tnr-search", type=int, default=None, metavar="R",
+                   help="with --tnr: motion-compensate the filter -- search every 16x16 cell of a P picture in the previous "
+                        "filtered picture within +-R whole pixels (luma SAD, full search on the GPU), move that picture cell by "
+                        "cell and blend against the moved picture, so that a moving object is blended with where it was; R, "
+                        "1 .. 32 (no default: without the option nothing is searched).  --report gains frame_tnr_moved and "
+                        "frame_tnr_mad_zero.  Whole-pixel vectors, no overlapped blocks")
+    e.add_argument("--tnr-penalty", type=int, default=None, metavar="L",
+                   help="with --tnr-search: what a pixel of vector length costs the search, in luma codes of the cell's SAD, "
+                        "0 .. 255 (default 4, an untuned placeholder)")
     e.add_argument("--redact", nargs="+", default=None, metavar="NAME",
                    help="with --roi-root: ROI redaction -- hand the codec every picture with the boxes of the named classes "
                         "(liplates, faces, motion) replaced on the GPU by a mosaic (--redact-tile) or a solid fill "
@@ -2142,13 +2164,18 @@ def _encode_command(ap, a):
             ap.error(f"--aq-strength / --aq-clamp: {ex}")
     if a.tnr is None and (a.tnr_floor is not None or a.tnr_pixel is not None):
         ap.error("--tnr-floor and --tnr-pixel belong to --tnr")
+    if a.tnr is None and (a.tnr_search is not None or a.tnr_penalty is not None):
+        ap.error("--tnr-search and --tnr-penalty belong to --tnr")
+    if a.tnr_search is None and a.tnr_penalty is not None:
+        ap.error("--tnr-penalty belongs to --tnr-search")
     if a.tnr is not None:
         from . import tnr as N
 
         try:
-            tnr = N.TNR(a.tnr, **({} if a.tnr_floor is None else {"floor": a.tnr_floor}), pixel=a.tnr_pixel)
+            tnr = N.TNR(a.tnr, **({} if a.tnr_floor is None else {"floor": a.tnr_floor}), pixel=a.tnr_pixel, search=a.tnr_search,
+                        **({} if a.tnr_penalty is None else {"penalty": a.tnr_penalty}))
         except ValueError as ex:
-            ap.error(f"--tnr / --tnr-floor / --tnr-pixel: {ex}")
+            ap.error(f"--tnr / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty: {ex}")
     factors = [a.plate_q, a.face_q, a.background_q] + ([a.motion_q] if motion else [])
     if a.base_scale is not None:
         from . import scale as SC

@@ -1,19 +1,25 @@
-"""A motion-adaptive temporal noise prefilter (include/dcvc_hip_tnr.h, csrc/tnr.hip) for fixed-camera content, where a
-P picture's bits are dominated by sensor noise: every P picture the codec is handed is blended with the previous filtered
-picture wherever the luma of the two stays close over a 5 x 5 window, and passed through untouched wherever something
-moves.  It is ENCODER SIDE ONLY: it replaces the picture the codec is handed and nothing else -- no side file, no change
+"""A motion-adaptive temporal noise prefilter (include/dcvc_hip_tnr.h, csrc/tnr.hip; with a motion search in front of it
+include/dcvc_hip_me.h, csrc/me.hip) for fixed-camera content, where a P picture's bits are dominated by sensor noise: every
+P picture the codec is handed is blended with the previous filtered picture wherever the luma of the two stays close over
+a 5 x 5 window, and passed through untouched wherever something moves.  It is ENCODER SIDE ONLY: it replaces the picture the codec is handed and nothing else -- no side file, no change
 of the .bin format, nothing for the decoder to know.  The arithmetic is stated in the header; tests/tnr_ref.py restates it
-in numpy.
+in numpy, tests/me_ref.py the search and the compensation.
 
-    TNR(threshold, floor=64, pixel=None)     the setting; .table() the 256 weights
+    TNR(threshold, floor=64, pixel=None, search=None, penalty=4)
+                                             the setting; .table() the 256 weights
     TnrFilter(tnr, size, device)             the state of ONE GOP stream on the device; .step(x_padded, intra)
     StreamFilter                             what TnrFilter shares with redact.Redactor: validation, pictures, totals
 
 There is deliberately NO default threshold, and `floor` and `pixel` are UNTUNED PLACEHOLDERS: no machine of the project
 holds a real video.  This is the mechanism -- filtered, coded, decoded by an unchanged decoder -- not a claim about rate
-or quality.  Moving pixels are passed through, not followed: there is no motion compensation.
+or quality.  Without `search`, moving pixels are passed through, not followed.  With search=R the filter is MOTION
+COMPENSATED (opt-in): every 16 x 16 cell of a P picture is searched for in the previous filtered picture within +-R whole
+pixels (dcvc_me_search: luma SAD plus `penalty` codes per pixel of vector length), that picture is moved cell by cell
+(dcvc_me_compensate) and the unchanged dcvc_tnr_step blends against the moved picture, so a moving object is blended with
+where it was.  `penalty` is an untuned placeholder too.  Vectors are whole pixels, blocks do not overlap, and the search
+is exhaustive on one level.
 
-The kernel runs on the caller's current stream and synchronises nothing.  There is no torch fallback: a CPU tensor is a
+The kernels run on the caller's current stream and synchronise nothing.  There is no torch fallback: a CPU tensor is a
 ValueError.
 """
 from __future__ import annotations
@@ -27,6 +33,7 @@ from .devargs import MAX_SIDE, whole
 from .roi import grid_of
 
 MAX_T, MAX_FLOOR, MAX_P, FULL = 64, 255, 255, 256
+MAX_R, MAX_LAMBDA, PENALTY = 32, 255, 4  # (DCVC_ME_MAX_R, DCVC_ME_MAX_LAMBDA; the placeholder)
 ROWS = 64  # pictures' totals kept on the device between two copies to the host
 
 
@@ -35,16 +42,26 @@ class TNR:
     """threshold T: a pixel whose 5 x 5 window differs from the previous filtered picture by T luma codes or more on
     average is passed through (1..64; no default exists).  floor: the weight of the current picture, in 1/256ths, where
     nothing differs at all (1..255); between 0 and T the weight rises linearly to 256.  pixel P: a pixel whose own luma
-    differs by more than P codes is passed through whatever its window says (0..255; None: min(255, 3 T)).  floor and
-    pixel are untuned placeholders."""
+    differs by more than P codes is passed through whatever its window says (0..255; None: min(255, 3 T)).  search R: the
+    reference of the blend is the previous filtered picture moved cell by cell by the vectors of a full search within +-R
+    pixels (1..32; None: no search, nothing moved).  penalty: what a pixel of vector length costs the search, in luma codes
+    of the cell's SAD (0..255; belongs to search).  floor, pixel and penalty are untuned placeholders."""
     threshold: int
     floor: int = 64
     pixel: int = None
+    search: int = None
+    penalty: int = PENALTY
 
     def __post_init__(self):
         object.__setattr__(self, "threshold", whole("threshold", self.threshold, 1, MAX_T))
         object.__setattr__(self, "floor", whole("floor", self.floor, 1, MAX_FLOOR))
         object.__setattr__(self, "pixel", min(MAX_P, 3 * self.threshold) if self.pixel is None else whole("pixel", self.pixel, 0, MAX_P))
+        object.__setattr__(self, "penalty", whole("penalty", self.penalty, 0, MAX_LAMBDA))
+        if self.search is None:
+            if self.penalty != PENALTY:
+                raise ValueError(f"penalty belongs to search: got penalty={self.penalty} without search")
+        else:
+            object.__setattr__(self, "search", whole("search", self.search, 1, MAX_R))
 
     def table(self):
         """wtab of dcvc_tnr_step: the weight of the current picture by the window's mean difference a = 0 .. 255, as
@@ -53,7 +70,8 @@ class TNR:
         return np.where(a >= self.threshold, FULL, self.floor + ((FULL - self.floor) * a) // self.threshold).astype(np.uint16)
 
     def to_json(self):
-        return {"threshold": self.threshold, "floor": self.floor, "pixel": self.pixel}
+        rd = {"threshold": self.threshold, "floor": self.floor, "pixel": self.pixel}
+        return rd if self.search is None else dict(rd, search=self.search, penalty=self.penalty)
 
 
 class StreamFilter:
@@ -125,7 +143,13 @@ class StreamFilter:
 class TnrFilter(StreamFilter):
     """The filter of one GOP stream: StreamFilter's two pictures, the table, and the cells' sad / held.  The filter restarts at
     every I picture, so what a GOP is coded from depends on its own pictures and the setting only.  One TnrFilter serves one
-    stream at a time.  .totals(): [(held pixels, sum of d)] of every step, (0, 0) for an I picture."""
+    stream at a time.  .totals(): [(held pixels, sum of d)] of every step, (0, 0) for an I picture.
+
+    With tnr.search the filter owns a third padded picture, the compensated reference, and the cells' mv / cost / zero; a
+    P step is then three launches on the current stream, nothing synchronised between them: dcvc_me_search(cur, ref),
+    dcvc_me_compensate(ref -> comp), dcvc_tnr_step(cur, comp -> out).  .totals(): [(held pixels, sum of d against the
+    compensated reference, cells with a nonzero vector, sum of d against the reference as it stood)], (0, 0, 0, 0) for an I
+    picture.  Without tnr.search none of this is allocated or launched."""
 
     def __init__(self, tnr, size, device, totals=True):
         import torch
@@ -133,19 +157,27 @@ class TnrFilter(StreamFilter):
         if not isinstance(tnr, TNR):
             raise ValueError(f"tnr: expected a tnr.TNR, got {type(tnr).__name__}")
         self.tnr = tnr
-        super().__init__(size, device, 2, totals)
+        if tnr.search is not None:
+            self.untouched = (0, 0, 0, 0)
+        super().__init__(size, device, len(self.untouched), totals)
         cells = self.grid[0] * self.grid[1]
         self.wtab = torch.from_numpy(tnr.table().view(np.int16)).to(self.device)  # (the bits of the uint16 table)
         self.sad = torch.empty(cells, dtype=torch.int32, device=self.device)   # (uint32 words; a cell's sum is < 2^16)
         self.held = torch.empty(cells, dtype=torch.int16, device=self.device)  # (uint16 words; a cell's count is <= 256)
         self.ref = None
+        if tnr.search is not None:
+            self.comp = torch.zeros((1, 3) + self.padded, dtype=torch.float32, device=self.device)  # (the crop is written, the padding never)
+            self.mv = torch.empty(2 * cells, dtype=torch.int16, device=self.device)   # (dy, dx) of every cell
+            self.cost = torch.empty(cells, dtype=torch.int32, device=self.device)     # (uint32 words; a cell's sum is < 2^16)
+            self.zero = torch.empty(cells, dtype=torch.int32, device=self.device)
         torch.cuda.synchronize(self.device)  # (the uploads above: a stream that uses them afterwards cannot race them)
 
     def step(self, x_padded, intra):
         """The padded picture to code in place of `x_padded`.  An I picture (intra=True) launches nothing and is returned
         itself; it becomes the next step's reference.  A P picture is one dcvc_tnr_step launch on the current stream from
         the crops of x_padded and of the previous step's result into the crop of one of the two buffers, which stays valid
-        until the step after the next."""
+        until the step after the next.  With tnr.search the search and the compensation are launched in front of it, and
+        the step blends against the compensated picture."""
         self._check(x_padded)
         t, self.n = self.n, self.n + 1
         if intra:
@@ -158,9 +190,19 @@ class TnrFilter(StreamFilter):
         (h, w), (Hp, Wp) = (self.height, self.width), self.padded
         cur, crs, cps = devargs.planar(x_padded.detach()[..., :h, :w])  # (the crops, read in place)
         ref, rrs, rps = devargs.planar(self.ref[..., :h, :w])
+        if self.tnr.search is not None:
+            devargs.launch("dcvc_me_search", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, h, w, self.tnr.search,
+                           self.tnr.penalty, self.mv.data_ptr(), self.cost.data_ptr(), self.zero.data_ptr())
+            devargs.launch("dcvc_me_compensate", self.device, ref.data_ptr(), rrs, rps, self.comp.data_ptr(), Wp, Hp * Wp, h, w,
+                           self.mv.data_ptr())
+            ref, rrs, rps = self.comp, Wp, Hp * Wp
+            self.launches += 2
         devargs.launch("dcvc_tnr_step", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, out.data_ptr(), Wp, Hp * Wp,
                        h, w, self.wtab.data_ptr(), self.tnr.pixel, self.sad.data_ptr(), self.held.data_ptr())
         self.launches += 1
-        self._keep(t, self.held, self.sad)
+        if self.tnr.search is None:
+            self._keep(t, self.held, self.sad)
+        elif self._rows is not None:  # (the cells that moved are counted only where somebody will read the count)
+            self._keep(t, self.held, self.sad, (self.mv.view(-1, 2) != 0).any(dim=1), self.zero)
         self.ref = out
         return out
