@@ -20,6 +20,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "crc_common.h"
 #include "dcvc_hip.h"
 #include "dcvc_hip_hash.h"
 #include "kernel_common.h"
@@ -35,31 +36,10 @@ const int32_t dcvc_hash_scratch_bytes = DCVC_HASH_SCRATCH_BYTES;
 
 namespace {
 
-constexpr uint32_t POLY = 0xEDB88320u, ONE = 0x80000000u;  // ONE: x^0 (bit 31 - k is the coefficient of x^k)
 constexpr int CHUNK = DCVC_HASH_CHUNK_BYTES, LANES = 256, WAVE = 64, LEVELS = 6;
 constexpr int CHUNK_WORDS = CHUNK / 4, CHUNK_PIXELS = CHUNK / 3, BATCH = 8;
 static_assert(CHUNK % 12 == 0 && DCVC_HASH_BLOCK_BYTES == LANES * CHUNK, "a chunk starts on a pixel and on a word");
 static_assert(CHUNK_WORDS % BATCH == 0 && CHUNK_PIXELS % 4 == 0 && (1 << LEVELS) == WAVE, "batches and the wave tree");
-
-// a(x) * b(x) mod P on reflected polynomials, branch-free
-__host__ __device__ constexpr uint32_t mulmod(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int k = 0; k < 32; ++k) {
-        p ^= b & (0u - ((a >> (31 - k)) & 1u));
-        b = (b >> 1) ^ (POLY & (0u - (b & 1u)));
-    }
-    return p;
-}
-
-// x^(8 n) mod P
-constexpr uint32_t x8n(uint64_t n) {
-    uint32_t out = ONE, sq = ONE >> 8;
-    for (; n; n >>= 1) {
-        if (n & 1) out = mulmod(out, sq);
-        sq = mulmod(sq, sq);
-    }
-    return out;
-}
 
 struct HashArgs {
     const float *src;

@@ -885,22 +885,36 @@ class _VideoSource:
 
 class _PngStage:
     """Output stage "PNG folder" of a file loop -- or, without a folder, nothing: put() writes the unpadded picture as
-    im%05d.png through a pool of PNG-encoding threads."""
+    im%05d.png through a pool of PNG-encoding threads.  png_device: the device the files are made on instead
+    (vcm_ts_amd/pngdev.py: two launches and one asynchronous copy per picture on the stream that made it; the threads
+    then only wait for the copy and write) -- None: the pictures are copied to the host and encoded there."""
     sums = 0  # (integer sums measure() adds to a picture's report row)
 
-    def __init__(self, path, io_workers):
-        self.path, self.io_workers, self.savers = path, io_workers, None
+    def __init__(self, path, io_workers, png_device=None):
+        if png_device is not None and not path:
+            raise ValueError("png_device belongs to recon_dir (the folder the PNGs are written to)")
+        self.path, self.io_workers, self.savers, self.png_device, self.dev = path, io_workers, None, png_device, None
 
     def open(self, size, streams=1, source=None):
         self.size = size
         if self.path:
+            if self.png_device is not None:  # (refuses by name, before any launch or file, what the kernels cannot take)
+                from . import pngdev
+
+                self.dev = pngdev.PngDevice(size, self.png_device, streams)
             os.makedirs(self.path, exist_ok=True)
             self.savers = PNGWriters(self.io_workers)
 
     def put(self, k, g, frame):
         if self.path:
             h, w = self.size
-            save_torch_image(frame[..., :h, :w], os.path.join(self.path, f"im{str(g + 1).zfill(5)}.png"), self.savers)
+            path = os.path.join(self.path, f"im{str(g + 1).zfill(5)}.png")
+            if self.dev is not None:
+                from .pngdev import save_handle
+
+                self.savers.submit(self.dev.put(k, frame), path, save_handle)
+            else:
+                save_torch_image(frame[..., :h, :w], path, self.savers)
 
     def flush(self):
         if self.savers:
@@ -1076,7 +1090,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
                   report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None, target_bpp=None,
                   q_range=None, residual_bins=None, residual_step=1, picture_hash=False, base_scale=None, aq=None, tnr=None,
-                  redact=None):
+                  redact=None, png_device=False):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -1170,10 +1184,14 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     redact (the setting) and frame_redacted (the fraction of the picture's pixels that were replaced).  residuals /
     residual_bins are taken from the unredacted source too, so those files would hold what was removed inside the boxes
     themselves: that combination is a ValueError unless redact.restorable is set.  A mosaic is not a security guarantee.
-    None: no launch, allocation, file, key or byte changes (a stale redact.json is removed)."""
+    None: no launch, allocation, file, key or byte changes (a stale redact.json is removed).
+    png_device: the PNGs of recon_dir are made on the device (vcm_ts_amd/pngdev.py; include/dcvc_hip_png.h): the same pixels
+    in other, usually somewhat larger, files, and no picture crosses to the host as float32.  A ValueError without recon_dir
+    and for a picture wider than 8191.  False: no launch, file or byte changes."""
     options = locals()
-    frames_dir, recon_dir, max_frames = (options.pop(name) for name in ("frames_dir", "recon_dir", "max_frames"))
-    return _encode_sequence(_PngSource(frames_dir, device, io_workers, max_frames), _PngStage(recon_dir, io_workers), **options)
+    frames_dir, recon_dir, max_frames, png_device = (options.pop(name) for name in ("frames_dir", "recon_dir", "max_frames", "png_device"))
+    return _encode_sequence(_PngSource(frames_dir, device, io_workers, max_frames),
+                            _PngStage(recon_dir, io_workers, device if png_device else None), **options)
 
 
 def _decode_bins(nets, bin_dir, height, width, plan, emit, q_map=None, aq=None):
@@ -1280,7 +1298,7 @@ def _decode_sequence(bin_dir, size, out, gop=None, device="cuda:0", precision=No
 
 
 def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
-                  io_workers=8, roi=None, residuals=None, residual_bins=None, verify=None, base_scale="file"):
+                  io_workers=8, roi=None, residuals=None, residual_bins=None, verify=None, base_scale="file", png_device=False):
     """roi, residuals: write video_coder.fuse_layers' picture instead of the reconstruction -- `residuals` is the decoded
     residual layer (a `.gbrp` file or a folder of im%05d.png, as encode_folder writes them) and `roi` the boxes and
     classes it was taken with.  Display side only: the decoder's reference pictures are not touched.
@@ -1308,8 +1326,9 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", 
     An aq.json beside the .bin files (encode_folder's aq=) is followed without any option: every P picture's q-scale map is
     rebuilt from the decoder's own reference picture (also in a base-only decode, from the base-size one).  Refused by
     name before any launch: an aq.json of an unknown version, with a value out of range, or whose tables this host builds
-    differently (aq.read_aq)."""
-    return _decode_sequence(bin_dir, (height, width), _PngStage(recon_dir, io_workers), gop, device, precision, i_ckpt, p_ckpt, roi,
+    differently (aq.read_aq).
+    png_device: the PNGs are made on the device, as encode_folder's png_device= makes them."""
+    return _decode_sequence(bin_dir, (height, width), _PngStage(recon_dir, io_workers, device if png_device else None), gop, device, precision, i_ckpt, p_ckpt, roi,
                             residuals, residual_bins, verify, base_scale)
 
 
@@ -1914,6 +1933,9 @@ def _parser():
     b.add_argument("--io-workers", type=int, default=8, help="host threads for PNG decoding (0: inline)")
     e.add_argument("--bins", required=True)
     e.add_argument("--recon")
+    e.add_argument("--png-device", action="store_true",
+                   help="with --recon: make the PNGs on the GPU (filter and deflate kernels; the same pixels, other files) and "
+                        "leave the host threads only the write()")
     e.add_argument("--recon-video", metavar="FILE", help="with --video: reconstructions as .y4m / .yuv")
     e.add_argument("--q", type=float, nargs=3, default=None, metavar=("I", "MV_Y", "Y"),
                    help="explicit q-scales (default 1 1 1 when no rate point is selected)")
@@ -2037,6 +2059,7 @@ def _parser():
                                                   "unfused base layer only")
     d.add_argument("--bins", required=True)
     d.add_argument("--recon", help="folder for PNGs (exactly one of --recon and --recon-video)")
+    d.add_argument("--png-device", action="store_true", help="with --recon: make the PNGs on the GPU, as encode --png-device does")
     d.add_argument("--recon-video", metavar="FILE", help=".y4m / .yuv output; size and colour from the bins' sequence.json")
     d.add_argument("--height", type=int, help="required unless sequence.json lies beside the .bin files")
     d.add_argument("--width", type=int)
@@ -2226,6 +2249,8 @@ def _encode_command(ap, a):
         ap.error("--recon-video, --size, --quantize8, --matrix, --range and --siting belong to --video")
     if a.video is not None and a.recon:
         ap.error("--recon (a PNG folder) belongs to --frames; use --recon-video with --video")
+    if a.png_device and not a.recon:
+        ap.error("--png-device belongs to --recon (the PNG folder)")
     size = fps = None
     if a.video is not None:
         from . import yuv as Y
@@ -2277,7 +2302,7 @@ def _encode_command(ap, a):
             spec = reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting)
             bits, size, *rd = encode_video(reader, a.bins, a.recon_video, spec=spec, quantize8=a.quantize8, **options)
     else:
-        bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, **options)
+        bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, png_device=a.png_device, **options)
     if rd:
         yuv_part = f", PSNR-YUV {rd[0]['ave_all_frame_psnr_yuv']:.3f} dB" if "ave_all_frame_psnr_yuv" in rd[0] else ""
         print(f"PSNR {rd[0]['ave_all_frame_psnr']:.3f} dB, MS-SSIM {rd[0]['ave_all_frame_msssim']:.5f}{yuv_part} -> {a.report}")
@@ -2300,6 +2325,8 @@ def _decode_command(ap, a):
                                       ((read_sequence_info(a.bins) or {}).get("roi") or {}).get("classes", [])})
     if (a.recon is None) == (a.recon_video is None):
         ap.error("give exactly one of --recon and --recon-video")
+    if a.png_device and a.recon is None:
+        ap.error("--png-device belongs to --recon (the PNG folder)")
     info = read_sequence_info(a.bins)
     if info is None and (a.height is None or a.width is None):
         ap.error(f"--height and --width are required (no {SEQUENCE_JSON} beside the .bin files)")
@@ -2322,7 +2349,8 @@ def _decode_command(ap, a):
         height, width = a.height or info["height"], a.width or info["width"]
         n = decode_folder(a.bins, a.recon, height, width, a.gop or (info or {}).get("gop"), a.device, a.precision,
                           a.i_ckpt, a.p_ckpt, io_workers=a.io_workers, roi=roi, residuals=a.residuals,
-                          residual_bins=a.residual_bins, verify=a.verify, base_scale=None if a.base_only else "file")
+                          residual_bins=a.residual_bins, verify=a.verify, base_scale=None if a.base_only else "file",
+                          png_device=a.png_device)
     print(f"{n} pictures decoded")
 
 
