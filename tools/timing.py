@@ -51,7 +51,8 @@ def event_us(fn, launches, warmup, sync="device"):
     (the records under profiles/ were made by these rules, and they are not the same rule):
 
         aq_time kernels                           warmup=min(launches, 32)  sync="device"
-        motion_time, tnr_time, redact_time        warmup=5                  sync="event"
+        motion_time, tnr_time, redact_time,       warmup=5                  sync="event"
+        grain_time kernels
         picturehash_time, scale_time kernels      warmup=5                  sync="event"
         scenecut_time kernels                     warmup=0                  sync="event", launches=BATCH (20); the tool warms every
                                                                             variant up 3 times and synchronises before round 1

@@ -24,6 +24,8 @@
                                          [--min-pixels P] [--grow G] [--min-cells C] [--max-boxes N]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT [--motion-border N] [--motion-q F]
     python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P] [--tnr-search R [--tnr-penalty L]]
+    python -m vcm_ts_amd.run_codec encode ... --tnr T --grain [--grain-min-samples N]
+    python -m vcm_ts_amd.run_codec decode ... --grain [PERCENT]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT --redact NAME [NAME ...] (--redact-tile N | --redact-fill K)
                                               [--redact-grow G] [--redact-hold N] [--redact-restorable]
 
@@ -89,6 +91,14 @@ nothing is claimed about rate or quality.  Motion compensation is opt-in: with -
 of a P picture is searched for in the previous filtered picture (whole-pixel full search on luma SAD plus --tnr-penalty codes
 per pixel of vector length, default 4, untuned), that picture is moved cell by cell and the blend runs against the moved
 picture: three kernels per P picture.  --report then also gains `frame_tnr_moved` and `frame_tnr_mad_zero`.
+
+With --tnr T --grain the encoder also measures what the filter took out of every P picture (vcm_ts_amd/grain.py: one more
+kernel per P picture, right behind the filter's) and leaves grain.json beside the .bin files: per GOP eight strengths by
+intensity, two taps and the sample counts.  Every other output is that of an encode without the option.  `decode --grain
+[PERCENT]` (1 .. 200, default 100) re-synthesises noise of that strength and shape on every P picture it writes: opt-in, never
+followed silently, display side only.  --verify keeps checking the ungrained picture; a grained folder deliberately does not
+pass `verify`, whose digests are of the ungrained picture.  P pictures only, achromatic, a 3-tap separable shape, per-GOP
+parameters; --grain-min-samples is an untuned placeholder and nothing is claimed about rate, quality or detection.
 
 With --redact NAME ... (and a ROI) the codec is handed every picture with the boxes of the named classes made unreadable
 (vcm_ts_amd/redact.py: one kernel per picture that has such a box): a mosaic of N x N tiles on a picture-aligned grid
@@ -995,12 +1005,12 @@ class _VideoStage:
 def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
                      coder="host", io_workers=8, nets=None, gop_streams=1, report=None, roi=None, residuals=None, scenecut=None,
                      min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1,
-                     picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None):
+                     picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None, grain=None):
     """The one encode loop: the pictures of `source` (a _PngSource or a _VideoSource, opened here and closed on every exit)
     through tnr, redact and the base layer's scaling into an _EncodeRun, and every reconstruction through the base layer's
     up-scaling to the residual outputs, the report and `out` (a _PngStage or a _VideoStage).  The options are
     encode_folder's.  Refusals in this order, all before any launch or file: the residual layer's arguments, roi_q, aq, tnr,
-    redact, bit_map; then what the source refuses about its files; the rate control's, base_scale, the scene cut's options,
+    grain, redact, bit_map; then what the source refuses about its files; the rate control's, base_scale, the scene cut's options,
     the boxes of every frame, the redaction's merged lists."""
     from . import aq as A
     from . import scale as SC
@@ -1009,6 +1019,7 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
     _roiq_args(roi, roi_q)
     _aq_args(aq)
     _tnr_args(tnr)
+    _grain_args(grain, tnr)
     _redact_args(redact, roi, residuals, residual_bins)
     bit_dir = _bitmap_args(bit_map, report)
     try:
@@ -1030,6 +1041,7 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
         rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
         filters = _tnr_filters(tnr, run, (h, w), report)
+        meters = _grain_meters(grain, bin_dir, run, (h, w))
         _write_redact(bin_dir, redact)
         redaction = _Redaction(redact, layer, held, run, report) if redact is not None else None
         out.open((h, w), run.K, source)
@@ -1042,7 +1054,9 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
                 if compared:
                     current[k] = (x, aux)  # (what on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
                 if filters:  # (the codec sees the filtered picture; current[k] stays the unfiltered one)
-                    x = filters[k].step(x, t in intra)
+                    src, x = x, filters[k].step(x, t in intra)
+                    if meters:  # (what the filter took out of this picture, right behind it on the same stream)
+                        meters[k].step(src, filters[k], run.global_index(k, t), t in intra)
                 if redaction:  # (after the filter, whose own state stays unredacted; current[k] stays the unredacted one)
                     x = redaction.step(k, run.global_index(k, t), x, t in intra)
                 yield base.down(x) if base else x
@@ -1070,6 +1084,8 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
             run.encode(frames, q, on_recon if (out.path or compared) else None,
                        (lambda g: layer.q_map(g, roi_q)) if roi_q is not None else None, aq)
             out.flush()
+            if meters:
+                _write_grain(bin_dir, grain, tnr, meters)
             failed = False
         finally:
             out.close(failed)
@@ -1090,7 +1106,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
                   report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None, target_bpp=None,
                   q_range=None, residual_bins=None, residual_step=1, picture_hash=False, base_scale=None, aq=None, tnr=None,
-                  redact=None, png_device=False):
+                  redact=None, png_device=False, grain=None):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -1187,7 +1203,13 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     None: no launch, allocation, file, key or byte changes (a stale redact.json is removed).
     png_device: the PNGs of recon_dir are made on the device (vcm_ts_amd/pngdev.py; include/dcvc_hip_png.h): the same pixels
     in other, usually somewhat larger, files, and no picture crosses to the host as float32.  A ValueError without recon_dir
-    and for a picture wider than 8191.  False: no launch, file or byte changes."""
+    and for a picture wider than 8191.  False: no launch, file or byte changes.
+    grain: a grain.Grain, with tnr= -- film-grain synthesis (vcm_ts_amd/grain.py): right behind the filter's
+    launch, one dcvc_grain_measure per P picture adds up what the filter took out of the cells it blended throughout, and
+    grain.json beside the .bin files keeps, per GOP, eight strengths by intensity, two taps and the sample counts -- the
+    same file with one or two GOP streams.  decode_folder(grain=) synthesises from it; nothing else reads it.  The .bin
+    files, recon_dir, the report and hashes.json are those of an encode without it.  Without tnr= a ValueError.  None: no
+    launch, allocation, key or byte changes (a stale grain.json is removed)."""
     options = locals()
     frames_dir, recon_dir, max_frames, png_device = (options.pop(name) for name in ("frames_dir", "recon_dir", "max_frames", "png_device"))
     return _encode_sequence(_PngSource(frames_dir, device, io_workers, max_frames),
@@ -1242,10 +1264,37 @@ def _verify_args(verify, bin_dir, plan, height, width):
     return record, mode
 
 
+def _decode_grain(grain, bin_dir, plan, residuals, residual_bins, base_scale):
+    """grain= of a decode loop (None, or the per cent of the measured strength) -> None, or (the folder's checked grain.json
+    record, per cent); refused by name before any GPU work."""
+    if grain is None:
+        return None
+    from . import grain as GR
+    from .devargs import whole
+
+    percent = whole("grain", grain, 1, GR.MAX_PERCENT, "per cent of the measured strength")
+    if residuals is not None or residual_bins is not None:
+        raise NotImplementedError("grain= with residuals= / residual_bins= (--grain with --residuals / --residual-bins): inside "
+                                  "lossless boxes the source's own noise is already there, and sparing boxes is not implemented")
+    if base_scale is None:
+        raise ValueError("a base-only decode (base_scale=None, --base-only) takes no grain= (--grain): the grain was measured "
+                         "at display size")
+    return GR.read_grain(bin_dir, plan), percent
+
+
+def _grain_synth(grain, plan, shown, dev):
+    """The grain.GrainSynth of a decode loop (None without grain=: nothing is allocated)."""
+    if grain is None:
+        return None
+    from .grain import GrainSynth
+
+    return GrainSynth(grain[0], plan, shown, dev, grain[1])
+
+
 def _decode_sequence(bin_dir, size, out, gop=None, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, roi=None,
-                     residuals=None, residual_bins=None, verify=None, base_scale="file", check=None):
+                     residuals=None, residual_bins=None, verify=None, base_scale="file", check=None, grain=None):
     """The one decode loop: the .bin files of `bin_dir`, pictures of the display `size` = (height, width), through the
-    verifier, the base layer's up-scaling and the ROI fusion into `out` (a _PngStage or a _VideoStage).  The options are
+    verifier, the base layer's up-scaling, the grain synthesis and the ROI fusion into `out` (a _PngStage or a _VideoStage).  The options are
     decode_folder's.  check(shown, coded, scaled): the caller's own refusals once the size of what is written is known.
     Every refusal comes before any launch and before `out` is opened."""
     from . import aq as A
@@ -1258,6 +1307,7 @@ def _decode_sequence(bin_dir, size, out, gop=None, device="cuda:0", precision=No
     roi_q = read_roiq(bin_dir, roi)
     aq = A.read_aq(bin_dir)  # (host work only: its refusals come here, the maps are made once every refusal has had its turn)
     record, verify = _verify_args(verify, bin_dir, plan, height, width)
+    grain = _decode_grain(grain, bin_dir, plan, residuals, residual_bins, base_scale)
     dev = torch.device(device)
     scaled, coded = _decode_scale(bin_dir, height, width, base_scale, roi, residuals, residual_bins)
     shown = (height, width) if scaled else coded  # (the size of what is written)
@@ -1272,6 +1322,7 @@ def _decode_sequence(bin_dir, size, out, gop=None, device="cuda:0", precision=No
         nets = _nets(dev, precision, i_ckpt, p_ckpt)
         checker = PH.Verifier(record, verify, plan, shown, nets[1].engine().precision, shown == (height, width)) \
             if verify != "off" else None
+        synth = _grain_synth(grain, plan, shown, dev)
         out.open(shown)
 
         def emit(t, ref_frame):
@@ -1280,6 +1331,8 @@ def _decode_sequence(bin_dir, size, out, gop=None, device="cuda:0", precision=No
                 checker.add(t, ref_frame, display=full)
             if full is not None:
                 ref_frame = full
+            if synth:  # (display side only, after the verifier: the digests and the DPB are of the ungrained picture)
+                ref_frame = synth.shown(t, ref_frame)
             # (without a ROI the padded reconstruction itself: the stage reads its top-left corner in place)
             out.put(0, t, ref_frame if fuse_roi is None else picture(t, ref_frame))
 
@@ -1298,7 +1351,8 @@ def _decode_sequence(bin_dir, size, out, gop=None, device="cuda:0", precision=No
 
 
 def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
-                  io_workers=8, roi=None, residuals=None, residual_bins=None, verify=None, base_scale="file", png_device=False):
+                  io_workers=8, roi=None, residuals=None, residual_bins=None, verify=None, base_scale="file", png_device=False,
+                  grain=None):
     """roi, residuals: write video_coder.fuse_layers' picture instead of the reconstruction -- `residuals` is the decoded
     residual layer (a `.gbrp` file or a folder of im%05d.png, as encode_folder writes them) and `roi` the boxes and
     classes it was taken with.  Display side only: the decoder's reference pictures are not touched.
@@ -1327,9 +1381,16 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", 
     rebuilt from the decoder's own reference picture (also in a base-only decode, from the base-size one).  Refused by
     name before any launch: an aq.json of an unknown version, with a value out of range, or whose tables this host builds
     differently (aq.read_aq).
-    png_device: the PNGs are made on the device, as encode_folder's png_device= makes them."""
+    png_device: the PNGs are made on the device, as encode_folder's png_device= makes them.
+    grain: None, or 1 .. 200 -- film-grain synthesis (vcm_ts_amd/grain.py) at that per cent of the strength the folder's
+    grain.json (encode_folder's grain=) measured.  OPT-IN: the file is never followed silently.  Every P picture that is
+    written is a grained copy (one dcvc_grain_apply launch, after the verifier and the base layer's up-scaling, so at display
+    size); I pictures, the DPB and the digests are untouched, so verify= keeps checking the ungrained picture, while the
+    PNGs of a grained folder deliberately do NOT pass `run_codec verify`.  Refused by name before any launch: no
+    grain.json, one of an unknown version, with a value out of range or whose GOPs are not the folder's plan, and a base-only
+    decode; with residuals= / residual_bins= a NotImplementedError."""
     return _decode_sequence(bin_dir, (height, width), _PngStage(recon_dir, io_workers, device if png_device else None), gop, device, precision, i_ckpt, p_ckpt, roi,
-                            residuals, residual_bins, verify, base_scale)
+                            residuals, residual_bins, verify, base_scale, grain=grain)
 
 
 # ------------------------------------------------------------------------------------------------- Y4M / raw YUV files
@@ -1625,6 +1686,36 @@ def _tnr_filters(tnr, run, size, report):
     return [TnrFilter(tnr, size, run.dev, totals=bool(report)) for _ in range(run.K)]
 
 
+def _grain_args(grain, tnr):
+    """grain= of an encode loop against its tnr=, refused by name before any GPU work."""
+    if grain is not None:
+        from .grain import Grain
+
+        if not isinstance(grain, Grain):
+            raise ValueError(f"grain: expected a grain.Grain, got {type(grain).__name__}")
+        if tnr is None:
+            raise ValueError("grain= needs tnr= (--grain needs --tnr): what is measured is what the prefilter took out")
+
+
+def _grain_meters(grain, bin_dir, run, size):
+    """grain= of an encode loop -> one grain.GrainMeter per GOP stream (None without: nothing is allocated).  A grain.json
+    of an earlier encode into the same folder must not describe these .bin files: ours is written when all is coded."""
+    from . import grain as GR
+
+    GR.write_grain(bin_dir, None)
+    return [GR.GrainMeter(size, run.dev) for _ in range(run.K)] if grain is not None else None
+
+
+def _write_grain(bin_dir, grain, tnr, meters):
+    """grain.json: once, when everything has been coded -- every GOP's record from its own sums, whichever stream coded it."""
+    from . import grain as GR
+
+    sums = {}
+    for m in meters:
+        sums.update(m.sums())
+    GR.write_grain(bin_dir, GR.record_of(grain, tnr, {g: GR.params(acc, grain.min_samples) for g, acc in sums.items()}))
+
+
 def _tnr_args(tnr):
     """tnr= of an encode loop, refused by name before any GPU work."""
     if tnr is not None:
@@ -1786,7 +1877,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
                  min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1,
-                 picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None):
+                 picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None, grain=None):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -1812,7 +1903,8 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     tnr: as encode_folder -- the filter comes after the colour conversion (RGB only); the YUV figures of the report stay
     against the file's own samples; sequence.json is the same with or without.
     redact: as encode_folder -- after the colour conversion and tnr (RGB only); redact.json lies beside sequence.json, which
-    is the same with or without."""
+    is the same with or without.
+    grain: as encode_folder (grain.json beside the .bin files; sequence.json is the same with or without)."""
     options = locals()
     video, recon_video = options.pop("video"), options.pop("recon_video")
     source = _VideoSource(video, device, **{name: options.pop(name) for name in ("size", "spec", "quantize8", "bit_depth", "fps",
@@ -1822,7 +1914,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
 
 def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=None, fps=None, device="cuda:0",
                  precision=None, i_ckpt=None, p_ckpt=None, roi=None, residuals=None, residual_bins=None, verify=None,
-                 base_scale="file"):
+                 base_scale="file", grain=None):
     """decode_folder's loop with the video output stage.  Size, GOP length, frame rate and colour description come from
     the sequence.json encode_video left in `bin_dir`; explicit arguments override it, and without the file height and
     width are required (gop then defaults to 32, the colour description to yuv.ColorSpec()).  Returns the picture count.
@@ -1830,7 +1922,8 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
     beside the .bin files is followed as decode_folder does.
     verify: as decode_folder (the digests are of the RGB reconstruction, before the conversion to YUV).
     base_scale: as decode_folder (None writes a video of the base size).
-    An aq.json beside the .bin files is followed as decode_folder does."""
+    An aq.json beside the .bin files is followed as decode_folder does.
+    grain: as decode_folder (the grained RGB picture is what is converted and written)."""
     from . import yuv as Y
 
     info = read_sequence_info(bin_dir) or {}
@@ -1848,7 +1941,7 @@ def decode_video(bin_dir, recon_video, height=None, width=None, gop=None, spec=N
                         interlace=info.get("interlace"), aspect=info.get("aspect"))
     # (gops.json, when encode left one, says where the I pictures are)
     return _decode_sequence(bin_dir, (height, width), stage, gop or info.get("gop"), device, precision, i_ckpt, p_ckpt, roi, residuals,
-                            residual_bins, verify, base_scale, check)
+                            residual_bins, verify, base_scale, check, grain)
 
 
 def _video_args(ap, a):
@@ -2023,6 +2116,14 @@ def _parser():
     e.add_argument("--tnr-penalty", type=int, default=None, metavar="L",
                    help="with --tnr-search: what a pixel of vector length costs the search, in luma codes of the cell's SAD, "
                         "0 .. 255 (default 4, an untuned placeholder)")
+    e.add_argument("--grain", action="store_true",
+                   help="with --tnr: film-grain synthesis, the encoder's half (vcm_ts_amd/grain.py) -- measure on the GPU what the "
+                        "prefilter took out of every P picture and leave grain.json beside the .bin files: per GOP eight "
+                        "strengths by intensity and two taps.  decode --grain synthesises from it.  Every other output is that "
+                        "of an encode without the option.  P pictures only; nothing is tuned, nothing is claimed")
+    e.add_argument("--grain-min-samples", type=int, default=None, metavar="N",
+                   help="with --grain: an intensity bin with fewer pixels than N in a GOP takes its nearest populated "
+                        "neighbour's strength (default 1024, an untuned placeholder)")
     e.add_argument("--redact", nargs="+", default=None, metavar="NAME",
                    help="with --roi-root: ROI redaction -- hand the codec every picture with the boxes of the named classes "
                         "(liplates, faces, motion) replaced on the GPU by a mosaic (--redact-tile) or a solid fill "
@@ -2051,6 +2152,14 @@ def _parser():
                         "this option as 'pixels': stop at the first picture whose 8-bit digest differs and warn once when only "
                         "the reference picture's does; strict: stop on either; warn: never stop; off: launch nothing.  "
                         "Refused without the file, except off")
+    d.add_argument("--grain", type=int, nargs="?", const=100, default=None, metavar="PERCENT",
+                   help="film-grain synthesis, the decoder's half: add to every P picture that is written noise of the strength "
+                        "and shape the folder's grain.json (encode --tnr T --grain) measured, at PERCENT of that strength, "
+                        "1 .. 200 (default 100).  Opt-in: the file is never followed without the option.  Display side only: "
+                        "--verify keeps checking the ungrained picture, and a grained folder deliberately does not pass the "
+                        "`verify` command, whose digests are of the ungrained picture.  Achromatic, a 3-tap separable shape, "
+                        "per-GOP parameters; I pictures are not grained.  Refused without a grain.json and with --base-only; "
+                        "not implemented with --residuals / --residual-bins")
     v = sub.add_parser("verify", description="Hold a folder of decoded PNGs against the `pixels` digests of a hashes.json, on "
                        "the host alone (zlib.crc32 of every picture's RGB bytes; no GPU).  For unfused base-layer PNG folders "
                        "only: a picture fused with a ROI residual layer is not the picture the digests are of.")
@@ -2199,6 +2308,18 @@ def _encode_command(ap, a):
                         **({} if a.tnr_penalty is None else {"penalty": a.tnr_penalty}))
         except ValueError as ex:
             ap.error(f"--tnr / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty: {ex}")
+    grain = None
+    if a.grain_min_samples is not None and not a.grain:
+        ap.error("--grain-min-samples belongs to --grain")
+    if a.grain:
+        from . import grain as GR
+
+        if tnr is None:
+            ap.error("--grain needs --tnr: what is measured is what the prefilter took out")
+        try:
+            grain = GR.Grain(**({} if a.grain_min_samples is None else {"min_samples": a.grain_min_samples}))
+        except ValueError as ex:
+            ap.error(f"--grain-min-samples: {ex}")
     factors = [a.plate_q, a.face_q, a.background_q] + ([a.motion_q] if motion else [])
     if a.base_scale is not None:
         from . import scale as SC
@@ -2296,7 +2417,7 @@ def _encode_command(ap, a):
                    io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report, roi=roi, residuals=a.residuals,
                    scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q, bit_map=a.bit_map, target_bpp=a.target_bpp,
                    q_range=a.q_range, residual_bins=a.residual_bins, residual_step=a.residual_step, picture_hash=a.picture_hash,
-                   base_scale=a.base_scale, aq=aq, tnr=tnr, redact=redact)
+                   base_scale=a.base_scale, aq=aq, tnr=tnr, redact=redact, grain=grain)
     if a.video is not None:
         with Y.open_video(a.video, size, a.bit_depth, fps) as reader:
             spec = reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting)
@@ -2321,6 +2442,18 @@ def _decode_command(ap, a):
         ap.error("give one of --residuals and --residual-bins")
     if a.roi_root is not None and not a.residuals and not a.residual_bins and not os.path.exists(os.path.join(a.bins, ROIQ_JSON)):
         ap.error("decode --roi-root needs --residuals (the decoded residual layer) or --residual-bins (the coded one)")
+    if a.grain is not None:
+        from . import grain as GR
+
+        if not 1 <= a.grain <= GR.MAX_PERCENT:
+            ap.error(f"--grain: PERCENT must be within 1..{GR.MAX_PERCENT}, got {a.grain}")
+        if a.base_only:
+            ap.error("--base-only takes no --grain: the grain was measured at display size")
+        if a.residuals or a.residual_bins:
+            ap.error("--grain with --residuals / --residual-bins is not implemented: inside lossless boxes the source's own "
+                     "noise is already there")
+        if not os.path.exists(os.path.join(a.bins, GR.GRAIN_JSON)):
+            ap.error(f"--grain: no {GR.GRAIN_JSON} in {a.bins} (encode --tnr T --grain writes one)")
     roi = _roi_option(ap, a, motion, {c["name"]: c["border"] for c in
                                       ((read_sequence_info(a.bins) or {}).get("roi") or {}).get("classes", [])})
     if (a.recon is None) == (a.recon_video is None):
@@ -2342,7 +2475,7 @@ def _decode_command(ap, a):
                                a.siting or base.siting, a.bit_depth or base.bit_depth)
         n = decode_video(a.bins, a.recon_video, a.height, a.width, a.gop, spec, None, a.device, a.precision, a.i_ckpt, a.p_ckpt,
                          roi=roi, residuals=a.residuals, residual_bins=a.residual_bins, verify=a.verify,
-                         base_scale=None if a.base_only else "file")
+                         base_scale=None if a.base_only else "file", grain=a.grain)
     else:
         if a.matrix or a.range or a.siting or a.bit_depth:
             ap.error("--matrix, --range, --siting and --bit-depth belong to --recon-video")
@@ -2350,7 +2483,7 @@ def _decode_command(ap, a):
         n = decode_folder(a.bins, a.recon, height, width, a.gop or (info or {}).get("gop"), a.device, a.precision,
                           a.i_ckpt, a.p_ckpt, io_workers=a.io_workers, roi=roi, residuals=a.residuals,
                           residual_bins=a.residual_bins, verify=a.verify, base_scale=None if a.base_only else "file",
-                          png_device=a.png_device)
+                          png_device=a.png_device, grain=a.grain)
     print(f"{n} pictures decoded")
 
 
