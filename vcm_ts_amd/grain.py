@@ -15,7 +15,9 @@ of the two kernels is stated in the header; tests/grain_ref.py restates it, and 
 `min_samples` is an UNTUNED PLACEHOLDER, and so is everything else here: this is the mechanism -- measured, recorded,
 synthesised -- not a claim about rate, quality or what a detector makes of it.  P pictures only (an I picture is not
 filtered, so it keeps what the codec kept of its own noise); achromatic; a 3-tap separable shape; one set of parameters
-per GOP.
+per GOP.  With the filter's look-ahead (tnr.TNR(intra=K)) the I picture loses its noise as well: it is then measured into
+its GOP's sums like a P picture, the record's "tnr" entry says "intra", and the synthesis grains I pictures exactly when it
+does -- the I picture's noise is pooled with the P pictures', still one set of parameters per GOP.
 
 The kernels run on the caller's current stream and synchronise nothing.  There is no torch fallback: a CPU tensor is a
 ValueError.
@@ -129,6 +131,12 @@ def check_record(record, plan, where=GRAIN_JSON):
     if not isinstance(gops, dict) or sorted(gops) != sorted(str(g) for g in plan.i_pictures):
         have = sorted(gops, key=str) if isinstance(gops, dict) else gops
         raise bad(f"GOPs that start at {have}, the folder's plan starts them at {list(plan.i_pictures)}")
+    setting = record.get("tnr")
+    if isinstance(setting, dict) and "intra" in setting:  # (the encoder's look-ahead: I pictures were filtered and measured)
+        try:
+            whole("intra", setting["intra"], 1, 4)
+        except ValueError as ex:
+            raise bad(f"tnr: {ex}") from None
     for g, rec in gops.items():
         try:
             if not isinstance(rec, dict) or not isinstance(rec.get("points"), list) or not isinstance(rec.get("counts"), list):
@@ -180,13 +188,15 @@ class GrainMeter:
 
     def step(self, src_padded, filt, g, intra):
         """Picture g of the sequence, right after filt.step(src_padded, intra) (filt: the stream's tnr.TnrFilter).  An I
-        picture sends the GOP before it to the host and starts its own with zeroed sums: no kernel.  A P picture is one
-        launch that reads the crops of src_padded and of the picture the filter just wrote, and the filter's held cells."""
+        picture sends the GOP before it to the host and starts its own with zeroed sums: no kernel, unless the filter blended
+        it (tnr.intra: filt.refs > 0) -- then it is measured like a P picture.  A P picture is one launch that reads the
+        crops of src_padded and of the picture the filter just wrote, and the filter's held cells."""
         if intra:
             self.flush()
             self._acc = self._torch.zeros(WORDS, dtype=self._torch.int64, device=self.device)
             self._log.add(int(g))
-            return
+            if not getattr(filt, "refs", 0):
+                return
         if self._acc is None:
             raise ValueError("GrainMeter.step: the first picture of a stream is an I picture")
         devargs.checked(src_padded, "GrainMeter.step", device=self.device, exact=filt.padded, owner="meter")
@@ -223,6 +233,7 @@ class GrainSynth:
         self.percent = whole("percent", percent, 1, MAX_PERCENT, "--grain")
         check_record(record, plan)
         self.plan, self.launches, self._gops = plan, 0, {}
+        self.intra = isinstance(record.get("tnr"), dict) and "intra" in record["tnr"]  # (I pictures were filtered: grain them too)
         for g in plan.i_pictures:
             rec = record["gops"][str(g)]
             tab = table(rec["points"], rec["kh"], rec["kv"], self.percent)
@@ -232,12 +243,12 @@ class GrainSynth:
         torch.cuda.synchronize(self.device)  # (the uploads above: a stream that uses them afterwards cannot race them)
 
     def shown(self, t, picture):
-        """The picture to display for frame t: `picture` itself -- nothing launched -- for an I picture and in a GOP whose
-        table is all zero; else a grained copy (one dcvc_grain_apply launch on the current stream) in one of two buffers of
+        """The picture to display for frame t: `picture` itself -- nothing launched -- for an I picture (unless the record's
+        setting has `intra`) and in a GOP whose table is all zero; else a grained copy (one dcvc_grain_apply launch on the current stream) in one of two buffers of
         the stage's own, valid until the call after the next.  The crop is grained; the rest of the copy is zero."""
         import torch
 
-        if self.plan.is_intra(t):
+        if self.plan.is_intra(t) and not self.intra:
             return picture
         gop = self._gops.get(self.plan.i_pictures[self.plan.gop_of(t)])
         if gop is None:

@@ -24,6 +24,7 @@
                                          [--min-pixels P] [--grow G] [--min-cells C] [--max-boxes N]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT [--motion-border N] [--motion-q F]
     python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P] [--tnr-search R [--tnr-penalty L]]
+    python -m vcm_ts_amd.run_codec encode ... --tnr T --tnr-intra K
     python -m vcm_ts_amd.run_codec encode ... --tnr T --grain [--grain-min-samples N]
     python -m vcm_ts_amd.run_codec decode ... --grain [PERCENT]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT --redact NAME [NAME ...] (--redact-tile N | --redact-fill K)
@@ -91,6 +92,13 @@ nothing is claimed about rate or quality.  Motion compensation is opt-in: with -
 of a P picture is searched for in the previous filtered picture (whole-pixel full search on luma SAD plus --tnr-penalty codes
 per pixel of vector length, default 4, untuned), that picture is moved cell by cell and the blend runs against the moved
 picture: three kernels per P picture.  --report then also gains `frame_tnr_moved` and `frame_tnr_mad_zero`.
+With --tnr-intra K (1 .. 4; opt-in, no default, untuned) the I picture is filtered too: it is blended in one pass (one
+dcvc_tnr_fuse launch) with up to K pictures that FOLLOW it in its own GOP -- never a picture of another GOP, so GOP streams,
+shards and scene cuts keep the bytes of sequential coding -- each searched for and moved onto it first with --tnr-search, and
+the recursive filter starts from the filtered I picture.  A GOP of one picture is left as it is.  --report's figures are then
+nonzero for such I pictures (against the picture that follows) and it gains `frame_tnr_refs`.  With --grain the I picture is
+measured too and `decode --grain` grains I pictures exactly when grain.json's `tnr` entry says `intra`.  Nothing is claimed
+about rate or quality.
 
 With --tnr T --grain the encoder also measures what the filter took out of every P picture (vcm_ts_amd/grain.py: one more
 kernel per P picture, right behind the filter's) and leaves grain.json beside the .bin files: per GOP eight strengths by
@@ -1050,11 +1058,16 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
 
         def frames(k):
             intra = run.intra(k) if filters or redaction else ()
-            for t, (x, aux) in enumerate(source.pictures(run.order(k), run.K)):
-                if compared:
+            pictures = source.pictures(run.order(k), run.K)
+            look = None
+            if filters and tnr.intra is not None:  # (an I picture sees up to tnr.intra pictures of its own GOP ahead of it)
+                pictures = look = _LookAhead(pictures, intra, tnr.intra, len(run.order(k)), _held_ahead)
+            for t, (x, aux) in enumerate(pictures):
+                if compared:  # (the picture being yielded, never one pulled ahead)
                     current[k] = (x, aux)  # (what on_recon's reconstruction belongs to: encode_steps codes it before pulling the next)
                 if filters:  # (the codec sees the filtered picture; current[k] stays the unfiltered one)
-                    src, x = x, filters[k].step(x, t in intra)
+                    src = x
+                    x = filters[k].step(x, t in intra, [a[0] for a in look.ahead]) if look else filters[k].step(x, t in intra)
                     if meters:  # (what the filter took out of this picture, right behind it on the same stream)
                         meters[k].step(src, filters[k], run.global_index(k, t), t in intra)
                 if redaction:  # (after the filter, whose own state stays unredacted; current[k] stays the unredacted one)
@@ -1189,6 +1202,10 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     for an I picture.  With tnr.search (motion compensation, opt-in) that previous picture is moved cell by cell by the
     vectors of a block search first, and the report also gains frame_tnr_moved (the cells with a nonzero vector among the
     cells that hold a pixel) and frame_tnr_mad_zero (frame_tnr_mad against the picture as it stood), 0.0 for an I picture.
+    With tnr.intra = K (look-ahead, opt-in) every I picture is blended in one dcvc_tnr_fuse launch with up to K pictures that
+    follow it in its own GOP (pulled ahead from the source by a _LookAhead, never past the next I picture), the P pictures
+    start from the filtered I picture, the figures above are those of reference 0 for such an I picture, and the report
+    gains frame_tnr_refs (n, 1 for a P picture, 0 for an I picture left as it was).
     None: no launch, allocation, key or byte changes.
     redact (with roi): a redact.Redact -- ROI redaction (vcm_ts_amd/redact.py).  Inside the boxes of the named
     classes (grown by redact.grow; with redact.hold also the boxes of that many pictures before and after) the picture the
@@ -1385,7 +1402,8 @@ def decode_folder(bin_dir, recon_dir, height, width, gop=None, device="cuda:0", 
     grain: None, or 1 .. 200 -- film-grain synthesis (vcm_ts_amd/grain.py) at that per cent of the strength the folder's
     grain.json (encode_folder's grain=) measured.  OPT-IN: the file is never followed silently.  Every P picture that is
     written is a grained copy (one dcvc_grain_apply launch, after the verifier and the base layer's up-scaling, so at display
-    size); I pictures, the DPB and the digests are untouched, so verify= keeps checking the ungrained picture, while the
+    size); I pictures (unless the record's tnr entry says intra: encode_folder's tnr=TNR(..., intra=K)), the DPB and the digests
+    are untouched, so verify= keeps checking the ungrained picture, while the
     PNGs of a grained folder deliberately do NOT pass `run_codec verify`.  Refused by name before any launch: no
     grain.json, one of an unknown version, with a value out of range or whose GOPs are not the folder's plan, and a base-only
     decode; with residuals= / residual_bins= a NotImplementedError."""
@@ -1676,6 +1694,47 @@ def _enh_report_keys(rec_out, h, w):
     return keys
 
 
+class _LookAhead:
+    """An iterator over `items` (the pictures of ONE GOP stream, in coding order) that yields every item exactly once and in
+    order and, at an I picture, lets the caller see the items that follow it in its own GOP: after next() has returned
+    item t, .ahead is the list of the next min(K, items before the stream's next I picture or its end) items when t is in
+    `intra`, and [] otherwise.  Nothing is ever pulled past the next I picture or past item n - 1; between two I pictures the
+    items pulled ahead are handed out before anything more is pulled.  hold(item) -> what is kept of an item pulled ahead
+    (a source whose items are views of recycled memory copies them here).  K None (or 0): one item is pulled per item
+    yielded, exactly as iter(items) would.  Plain Python: no GPU, no torch."""
+
+    def __init__(self, items, intra, K, n, hold=None):
+        from collections import deque
+
+        self._items, self._intra, self._K, self._n, self._hold = iter(items), intra, K or 0, n, hold
+        self._held, self._t, self.ahead = deque(), 0, []
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        item = self._held.popleft() if self._held else next(self._items)
+        t, self._t = self._t, self._t + 1
+        self.ahead = []
+        if self._K and t in self._intra:
+            while len(self._held) < self._K:
+                nxt = t + 1 + len(self._held)
+                if nxt >= self._n or nxt in self._intra:
+                    break
+                pulled = next(self._items)
+                self._held.append(pulled if self._hold is None else self._hold(pulled))
+            self.ahead = list(self._held)
+        return item
+
+
+def _held_ahead(item):
+    """_LookAhead's hold= of a source's (picture, aux): the padded RGB picture is a fresh tensor of its own; the file's
+    samples (a video source's aux) came up through the pinned ring on the copy stream, so a picture that waits is given a
+    copy made on the stream that will read it."""
+    x, aux = item
+    return x, (aux.clone() if aux is not None else None)
+
+
 def _tnr_filters(tnr, run, size, report):
     """tnr= of an encode loop -> one tnr.TnrFilter per GOP stream (None without: nothing is allocated).  Per-picture totals
     are kept only for a report."""
@@ -1741,7 +1800,10 @@ def _tnr_report_keys(tnr, filters, run, h, w):
     blended and the mean absolute luma difference to the previous filtered picture, both 0.0 for an I picture.  With
     tnr.search that picture is the motion-compensated one, and two more keys speak of the search: frame_tnr_moved, the
     cells with a nonzero vector among the cells that hold a pixel, and frame_tnr_mad_zero, what frame_tnr_mad would have
-    been against the uncompensated picture; 0.0 for an I picture too."""
+    been against the uncompensated picture; 0.0 for an I picture too.  With tnr.intra an I picture that had pictures ahead
+    of it is filtered and has figures of its own (against reference 0, the picture that follows it), and frame_tnr_refs
+    is the number of references of every picture: n for such an I picture, 1 for a P picture, 0 for an I picture left as
+    it was."""
     def keys(rd, types, values):
         totals = _stream_totals(filters, run)
         order = sorted(totals)
@@ -1752,6 +1814,8 @@ def _tnr_report_keys(tnr, filters, run, h, w):
             cells = -(-h // 16) * -(-w // 16)  # the cells that hold a pixel
             rd["frame_tnr_moved"] = [totals[g][2] / cells for g in order]
             rd["frame_tnr_mad_zero"] = [totals[g][3] / (h * w) for g in order]
+        if tnr.intra is not None:  # (every row then ends with the number of references of the step)
+            rd["frame_tnr_refs"] = [totals[g][-1] for g in order]
 
     return keys
 
@@ -2116,6 +2180,11 @@ def _parser():
     e.add_argument("--tnr-penalty", type=int, default=None, metavar="L",
                    help="with --tnr-search: what a pixel of vector length costs the search, in luma codes of the cell's SAD, "
                         "0 .. 255 (default 4, an untuned placeholder)")
+    e.add_argument("--tnr-intra", type=int, default=None, metavar="K",
+                   help="with --tnr: filter I pictures too -- blend every I picture in one pass (dcvc_tnr_fuse) with up to K "
+                        "pictures that follow it in its own GOP, each moved onto it first with --tnr-search, and start the "
+                        "recursive filter from the filtered picture; 1 .. 4 (no default: without the option I pictures are "
+                        "passed through).  --report gains frame_tnr_refs.  Untuned; nothing is claimed about rate or quality")
     e.add_argument("--grain", action="store_true",
                    help="with --tnr: film-grain synthesis, the encoder's half (vcm_ts_amd/grain.py) -- measure on the GPU what the "
                         "prefilter took out of every P picture and leave grain.json beside the .bin files: per GOP eight "
@@ -2158,7 +2227,8 @@ def _parser():
                         "1 .. 200 (default 100).  Opt-in: the file is never followed without the option.  Display side only: "
                         "--verify keeps checking the ungrained picture, and a grained folder deliberately does not pass the "
                         "`verify` command, whose digests are of the ungrained picture.  Achromatic, a 3-tap separable shape, "
-                        "per-GOP parameters; I pictures are not grained.  Refused without a grain.json and with --base-only; "
+                        "per-GOP parameters; I pictures are grained only where the record's tnr entry says intra (encode --tnr-intra).  "
+                        "Refused without a grain.json and with --base-only; "
                         "not implemented with --residuals / --residual-bins")
     v = sub.add_parser("verify", description="Hold a folder of decoded PNGs against the `pixels` digests of a hashes.json, on "
                        "the host alone (zlib.crc32 of every picture's RGB bytes; no GPU).  For unfused base-layer PNG folders "
@@ -2300,14 +2370,16 @@ def _encode_command(ap, a):
         ap.error("--tnr-search and --tnr-penalty belong to --tnr")
     if a.tnr_search is None and a.tnr_penalty is not None:
         ap.error("--tnr-penalty belongs to --tnr-search")
+    if a.tnr is None and a.tnr_intra is not None:
+        ap.error("--tnr-intra belongs to --tnr")
     if a.tnr is not None:
         from . import tnr as N
 
         try:
             tnr = N.TNR(a.tnr, **({} if a.tnr_floor is None else {"floor": a.tnr_floor}), pixel=a.tnr_pixel, search=a.tnr_search,
-                        **({} if a.tnr_penalty is None else {"penalty": a.tnr_penalty}))
+                        **({} if a.tnr_penalty is None else {"penalty": a.tnr_penalty}), intra=a.tnr_intra)
         except ValueError as ex:
-            ap.error(f"--tnr / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty: {ex}")
+            ap.error(f"--tnr / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty / --tnr-intra: {ex}")
     grain = None
     if a.grain_min_samples is not None and not a.grain:
         ap.error("--grain-min-samples belongs to --grain")

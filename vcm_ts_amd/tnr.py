@@ -5,9 +5,9 @@ a 5 x 5 window, and passed through untouched wherever something moves.  It is EN
 of the .bin format, nothing for the decoder to know.  The arithmetic is stated in the header; tests/tnr_ref.py restates it
 in numpy, tests/me_ref.py the search and the compensation.
 
-    TNR(threshold, floor=64, pixel=None, search=None, penalty=4)
-                                             the setting; .table() the 256 weights
-    TnrFilter(tnr, size, device)             the state of ONE GOP stream on the device; .step(x_padded, intra)
+    TNR(threshold, floor=64, pixel=None, search=None, penalty=4, intra=None)
+                                             the setting; .table() the 256 weights, .rcp_table() dcvc_tnr_fuse's reciprocals
+    TnrFilter(tnr, size, device)             the state of ONE GOP stream on the device; .step(x_padded, intra, ahead=())
     StreamFilter                             what TnrFilter shares with redact.Redactor: validation, pictures, totals
 
 There is deliberately NO default threshold, and `floor` and `pixel` are UNTUNED PLACEHOLDERS: no machine of the project
@@ -18,6 +18,11 @@ pixels (dcvc_me_search: luma SAD plus `penalty` codes per pixel of vector length
 (dcvc_me_compensate) and the unchanged dcvc_tnr_step blends against the moved picture, so a moving object is blended with
 where it was.  `penalty` is an untuned placeholder too.  Vectors are whole pixels, blocks do not overlap, and the search
 is exhaustive on one level.
+
+With intra=K (opt-in, 1 .. 4, no default) the I picture is filtered too (include/dcvc_hip_tnr_fuse.h, csrc/tnr_fuse.hip;
+tests/tnr_fuse_ref.py restates it): it has no filtered predecessor, so it is blended in ONE pass with up to K pictures
+that FOLLOW it in its own GOP, each weighted on its own by the same window and weight rule -- with `search`, each moved onto
+the I picture first.  The filtered I picture is the first reference of the recursive filter.  K is untuned as well.
 
 The kernels run on the caller's current stream and synchronise nothing.  There is no torch fallback: a CPU tensor is a
 ValueError.
@@ -34,6 +39,7 @@ from .roi import grid_of
 
 MAX_T, MAX_FLOOR, MAX_P, FULL = 64, 255, 255, 256
 MAX_R, MAX_LAMBDA, PENALTY = 32, 255, 4  # (DCVC_ME_MAX_R, DCVC_ME_MAX_LAMBDA; the placeholder)
+MAX_REFS, RCP = 4, 1021  # (DCVC_TNR_FUSE_MAX_REFS, DCVC_TNR_FUSE_RCP)
 ROWS = 64  # pictures' totals kept on the device between two copies to the host
 
 
@@ -45,12 +51,15 @@ class TNR:
     differs by more than P codes is passed through whatever its window says (0..255; None: min(255, 3 T)).  search R: the
     reference of the blend is the previous filtered picture moved cell by cell by the vectors of a full search within +-R
     pixels (1..32; None: no search, nothing moved).  penalty: what a pixel of vector length costs the search, in luma codes
-    of the cell's SAD (0..255; belongs to search).  floor, pixel and penalty are untuned placeholders."""
+    of the cell's SAD (0..255; belongs to search).  floor, pixel and penalty are untuned placeholders.  intra K: an I
+    picture is blended with up to K pictures that follow it in its GOP (1..4; None: I pictures are passed through; no
+    default of substance exists and no value is tuned)."""
     threshold: int
     floor: int = 64
     pixel: int = None
     search: int = None
     penalty: int = PENALTY
+    intra: int = None
 
     def __post_init__(self):
         object.__setattr__(self, "threshold", whole("threshold", self.threshold, 1, MAX_T))
@@ -62,6 +71,8 @@ class TNR:
                 raise ValueError(f"penalty belongs to search: got penalty={self.penalty} without search")
         else:
             object.__setattr__(self, "search", whole("search", self.search, 1, MAX_R))
+        if self.intra is not None:
+            object.__setattr__(self, "intra", whole("intra", self.intra, 1, MAX_REFS))
 
     def table(self):
         """wtab of dcvc_tnr_step: the weight of the current picture by the window's mean difference a = 0 .. 255, as
@@ -71,7 +82,16 @@ class TNR:
 
     def to_json(self):
         rd = {"threshold": self.threshold, "floor": self.floor, "pixel": self.pixel}
-        return rd if self.search is None else dict(rd, search=self.search, penalty=self.penalty)
+        if self.search is not None:
+            rd.update(search=self.search, penalty=self.penalty)
+        if self.intra is not None:  # (a setting without it is written as it always was)
+            rd["intra"] = self.intra
+        return rd
+
+    @staticmethod
+    def rcp_table():
+        """rtab of dcvc_tnr_fuse, 1021 float32: entry U is the float32 nearest the float64 quotient 1 / (256 + U)."""
+        return (1.0 / (256.0 + np.arange(RCP, dtype=np.float64))).astype(np.float32)
 
 
 class StreamFilter:
@@ -149,7 +169,14 @@ class TnrFilter(StreamFilter):
     P step is then three launches on the current stream, nothing synchronised between them: dcvc_me_search(cur, ref),
     dcvc_me_compensate(ref -> comp), dcvc_tnr_step(cur, comp -> out).  .totals(): [(held pixels, sum of d against the
     compensated reference, cells with a nonzero vector, sum of d against the reference as it stood)], (0, 0, 0, 0) for an I
-    picture.  Without tnr.search none of this is allocated or launched."""
+    picture.  Without tnr.search none of this is allocated or launched.
+
+    With tnr.intra the filter also owns dcvc_tnr_fuse's reciprocal table and ONE (4, 3, Hp, Wp) allocation for the
+    references of an I picture (with tnr.search also four sets of mv / cost / zero, one per reference), and an I picture
+    that is handed pictures `ahead` is filtered: 2 n + 1 launches with the search, 1 without.  Every row of .totals() then
+    ends with one more number, the references of the step: n for a filtered I picture, 1 for a P picture, 0 for an I
+    picture that was left as it was; an I picture's moved and zero are those of reference 0.  Without tnr.intra none of
+    this is allocated or launched, and the rows are as above."""
 
     def __init__(self, tnr, size, device, totals=True):
         import torch
@@ -159,30 +186,95 @@ class TnrFilter(StreamFilter):
         self.tnr = tnr
         if tnr.search is not None:
             self.untouched = (0, 0, 0, 0)
+        if tnr.intra is not None:  # (one more column: the number of references of the step)
+            self.untouched = self.untouched + (0,)
         super().__init__(size, device, len(self.untouched), totals)
         cells = self.grid[0] * self.grid[1]
         self.wtab = torch.from_numpy(tnr.table().view(np.int16)).to(self.device)  # (the bits of the uint16 table)
         self.sad = torch.empty(cells, dtype=torch.int32, device=self.device)   # (uint32 words; a cell's sum is < 2^16)
         self.held = torch.empty(cells, dtype=torch.int16, device=self.device)  # (uint16 words; a cell's count is <= 256)
-        self.ref = None
-        if tnr.search is not None:
+        self.ref, self.refs = None, 0  # the last step's result; how many references it was blended with
+        if tnr.intra is not None:
+            self.rtab = torch.from_numpy(tnr.rcp_table()).to(self.device)
+            # the references of an I picture where they cannot be used as they lie: ONE allocation (the crops are
+            # written, the padding never).  With search, the first of them serves the P pictures as well.
+            self.comps = torch.zeros((MAX_REFS, 3) + self.padded, dtype=torch.float32, device=self.device)
+        if tnr.search is not None and tnr.intra is None:
             self.comp = torch.zeros((1, 3) + self.padded, dtype=torch.float32, device=self.device)  # (the crop is written, the padding never)
             self.mv = torch.empty(2 * cells, dtype=torch.int16, device=self.device)   # (dy, dx) of every cell
             self.cost = torch.empty(cells, dtype=torch.int32, device=self.device)     # (uint32 words; a cell's sum is < 2^16)
             self.zero = torch.empty(cells, dtype=torch.int32, device=self.device)
+        elif tnr.search is not None:  # (every reference of an I picture has its own mv / cost / zero; a P picture uses the first)
+            self.mvs = torch.empty((MAX_REFS, 2 * cells), dtype=torch.int16, device=self.device)
+            self.costs = torch.empty((MAX_REFS, cells), dtype=torch.int32, device=self.device)
+            self.zeros = torch.empty((MAX_REFS, cells), dtype=torch.int32, device=self.device)
+            self.comp, self.mv, self.cost, self.zero = self.comps[:1], self.mvs[0], self.costs[0], self.zeros[0]
         torch.cuda.synchronize(self.device)  # (the uploads above: a stream that uses them afterwards cannot race them)
 
-    def step(self, x_padded, intra):
+    def _keep_step(self, t, n):
+        """The totals' row of a step that launched: (held, sad), with search (held, sad, moved, zero) of reference 0, and
+        with tnr.intra one more column, the number n of references."""
+        if self._rows is None:  # (the cells that moved are counted only where somebody will read the count)
+            return
+        cells = (self.held, self.sad)
+        if self.tnr.search is not None:
+            cells += ((self.mv.view(-1, 2) != 0).any(dim=1), self.zero)
+        if self.tnr.intra is not None:
+            self._rows[len(self._log.keys), len(cells)] = n
+        self._keep(t, *cells)
+
+    def _fuse(self, t, x_padded, ahead):
+        """An I picture blended with the pictures `ahead` (1 .. 4 of them, checked): with tnr.search a search from the I
+        source and a compensation per reference, then ONE dcvc_tnr_fuse launch into one of the two buffers."""
+        out = self.bufs[0] if self.ref is not self.bufs[0] else self.bufs[1]
+        (h, w), (Hp, Wp) = (self.height, self.width), self.padded
+        cur, crs, cps = devargs.planar(x_padded.detach()[..., :h, :w])  # (the crops, read in place)
+        refs = [devargs.planar(r.detach()[..., :h, :w]) for r in ahead]
+        if self.tnr.search is not None:
+            for j, (r, rrs, rps) in enumerate(refs):
+                devargs.launch("dcvc_me_search", self.device, cur.data_ptr(), crs, cps, r.data_ptr(), rrs, rps, h, w, self.tnr.search,
+                               self.tnr.penalty, self.mvs[j].data_ptr(), self.costs[j].data_ptr(), self.zeros[j].data_ptr())
+                devargs.launch("dcvc_me_compensate", self.device, r.data_ptr(), rrs, rps, self.comps[j].data_ptr(), Wp, Hp * Wp, h, w,
+                               self.mvs[j].data_ptr())
+                refs[j] = (self.comps[j], Wp, Hp * Wp)
+            self.launches += 2 * len(refs)
+        elif len({r[1:] for r in refs}) > 1:  # (the kernel takes ONE pair of strides: the odd ones out are copied)
+            for j, (r, rrs, rps) in enumerate(refs):
+                if (rrs, rps) != (Wp, Hp * Wp):
+                    self.comps[j, :, :h, :w].copy_(r[0])
+                    refs[j] = (self.comps[j], Wp, Hp * Wp)
+        ptrs = [r[0].data_ptr() for r in refs] + [None] * (MAX_REFS - len(refs))
+        devargs.launch("dcvc_tnr_fuse", self.device, cur.data_ptr(), crs, cps, *ptrs, refs[0][1], refs[0][2], len(refs), out.data_ptr(),
+                       Wp, Hp * Wp, h, w, self.wtab.data_ptr(), self.rtab.data_ptr(), self.tnr.pixel, self.sad.data_ptr(),
+                       self.held.data_ptr())
+        self.launches += 1
+        self._keep_step(t, len(refs))
+        self.ref, self.refs = out, len(refs)
+        return out
+
+    def step(self, x_padded, intra, ahead=()):
         """The padded picture to code in place of `x_padded`.  An I picture (intra=True) launches nothing and is returned
         itself; it becomes the next step's reference.  A P picture is one dcvc_tnr_step launch on the current stream from
         the crops of x_padded and of the previous step's result into the crop of one of the two buffers, which stays valid
         until the step after the next.  With tnr.search the search and the compensation are launched in front of it, and
-        the step blends against the compensated picture."""
+        the step blends against the compensated picture.
+
+        ahead: with tnr.intra = K, the padded pictures that FOLLOW an I picture in its own GOP, nearest first (the caller
+        answers for the GOP); the first K of them are its references, and the I picture is then filtered too -- per
+        reference a search from the I source and a compensation where tnr.search asks for them, then ONE dcvc_tnr_fuse
+        launch into one of the two buffers.  The result is returned and is the next step's reference.  No picture ahead
+        (a GOP of one picture): nothing is launched and the source is returned.  Without tnr.intra, and for a P picture,
+        `ahead` is ignored."""
         self._check(x_padded)
         t, self.n = self.n, self.n + 1
         if intra:
             self.flush()  # (the GOP before this one: its totals go to the host in one copy)
-            self.ref = x_padded.detach()
+            ahead = list(ahead[:self.tnr.intra]) if self.tnr.intra is not None else []
+            if ahead:
+                for r in ahead:
+                    self._check(r)
+                return self._fuse(t, x_padded, ahead)
+            self.ref, self.refs = x_padded.detach(), 0
             return x_padded
         if self.ref is None:
             raise ValueError("TnrFilter.step: the first picture of a stream is an I picture")
@@ -200,9 +292,6 @@ class TnrFilter(StreamFilter):
         devargs.launch("dcvc_tnr_step", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, out.data_ptr(), Wp, Hp * Wp,
                        h, w, self.wtab.data_ptr(), self.tnr.pixel, self.sad.data_ptr(), self.held.data_ptr())
         self.launches += 1
-        if self.tnr.search is None:
-            self._keep(t, self.held, self.sad)
-        elif self._rows is not None:  # (the cells that moved are counted only where somebody will read the count)
-            self._keep(t, self.held, self.sad, (self.mv.view(-1, 2) != 0).any(dim=1), self.zero)
-        self.ref = out
+        self._keep_step(t, 1)
+        self.ref, self.refs = out, 1
         return out
