@@ -23,7 +23,7 @@
     python -m vcm_ts_amd.run_codec boxes (--frames DIR | --video FILE [--size WxH]) --out ROOT --threshold T [--learn KB KF]
                                          [--min-pixels P] [--grow G] [--min-cells C] [--max-boxes N]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT [--motion-border N] [--motion-q F]
-    python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P] [--tnr-search R [--tnr-penalty L]]
+    python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P] [--tnr-search R [--tnr-penalty L] [--tnr-subpel]]
     python -m vcm_ts_amd.run_codec encode ... --tnr T --tnr-intra K
     python -m vcm_ts_amd.run_codec encode ... --tnr T --grain [--grain-min-samples N]
     python -m vcm_ts_amd.run_codec decode ... --grain [PERCENT]
@@ -92,6 +92,9 @@ nothing is claimed about rate or quality.  Motion compensation is opt-in: with -
 of a P picture is searched for in the previous filtered picture (whole-pixel full search on luma SAD plus --tnr-penalty codes
 per pixel of vector length, default 4, untuned), that picture is moved cell by cell and the blend runs against the moved
 picture: three kernels per P picture.  --report then also gains `frame_tnr_moved` and `frame_tnr_mad_zero`.
+With --tnr-subpel (opt-in, belongs to --tnr-search) every vector is refined to quarter pixels and the previous filtered
+picture is moved through a 7/8-tap interpolation filter (vcm_ts_amd/tnr.py): four kernels per P picture, and
+--report gains `frame_tnr_subpel`, the cells whose vector has a fractional component.
 With --tnr-intra K (1 .. 4; opt-in, no default, untuned) the I picture is filtered too: it is blended in one pass (one
 dcvc_tnr_fuse launch) with up to K pictures that FOLLOW it in its own GOP -- never a picture of another GOP, so GOP streams,
 shards and scene cuts keep the bytes of sequential coding -- each searched for and moved onto it first with --tnr-search, and
@@ -1202,6 +1205,8 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     for an I picture.  With tnr.search (motion compensation, opt-in) that previous picture is moved cell by cell by the
     vectors of a block search first, and the report also gains frame_tnr_moved (the cells with a nonzero vector among the
     cells that hold a pixel) and frame_tnr_mad_zero (frame_tnr_mad against the picture as it stood), 0.0 for an I picture.
+    With tnr.subpel (opt-in, with tnr.search) the vectors are refined to quarter pixels and that picture is interpolated;
+    the report gains frame_tnr_subpel (the cells whose vector has a fractional component among the cells that hold a pixel).
     With tnr.intra = K (look-ahead, opt-in) every I picture is blended in one dcvc_tnr_fuse launch with up to K pictures that
     follow it in its own GOP (pulled ahead from the source by a _LookAhead, never past the next I picture), the P pictures
     start from the filtered I picture, the figures above are those of reference 0 for such an I picture, and the report
@@ -1803,7 +1808,8 @@ def _tnr_report_keys(tnr, filters, run, h, w):
     been against the uncompensated picture; 0.0 for an I picture too.  With tnr.intra an I picture that had pictures ahead
     of it is filtered and has figures of its own (against reference 0, the picture that follows it), and frame_tnr_refs
     is the number of references of every picture: n for such an I picture, 1 for a P picture, 0 for an I picture left as
-    it was."""
+    it was.  With tnr.subpel the vectors are quarter pixels, and frame_tnr_subpel is the cells whose vector has a fractional
+    component among the cells that hold a pixel, 0.0 where nothing was searched."""
     def keys(rd, types, values):
         totals = _stream_totals(filters, run)
         order = sorted(totals)
@@ -1814,6 +1820,8 @@ def _tnr_report_keys(tnr, filters, run, h, w):
             cells = -(-h // 16) * -(-w // 16)  # the cells that hold a pixel
             rd["frame_tnr_moved"] = [totals[g][2] / cells for g in order]
             rd["frame_tnr_mad_zero"] = [totals[g][3] / (h * w) for g in order]
+            if tnr.subpel:  # (the rows are then (held, sad, moved, zero, frac); moved counts quarter-pel vectors)
+                rd["frame_tnr_subpel"] = [totals[g][4] / cells for g in order]
         if tnr.intra is not None:  # (every row then ends with the number of references of the step)
             rd["frame_tnr_refs"] = [totals[g][-1] for g in order]
 
@@ -2180,6 +2188,11 @@ def _parser():
     e.add_argument("--tnr-penalty", type=int, default=None, metavar="L",
                    help="with --tnr-search: what a pixel of vector length costs the search, in luma codes of the cell's SAD, "
                         "0 .. 255 (default 4, an untuned placeholder)")
+    e.add_argument("--tnr-subpel", action="store_true",
+                   help="with --tnr-search: refine every cell's vector to quarter pixels (dcvc_me_refine: the 49 candidates "
+                        "around the whole-pel vector, luma SAD against a 7/8-tap interpolation) and move the previous filtered "
+                        "picture through that interpolation (dcvc_me_compensate_sub): four kernels per P picture.  --report "
+                        "gains frame_tnr_subpel.  No overlapped blocks; nothing is claimed about rate or quality")
     e.add_argument("--tnr-intra", type=int, default=None, metavar="K",
                    help="with --tnr: filter I pictures too -- blend every I picture in one pass (dcvc_tnr_fuse) with up to K "
                         "pictures that follow it in its own GOP, each moved onto it first with --tnr-search, and start the "
@@ -2370,6 +2383,8 @@ def _encode_command(ap, a):
         ap.error("--tnr-search and --tnr-penalty belong to --tnr")
     if a.tnr_search is None and a.tnr_penalty is not None:
         ap.error("--tnr-penalty belongs to --tnr-search")
+    if a.tnr_search is None and a.tnr_subpel:
+        ap.error("--tnr-subpel belongs to --tnr-search")
     if a.tnr is None and a.tnr_intra is not None:
         ap.error("--tnr-intra belongs to --tnr")
     if a.tnr is not None:
@@ -2377,9 +2392,10 @@ def _encode_command(ap, a):
 
         try:
             tnr = N.TNR(a.tnr, **({} if a.tnr_floor is None else {"floor": a.tnr_floor}), pixel=a.tnr_pixel, search=a.tnr_search,
-                        **({} if a.tnr_penalty is None else {"penalty": a.tnr_penalty}), intra=a.tnr_intra)
+                        **({} if a.tnr_penalty is None else {"penalty": a.tnr_penalty}), intra=a.tnr_intra,
+                        **({"subpel": True} if a.tnr_subpel else {}))
         except ValueError as ex:
-            ap.error(f"--tnr / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty / --tnr-intra: {ex}")
+            ap.error(f"--tnr / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty / --tnr-intra / --tnr-subpel: {ex}")
     grain = None
     if a.grain_min_samples is not None and not a.grain:
         ap.error("--grain-min-samples belongs to --grain")

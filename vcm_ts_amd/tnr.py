@@ -1,11 +1,12 @@
 """A motion-adaptive temporal noise prefilter (include/dcvc_hip_tnr.h, csrc/tnr.hip; with a motion search in front of it
-include/dcvc_hip_me.h, csrc/me.hip) for fixed-camera content, where a P picture's bits are dominated by sensor noise: every
+include/dcvc_hip_me.h, csrc/me.hip, and to quarter pixels include/dcvc_hip_mesub.h, csrc/mesub.hip) for fixed-camera
+content, where a P picture's bits are dominated by sensor noise: every
 P picture the codec is handed is blended with the previous filtered picture wherever the luma of the two stays close over
 a 5 x 5 window, and passed through untouched wherever something moves.  It is ENCODER SIDE ONLY: it replaces the picture the codec is handed and nothing else -- no side file, no change
 of the .bin format, nothing for the decoder to know.  The arithmetic is stated in the header; tests/tnr_ref.py restates it
-in numpy, tests/me_ref.py the search and the compensation.
+in numpy, tests/me_ref.py the search and the compensation, tests/mesub_ref.py the quarter-pel refinement and interpolation.
 
-    TNR(threshold, floor=64, pixel=None, search=None, penalty=4, intra=None)
+    TNR(threshold, floor=64, pixel=None, search=None, penalty=4, intra=None, subpel=False)
                                              the setting; .table() the 256 weights, .rcp_table() dcvc_tnr_fuse's reciprocals
     TnrFilter(tnr, size, device)             the state of ONE GOP stream on the device; .step(x_padded, intra, ahead=())
     StreamFilter                             what TnrFilter shares with redact.Redactor: validation, pictures, totals
@@ -17,7 +18,10 @@ COMPENSATED (opt-in): every 16 x 16 cell of a P picture is searched for in the p
 pixels (dcvc_me_search: luma SAD plus `penalty` codes per pixel of vector length), that picture is moved cell by cell
 (dcvc_me_compensate) and the unchanged dcvc_tnr_step blends against the moved picture, so a moving object is blended with
 where it was.  `penalty` is an untuned placeholder too.  Vectors are whole pixels, blocks do not overlap, and the search
-is exhaustive on one level.
+is exhaustive on one level.  With subpel=True (opt-in, belongs to search) every vector is refined to QUARTER pixels over the
+49 candidates around it (dcvc_me_refine) and the picture is moved through a separable 7/8-tap interpolation filter
+(dcvc_me_compensate_sub in place of dcvc_me_compensate): an object that moves by a fraction of a pixel is blended with an
+interpolated copy of where it was, not with a misregistered one.
 
 With intra=K (opt-in, 1 .. 4, no default) the I picture is filtered too (include/dcvc_hip_tnr_fuse.h, csrc/tnr_fuse.hip;
 tests/tnr_fuse_ref.py restates it): it has no filtered predecessor, so it is blended in ONE pass with up to K pictures
@@ -40,6 +44,7 @@ from .roi import grid_of
 MAX_T, MAX_FLOOR, MAX_P, FULL = 64, 255, 255, 256
 MAX_R, MAX_LAMBDA, PENALTY = 32, 255, 4  # (DCVC_ME_MAX_R, DCVC_ME_MAX_LAMBDA; the placeholder)
 MAX_REFS, RCP = 4, 1021  # (DCVC_TNR_FUSE_MAX_REFS, DCVC_TNR_FUSE_RCP)
+SUBPEL = 4  # (DCVC_MESUB_UNIT: with subpel, vectors are in 1 / 4 pixels)
 ROWS = 64  # pictures' totals kept on the device between two copies to the host
 
 
@@ -53,13 +58,15 @@ class TNR:
     pixels (1..32; None: no search, nothing moved).  penalty: what a pixel of vector length costs the search, in luma codes
     of the cell's SAD (0..255; belongs to search).  floor, pixel and penalty are untuned placeholders.  intra K: an I
     picture is blended with up to K pictures that follow it in its GOP (1..4; None: I pictures are passed through; no
-    default of substance exists and no value is tuned)."""
+    default of substance exists and no value is tuned).  subpel: the search's vectors are refined to quarter pixels and the
+    reference is interpolated (belongs to search; False: whole pixels)."""
     threshold: int
     floor: int = 64
     pixel: int = None
     search: int = None
     penalty: int = PENALTY
     intra: int = None
+    subpel: bool = False
 
     def __post_init__(self):
         object.__setattr__(self, "threshold", whole("threshold", self.threshold, 1, MAX_T))
@@ -73,6 +80,10 @@ class TNR:
             object.__setattr__(self, "search", whole("search", self.search, 1, MAX_R))
         if self.intra is not None:
             object.__setattr__(self, "intra", whole("intra", self.intra, 1, MAX_REFS))
+        if not isinstance(self.subpel, bool):
+            raise ValueError(f"subpel must be True or False, got {self.subpel!r}")
+        if self.subpel and self.search is None:
+            raise ValueError("subpel belongs to search: got subpel=True without search")
 
     def table(self):
         """wtab of dcvc_tnr_step: the weight of the current picture by the window's mean difference a = 0 .. 255, as
@@ -86,6 +97,8 @@ class TNR:
             rd.update(search=self.search, penalty=self.penalty)
         if self.intra is not None:  # (a setting without it is written as it always was)
             rd["intra"] = self.intra
+        if self.subpel:  # (the unit of the vectors: quarter pixels)
+            rd["subpel"] = SUBPEL
         return rd
 
     @staticmethod
@@ -176,7 +189,13 @@ class TnrFilter(StreamFilter):
     that is handed pictures `ahead` is filtered: 2 n + 1 launches with the search, 1 without.  Every row of .totals() then
     ends with one more number, the references of the step: n for a filtered I picture, 1 for a P picture, 0 for an I
     picture that was left as it was; an I picture's moved and zero are those of reference 0.  Without tnr.intra none of
-    this is allocated or launched, and the rows are as above."""
+    this is allocated or launched, and the rows are as above.
+
+    With tnr.subpel the filter also owns mvq / costq, the quarter-pel vectors of every cell and their SADs (with tnr.intra
+    mvqs / costqs, one set per reference), and every search is followed by dcvc_me_refine, every compensation is a
+    dcvc_me_compensate_sub: four launches a P step, 3 n + 1 a filtered I picture.  `moved` then counts the nonzero
+    quarter-pel vectors, and the row gains `frac`, the cells whose vector has a fractional component, after `zero` and
+    before tnr.intra's number of references.  Without tnr.subpel none of this is allocated or launched."""
 
     def __init__(self, tnr, size, device, totals=True):
         import torch
@@ -185,7 +204,7 @@ class TnrFilter(StreamFilter):
             raise ValueError(f"tnr: expected a tnr.TNR, got {type(tnr).__name__}")
         self.tnr = tnr
         if tnr.search is not None:
-            self.untouched = (0, 0, 0, 0)
+            self.untouched = (0, 0, 0, 0) + ((0,) if tnr.subpel else ())
         if tnr.intra is not None:  # (one more column: the number of references of the step)
             self.untouched = self.untouched + (0,)
         super().__init__(size, device, len(self.untouched), totals)
@@ -209,6 +228,13 @@ class TnrFilter(StreamFilter):
             self.costs = torch.empty((MAX_REFS, cells), dtype=torch.int32, device=self.device)
             self.zeros = torch.empty((MAX_REFS, cells), dtype=torch.int32, device=self.device)
             self.comp, self.mv, self.cost, self.zero = self.comps[:1], self.mvs[0], self.costs[0], self.zeros[0]
+        if tnr.subpel and tnr.intra is None:
+            self.mvq = torch.empty(2 * cells, dtype=torch.int16, device=self.device)   # (vy, vx) of every cell, quarter pixels
+            self.costq = torch.empty(cells, dtype=torch.int32, device=self.device)     # (uint32 words; a cell's sum is < 2^16)
+        elif tnr.subpel:
+            self.mvqs = torch.empty((MAX_REFS, 2 * cells), dtype=torch.int16, device=self.device)
+            self.costqs = torch.empty((MAX_REFS, cells), dtype=torch.int32, device=self.device)
+            self.mvq, self.costq = self.mvqs[0], self.costqs[0]
         torch.cuda.synchronize(self.device)  # (the uploads above: a stream that uses them afterwards cannot race them)
 
     def _keep_step(self, t, n):
@@ -217,11 +243,25 @@ class TnrFilter(StreamFilter):
         if self._rows is None:  # (the cells that moved are counted only where somebody will read the count)
             return
         cells = (self.held, self.sad)
-        if self.tnr.search is not None:
+        if self.tnr.subpel:  # (moved and frac of the quarter-pel vectors)
+            cells += ((self.mvq.view(-1, 2) != 0).any(dim=1), self.zero, (self.mvq.view(-1, 2) & 3 != 0).any(dim=1))
+        elif self.tnr.search is not None:
             cells += ((self.mv.view(-1, 2) != 0).any(dim=1), self.zero)
         if self.tnr.intra is not None:
             self._rows[len(self._log.keys), len(cells)] = n
         self._keep(t, *cells)
+
+    def _move(self, cur, crs, cps, ref, rrs, rps, comp, mv, j):
+        """ref moved onto cur into comp by the searched vectors mv: dcvc_me_compensate, or with tnr.subpel dcvc_me_refine
+        into the quarter-pel vectors of reference j and dcvc_me_compensate_sub."""
+        (h, w), (Hp, Wp) = (self.height, self.width), self.padded
+        if not self.tnr.subpel:
+            devargs.launch("dcvc_me_compensate", self.device, ref.data_ptr(), rrs, rps, comp.data_ptr(), Wp, Hp * Wp, h, w, mv.data_ptr())
+            return
+        mvq, costq = (self.mvq, self.costq) if self.tnr.intra is None else (self.mvqs[j], self.costqs[j])
+        devargs.launch("dcvc_me_refine", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, h, w, self.tnr.penalty,
+                       mv.data_ptr(), mvq.data_ptr(), costq.data_ptr())
+        devargs.launch("dcvc_me_compensate_sub", self.device, ref.data_ptr(), rrs, rps, comp.data_ptr(), Wp, Hp * Wp, h, w, mvq.data_ptr())
 
     def _fuse(self, t, x_padded, ahead):
         """An I picture blended with the pictures `ahead` (1 .. 4 of them, checked): with tnr.search a search from the I
@@ -234,10 +274,9 @@ class TnrFilter(StreamFilter):
             for j, (r, rrs, rps) in enumerate(refs):
                 devargs.launch("dcvc_me_search", self.device, cur.data_ptr(), crs, cps, r.data_ptr(), rrs, rps, h, w, self.tnr.search,
                                self.tnr.penalty, self.mvs[j].data_ptr(), self.costs[j].data_ptr(), self.zeros[j].data_ptr())
-                devargs.launch("dcvc_me_compensate", self.device, r.data_ptr(), rrs, rps, self.comps[j].data_ptr(), Wp, Hp * Wp, h, w,
-                               self.mvs[j].data_ptr())
+                self._move(cur, crs, cps, r, rrs, rps, self.comps[j], self.mvs[j], j)
                 refs[j] = (self.comps[j], Wp, Hp * Wp)
-            self.launches += 2 * len(refs)
+            self.launches += (3 if self.tnr.subpel else 2) * len(refs)
         elif len({r[1:] for r in refs}) > 1:  # (the kernel takes ONE pair of strides: the odd ones out are copied)
             for j, (r, rrs, rps) in enumerate(refs):
                 if (rrs, rps) != (Wp, Hp * Wp):
@@ -285,10 +324,9 @@ class TnrFilter(StreamFilter):
         if self.tnr.search is not None:
             devargs.launch("dcvc_me_search", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, h, w, self.tnr.search,
                            self.tnr.penalty, self.mv.data_ptr(), self.cost.data_ptr(), self.zero.data_ptr())
-            devargs.launch("dcvc_me_compensate", self.device, ref.data_ptr(), rrs, rps, self.comp.data_ptr(), Wp, Hp * Wp, h, w,
-                           self.mv.data_ptr())
+            self._move(cur, crs, cps, ref, rrs, rps, self.comp, self.mv, 0)
             ref, rrs, rps = self.comp, Wp, Hp * Wp
-            self.launches += 2
+            self.launches += 3 if self.tnr.subpel else 2
         devargs.launch("dcvc_tnr_step", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, out.data_ptr(), Wp, Hp * Wp,
                        h, w, self.wtab.data_ptr(), self.tnr.pixel, self.sad.data_ptr(), self.held.data_ptr())
         self.launches += 1
