@@ -23,28 +23,23 @@
 // bases, the strides and the vector allow it.  Any other cell stages the 23 x 23 samples around its 16 x 16 pixels (taps
 // -3 .. +4) of the three planes in LDS, coordinates clamped before the load, makes the horizontal pass of every staged row
 // into LDS and the vertical pass per pixel, a thread a pixel.
+//
+// The filters, the luma, the packed key and the two ways of moving a block by one vector live in mesub_common.h, which
+// mesplit.hip takes them from as well.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "dcvc_hip.h"
 #include "dcvc_hip_mesub.h"
 #include "kernel_common.h"
-#include "roi_common.h"
-
-#pragma clang fp contract(off)  // (the fp32 folds are part of the interface: every product and every sum rounded)
+#include "mesub_common.h"
 
 namespace {
 
-constexpr int CELL = DCVC_ROI_CELL, THREADS = 256, NF = 7, NT = 9, WIN = CELL + NT - 1;
-constexpr int ITEMS = NF * NF * CELL, ROUNDS = (ITEMS + THREADS - 1) / THREADS, BIAS = 256;
+constexpr int WIN = CELL + NT - 1;
+constexpr int ITEMS = NF * NF * CELL, ROUNDS = (ITEMS + THREADS - 1) / THREADS;
 constexpr int WPIX = WIN * WIN, PER = (WPIX + THREADS - 1) / THREADS;
-static_assert(CELL == 16 && THREADS == CELL * CELL && WIN == 24 && DCVC_MESUB_UNIT == 4, "a thread per pixel; offsets -4 .. +4");
-static_assert(4 * DCVC_ME_MAX_R + 3 < BIAS, "vy + 256 and vx + 256 fit 9 bits");
-
-// the filter of f = -3 .. 3 over the whole offsets -4 .. +4 around d
-__constant__ int TAP9[NF][NT] = {{-1, 4, -10, 58, 17, -5, 1, 0, 0}, {-1, 4, -11, 40, 40, -11, 4, -1, 0}, {0, 1, -5, 17, 58, -10, 4, -1, 0},
-                                 {0, 0, 0, 0, 64, 0, 0, 0, 0},
-                                 {0, -1, 4, -10, 58, 17, -5, 1, 0}, {0, -1, 4, -11, 40, 40, -11, 4, -1}, {0, 0, 1, -5, 17, 58, -10, 4, -1}};
+static_assert(WIN == 24, "offsets -4 .. +4");
 
 struct RefineArgs {
     const float *cur, *ref;
@@ -54,17 +49,6 @@ struct RefineArgs {
     int64_t cps, rps;
     int32_t crs, rrs, H, W, wc, lambda;
 };
-
-__device__ __forceinline__ unsigned luma_of(const float (&v)[3]) { return (unsigned)luma8(code8(v[0]), code8(v[1]), code8(v[2])); }
-
-typedef short short2v __attribute__((ext_vector_type(2)));
-
-// the sum of two int16 products on top of acc: one v_dot2_i32_i16
-__device__ __forceinline__ int dot2(unsigned a, unsigned b, int acc) {
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b), acc, false);
-}
-
-__device__ __forceinline__ unsigned pair16(int lo, int hi) { return ((unsigned)lo & 0xffffu) | (unsigned)hi << 16; }
 
 __global__ __launch_bounds__(THREADS) void me_refine_kernel(const RefineArgs p) {
     __shared__ __align__(16) uint8_t win[WIN][WIN];   // Y of ref: row = y - Y0 - dy + 4, byte = x - X0 - dx + 4
@@ -167,45 +151,22 @@ __global__ __launch_bounds__(THREADS) void me_refine_kernel(const RefineArgs p) 
 #pragma unroll
         for (int off = 8; off; off >>= 1) sad += __shfl_xor(sad, off);  // (the 16 lanes of a candidate are neighbours)
         if (item < ITEMS && x == 0) {
-            const int vy = 4 * dy + fyi - 3, vx = 4 * dx + fxi - 3;
-            const unsigned len = (unsigned)(abs(vy) + abs(vx)), J = 4u * sad + (unsigned)p.lambda * len;
-            const unsigned long long cnd = (unsigned long long)J << 27 | (unsigned long long)(len << 18 | (unsigned)(vy + BIAS) << 9 | (unsigned)(vx + BIAS));
+            const unsigned long long cnd = key_of(sad, 4 * dy + fyi - 3, 4 * dx + fxi - 3, p.lambda);
             key = cnd < key ? cnd : key;
         }
     }
     // ---- the minimum: inside the wave, then across the waves
-#pragma unroll
-    for (int off = 32; off; off >>= 1) {
-        const unsigned long long other = __shfl_xor(key, off);
-        key = other < key ? other : key;
-    }
+    key = key_min_wave(key);
     if ((tid & 63) == 0) best[tid >> 6] = key;
     __syncthreads();
     if (tid == 0) {
 #pragma unroll
         for (int v = 1; v < THREADS / 64; ++v) key = best[v] < key ? best[v] : key;
-        const unsigned len = (unsigned)(key >> 18) & 511u;
-        p.mvq[2 * at] = (int16_t)((int)((key >> 9) & 511u) - BIAS);
-        p.mvq[2 * at + 1] = (int16_t)((int)(key & 511u) - BIAS);
-        p.cost[at] = ((unsigned)(key >> 27) - (unsigned)p.lambda * len) >> 2;
+        p.mvq[2 * at] = (int16_t)key_vy(key);
+        p.mvq[2 * at + 1] = (int16_t)key_vx(key);
+        p.cost[at] = key_sad(key, p.lambda);
     }
 }
-
-// the filters of the phases 1 .. 3 as (first offset, taps, tap / 64): phase 0 is the identity and has no row here
-__constant__ int FIRST[4] = {0, -3, -3, -2}, COUNT[4] = {1, 7, 8, 7};
-__constant__ float TAPF[4][8] = {{1.0f, 0, 0, 0, 0, 0, 0, 0},
-                                 {-1 / 64.0f, 4 / 64.0f, -10 / 64.0f, 58 / 64.0f, 17 / 64.0f, -5 / 64.0f, 1 / 64.0f, 0},
-                                 {-1 / 64.0f, 4 / 64.0f, -11 / 64.0f, 40 / 64.0f, 40 / 64.0f, -11 / 64.0f, 4 / 64.0f, -1 / 64.0f},
-                                 {1 / 64.0f, -5 / 64.0f, 17 / 64.0f, 58 / 64.0f, -10 / 64.0f, 4 / 64.0f, -1 / 64.0f, 0}};
-constexpr int SWIN = CELL + 7, SPITCH = SWIN + 1, LEAD = 3;  // samples at offsets -3 .. +4 around the 16 pixels
-
-struct SubArgs {
-    const float *ref;
-    float *out;
-    const int16_t *mv;
-    int64_t rps, ops;
-    int32_t rrs, ors, H, W, wc, rvec, ovec;
-};
 
 __global__ __launch_bounds__(THREADS) void me_compensate_sub_kernel(const SubArgs p) {
     __shared__ float win[3][SWIN][SPITCH];  // ref: row = y - Y0 - iy + 3, column = x - X0 - ix + 3
@@ -215,67 +176,8 @@ __global__ __launch_bounds__(THREADS) void me_compensate_sub_kernel(const SubArg
     if (X0 >= p.W || Y0 >= p.H) return;  // (uniform across the workgroup)
     const int64_t at = (int64_t)blockIdx.y * p.wc + blockIdx.x;
     const int vy = __builtin_amdgcn_readfirstlane((int)p.mv[2 * at]), vx = __builtin_amdgcn_readfirstlane((int)p.mv[2 * at + 1]);
-    const int iy = vy >> 2, py = vy & 3, ix = vx >> 2, px = vx & 3;
-
-    if (py == 0 && px == 0) {  // (uniform) a whole vector: the bits, a quad of one plane a lane
-        const int k = tid >> 6, y = Y0 + ((tid & 63) >> 2), x0 = X0 + 4 * (tid & 3);
-        if (k >= 3 || y >= p.H || x0 >= p.W) return;
-        const int sy = min(max(y + iy, 0), p.H - 1), sx = x0 + ix;
-        const bool rv = p.rvec && (ix & 3) == 0 && sx >= 0 && sx + 4 <= p.W, ov = p.ovec && x0 + 4 <= p.W;
-        const float *src = p.ref + k * p.rps + (int64_t)sy * p.rrs;
-        float *dst = p.out + k * p.ops + (int64_t)y * p.ors + x0;
-        float v[4];
-        if (rv) {
-            const float4 t = *reinterpret_cast<const float4 *>(src + sx);
-            v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = src[min(max(sx + q, 0), p.W - 1)];
-        }
-        if (ov) {
-            *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (x0 + q < p.W) dst[q] = v[q];
-        }
-        return;
-    }
-
-    // ---- the samples around the cell, coordinates clamped before the load
-    for (int o = tid; o < 3 * SWIN * SWIN; o += THREADS) {
-        const int k = o / (SWIN * SWIN), rest = o - k * (SWIN * SWIN), r = rest / SWIN, cc = rest - r * SWIN;
-        const int y = min(max(Y0 + iy - LEAD + r, 0), p.H - 1), x = min(max(X0 + ix - LEAD + cc, 0), p.W - 1);
-        win[k][r][cc] = p.ref[k * p.rps + (int64_t)y * p.rrs + x];
-    }
-    __syncthreads();
-    // ---- horizontal: the identity at phase 0, else the fold in increasing offset
-    const int hfirst = LEAD + FIRST[px], hn = COUNT[px];
-    for (int o = tid; o < 3 * SWIN * CELL; o += THREADS) {
-        const int k = o / (SWIN * CELL), rest = o - k * (SWIN * CELL), r = rest / CELL, x = rest % CELL;
-        const float *s = &win[k][r][x + hfirst];
-        float a = s[0];
-        if (px != 0) {
-            a = TAPF[px][0] * s[0];
-            for (int j = 1; j < hn; ++j) a = a + TAPF[px][j] * s[j];
-        }
-        hz[k][r][x] = a;
-    }
-    __syncthreads();
-    // ---- vertical, a thread a pixel
-    const int yy = tid / CELL, xx = tid % CELL;
-    if (Y0 + yy >= p.H || X0 + xx >= p.W) return;
-    const int vfirst = LEAD + FIRST[py], vn = COUNT[py];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        float a = hz[k][yy + vfirst][xx];
-        if (py != 0) {
-            a = TAPF[py][0] * a;
-            for (int j = 1; j < vn; ++j) a = a + TAPF[py][j] * hz[k][yy + vfirst + j][xx];
-        }
-        a = fminf(fmaxf(a, 0.0f), 1.0f);
-        p.out[k * p.ops + (int64_t)(Y0 + yy) * p.ors + X0 + xx] = a == 0.0f ? 0.0f : a;  // (a zero of either sign is +0)
-    }
+    if (((vy | vx) & 3) == 0) move_cell_whole(p, tid, Y0, X0, vy >> 2, vx >> 2);  // (uniform) a whole vector: the bits
+    else move_block_frac<CELL>(p, tid, Y0, X0, vy, vx, win, hz, false);
 }
 
 }  // namespace

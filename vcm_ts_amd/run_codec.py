@@ -23,7 +23,7 @@
     python -m vcm_ts_amd.run_codec boxes (--frames DIR | --video FILE [--size WxH]) --out ROOT --threshold T [--learn KB KF]
                                          [--min-pixels P] [--grow G] [--min-cells C] [--max-boxes N]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT [--motion-border N] [--motion-q F]
-    python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P] [--tnr-search R [--tnr-penalty L] [--tnr-subpel]]
+    python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P] [--tnr-search R [--tnr-penalty L] [--tnr-subpel] [--tnr-split]]
     python -m vcm_ts_amd.run_codec encode ... --tnr T --tnr-intra K
     python -m vcm_ts_amd.run_codec encode ... --tnr T --grain [--grain-min-samples N]
     python -m vcm_ts_amd.run_codec decode ... --grain [PERCENT]
@@ -95,6 +95,10 @@ picture: three kernels per P picture.  --report then also gains `frame_tnr_moved
 With --tnr-subpel (opt-in, belongs to --tnr-search) every vector is refined to quarter pixels and the previous filtered
 picture is moved through a 7/8-tap interpolation filter (vcm_ts_amd/tnr.py): four kernels per P picture, and
 --report gains `frame_tnr_subpel`, the cells whose vector has a fractional component.
+With --tnr-split (opt-in, belongs to --tnr-search, with or without --tnr-subpel) every 8 x 8 quarter of a cell chooses again
+among its own cell's vector and the eight neighbours' and the previous filtered picture is moved sub-cell by sub-cell
+(vcm_ts_amd/tnr.py): one more kernel per P picture, and --report gains `frame_tnr_split`, the sub-cells whose
+vector differs from their cell's.
 With --tnr-intra K (1 .. 4; opt-in, no default, untuned) the I picture is filtered too: it is blended in one pass (one
 dcvc_tnr_fuse launch) with up to K pictures that FOLLOW it in its own GOP -- never a picture of another GOP, so GOP streams,
 shards and scene cuts keep the bytes of sequential coding -- each searched for and moved onto it first with --tnr-search, and
@@ -1207,6 +1211,9 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     cells that hold a pixel) and frame_tnr_mad_zero (frame_tnr_mad against the picture as it stood), 0.0 for an I picture.
     With tnr.subpel (opt-in, with tnr.search) the vectors are refined to quarter pixels and that picture is interpolated;
     the report gains frame_tnr_subpel (the cells whose vector has a fractional component among the cells that hold a pixel).
+    With tnr.split (opt-in, with tnr.search) every 8 x 8 sub-cell chooses again among its cell's vector and the neighbours'
+    and that picture is moved sub-cell by sub-cell; the report gains frame_tnr_split (the sub-cells whose vector differs from
+    their cell's among the sub-cells that hold a pixel).
     With tnr.intra = K (look-ahead, opt-in) every I picture is blended in one dcvc_tnr_fuse launch with up to K pictures that
     follow it in its own GOP (pulled ahead from the source by a _LookAhead, never past the next I picture), the P pictures
     start from the filtered I picture, the figures above are those of reference 0 for such an I picture, and the report
@@ -1809,7 +1816,9 @@ def _tnr_report_keys(tnr, filters, run, h, w):
     of it is filtered and has figures of its own (against reference 0, the picture that follows it), and frame_tnr_refs
     is the number of references of every picture: n for such an I picture, 1 for a P picture, 0 for an I picture left as
     it was.  With tnr.subpel the vectors are quarter pixels, and frame_tnr_subpel is the cells whose vector has a fractional
-    component among the cells that hold a pixel, 0.0 where nothing was searched."""
+    component among the cells that hold a pixel, 0.0 where nothing was searched.  With tnr.split frame_tnr_split is the
+    sub-cells whose vector differs from their cell's among the 8 x 8 sub-cells that hold a pixel, 0.0 where nothing was
+    searched."""
     def keys(rd, types, values):
         totals = _stream_totals(filters, run)
         order = sorted(totals)
@@ -1822,6 +1831,9 @@ def _tnr_report_keys(tnr, filters, run, h, w):
             rd["frame_tnr_mad_zero"] = [totals[g][3] / (h * w) for g in order]
             if tnr.subpel:  # (the rows are then (held, sad, moved, zero, frac); moved counts quarter-pel vectors)
                 rd["frame_tnr_subpel"] = [totals[g][4] / cells for g in order]
+            if tnr.split:  # (the next column: the sub-cells that left their cell's vector)
+                subs = -(-h // 8) * -(-w // 8)  # the sub-cells that hold a pixel
+                rd["frame_tnr_split"] = [totals[g][5 if tnr.subpel else 4] / subs for g in order]
         if tnr.intra is not None:  # (every row then ends with the number of references of the step)
             rd["frame_tnr_refs"] = [totals[g][-1] for g in order]
 
@@ -2193,6 +2205,11 @@ def _parser():
                         "around the whole-pel vector, luma SAD against a 7/8-tap interpolation) and move the previous filtered "
                         "picture through that interpolation (dcvc_me_compensate_sub): four kernels per P picture.  --report "
                         "gains frame_tnr_subpel.  No overlapped blocks; nothing is claimed about rate or quality")
+    e.add_argument("--tnr-split", action="store_true",
+                   help="with --tnr-search: let every 8 x 8 quarter of a cell choose again among its cell's vector and the eight "
+                        "neighbours' (dcvc_me_split) and move the previous filtered picture sub-cell by sub-cell "
+                        "(dcvc_me_compensate_split): one more kernel per P picture.  --report gains frame_tnr_split.  Cells on "
+                        "an object's edge stay worse than the unfiltered source; nothing is claimed about rate or quality")
     e.add_argument("--tnr-intra", type=int, default=None, metavar="K",
                    help="with --tnr: filter I pictures too -- blend every I picture in one pass (dcvc_tnr_fuse) with up to K "
                         "pictures that follow it in its own GOP, each moved onto it first with --tnr-search, and start the "
@@ -2385,6 +2402,8 @@ def _encode_command(ap, a):
         ap.error("--tnr-penalty belongs to --tnr-search")
     if a.tnr_search is None and a.tnr_subpel:
         ap.error("--tnr-subpel belongs to --tnr-search")
+    if a.tnr_search is None and a.tnr_split:
+        ap.error("--tnr-split belongs to --tnr-search")
     if a.tnr is None and a.tnr_intra is not None:
         ap.error("--tnr-intra belongs to --tnr")
     if a.tnr is not None:
@@ -2393,9 +2412,9 @@ def _encode_command(ap, a):
         try:
             tnr = N.TNR(a.tnr, **({} if a.tnr_floor is None else {"floor": a.tnr_floor}), pixel=a.tnr_pixel, search=a.tnr_search,
                         **({} if a.tnr_penalty is None else {"penalty": a.tnr_penalty}), intra=a.tnr_intra,
-                        **({"subpel": True} if a.tnr_subpel else {}))
+                        **({"subpel": True} if a.tnr_subpel else {}), **({"split": True} if a.tnr_split else {}))
         except ValueError as ex:
-            ap.error(f"--tnr / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty / --tnr-intra / --tnr-subpel: {ex}")
+            ap.error(f"--tnr / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty / --tnr-intra / --tnr-subpel / --tnr-split: {ex}")
     grain = None
     if a.grain_min_samples is not None and not a.grain:
         ap.error("--grain-min-samples belongs to --grain")

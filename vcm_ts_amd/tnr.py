@@ -1,12 +1,14 @@
 """A motion-adaptive temporal noise prefilter (include/dcvc_hip_tnr.h, csrc/tnr.hip; with a motion search in front of it
-include/dcvc_hip_me.h, csrc/me.hip, and to quarter pixels include/dcvc_hip_mesub.h, csrc/mesub.hip) for fixed-camera
+include/dcvc_hip_me.h, csrc/me.hip, to quarter pixels include/dcvc_hip_mesub.h, csrc/mesub.hip, and per 8 x 8 sub-cell
+include/dcvc_hip_mesplit.h, csrc/mesplit.hip) for fixed-camera
 content, where a P picture's bits are dominated by sensor noise: every
 P picture the codec is handed is blended with the previous filtered picture wherever the luma of the two stays close over
 a 5 x 5 window, and passed through untouched wherever something moves.  It is ENCODER SIDE ONLY: it replaces the picture the codec is handed and nothing else -- no side file, no change
 of the .bin format, nothing for the decoder to know.  The arithmetic is stated in the header; tests/tnr_ref.py restates it
-in numpy, tests/me_ref.py the search and the compensation, tests/mesub_ref.py the quarter-pel refinement and interpolation.
+in numpy, tests/me_ref.py the search and the compensation, tests/mesub_ref.py the quarter-pel refinement and interpolation,
+tests/mesplit_ref.py the re-selection per sub-cell.
 
-    TNR(threshold, floor=64, pixel=None, search=None, penalty=4, intra=None, subpel=False)
+    TNR(threshold, floor=64, pixel=None, search=None, penalty=4, intra=None, subpel=False, split=False)
                                              the setting; .table() the 256 weights, .rcp_table() dcvc_tnr_fuse's reciprocals
     TnrFilter(tnr, size, device)             the state of ONE GOP stream on the device; .step(x_padded, intra, ahead=())
     StreamFilter                             what TnrFilter shares with redact.Redactor: validation, pictures, totals
@@ -21,7 +23,12 @@ where it was.  `penalty` is an untuned placeholder too.  Vectors are whole pixel
 is exhaustive on one level.  With subpel=True (opt-in, belongs to search) every vector is refined to QUARTER pixels over the
 49 candidates around it (dcvc_me_refine) and the picture is moved through a separable 7/8-tap interpolation filter
 (dcvc_me_compensate_sub in place of dcvc_me_compensate): an object that moves by a fraction of a pixel is blended with an
-interpolated copy of where it was, not with a misregistered one.
+interpolated copy of where it was, not with a misregistered one.  With split=True (opt-in, belongs to search, with or without
+subpel) every 8 x 8 quarter of a cell chooses again among the vectors that exist already, its own cell's and the eight
+neighbours' (dcvc_me_split: the same luma SAD and penalty, over 64 pixels), and the picture is moved sub-cell by sub-cell
+(dcvc_me_compensate_split in place of the cell compensation): a cell that straddles an object's edge no longer moves all of
+its pixels by a vector that is right for a part of them.  No new search range and no new filter; cells on an edge are still
+worse than the unfiltered source (what remains is the blend's window test, which is unchanged).
 
 With intra=K (opt-in, 1 .. 4, no default) the I picture is filtered too (include/dcvc_hip_tnr_fuse.h, csrc/tnr_fuse.hip;
 tests/tnr_fuse_ref.py restates it): it has no filtered predecessor, so it is blended in ONE pass with up to K pictures
@@ -45,6 +52,7 @@ MAX_T, MAX_FLOOR, MAX_P, FULL = 64, 255, 255, 256
 MAX_R, MAX_LAMBDA, PENALTY = 32, 255, 4  # (DCVC_ME_MAX_R, DCVC_ME_MAX_LAMBDA; the placeholder)
 MAX_REFS, RCP = 4, 1021  # (DCVC_TNR_FUSE_MAX_REFS, DCVC_TNR_FUSE_RCP)
 SUBPEL = 4  # (DCVC_MESUB_UNIT: with subpel, vectors are in 1 / 4 pixels)
+SPLIT = 8  # (DCVC_MESPLIT_SUB: with split, a vector per 8 x 8 sub-cell)
 ROWS = 64  # pictures' totals kept on the device between two copies to the host
 
 
@@ -59,7 +67,9 @@ class TNR:
     of the cell's SAD (0..255; belongs to search).  floor, pixel and penalty are untuned placeholders.  intra K: an I
     picture is blended with up to K pictures that follow it in its GOP (1..4; None: I pictures are passed through; no
     default of substance exists and no value is tuned).  subpel: the search's vectors are refined to quarter pixels and the
-    reference is interpolated (belongs to search; False: whole pixels)."""
+    reference is interpolated (belongs to search; False: whole pixels).  split: every 8 x 8 sub-cell chooses again among its
+    cell's vector and the eight neighbours' and the reference is moved sub-cell by sub-cell (belongs to search; False: one
+    vector a cell)."""
     threshold: int
     floor: int = 64
     pixel: int = None
@@ -67,6 +77,7 @@ class TNR:
     penalty: int = PENALTY
     intra: int = None
     subpel: bool = False
+    split: bool = False
 
     def __post_init__(self):
         object.__setattr__(self, "threshold", whole("threshold", self.threshold, 1, MAX_T))
@@ -84,6 +95,10 @@ class TNR:
             raise ValueError(f"subpel must be True or False, got {self.subpel!r}")
         if self.subpel and self.search is None:
             raise ValueError("subpel belongs to search: got subpel=True without search")
+        if not isinstance(self.split, bool):
+            raise ValueError(f"split must be True or False, got {self.split!r}")
+        if self.split and self.search is None:
+            raise ValueError("split belongs to search: got split=True without search")
 
     def table(self):
         """wtab of dcvc_tnr_step: the weight of the current picture by the window's mean difference a = 0 .. 255, as
@@ -99,6 +114,8 @@ class TNR:
             rd["intra"] = self.intra
         if self.subpel:  # (the unit of the vectors: quarter pixels)
             rd["subpel"] = SUBPEL
+        if self.split:  # (the side of a sub-cell)
+            rd["split"] = SPLIT
         return rd
 
     @staticmethod
@@ -195,7 +212,14 @@ class TnrFilter(StreamFilter):
     mvqs / costqs, one set per reference), and every search is followed by dcvc_me_refine, every compensation is a
     dcvc_me_compensate_sub: four launches a P step, 3 n + 1 a filtered I picture.  `moved` then counts the nonzero
     quarter-pel vectors, and the row gains `frac`, the cells whose vector has a fractional component, after `zero` and
-    before tnr.intra's number of references.  Without tnr.subpel none of this is allocated or launched."""
+    before tnr.intra's number of references.  Without tnr.subpel none of this is allocated or launched.
+
+    With tnr.split the filter also owns mv8 / cost8, the quarter-pel vector of every 8 x 8 sub-cell and its SAD (with
+    tnr.intra mv8s / cost8s, one set per reference); every search (and refinement) is followed by dcvc_me_split, on mvq at
+    unit 4 with tnr.subpel and on mv at unit 1 without, and every compensation is a dcvc_me_compensate_split: four launches a
+    P step without tnr.subpel and five with, 3 n + 1 and 4 n + 1 a filtered I picture.  moved, zero and frac stay the
+    cells'; the row gains `split`, the sub-cells whose vector differs from their cell's, after frac (after zero without
+    tnr.subpel) and before tnr.intra's number of references.  Without tnr.split none of this is allocated or launched."""
 
     def __init__(self, tnr, size, device, totals=True):
         import torch
@@ -204,7 +228,7 @@ class TnrFilter(StreamFilter):
             raise ValueError(f"tnr: expected a tnr.TNR, got {type(tnr).__name__}")
         self.tnr = tnr
         if tnr.search is not None:
-            self.untouched = (0, 0, 0, 0) + ((0,) if tnr.subpel else ())
+            self.untouched = (0, 0, 0, 0) + ((0,) if tnr.subpel else ()) + ((0,) if tnr.split else ())
         if tnr.intra is not None:  # (one more column: the number of references of the step)
             self.untouched = self.untouched + (0,)
         super().__init__(size, device, len(self.untouched), totals)
@@ -235,6 +259,13 @@ class TnrFilter(StreamFilter):
             self.mvqs = torch.empty((MAX_REFS, 2 * cells), dtype=torch.int16, device=self.device)
             self.costqs = torch.empty((MAX_REFS, cells), dtype=torch.int32, device=self.device)
             self.mvq, self.costq = self.mvqs[0], self.costqs[0]
+        if tnr.split and tnr.intra is None:
+            self.mv8 = torch.empty(8 * cells, dtype=torch.int16, device=self.device)    # (vy, vx) of every sub-cell, quarter pixels
+            self.cost8 = torch.empty(4 * cells, dtype=torch.int32, device=self.device)  # (uint32 words; a sub-cell's sum is < 2^14)
+        elif tnr.split:
+            self.mv8s = torch.empty((MAX_REFS, 8 * cells), dtype=torch.int16, device=self.device)
+            self.cost8s = torch.empty((MAX_REFS, 4 * cells), dtype=torch.int32, device=self.device)
+            self.mv8, self.cost8 = self.mv8s[0], self.cost8s[0]
         torch.cuda.synchronize(self.device)  # (the uploads above: a stream that uses them afterwards cannot race them)
 
     def _keep_step(self, t, n):
@@ -247,21 +278,36 @@ class TnrFilter(StreamFilter):
             cells += ((self.mvq.view(-1, 2) != 0).any(dim=1), self.zero, (self.mvq.view(-1, 2) & 3 != 0).any(dim=1))
         elif self.tnr.search is not None:
             cells += ((self.mv.view(-1, 2) != 0).any(dim=1), self.zero)
+        if self.tnr.split:  # (the sub-cells that hold a pixel and left their cell's vector, both in quarter pixels)
+            hc, wc = self.grid
+            own = (self.mvq if self.tnr.subpel else SUBPEL * self.mv).view(hc, 1, wc, 1, 2)
+            left = (self.mv8.view(hc, 2, wc, 2, 2) != own).any(dim=4).view(2 * hc, 2 * wc)
+            cells += (left[:-(-self.height // SPLIT), :-(-self.width // SPLIT)],)
         if self.tnr.intra is not None:
             self._rows[len(self._log.keys), len(cells)] = n
         self._keep(t, *cells)
 
     def _move(self, cur, crs, cps, ref, rrs, rps, comp, mv, j):
         """ref moved onto cur into comp by the searched vectors mv: dcvc_me_compensate, or with tnr.subpel dcvc_me_refine
-        into the quarter-pel vectors of reference j and dcvc_me_compensate_sub."""
+        into the quarter-pel vectors of reference j and dcvc_me_compensate_sub; with tnr.split dcvc_me_split on the cells'
+        vectors into the sub-cells' of reference j and dcvc_me_compensate_split in place of either compensation."""
         (h, w), (Hp, Wp) = (self.height, self.width), self.padded
-        if not self.tnr.subpel:
+        if not self.tnr.subpel and not self.tnr.split:
             devargs.launch("dcvc_me_compensate", self.device, ref.data_ptr(), rrs, rps, comp.data_ptr(), Wp, Hp * Wp, h, w, mv.data_ptr())
             return
-        mvq, costq = (self.mvq, self.costq) if self.tnr.intra is None else (self.mvqs[j], self.costqs[j])
-        devargs.launch("dcvc_me_refine", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, h, w, self.tnr.penalty,
-                       mv.data_ptr(), mvq.data_ptr(), costq.data_ptr())
-        devargs.launch("dcvc_me_compensate_sub", self.device, ref.data_ptr(), rrs, rps, comp.data_ptr(), Wp, Hp * Wp, h, w, mvq.data_ptr())
+        unit = 1
+        if self.tnr.subpel:
+            mvq, costq = (self.mvq, self.costq) if self.tnr.intra is None else (self.mvqs[j], self.costqs[j])
+            devargs.launch("dcvc_me_refine", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, h, w, self.tnr.penalty,
+                           mv.data_ptr(), mvq.data_ptr(), costq.data_ptr())
+            mv, unit = mvq, SUBPEL
+        if not self.tnr.split:
+            devargs.launch("dcvc_me_compensate_sub", self.device, ref.data_ptr(), rrs, rps, comp.data_ptr(), Wp, Hp * Wp, h, w, mv.data_ptr())
+            return
+        mv8, cost8 = (self.mv8, self.cost8) if self.tnr.intra is None else (self.mv8s[j], self.cost8s[j])
+        devargs.launch("dcvc_me_split", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, h, w, self.tnr.penalty, unit,
+                       mv.data_ptr(), mv8.data_ptr(), cost8.data_ptr())
+        devargs.launch("dcvc_me_compensate_split", self.device, ref.data_ptr(), rrs, rps, comp.data_ptr(), Wp, Hp * Wp, h, w, mv8.data_ptr())
 
     def _fuse(self, t, x_padded, ahead):
         """An I picture blended with the pictures `ahead` (1 .. 4 of them, checked): with tnr.search a search from the I
@@ -276,7 +322,7 @@ class TnrFilter(StreamFilter):
                                self.tnr.penalty, self.mvs[j].data_ptr(), self.costs[j].data_ptr(), self.zeros[j].data_ptr())
                 self._move(cur, crs, cps, r, rrs, rps, self.comps[j], self.mvs[j], j)
                 refs[j] = (self.comps[j], Wp, Hp * Wp)
-            self.launches += (3 if self.tnr.subpel else 2) * len(refs)
+            self.launches += (2 + self.tnr.subpel + self.tnr.split) * len(refs)
         elif len({r[1:] for r in refs}) > 1:  # (the kernel takes ONE pair of strides: the odd ones out are copied)
             for j, (r, rrs, rps) in enumerate(refs):
                 if (rrs, rps) != (Wp, Hp * Wp):
@@ -326,7 +372,7 @@ class TnrFilter(StreamFilter):
                            self.tnr.penalty, self.mv.data_ptr(), self.cost.data_ptr(), self.zero.data_ptr())
             self._move(cur, crs, cps, ref, rrs, rps, self.comp, self.mv, 0)
             ref, rrs, rps = self.comp, Wp, Hp * Wp
-            self.launches += 3 if self.tnr.subpel else 2
+            self.launches += 2 + self.tnr.subpel + self.tnr.split
         devargs.launch("dcvc_tnr_step", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, out.data_ptr(), Wp, Hp * Wp,
                        h, w, self.wtab.data_ptr(), self.tnr.pixel, self.sad.data_ptr(), self.held.data_ptr())
         self.launches += 1
