@@ -23,7 +23,7 @@
     python -m vcm_ts_amd.run_codec boxes (--frames DIR | --video FILE [--size WxH]) --out ROOT --threshold T [--learn KB KF]
                                          [--min-pixels P] [--grow G] [--min-cells C] [--max-boxes N]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT [--motion-border N] [--motion-q F]
-    python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P] [--tnr-search R [--tnr-penalty L] [--tnr-subpel] [--tnr-split]]
+    python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P] [--tnr-search R [--tnr-penalty L] [--tnr-subpel] [--tnr-split] [--tnr-levels L]]
     python -m vcm_ts_amd.run_codec encode ... --tnr T --tnr-intra K
     python -m vcm_ts_amd.run_codec encode ... --tnr T --grain [--grain-min-samples N]
     python -m vcm_ts_amd.run_codec decode ... --grain [PERCENT]
@@ -99,6 +99,12 @@ With --tnr-split (opt-in, belongs to --tnr-search, with or without --tnr-subpel)
 among its own cell's vector and the eight neighbours' and the previous filtered picture is moved sub-cell by sub-cell
 (vcm_ts_amd/tnr.py): one more kernel per P picture, and --report gains `frame_tnr_split`, the sub-cells whose
 vector differs from their cell's.
+With --tnr-levels L (1 or 2; opt-in, belongs to --tnr-search) the search is hierarchical and R may be 2 .. 64 (L = 1) or
+4 .. 128 (L = 2): the luma of both pictures is reduced to L coarser levels of 2 x 2 means, the coarsest is searched
+exhaustively and every level below chooses among the few vectors around twice the level above's and (0, 0)
+(vcm_ts_amd/tnr.py): 3 + L more kernels per P picture, and --report gains `frame_tnr_far`, the cells whose
+vector has a component beyond 32.  Fine texture defeats it (the means alias it), nothing is tuned, and --tnr-subpel and
+--tnr-split stop at R = 32 until their kernels are widened.
 With --tnr-intra K (1 .. 4; opt-in, no default, untuned) the I picture is filtered too: it is blended in one pass (one
 dcvc_tnr_fuse launch) with up to K pictures that FOLLOW it in its own GOP -- never a picture of another GOP, so GOP streams,
 shards and scene cuts keep the bytes of sequential coding -- each searched for and moved onto it first with --tnr-search, and
@@ -1214,6 +1220,9 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     With tnr.split (opt-in, with tnr.search) every 8 x 8 sub-cell chooses again among its cell's vector and the neighbours'
     and that picture is moved sub-cell by sub-cell; the report gains frame_tnr_split (the sub-cells whose vector differs from
     their cell's among the sub-cells that hold a pixel).
+    With tnr.levels = L (opt-in, with tnr.search, which may then reach 64 L pixels) the search is hierarchical over L coarser
+    levels of 2 x 2 luma means; the report gains frame_tnr_far (the cells whose vector has a component beyond 32 pixels among
+    the cells that hold a pixel).
     With tnr.intra = K (look-ahead, opt-in) every I picture is blended in one dcvc_tnr_fuse launch with up to K pictures that
     follow it in its own GOP (pulled ahead from the source by a _LookAhead, never past the next I picture), the P pictures
     start from the filtered I picture, the figures above are those of reference 0 for such an I picture, and the report
@@ -1818,7 +1827,8 @@ def _tnr_report_keys(tnr, filters, run, h, w):
     it was.  With tnr.subpel the vectors are quarter pixels, and frame_tnr_subpel is the cells whose vector has a fractional
     component among the cells that hold a pixel, 0.0 where nothing was searched.  With tnr.split frame_tnr_split is the
     sub-cells whose vector differs from their cell's among the 8 x 8 sub-cells that hold a pixel, 0.0 where nothing was
-    searched."""
+    searched.  With tnr.levels frame_tnr_far is the cells whose vector has a component beyond 32 pixels among the cells that
+    hold a pixel, 0.0 where nothing was searched."""
     def keys(rd, types, values):
         totals = _stream_totals(filters, run)
         order = sorted(totals)
@@ -1834,6 +1844,8 @@ def _tnr_report_keys(tnr, filters, run, h, w):
             if tnr.split:  # (the next column: the sub-cells that left their cell's vector)
                 subs = -(-h // 8) * -(-w // 8)  # the sub-cells that hold a pixel
                 rd["frame_tnr_split"] = [totals[g][5 if tnr.subpel else 4] / subs for g in order]
+            if tnr.levels is not None:  # (the next column: the cells beyond the full search's reach)
+                rd["frame_tnr_far"] = [totals[g][4 + tnr.subpel + tnr.split] / cells for g in order]
         if tnr.intra is not None:  # (every row then ends with the number of references of the step)
             rd["frame_tnr_refs"] = [totals[g][-1] for g in order]
 
@@ -2210,6 +2222,12 @@ def _parser():
                         "neighbours' (dcvc_me_split) and move the previous filtered picture sub-cell by sub-cell "
                         "(dcvc_me_compensate_split): one more kernel per P picture.  --report gains frame_tnr_split.  Cells on "
                         "an object's edge stay worse than the unfiltered source; nothing is claimed about rate or quality")
+    e.add_argument("--tnr-levels", type=int, default=None, metavar="L",
+                   help="with --tnr-search: search hierarchically over L coarser levels of 2 x 2 luma means, 1 or 2 "
+                        "(dcvc_me_pyramid, dcvc_me_coarse, dcvc_me_descend in place of dcvc_me_search: 3 + L more kernels per P "
+                        "picture); --tnr-search may then be 2 .. 64 (L = 1) or 4 .. 128 (L = 2).  --report gains frame_tnr_far.  "
+                        "Fine texture defeats it; --tnr-subpel and --tnr-split stop at R = 32; untuned, and nothing is claimed "
+                        "about rate or quality")
     e.add_argument("--tnr-intra", type=int, default=None, metavar="K",
                    help="with --tnr: filter I pictures too -- blend every I picture in one pass (dcvc_tnr_fuse) with up to K "
                         "pictures that follow it in its own GOP, each moved onto it first with --tnr-search, and start the "
@@ -2404,6 +2422,8 @@ def _encode_command(ap, a):
         ap.error("--tnr-subpel belongs to --tnr-search")
     if a.tnr_search is None and a.tnr_split:
         ap.error("--tnr-split belongs to --tnr-search")
+    if a.tnr_search is None and a.tnr_levels is not None:
+        ap.error("--tnr-levels belongs to --tnr-search")
     if a.tnr is None and a.tnr_intra is not None:
         ap.error("--tnr-intra belongs to --tnr")
     if a.tnr is not None:
@@ -2412,9 +2432,10 @@ def _encode_command(ap, a):
         try:
             tnr = N.TNR(a.tnr, **({} if a.tnr_floor is None else {"floor": a.tnr_floor}), pixel=a.tnr_pixel, search=a.tnr_search,
                         **({} if a.tnr_penalty is None else {"penalty": a.tnr_penalty}), intra=a.tnr_intra,
-                        **({"subpel": True} if a.tnr_subpel else {}), **({"split": True} if a.tnr_split else {}))
+                        **({"subpel": True} if a.tnr_subpel else {}), **({"split": True} if a.tnr_split else {}),
+                        **({} if a.tnr_levels is None else {"levels": a.tnr_levels}))
         except ValueError as ex:
-            ap.error(f"--tnr / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty / --tnr-intra / --tnr-subpel / --tnr-split: {ex}")
+            ap.error(f"--tnr / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty / --tnr-intra / --tnr-subpel / --tnr-split / --tnr-levels: {ex}")
     grain = None
     if a.grain_min_samples is not None and not a.grain:
         ap.error("--grain-min-samples belongs to --grain")

@@ -1,14 +1,15 @@
 """A motion-adaptive temporal noise prefilter (include/dcvc_hip_tnr.h, csrc/tnr.hip; with a motion search in front of it
 include/dcvc_hip_me.h, csrc/me.hip, to quarter pixels include/dcvc_hip_mesub.h, csrc/mesub.hip, and per 8 x 8 sub-cell
-include/dcvc_hip_mesplit.h, csrc/mesplit.hip) for fixed-camera
+include/dcvc_hip_mesplit.h, csrc/mesplit.hip, and a hierarchical search that reaches 128 pixels include/dcvc_hip_mepyr.h,
+csrc/mepyr.hip) for fixed-camera
 content, where a P picture's bits are dominated by sensor noise: every
 P picture the codec is handed is blended with the previous filtered picture wherever the luma of the two stays close over
 a 5 x 5 window, and passed through untouched wherever something moves.  It is ENCODER SIDE ONLY: it replaces the picture the codec is handed and nothing else -- no side file, no change
 of the .bin format, nothing for the decoder to know.  The arithmetic is stated in the header; tests/tnr_ref.py restates it
 in numpy, tests/me_ref.py the search and the compensation, tests/mesub_ref.py the quarter-pel refinement and interpolation,
-tests/mesplit_ref.py the re-selection per sub-cell.
+tests/mesplit_ref.py the re-selection per sub-cell, tests/mepyr_ref.py the hierarchical search.
 
-    TNR(threshold, floor=64, pixel=None, search=None, penalty=4, intra=None, subpel=False, split=False)
+    TNR(threshold, floor=64, pixel=None, search=None, penalty=4, intra=None, subpel=False, split=False, levels=None)
                                              the setting; .table() the 256 weights, .rcp_table() dcvc_tnr_fuse's reciprocals
     TnrFilter(tnr, size, device)             the state of ONE GOP stream on the device; .step(x_padded, intra, ahead=())
     StreamFilter                             what TnrFilter shares with redact.Redactor: validation, pictures, totals
@@ -20,7 +21,7 @@ COMPENSATED (opt-in): every 16 x 16 cell of a P picture is searched for in the p
 pixels (dcvc_me_search: luma SAD plus `penalty` codes per pixel of vector length), that picture is moved cell by cell
 (dcvc_me_compensate) and the unchanged dcvc_tnr_step blends against the moved picture, so a moving object is blended with
 where it was.  `penalty` is an untuned placeholder too.  Vectors are whole pixels, blocks do not overlap, and the search
-is exhaustive on one level.  With subpel=True (opt-in, belongs to search) every vector is refined to QUARTER pixels over the
+is exhaustive on one level (hierarchical with levels, below).  With subpel=True (opt-in, belongs to search) every vector is refined to QUARTER pixels over the
 49 candidates around it (dcvc_me_refine) and the picture is moved through a separable 7/8-tap interpolation filter
 (dcvc_me_compensate_sub in place of dcvc_me_compensate): an object that moves by a fraction of a pixel is blended with an
 interpolated copy of where it was, not with a misregistered one.  With split=True (opt-in, belongs to search, with or without
@@ -29,6 +30,20 @@ neighbours' (dcvc_me_split: the same luma SAD and penalty, over 64 pixels), and 
 (dcvc_me_compensate_split in place of the cell compensation): a cell that straddles an object's edge no longer moves all of
 its pixels by a vector that is right for a part of them.  No new search range and no new filter; cells on an edge are still
 worse than the unfiltered source (what remains is the blend's window test, which is unchanged).
+
+With levels=L (opt-in, 1 or 2, belongs to search) the search is HIERARCHICAL and search may be 2 .. 64 (L = 1) or 4 .. 128
+(L = 2): the luma of both pictures is reduced to L coarser levels of 2 x 2 rounded means (dcvc_me_pyramid), the coarsest level
+is searched exhaustively within ceil(R / 2^L) of its pixels (dcvc_me_coarse), and every level below chooses among the few
+vectors around twice the level above's and (0, 0) (dcvc_me_descend: 9 + 1 candidates at level 1, 25 + 1 at level 0).  It
+writes the three arrays dcvc_me_search writes, so everything behind it is unchanged.  On tests/mepyr_ref.py's fast clip
+(band-limited texture, an object moving 39 .. 61 pixels a picture) the full search at R = 32 finds the true vector in NO cell
+inside the object and leaves 6.6 .. 14.8 times the noisy source's squared error there; L = 1 at R = 64 finds it in every such
+cell, L = 2 in 75 .. 100 % of them, at 0.30 .. 1.51 and 0.42 .. 1.23 (one picture 3.40) of the source's error, and static
+ground stays at (0, 0).  FINE TEXTURE DEFEATS IT: with the frequencies of tests/mesub_ref.py's clip (0.08 .. 0.16 cycles a
+pixel) the 2 x 2 means alias the texture and the true vector is found only where the step is a multiple of the coarsest
+level's pixel.  Cells on the object's edge remain what they are.  Nothing is tuned: not the descents' windows, not the
+scaling of the penalty between levels.  subpel and split stop at search = 32 until their kernels (which clamp incoming
+vectors to +-32 and pack 9 bits a component) are widened: beyond it both are refused.
 
 With intra=K (opt-in, 1 .. 4, no default) the I picture is filtered too (include/dcvc_hip_tnr_fuse.h, csrc/tnr_fuse.hip;
 tests/tnr_fuse_ref.py restates it): it has no filtered predecessor, so it is blended in ONE pass with up to K pictures
@@ -53,6 +68,7 @@ MAX_R, MAX_LAMBDA, PENALTY = 32, 255, 4  # (DCVC_ME_MAX_R, DCVC_ME_MAX_LAMBDA; t
 MAX_REFS, RCP = 4, 1021  # (DCVC_TNR_FUSE_MAX_REFS, DCVC_TNR_FUSE_RCP)
 SUBPEL = 4  # (DCVC_MESUB_UNIT: with subpel, vectors are in 1 / 4 pixels)
 SPLIT = 8  # (DCVC_MESPLIT_SUB: with split, a vector per 8 x 8 sub-cell)
+MAX_LEVELS, PYR_R = 2, 64  # (DCVC_MEPYR_MAX_LEVELS; with levels = L, search is 2 L .. 64 L)
 ROWS = 64  # pictures' totals kept on the device between two copies to the host
 
 
@@ -69,7 +85,9 @@ class TNR:
     default of substance exists and no value is tuned).  subpel: the search's vectors are refined to quarter pixels and the
     reference is interpolated (belongs to search; False: whole pixels).  split: every 8 x 8 sub-cell chooses again among its
     cell's vector and the eight neighbours' and the reference is moved sub-cell by sub-cell (belongs to search; False: one
-    vector a cell)."""
+    vector a cell).  levels L: the search is hierarchical over L coarser levels of 2 x 2 means (1 or 2; belongs to search,
+    which may then be 2..64 for L = 1 and 4..128 for L = 2; None: the full search on one level, search 1..32); subpel and
+    split stop at search = 32."""
     threshold: int
     floor: int = 64
     pixel: int = None
@@ -78,6 +96,7 @@ class TNR:
     intra: int = None
     subpel: bool = False
     split: bool = False
+    levels: int = None
 
     def __post_init__(self):
         object.__setattr__(self, "threshold", whole("threshold", self.threshold, 1, MAX_T))
@@ -87,8 +106,13 @@ class TNR:
         if self.search is None:
             if self.penalty != PENALTY:
                 raise ValueError(f"penalty belongs to search: got penalty={self.penalty} without search")
-        else:
+            if self.levels is not None:
+                raise ValueError(f"levels belongs to search: got levels={self.levels} without search")
+        elif self.levels is None:
             object.__setattr__(self, "search", whole("search", self.search, 1, MAX_R))
+        else:
+            object.__setattr__(self, "levels", whole("levels", self.levels, 1, MAX_LEVELS))
+            object.__setattr__(self, "search", whole("search", self.search, 2 * self.levels, PYR_R * self.levels, f"with levels={self.levels}"))
         if self.intra is not None:
             object.__setattr__(self, "intra", whole("intra", self.intra, 1, MAX_REFS))
         if not isinstance(self.subpel, bool):
@@ -99,6 +123,9 @@ class TNR:
             raise ValueError(f"split must be True or False, got {self.split!r}")
         if self.split and self.search is None:
             raise ValueError("split belongs to search: got split=True without search")
+        for name in ("subpel", "split"):  # (dcvc_me_refine and dcvc_me_split clamp incoming vectors to +-32)
+            if getattr(self, name) and self.search > MAX_R:
+                raise ValueError(f"{name} stops at search={MAX_R} until its kernel is widened: got {name}=True with search={self.search}")
 
     def table(self):
         """wtab of dcvc_tnr_step: the weight of the current picture by the window's mean difference a = 0 .. 255, as
@@ -116,6 +143,8 @@ class TNR:
             rd["subpel"] = SUBPEL
         if self.split:  # (the side of a sub-cell)
             rd["split"] = SPLIT
+        if self.levels is not None:  # (the coarser levels of the hierarchical search)
+            rd["levels"] = self.levels
         return rd
 
     @staticmethod
@@ -219,7 +248,15 @@ class TnrFilter(StreamFilter):
     unit 4 with tnr.subpel and on mv at unit 1 without, and every compensation is a dcvc_me_compensate_split: four launches a
     P step without tnr.subpel and five with, 3 n + 1 and 4 n + 1 a filtered I picture.  moved, zero and frac stay the
     cells'; the row gains `split`, the sub-cells whose vector differs from their cell's, after frac (after zero without
-    tnr.subpel) and before tnr.intra's number of references.  Without tnr.split none of this is allocated or launched."""
+    tnr.subpel) and before tnr.intra's number of references.  Without tnr.split none of this is allocated or launched.
+
+    With tnr.levels = L the filter also owns the byte planes of the current picture and of the reference, ycur / yref (L + 1
+    levels each, rows padded to 4 bytes; with tnr.intra yrefs, one set per reference), and the coarser levels' vectors mvl
+    (with tnr.intra mvls, one set per reference), and in place of every dcvc_me_search it launches dcvc_me_pyramid(cur),
+    dcvc_me_pyramid(ref), dcvc_me_coarse, dcvc_me_descend to level 1 when L = 2 and dcvc_me_descend to level 0, which writes
+    mv / cost / zero: 3 + L more launches a P step, 1 + (1 + L) n more a filtered I picture, whose own pyramid is built once.
+    The row gains `far`, the cells whose vector has a component beyond 32, after split, frac or zero (whichever is last) and
+    before tnr.intra's number of references.  Without tnr.levels none of this is allocated or launched."""
 
     def __init__(self, tnr, size, device, totals=True):
         import torch
@@ -228,7 +265,7 @@ class TnrFilter(StreamFilter):
             raise ValueError(f"tnr: expected a tnr.TNR, got {type(tnr).__name__}")
         self.tnr = tnr
         if tnr.search is not None:
-            self.untouched = (0, 0, 0, 0) + ((0,) if tnr.subpel else ()) + ((0,) if tnr.split else ())
+            self.untouched = (0, 0, 0, 0) + ((0,) if tnr.subpel else ()) + ((0,) if tnr.split else ()) + ((0,) if tnr.levels else ())
         if tnr.intra is not None:  # (one more column: the number of references of the step)
             self.untouched = self.untouched + (0,)
         super().__init__(size, device, len(self.untouched), totals)
@@ -266,6 +303,23 @@ class TnrFilter(StreamFilter):
             self.mv8s = torch.empty((MAX_REFS, 8 * cells), dtype=torch.int16, device=self.device)
             self.cost8s = torch.empty((MAX_REFS, 4 * cells), dtype=torch.int32, device=self.device)
             self.mv8, self.cost8 = self.mv8s[0], self.cost8s[0]
+        if tnr.levels is not None:
+            def planes():  # one level's luma a tensor, a byte per pixel, rows padded to a multiple of 4
+                sides, out = (self.height, self.width), []
+                for _ in range(tnr.levels + 1):
+                    out.append(torch.empty((sides[0], -(-sides[1] // 4) * 4), dtype=torch.uint8, device=self.device))
+                    sides = (-(-sides[0] // 2), -(-sides[1] // 2))
+                return out
+
+            def vectors():  # (dy, dx) of every cell at level 1 (and 2), in pixels of the level
+                return [torch.empty(2 * cells, dtype=torch.int16, device=self.device) for _ in range(tnr.levels)]
+
+            self.ycur = planes()
+            if tnr.intra is None:
+                self.yref, self.mvl = planes(), vectors()
+            else:
+                self.yrefs, self.mvls = [planes() for _ in range(MAX_REFS)], [vectors() for _ in range(MAX_REFS)]
+                self.yref, self.mvl = self.yrefs[0], self.mvls[0]
         torch.cuda.synchronize(self.device)  # (the uploads above: a stream that uses them afterwards cannot race them)
 
     def _keep_step(self, t, n):
@@ -283,9 +337,37 @@ class TnrFilter(StreamFilter):
             own = (self.mvq if self.tnr.subpel else SUBPEL * self.mv).view(hc, 1, wc, 1, 2)
             left = (self.mv8.view(hc, 2, wc, 2, 2) != own).any(dim=4).view(2 * hc, 2 * wc)
             cells += (left[:-(-self.height // SPLIT), :-(-self.width // SPLIT)],)
+        if self.tnr.levels is not None:  # (the cells that the full search could not have reached)
+            cells += ((self.mv.view(-1, 2).abs() > MAX_R).any(dim=1),)
         if self.tnr.intra is not None:
             self._rows[len(self._log.keys), len(cells)] = n
         self._keep(t, *cells)
+
+    def _pyramid(self, pic, rs, ps, planes):
+        """The byte planes of a picture's crop: dcvc_me_pyramid, the only reader of fp32 in the hierarchical search."""
+        y = planes + [None] * (MAX_LEVELS + 1 - len(planes))
+        devargs.launch("dcvc_me_pyramid", self.device, pic.data_ptr(), rs, ps, self.height, self.width, self.tnr.levels,
+                       *(v for p in y for v in ((p.data_ptr(), p.shape[1]) if p is not None else (None, 0))))
+
+    def _search(self, cur, crs, cps, ref, rrs, rps, mv, cost, zero, j, built=False):
+        """The vectors of cur in ref into mv / cost / zero of reference j: dcvc_me_search, or with tnr.levels the chain that
+        stands in its place (built: cur's byte planes are there already).  -> the launches."""
+        (h, w), L, R, lam = (self.height, self.width), self.tnr.levels, self.tnr.search, self.tnr.penalty
+        if L is None:
+            devargs.launch("dcvc_me_search", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, h, w, R, lam, mv.data_ptr(),
+                           cost.data_ptr(), zero.data_ptr())
+            return 1
+        yc, (yr, mvl) = self.ycur, (self.yref, self.mvl) if self.tnr.intra is None else (self.yrefs[j], self.mvls[j])
+        if not built:
+            self._pyramid(cur, crs, cps, yc)
+        self._pyramid(ref, rrs, rps, yr)
+        devargs.launch("dcvc_me_coarse", self.device, yc[L].data_ptr(), yc[L].shape[1], yr[L].data_ptr(), yr[L].shape[1], h, w, R, L, lam,
+                       mvl[L - 1].data_ptr())
+        for level in range(L - 1, -1, -1):
+            out = (mvl[level - 1].data_ptr(), None, None) if level else (mv.data_ptr(), cost.data_ptr(), zero.data_ptr())
+            devargs.launch("dcvc_me_descend", self.device, yc[level].data_ptr(), yc[level].shape[1], yr[level].data_ptr(), yr[level].shape[1],
+                           h, w, R, L, level, lam, mvl[level].data_ptr(), *out)
+        return (0 if built else 1) + 2 + L
 
     def _move(self, cur, crs, cps, ref, rrs, rps, comp, mv, j):
         """ref moved onto cur into comp by the searched vectors mv: dcvc_me_compensate, or with tnr.subpel dcvc_me_refine
@@ -317,12 +399,11 @@ class TnrFilter(StreamFilter):
         cur, crs, cps = devargs.planar(x_padded.detach()[..., :h, :w])  # (the crops, read in place)
         refs = [devargs.planar(r.detach()[..., :h, :w]) for r in ahead]
         if self.tnr.search is not None:
-            for j, (r, rrs, rps) in enumerate(refs):
-                devargs.launch("dcvc_me_search", self.device, cur.data_ptr(), crs, cps, r.data_ptr(), rrs, rps, h, w, self.tnr.search,
-                               self.tnr.penalty, self.mvs[j].data_ptr(), self.costs[j].data_ptr(), self.zeros[j].data_ptr())
+            for j, (r, rrs, rps) in enumerate(refs):  # (the I source's byte planes are built once, with reference 0)
+                self.launches += self._search(cur, crs, cps, r, rrs, rps, self.mvs[j], self.costs[j], self.zeros[j], j, built=j > 0)
                 self._move(cur, crs, cps, r, rrs, rps, self.comps[j], self.mvs[j], j)
                 refs[j] = (self.comps[j], Wp, Hp * Wp)
-            self.launches += (2 + self.tnr.subpel + self.tnr.split) * len(refs)
+            self.launches += (1 + self.tnr.subpel + self.tnr.split) * len(refs)
         elif len({r[1:] for r in refs}) > 1:  # (the kernel takes ONE pair of strides: the odd ones out are copied)
             for j, (r, rrs, rps) in enumerate(refs):
                 if (rrs, rps) != (Wp, Hp * Wp):
@@ -368,11 +449,10 @@ class TnrFilter(StreamFilter):
         cur, crs, cps = devargs.planar(x_padded.detach()[..., :h, :w])  # (the crops, read in place)
         ref, rrs, rps = devargs.planar(self.ref[..., :h, :w])
         if self.tnr.search is not None:
-            devargs.launch("dcvc_me_search", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, h, w, self.tnr.search,
-                           self.tnr.penalty, self.mv.data_ptr(), self.cost.data_ptr(), self.zero.data_ptr())
+            self.launches += self._search(cur, crs, cps, ref, rrs, rps, self.mv, self.cost, self.zero, 0)
             self._move(cur, crs, cps, ref, rrs, rps, self.comp, self.mv, 0)
             ref, rrs, rps = self.comp, Wp, Hp * Wp
-            self.launches += 2 + self.tnr.subpel + self.tnr.split
+            self.launches += 1 + self.tnr.subpel + self.tnr.split
         devargs.launch("dcvc_tnr_step", self.device, cur.data_ptr(), crs, cps, ref.data_ptr(), rrs, rps, out.data_ptr(), Wp, Hp * Wp,
                        h, w, self.wtab.data_ptr(), self.tnr.pixel, self.sad.data_ptr(), self.held.data_ptr())
         self.launches += 1
