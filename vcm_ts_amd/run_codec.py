@@ -837,17 +837,34 @@ def _png_pictures(reader, order, size, dev, pool, io_workers, sharers):
         yield pad_frame(u8_to_unit_float(ring.upload()))
 
 
-def _video_pictures(reader, order, spec, quantize8, dev):
+def _video_pictures(reader, order, spec, quantize8, dev, deinterlace=None, moved=None):
     """(the padded RGB picture the codec takes, the file's samples on the device) of every frame of a yuv reader that
     `order` names: the one path from the file to the codec (a ring of pinned buffers, one asynchronous copy, the colour
-    conversion on the device) of the coding pass, the scene-cut scan and the motion scan."""
+    conversion on the device) of the coding pass, the scene-cut scan and the motion scan.
+    deinterlace: a deint.Deinterlace -- `order` then names OUTPUT PICTURES; the up to three file frames a picture needs
+    go up through the same ring (what the previous picture uploaded is kept: a sequential order uploads every frame once),
+    one dcvc_deinterlace420 launch makes the progressive I420 buffer, and that buffer is the `samples` of the pair and what
+    the unchanged colour conversion reads.  moved: a dictionary that then takes {picture: the sum of its `moved` words, on
+    the device}."""
     from . import yuv as Y
 
     sample_dtype = torch.uint8 if spec.bit_depth == 8 else torch.int16
     ring = _PinnedRing(dev, reader.frame_bytes)
+
+    def upload(n):
+        reader.read_into(n, ring.host())
+        return ring.upload().view(sample_dtype)
+
+    held = {}  # file frame -> its samples on the device, of the picture before
     for g in order:
-        reader.read_into(g, ring.host())
-        samples = ring.upload().view(sample_dtype)
+        if deinterlace is None:
+            samples = upload(g)
+        else:
+            frames, second = deinterlace.needs(g, reader.n_frames)
+            held = {n: held[n] if n in held else upload(n) for n in sorted(set(frames))}
+            samples, words = deinterlace.step(*(held[n] for n in frames), reader.height, reader.width, spec.bit_depth, second)
+            if moved is not None:
+                moved[g] = words.sum(dtype=torch.int64)
         yield Y.yuv420_to_rgb(samples, reader.height, reader.width, spec, pad=True, quantize8=quantize8), samples
 
 
@@ -887,27 +904,55 @@ class _VideoSource:
     """A `.y4m` / raw `.yuv` file (or an open yuv reader, which then stays the caller's to close) as the source of a file
     loop.  open() opens the file: the reader, the colour description, `size` and `n_frames`.  Every refusal about the file
     happens there, before any GPU work: what yuv.open_video refuses, a bit depth that is not the description's, a file
-    without frames."""
+    without frames.
+    deinterlace: None, a deint.Deinterlace, or a mode ("frame" / "field") whose field order the file's header gives -- the
+    file is then opened as interlaced material, `n_frames` is the number of OUTPUT PICTURES (which max_frames counts) and
+    pictures() numbers pictures; refused in open() as well: a height that is no multiple of 4, a missing field order.
+    keep_moved: keep every picture's `moved` total on the device for the report (deint_moved())."""
 
-    def __init__(self, video, device, size=None, spec=None, quantize8=False, bit_depth=8, fps=None, max_frames=None):
+    def __init__(self, video, device, size=None, spec=None, quantize8=False, bit_depth=8, fps=None, max_frames=None, deinterlace=None,
+                 keep_moved=False):
         self.video, self.dev, self.args, self.spec, self.quantize8 = video, torch.device(device), (size, bit_depth, fps), spec, quantize8
-        self.max_frames, self.reader = max_frames, None
+        self.max_frames, self.reader, self.deinterlace = max_frames, None, deinterlace
+        self.moved = {} if keep_moved and deinterlace is not None else None
 
     def open(self):
         from . import yuv as Y
 
-        self.reader = reader = Y.open_video(self.video, *self.args) if isinstance(self.video, (str, os.PathLike)) else self.video
+        if isinstance(self.video, (str, os.PathLike)):
+            more = {} if self.deinterlace is None else {"interlaced": True, "field_order": getattr(self.deinterlace, "order", None)}
+            self.reader = Y.open_video(self.video, *self.args, **more)
+        else:
+            self.reader = self.video
+        reader = self.reader
         self.spec = self.spec or reader.spec()
         if self.spec.bit_depth != reader.bit_depth:
             raise ValueError(f"the file holds {reader.bit_depth}-bit samples, the colour description says {self.spec.bit_depth}")
         self.size = (reader.height, reader.width)
-        self.n_frames = reader.n_frames if self.max_frames is None else min(reader.n_frames, int(self.max_frames))
+        n = reader.n_frames
+        if self.deinterlace is not None:
+            from . import deint as DI
+
+            if not isinstance(self.deinterlace, DI.Deinterlace):
+                if reader.field_order is None:
+                    raise ValueError(f"{getattr(reader, 'path', self.video)}: deinterlacing needs a field order and the file names none "
+                                     f"(--field-order tff|bff)")
+                self.deinterlace = DI.Deinterlace(self.deinterlace, reader.field_order)
+            DI.check_height(reader.height)
+            n = self.deinterlace.pictures_of(n)
+        self.n_frames = n if self.max_frames is None else min(n, int(self.max_frames))
         if self.n_frames < 1:
             raise ValueError(f"{getattr(reader, 'path', self.video)}: no frames")
 
     def pictures(self, order, sharers=1):
-        """(the padded picture the codec takes, the file's samples on the device) of every frame `order` names."""
-        return _video_pictures(self.reader, order, self.spec, self.quantize8, self.dev)
+        """(the padded picture the codec takes, the file's samples on the device) of every frame `order` names -- with
+        deinterlace, of every output picture it names and the progressive samples made for it."""
+        return _video_pictures(self.reader, order, self.spec, self.quantize8, self.dev, self.deinterlace, self.moved)
+
+    def deint_moved(self):
+        """[the `moved` total of every output picture], one copy to the host after the device has finished."""
+        torch.cuda.synchronize(self.dev)
+        return torch.stack([self.moved[g] for g in range(self.n_frames)]).tolist()
 
     def close(self):
         if self.reader is not None and self.reader is not self.video:
@@ -971,7 +1016,7 @@ class _VideoStage:
     def __init__(self, path, spec=None, fps=None, **extras):
         """spec, fps, extras (chroma, interlace, aspect): of the file to write; an encode takes them from its source."""
         self.path, self.spec, self.fps, self.container, self.extras = path, spec, fps, None, extras
-        self.writer, self.outs, self.cur = None, None, {}
+        self.writer, self.outs, self.cur, self.deinterlace = None, None, {}, None
 
     def open(self, size, streams=1, source=None):
         from . import yuv as Y
@@ -981,6 +1026,11 @@ class _VideoStage:
             reader = source.reader
             self.spec, self.fps, self.container = source.spec, reader.fps, "y4m" if isinstance(reader, Y.Y4MReader) else "yuv"
             self.extras = {name: getattr(reader, name, None) for name in ("chroma", "interlace", "aspect")}
+            self.deinterlace = source.deinterlace
+            if self.deinterlace is not None:  # (what was coded is progressive: a picture per field doubles the rate)
+                self.extras["interlace"] = "p"
+                if self.fps and self.deinterlace.mode == "field":
+                    self.fps = (2 * self.fps[0], self.fps[1])
         if self.path:
             self.writer = Y.create_video(self.path, size[1], size[0], self.spec, self.fps, **self.extras)
             self.outs = [_VideoOut(self.writer) for _ in range(streams)]
@@ -1020,7 +1070,7 @@ class _VideoStage:
 
     def finish(self, bin_dir, n_frames, gop, roi, residual_step):
         write_sequence_info(bin_dir, self.size[1], self.size[0], n_frames, gop, self.fps, self.spec, self.container, **self.extras,
-                            roi=roi, residual_step=residual_step)
+                            roi=roi, residual_step=residual_step, deinterlace=self.deinterlace)
 
 
 def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
@@ -1122,7 +1172,8 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
     finally:
         source.close()
     out.finish(bin_dir, plan.n_frames, gop, layer.roi if layer else None, residual_step if rec_out else None)
-    keys = [_roi_report_keys(h, w) if layer else None, out.report_keys(), _enh_report_keys(rec_out, h, w) if rec_out else None,
+    keys = [_roi_report_keys(h, w) if layer else None, out.report_keys(), _deint_report_keys(source) if report else None,
+            _enh_report_keys(rec_out, h, w) if rec_out else None,
             _tnr_report_keys(tnr, filters, run, h, w) if filters else None,
             _redact_report_keys(redact, redaction, run, h, w) if redaction else None]
     return run.results(report, [k for k in keys if k])
@@ -1437,9 +1488,10 @@ SEQUENCE_JSON = "sequence.json"
 
 
 def write_sequence_info(bin_dir, width, height, frames, gop, fps, spec, container, chroma=None, interlace=None, aspect=None,
-                        roi=None, residual_step=None):
+                        roi=None, residual_step=None, deinterlace=None):
     """What decode_video needs beside the .bin files (which stay what they are): size, frame count, GOP length, frame
-    rate and colour description of the source, and the container it came in."""
+    rate and colour description of the source, and the container it came in.  deinterlace: the deint.Deinterlace the
+    pictures were made with, for information (frames, fps and interlace are then the coded pictures': progressive)."""
     info = {"width": int(width), "height": int(height), "frames": int(frames), "gop": int(gop),
             "fps": list(fps) if fps else None, "color": spec.to_json(), "container": container, "chroma": chroma,
             "interlace": interlace, "aspect": aspect}
@@ -1447,6 +1499,8 @@ def write_sequence_info(bin_dir, width, height, frames, gop, fps, spec, containe
         info["roi"] = roi.to_json()
     if residual_step is not None:  # the step of the coded residual layer (residual_bins=; every record carries it too)
         info["residual_step"] = int(residual_step)
+    if deinterlace is not None:
+        info["deinterlace"] = deinterlace.to_json()
     return S.write_sidecar(bin_dir, SEQUENCE_JSON, info)
 
 
@@ -1941,6 +1995,19 @@ def _bit_log(bit_map, bit_dir, layer, roi_q):
     return (lambda g: labels_from_boxes(layer.boxes(g), layer.size[0], layer.size[1], grow, device=layer.dev)), bit_dir
 
 
+def _deint_report_keys(source):
+    """`deinterlace` (the setting) and `frame_deint_moved` (per picture, the missing luma samples that were not simply
+    woven) of a source that deinterlaces; None for any other."""
+    if getattr(source, "moved", None) is None:
+        return None
+
+    def keys(rd, types, values):
+        rd["deinterlace"] = source.deinterlace.to_json()
+        rd["frame_deint_moved"] = source.deint_moved()
+
+    return keys
+
+
 def _roi_report_keys(h, w):
     def keys(rd, types, values):
         from . import roi as X
@@ -1973,7 +2040,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
                  min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1,
-                 picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None, grain=None):
+                 picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None, grain=None, deinterlace=None):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -2000,11 +2067,19 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     against the file's own samples; sequence.json is the same with or without.
     redact: as encode_folder -- after the colour conversion and tnr (RGB only); redact.json lies beside sequence.json, which
     is the same with or without.
-    grain: as encode_folder (grain.json beside the .bin files; sequence.json is the same with or without)."""
+    grain: as encode_folder (grain.json beside the .bin files; sequence.json is the same with or without).
+    deinterlace: None, a deint.Deinterlace, or "frame" / "field" with the field order of the file's header -- the file is
+    interlaced material (a Y4M It / Ib, any file with an explicit order) and what is coded are progressive pictures made
+    from its fields on the device (vcm_ts_amd/deint.py), one per frame or one per field, in front of the colour
+    conversion.  Everything above then speaks of those pictures: max_frames counts them, the report's YUV figures are
+    against their samples, recon_video is progressive (the frame rate doubled in "field" mode), and sequence.json says
+    so and records the setting.  The report gains `deinterlace` and `frame_deint_moved`.  An open reader must have been
+    opened with interlaced=True.  Picture g depends on the file and g alone: not on GOPs, gop_streams or max_frames."""
     options = locals()
     video, recon_video = options.pop("video"), options.pop("recon_video")
     source = _VideoSource(video, device, **{name: options.pop(name) for name in ("size", "spec", "quantize8", "bit_depth", "fps",
-                                                                                 "max_frames")})
+                                                                                 "max_frames", "deinterlace")},
+                          keep_moved=bool(report))
     return _encode_sequence(source, _VideoStage(recon_video), **options)
 
 
@@ -2056,6 +2131,31 @@ def _video_args(ap, a):
         ap.error(str(ex))
 
 
+def _deint_option(ap, a):
+    """--deinterlace / --field-order of encode and boxes before the file is opened: (the keywords of yuv.open_video, the
+    function that makes the deint.Deinterlace of the opened reader or refuses through ap.error)."""
+    if a.field_order is not None and a.deinterlace is None:
+        ap.error("--field-order belongs to --deinterlace")
+    if a.deinterlace is not None and a.video is None:
+        ap.error("--deinterlace belongs to --video: a PNG folder holds progressive pictures")
+    if a.deinterlace is None:
+        return {}, lambda reader: None
+
+    def setting(reader):
+        from . import deint as DI
+
+        if reader.field_order is None:
+            ap.error(f"--deinterlace: {a.video} names no field order (a .yuv file, or a Y4M header that says progressive): "
+                     f"give --field-order tff|bff")
+        try:
+            DI.check_height(reader.height)
+            return DI.Deinterlace(a.deinterlace, reader.field_order)
+        except ValueError as ex:
+            ap.error(f"--deinterlace: {ex}")
+
+    return {"interlaced": True, "field_order": a.field_order}, setting
+
+
 def _motion_boxes(source, root, params):
     """The motion scan of motion_boxes_folder / motion_boxes_video over a source, which is closed on every exit."""
     from . import motionroi as M
@@ -2080,10 +2180,11 @@ def motion_boxes_folder(frames_dir, root, params, device="cuda:0", io_workers=8,
 
 
 def motion_boxes_video(video, root, params, device="cuda:0", size=None, spec=None, quantize8=False, bit_depth=8, fps=None,
-                       max_frames=None):
+                       max_frames=None, deinterlace=None):
     """motion_boxes_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height): the pictures come
-    through the ring, copy and colour conversion (spec, quantize8) of encode_video's coding pass."""
-    return _motion_boxes(_VideoSource(video, device, size, spec, quantize8, bit_depth, fps, max_frames), root, params)
+    through the ring, copy and colour conversion (spec, quantize8) of encode_video's coding pass -- with deinterlace
+    (encode_video's) through its deinterlacer too, so the boxes are numbered as the pictures it codes."""
+    return _motion_boxes(_VideoSource(video, device, size, spec, quantize8, bit_depth, fps, max_frames, deinterlace), root, params)
 
 
 def _parser():
@@ -2103,6 +2204,14 @@ def _parser():
         p.add_argument("--matrix", default=None, choices=["bt709", "bt601"], help="default bt709")
         p.add_argument("--range", default=None, choices=["limited", "full"], help="default: the Y4M header's XCOLORRANGE, else limited")
         p.add_argument("--siting", default=None, choices=["left", "center"], help="chroma siting; default: the Y4M header's, else left")
+        p.add_argument("--deinterlace", default=None, choices=["frame", "field"],
+                       help="with --video: the file is interlaced 4:2:0 material; make progressive pictures from its fields on the "
+                            "GPU (a motion-adaptive deinterlacer on the sample planes, vcm_ts_amd/deint.py) and code those: one per "
+                            "frame (the earlier field kept) or one per field (twice the pictures, twice the frame rate).  "
+                            "Every picture number then counts output pictures.  Untuned; no inverse telecine")
+        p.add_argument("--field-order", default=None, choices=["tff", "bff"],
+                       help="with --deinterlace: which field of a frame is earlier.  A Y4M header (It / Ib) decides and this "
+                            "overrides it; required for a .yuv file, for Im and for a file whose header says Ip")
         p.add_argument("--quantize8", action="store_true",
                        help="with --video: round the converted picture to 8-bit RGB before coding it (what a PNG of it would hold)")
     b.add_argument("--out", required=True, metavar="ROOT", help="where motion_coords/ and motion.json go")
@@ -2356,11 +2465,12 @@ def _boxes_command(ap, a):
         params = M.MotionParams(a.threshold, **given)
     except ValueError as ex:
         ap.error(f"boxes: {ex}")
+    more, setting = _deint_option(ap, a)
     try:
         if a.video is not None:
             size, fps = _video_args(ap, a)
-            with Y.open_video(a.video, size, a.bit_depth, fps) as reader:
-                boxes = motion_boxes_video(reader, a.out, params, a.device, quantize8=a.quantize8,
+            with Y.open_video(a.video, size, a.bit_depth, fps, **more) as reader:
+                boxes = motion_boxes_video(reader, a.out, params, a.device, quantize8=a.quantize8, deinterlace=setting(reader),
                                            spec=reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting))
         else:
             boxes = motion_boxes_folder(a.frames, a.out, params, a.device, io_workers=a.io_workers)
@@ -2500,6 +2610,7 @@ def _encode_command(ap, a):
         ap.error("--recon (a PNG folder) belongs to --frames; use --recon-video with --video")
     if a.png_device and not a.recon:
         ap.error("--png-device belongs to --recon (the PNG folder)")
+    more, setting = _deint_option(ap, a)
     size = fps = None
     if a.video is not None:
         from . import yuv as Y
@@ -2547,9 +2658,16 @@ def _encode_command(ap, a):
                    q_range=a.q_range, residual_bins=a.residual_bins, residual_step=a.residual_step, picture_hash=a.picture_hash,
                    base_scale=a.base_scale, aq=aq, tnr=tnr, redact=redact, grain=grain)
     if a.video is not None:
-        with Y.open_video(a.video, size, a.bit_depth, fps) as reader:
+        try:
+            reader = Y.open_video(a.video, size, a.bit_depth, fps, **more)
+        except ValueError as ex:
+            if not more:
+                raise
+            ap.error(f"--deinterlace: {ex}")
+        with reader:
             spec = reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting)
-            bits, size, *rd = encode_video(reader, a.bins, a.recon_video, spec=spec, quantize8=a.quantize8, **options)
+            bits, size, *rd = encode_video(reader, a.bins, a.recon_video, spec=spec, quantize8=a.quantize8, **options,
+                                           **({"deinterlace": setting(reader)} if more else {}))
     else:
         bits, size, *rd = encode_folder(a.frames, a.bins, a.recon, png_device=a.png_device, **options)
     if rd:

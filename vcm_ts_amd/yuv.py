@@ -223,9 +223,14 @@ class _Indexed:
 
 
 class RawYUVReader(_Indexed):
-    """Headerless I420 (`.yuv`): the caller knows size and depth."""
+    """Headerless I420 (`.yuv`): the caller knows size and depth -- and, for interlaced material, the field order
+    (`field_order`: "tff", "bff" or None; the reader only carries it, vcm_ts_amd/deint.py uses it)."""
+    field_order = None
 
-    def __init__(self, path, width, height, bit_depth=8):
+    def __init__(self, path, width, height, bit_depth=8, field_order=None):
+        if field_order not in (None, "tff", "bff"):
+            raise ValueError(f"field_order must be 'tff' or 'bff', got {field_order!r}")
+        self.field_order = field_order
         check_size(height, width)
         if bit_depth not in (8, 10):
             raise ValueError(f"bit_depth must be 8 or 10, got {bit_depth!r}")
@@ -253,9 +258,16 @@ class RawYUVReader(_Indexed):
 
 
 class Y4MReader(RawYUVReader):
-    """YUV4MPEG2, progressive 4:2:0 at 8 or 10 bits.  Everything is validated when the file is opened."""
+    """YUV4MPEG2, progressive 4:2:0 at 8 or 10 bits.  Everything is validated when the file is opened.
+    interlaced=True (opt-in: the caller deinterlaces, vcm_ts_amd/deint.py) also accepts It and Ib, and Im when a
+    field_order is given; `field_order` is then "tff" / "bff" -- the explicit one, else the header's -- or None for a file
+    whose header says progressive and no explicit order."""
 
-    def __init__(self, path):
+    def __init__(self, path, interlaced=False, field_order=None):
+        if field_order not in (None, "tff", "bff"):
+            raise ValueError(f"field_order must be 'tff' or 'bff', got {field_order!r}")
+        if field_order is not None and not interlaced:
+            raise ValueError("field_order belongs to interlaced=True")
         with open(path, "rb") as f:
             head = f.read(1024)
         end = head.find(b"\n")
@@ -276,8 +288,14 @@ class Y4MReader(RawYUVReader):
             width, height = int(h["W"]), int(h["H"])
         except ValueError:
             raise ValueError(f"{path}: bad size in Y4M header {h.get('W')!r} x {h.get('H')!r}") from None
-        if h.get("I", "p") not in ("p", "?"):
-            raise ValueError(f"{path}: interlaced material (I{h['I']}) is not supported")
+        mark = h.get("I", "p")
+        if mark not in ("p", "?") and not interlaced:
+            raise ValueError(f"{path}: interlaced material (I{h['I']}) is not supported (encode --deinterlace takes It and Ib)")
+        if mark not in ("p", "?", "t", "b", "m"):
+            raise ValueError(f"{path}: unknown interlacing mark I{mark}")
+        if mark == "m" and field_order is None:
+            raise ValueError(f"{path}: mixed interlaced material (Im) names no field order: give one (--field-order)")
+        self.field_order = field_order or {"t": "tff", "b": "bff"}.get(mark)
         chroma = h.get("C", "420")
         if chroma not in Y4M_CHROMA:
             raise ValueError(f"{path}: chroma format C{chroma} is not supported (4:2:0 at 8 or 10 bits only)")
@@ -372,15 +390,18 @@ class Y4MWriter(RawYUVWriter):
         self.start, self.lead = len(self._head), 6
 
 
-def open_video(path, size=None, bit_depth=8, fps=None):
-    """A reader for `path` by its extension: `.y4m`, or `.yuv` with size=(width, height)."""
+def open_video(path, size=None, bit_depth=8, fps=None, interlaced=False, field_order=None):
+    """A reader for `path` by its extension: `.y4m`, or `.yuv` with size=(width, height).  interlaced, field_order: as
+    Y4MReader's; a `.yuv` reader carries the field_order it is given."""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".y4m":
-        return Y4MReader(path)
+        return Y4MReader(path, interlaced, field_order) if interlaced else Y4MReader(path)
     if ext == ".yuv":
         if size is None:
             raise ValueError(f"{path}: a raw .yuv file needs its size (--size WxH)")
-        r = RawYUVReader(path, size[0], size[1], bit_depth)
+        if field_order is not None and not interlaced:
+            raise ValueError("field_order belongs to interlaced=True")
+        r = RawYUVReader(path, size[0], size[1], bit_depth, field_order)
         r.fps = tuple(fps) if fps else None
         return r
     raise ValueError(f"{path}: unknown video extension {ext!r} (expected .y4m or .yuv)")
