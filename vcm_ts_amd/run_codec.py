@@ -25,6 +25,8 @@
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT [--motion-border N] [--motion-q F]
     python -m vcm_ts_amd.run_codec encode ... --tnr T [--tnr-floor W] [--tnr-pixel P] [--tnr-search R [--tnr-penalty L] [--tnr-subpel] [--tnr-split] [--tnr-levels L]]
     python -m vcm_ts_amd.run_codec encode ... --tnr T --tnr-intra K
+    python -m vcm_ts_amd.run_codec encode ... --tnr-auto [K] [--tnr-auto-min-cells N] [every --tnr-* option]
+    python -m vcm_ts_amd.run_codec noise (--frames DIR | --video FILE) [--out FILE] [--max-frames N] [--min-cells N] [--scale K]
     python -m vcm_ts_amd.run_codec encode ... --tnr T --grain [--grain-min-samples N]
     python -m vcm_ts_amd.run_codec decode ... --grain [PERCENT]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT --redact NAME [NAME ...] (--redact-tile N | --redact-fill K)
@@ -87,8 +89,8 @@ With --tnr T (1 .. 64 luma codes) the codec is handed a temporally filtered pict
 blended with the previous filtered picture wherever their luma differs by fewer than T codes on average over a 5x5 window, the
 source itself wherever something moves.  The filter restarts at every I picture.  It is encoder side only: the .bin format is
 unchanged, no file is written and `decode` needs nothing; --report keeps measuring against the unfiltered source and gains
-`tnr`, `frame_tnr_held` and `frame_tnr_mad`.  There is no default T, --tnr-floor and --tnr-pixel are untuned placeholders, and
-nothing is claimed about rate or quality.  Motion compensation is opt-in: with --tnr-search R (1 .. 32 pixels) every 16x16 cell
+`tnr`, `frame_tnr_held` and `frame_tnr_mad`.  There is no default T (--tnr-auto measures one, below), --tnr-floor and
+--tnr-pixel are untuned placeholders, and nothing is claimed about rate or quality.  Motion compensation is opt-in: with --tnr-search R (1 .. 32 pixels) every 16x16 cell
 of a P picture is searched for in the previous filtered picture (whole-pixel full search on luma SAD plus --tnr-penalty codes
 per pixel of vector length, default 4, untuned), that picture is moved cell by cell and the blend runs against the moved
 picture: three kernels per P picture.  --report then also gains `frame_tnr_moved` and `frame_tnr_mad_zero`.
@@ -113,6 +115,14 @@ nonzero for such I pictures (against the picture that follows) and it gains `fra
 measured too and `decode --grain` grains I pictures exactly when grain.json's `tnr` entry says `intra`.  Nothing is claimed
 about rate or quality.
 
+With --tnr-auto [K] in place of --tnr T the threshold is MEASURED (vcm_ts_amd/noise.py): a scan pass over the
+whole source before anything is coded -- the --scenecut scan's own pass where that is given too -- takes per 16x16 cell the mean
+absolute luma difference of consecutive pictures (two kernels on the GPU), the lower quartile of the cells is the noise level,
+and T = ceil(K x that level) clamped to 1 .. 64 (K within 0.50 .. 16.00, default 3.0; K and --tnr-auto-min-cells, the counted
+cells an estimate needs, default 1024, are untuned placeholders).  Every --tnr-* option and --grain belong to either.  The
+.bin files are those of --tnr T; noise.json beside them and --report's `noise` hold the estimate and the chosen T.  Fixed
+camera only: a pan is measured as noise and nothing warns of it.  A source without an estimate is refused: pass --tnr T.
+`run_codec noise` is the scan alone and prints the same JSON.
 With --tnr T --grain the encoder also measures what the filter took out of every P picture (vcm_ts_amd/grain.py: one more
 kernel per P picture, right behind the filter's) and leaves grain.json beside the .bin files: per GOP eight strengths by
 intensity, two taps and the sample counts.  Every other output is that of an encode without the option.  `decode --grain
@@ -634,24 +644,38 @@ class _EncodeRun:
 GOPS_JSON = "gops.json"
 
 
-def _scene_plan(source, gop, scenecut, min_gop):
-    """The GopPlan of an encode loop.  Without `scenecut` the fixed one, and the source is not read.  With it the scan
-    pass: every picture of the source once, in order, as the coding pass will see it (same reader, same conversion);
-    each is summarised on the device (scenecut.SceneScan: one kernel per picture, nothing synchronised) and the
-    distances are read back in one copy at the end."""
+def _scan_pass(source, gop, scenecut, min_gop, auto=None):
+    """(the GopPlan of an encode loop, the noise estimate of its source or None).  Without `scenecut` the fixed plan, and
+    the source is not read.  With it the scan pass: every picture of the source once, in order, as the coding pass will see
+    it (same reader, same conversion); each is summarised on the device (scenecut.SceneScan: one kernel per picture,
+    nothing synchronised) and the distances are read back in one copy at the end.
+
+    auto: a tnr.AutoTNR -- the pictures of the SAME pass also go through a noise.NoiseScan (one more kernel per picture,
+    nothing synchronised) and the second value is the noise.NoiseEstimate of the whole source: with scenecut the source is
+    still read once before it is coded, and without scenecut this is the one pass that reads it."""
     from . import scenecut as SC
 
     n_frames = source.n_frames
     SC.check_options(gop, scenecut, min_gop)
-    if scenecut is None:
-        return GopPlan.fixed(n_frames, gop)
-    scan = SC.SceneScan(source.dev, source.size[0], source.size[1], n_frames)
+    if scenecut is None and auto is None:
+        return GopPlan.fixed(n_frames, gop), None
+    scan = SC.SceneScan(source.dev, source.size[0], source.size[1], n_frames) if scenecut is not None else None
+    if auto is not None:
+        from . import noise as NS
+
+        meter = NS.NoiseScan(source.dev, source.size[0], source.size[1])
+    seen = 0
     with torch.no_grad():
         for x, _ in source.pictures(range(n_frames)):
-            scan.add(x)
-    if scan.n != n_frames:
-        raise ValueError(f"the scan pass saw {scan.n} pictures of {n_frames}")
-    return GopPlan(n_frames, SC.plan(scan.distances(), gop, scenecut, min_gop))
+            if scan is not None:
+                scan.add(x)
+            if auto is not None:
+                meter.add(x)
+            seen += 1
+    if seen != n_frames:
+        raise ValueError(f"the scan pass saw {seen} pictures of {n_frames}")
+    plan = GopPlan.fixed(n_frames, gop) if scan is None else GopPlan(n_frames, SC.plan(scan.distances(), gop, scenecut, min_gop))
+    return plan, (None if auto is None else NS.estimate(meter.histogram(), auto.min_cells, meter.pairs))
 
 
 def write_gop_plan(bin_dir, plan, gop, scenecut, min_gop):
@@ -1099,7 +1123,8 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
         rate = _rate_args(target_bpp, q_range, h, w, gop)
         dev = torch.device(device)
         base = _base_args(base_scale, roi, roi_q, bit_map, (h, w), dev)
-        plan = _scene_plan(source, gop, scenecut, min_gop)
+        plan, estimate = _scan_pass(source, gop, scenecut, min_gop, _tnr_auto(tnr))
+        tnr, measured = _resolve_tnr(tnr, estimate)  # (from here on a plain tnr.TNR: nothing below knows the difference)
         layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
         held = _redact_frames(redact, layer)
         run = _EncodeRun(bin_dir, plan, base.size if base else (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets,
@@ -1109,6 +1134,7 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
         write_roiq(bin_dir, roi_q, layer.roi.names if layer else ())
         SC.write_scale(bin_dir, base.scale if base else None)
         A.write_aq(bin_dir, aq)
+        S.write_sidecar(bin_dir, NOISE_JSON, measured)
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
         rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
         filters = _tnr_filters(tnr, run, (h, w), report)
@@ -1175,6 +1201,7 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
     keys = [_roi_report_keys(h, w) if layer else None, out.report_keys(), _deint_report_keys(source) if report else None,
             _enh_report_keys(rec_out, h, w) if rec_out else None,
             _tnr_report_keys(tnr, filters, run, h, w) if filters else None,
+            _noise_report_keys(measured) if measured and report else None,
             _redact_report_keys(redact, redaction, run, h, w) if redaction else None]
     return run.results(report, [k for k in keys if k])
 
@@ -1278,7 +1305,13 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     follow it in its own GOP (pulled ahead from the source by a _LookAhead, never past the next I picture), the P pictures
     start from the filtered I picture, the figures above are those of reference 0 for such an I picture, and the report
     gains frame_tnr_refs (n, 1 for a P picture, 0 for an I picture left as it was).
-    None: no launch, allocation, key or byte changes.
+    A tnr.AutoTNR in place of the TNR: the threshold is measured.  Before anything is coded a scan pass --
+    the scene-cut scan's own pass where scenecut is given too, so the source is read once before it is coded either way --
+    hands every picture to a noise.NoiseScan, the whole source's estimate resolves the setting to a plain TNR, and everything
+    above holds for that TNR; one estimate for every GOP, so gop_streams keeps the bytes of sequential coding.  noise.json
+    beside the .bin files (informational: no decoder reads it) and the report's `noise` key hold the estimate, the scale and
+    the resolved threshold and pixel.  A source without an estimate is a ValueError that says to pass a TNR.
+    None: no launch, allocation, key or byte changes (a stale noise.json is removed).
     redact (with roi): a redact.Redact -- ROI redaction (vcm_ts_amd/redact.py).  Inside the boxes of the named
     classes (grown by redact.grow; with redact.hold also the boxes of that many pictures before and after) the picture the
     codec is handed is a mosaic of the source on a picture-aligned grid, or a solid fill: one launch per picture that has
@@ -1853,10 +1886,39 @@ def _write_grain(bin_dir, grain, tnr, meters):
 def _tnr_args(tnr):
     """tnr= of an encode loop, refused by name before any GPU work."""
     if tnr is not None:
-        from .tnr import TNR
+        from .tnr import TNR, AutoTNR
 
-        if not isinstance(tnr, TNR):
-            raise ValueError(f"tnr: expected a tnr.TNR, got {type(tnr).__name__}")
+        if not isinstance(tnr, (TNR, AutoTNR)):
+            raise ValueError(f"tnr: expected a tnr.TNR or a tnr.AutoTNR, got {type(tnr).__name__}")
+
+
+NOISE_JSON = "noise.json"
+
+
+def _tnr_auto(tnr):
+    """tnr= of an encode loop where it is a tnr.AutoTNR (checked by _tnr_args), else None."""
+    from .tnr import AutoTNR
+
+    return tnr if isinstance(tnr, AutoTNR) else None
+
+
+def _resolve_tnr(tnr, estimate):
+    """(the tnr.TNR of an encode loop's tnr=, what noise.json and --report's `noise` say).  A TNR, or None, is itself and
+    says nothing; a tnr.AutoTNR is resolved with the scan pass's estimate of the whole source -- one estimate for every GOP,
+    GOP stream and shard -- or refuses by name where there is none."""
+    auto = _tnr_auto(tnr)
+    if auto is None:
+        return tnr, None
+    resolved = auto.resolve(estimate)
+    return resolved, dict(estimate.to_json(), scale=auto.scale, threshold=resolved.threshold, pixel=resolved.pixel)
+
+
+def _noise_report_keys(measured):
+    """--report's `noise` key: what noise.json holds."""
+    def keys(rd, types, values):
+        rd["noise"] = dict(measured)
+
+    return keys
 
 
 def _stream_totals(steps, run):
@@ -2195,7 +2257,11 @@ def _parser():
                        "source (a background model of the luma on the GPU, vcm_ts_amd/motionroi.py) that writes "
                        "ROOT/motion_coords/%%05d and ROOT/motion.json; ROOT is then an ordinary --roi-root whose third box "
                        "class is \"motion\".  The mechanism only: nothing is claimed about detection quality")
-    for p in (e, b):
+    n = sub.add_parser("noise", description="The sensor noise of a fixed-camera source, measured from the source alone: a scan "
+                       "pass (two small kernels on the GPU, vcm_ts_amd/noise.py) over consecutive pictures' luma difference "
+                       "per 16x16 cell, the lower quartile of it, and the threshold encode --tnr-auto K would choose, as JSON on "
+                       "stdout.  Fixed camera only: a pan is measured as noise and nothing warns of it")
+    for p in (e, b, n):
         p.add_argument("--frames", help="folder of im1.png / im00001.png ... (exactly one of --frames and --video)")
         p.add_argument("--video", metavar="FILE", help="a .y4m file, or a raw I420 .yuv file with --size")
         p.add_argument("--size", metavar="WxH", help="picture size of a raw .yuv file")
@@ -2229,6 +2295,14 @@ def _parser():
     b.add_argument("--max-boxes", type=int, default=None, metavar="N", help="keep the N strongest boxes of a picture (default 64)")
     b.add_argument("--device", default="cuda:0")
     b.add_argument("--io-workers", type=int, default=8, help="host threads for PNG decoding (0: inline)")
+    n.add_argument("--out", metavar="FILE", help="also write the JSON there")
+    n.add_argument("--max-frames", type=int, default=None, metavar="N", help="scan the first N pictures only")
+    n.add_argument("--min-cells", type=int, default=None, metavar="N",
+                   help="the counted cells an estimate needs (default 1024, an untuned placeholder)")
+    n.add_argument("--scale", type=float, default=None, metavar="K",
+                   help="the K of encode --tnr-auto K whose threshold is reported, 0.50 .. 16.00 (default 3.0, an untuned placeholder)")
+    n.add_argument("--device", default="cuda:0")
+    n.add_argument("--io-workers", type=int, default=8, help="host threads for PNG decoding (0: inline)")
     e.add_argument("--bins", required=True)
     e.add_argument("--recon")
     e.add_argument("--png-device", action="store_true",
@@ -2342,6 +2416,15 @@ def _parser():
                         "pictures that follow it in its own GOP, each moved onto it first with --tnr-search, and start the "
                         "recursive filter from the filtered picture; 1 .. 4 (no default: without the option I pictures are "
                         "passed through).  --report gains frame_tnr_refs.  Untuned; nothing is claimed about rate or quality")
+    e.add_argument("--tnr-auto", type=float, nargs="?", const=3.0, default=None, metavar="K",
+                   help="in place of --tnr T: measure the source's noise level first (vcm_ts_amd/noise.py: a scan pass over "
+                        "the whole source, shared with --scenecut's; the lower quartile of the 16x16 cells' mean absolute luma "
+                        "difference of consecutive pictures) and filter with T = ceil(K x that level), clamped to 1 .. 64; K "
+                        "within 0.50 .. 16.00 (default 3.0, an UNTUNED PLACEHOLDER).  Every --tnr-* option belongs to either.  "
+                        "noise.json beside the .bin files and --report's `noise` hold the estimate and the chosen T.  Fixed "
+                        "camera only: a pan is measured as noise.  A source without an estimate is refused: pass --tnr T")
+    e.add_argument("--tnr-auto-min-cells", type=int, default=None, metavar="N",
+                   help="with --tnr-auto: the counted cells an estimate needs (default 1024, an untuned placeholder)")
     e.add_argument("--grain", action="store_true",
                    help="with --tnr: film-grain synthesis, the encoder's half (vcm_ts_amd/grain.py) -- measure on the GPU what the "
                         "prefilter took out of every P picture and leave grain.json beside the .bin files: per GOP eight "
@@ -2479,6 +2562,50 @@ def _boxes_command(ap, a):
     print(f"{len(boxes)} pictures, {sum(len(x) for x in boxes)} boxes -> {os.path.join(a.out, M.COORDS)}")
 
 
+def noise_estimate(source, auto):
+    """The noise.NoiseEstimate of a source (a _PngSource or a _VideoSource, opened here and closed on every exit) for the
+    tnr.AutoTNR `auto`: the scan pass of encode --tnr-auto on its own -- every picture once, through the reader and
+    conversion of the coding pass."""
+    try:
+        source.open()
+        return _scan_pass(source, 1, None, 1, auto)[1]
+    finally:
+        source.close()
+
+
+def _noise_command(ap, a):
+    import json
+
+    from . import tnr as N
+    from . import yuv as Y
+
+    if (a.frames is None) == (a.video is None):
+        ap.error("give exactly one of --frames and --video")
+    if a.video is None and (a.size or a.quantize8 or a.matrix or a.range or a.siting):
+        ap.error("--size, --quantize8, --matrix, --range and --siting belong to --video")
+    try:
+        auto = N.AutoTNR(**({} if a.scale is None else {"scale": a.scale}), **({} if a.min_cells is None else {"min_cells": a.min_cells}))
+    except ValueError as ex:
+        ap.error(f"noise: --scale / --min-cells: {ex}")
+    more, setting = _deint_option(ap, a)
+    try:
+        if a.video is not None:
+            size, fps = _video_args(ap, a)
+            with Y.open_video(a.video, size, a.bit_depth, fps, **more) as reader:
+                spec = reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting)
+                est = noise_estimate(_VideoSource(reader, a.device, None, spec, a.quantize8, 8, None, a.max_frames, setting(reader)), auto)
+        else:
+            est = noise_estimate(_PngSource(a.frames, a.device, a.io_workers, a.max_frames), auto)
+        _, record = _resolve_tnr(auto, est)
+    except (ValueError, OSError) as ex:
+        ap.error(f"noise: {ex}")
+    text = json.dumps(record, indent=2)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
 def _motion_option(ap, a):
     """Whether --roi-root holds motion boxes; --motion-border and --motion-q are refused without them."""
     from .roi import PickleBoxes
@@ -2522,9 +2649,14 @@ def _encode_command(ap, a):
             aq = A.AQ(a.aq_strength, *(a.aq_clamp or (A.MIN_Q, A.MAX_Q)))
         except ValueError as ex:
             ap.error(f"--aq-strength / --aq-clamp: {ex}")
-    if a.tnr is None and (a.tnr_floor is not None or a.tnr_pixel is not None):
+    if a.tnr is not None and a.tnr_auto is not None:
+        ap.error("give one of --tnr T and --tnr-auto [K]: the threshold is either given or measured")
+    if a.tnr_auto is None and a.tnr_auto_min_cells is not None:
+        ap.error("--tnr-auto-min-cells belongs to --tnr-auto")
+    filtered = a.tnr is not None or a.tnr_auto is not None  # (every --tnr-* option below belongs to either)
+    if not filtered and (a.tnr_floor is not None or a.tnr_pixel is not None):
         ap.error("--tnr-floor and --tnr-pixel belong to --tnr")
-    if a.tnr is None and (a.tnr_search is not None or a.tnr_penalty is not None):
+    if not filtered and (a.tnr_search is not None or a.tnr_penalty is not None):
         ap.error("--tnr-search and --tnr-penalty belong to --tnr")
     if a.tnr_search is None and a.tnr_penalty is not None:
         ap.error("--tnr-penalty belongs to --tnr-search")
@@ -2534,18 +2666,21 @@ def _encode_command(ap, a):
         ap.error("--tnr-split belongs to --tnr-search")
     if a.tnr_search is None and a.tnr_levels is not None:
         ap.error("--tnr-levels belongs to --tnr-search")
-    if a.tnr is None and a.tnr_intra is not None:
+    if not filtered and a.tnr_intra is not None:
         ap.error("--tnr-intra belongs to --tnr")
-    if a.tnr is not None:
+    if filtered:
         from . import tnr as N
 
+        shared = dict(**({} if a.tnr_floor is None else {"floor": a.tnr_floor}), pixel=a.tnr_pixel, search=a.tnr_search,
+                      **({} if a.tnr_penalty is None else {"penalty": a.tnr_penalty}), intra=a.tnr_intra,
+                      **({"subpel": True} if a.tnr_subpel else {}), **({"split": True} if a.tnr_split else {}),
+                      **({} if a.tnr_levels is None else {"levels": a.tnr_levels}))
+        first = "--tnr" if a.tnr is not None else "--tnr-auto / --tnr-auto-min-cells"
         try:
-            tnr = N.TNR(a.tnr, **({} if a.tnr_floor is None else {"floor": a.tnr_floor}), pixel=a.tnr_pixel, search=a.tnr_search,
-                        **({} if a.tnr_penalty is None else {"penalty": a.tnr_penalty}), intra=a.tnr_intra,
-                        **({"subpel": True} if a.tnr_subpel else {}), **({"split": True} if a.tnr_split else {}),
-                        **({} if a.tnr_levels is None else {"levels": a.tnr_levels}))
+            tnr = N.TNR(a.tnr, **shared) if a.tnr is not None else \
+                N.AutoTNR(a.tnr_auto, **({} if a.tnr_auto_min_cells is None else {"min_cells": a.tnr_auto_min_cells}), **shared)
         except ValueError as ex:
-            ap.error(f"--tnr / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty / --tnr-intra / --tnr-subpel / --tnr-split / --tnr-levels: {ex}")
+            ap.error(f"{first} / --tnr-floor / --tnr-pixel / --tnr-search / --tnr-penalty / --tnr-intra / --tnr-subpel / --tnr-split / --tnr-levels: {ex}")
     grain = None
     if a.grain_min_samples is not None and not a.grain:
         ap.error("--grain-min-samples belongs to --grain")
@@ -2736,7 +2871,7 @@ def _decode_command(ap, a):
 def main(argv=None):
     ap = _parser()
     a = ap.parse_args(argv)
-    {"verify": _verify_command, "boxes": _boxes_command, "encode": _encode_command, "decode": _decode_command}[a.cmd](ap, a)
+    {"verify": _verify_command, "boxes": _boxes_command, "noise": _noise_command, "encode": _encode_command, "decode": _decode_command}[a.cmd](ap, a)
 
 
 if __name__ == "__main__":

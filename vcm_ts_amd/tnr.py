@@ -11,11 +11,14 @@ tests/mesplit_ref.py the re-selection per sub-cell, tests/mepyr_ref.py the hiera
 
     TNR(threshold, floor=64, pixel=None, search=None, penalty=4, intra=None, subpel=False, split=False, levels=None)
                                              the setting; .table() the 256 weights, .rcp_table() dcvc_tnr_fuse's reciprocals
+    AutoTNR(scale=3.0, min_cells=1024, ...)   the setting without its threshold; .resolve(noise estimate) -> TNR
     TnrFilter(tnr, size, device)             the state of ONE GOP stream on the device; .step(x_padded, intra, ahead=())
     StreamFilter                             what TnrFilter shares with redact.Redactor: validation, pictures, totals
 
 There is deliberately NO default threshold, and `floor` and `pixel` are UNTUNED PLACEHOLDERS: no machine of the project
-holds a real video.  This is the mechanism -- filtered, coded, decoded by an unchanged decoder -- not a claim about rate
+holds a real video.  (AutoTNR takes the threshold from the source's own measured noise level instead, vcm_ts_amd/noise.py;
+its `scale` and `min_cells` are untuned placeholders too.)  This is the mechanism -- filtered, coded, decoded by an
+unchanged decoder -- not a claim about rate
 or quality.  Without `search`, moving pixels are passed through, not followed.  With search=R the filter is MOTION
 COMPENSATED (opt-in): every 16 x 16 cell of a P picture is searched for in the previous filtered picture within +-R whole
 pixels (dcvc_me_search: luma SAD plus `penalty` codes per pixel of vector length), that picture is moved cell by cell
@@ -75,7 +78,8 @@ ROWS = 64  # pictures' totals kept on the device between two copies to the host
 @dataclass(frozen=True)
 class TNR:
     """threshold T: a pixel whose 5 x 5 window differs from the previous filtered picture by T luma codes or more on
-    average is passed through (1..64; no default exists).  floor: the weight of the current picture, in 1/256ths, where
+    average is passed through (1..64; no default exists -- AutoTNR measures one from the source).  floor: the weight of
+    the current picture, in 1/256ths, where
     nothing differs at all (1..255); between 0 and T the weight rises linearly to 256.  pixel P: a pixel whose own luma
     differs by more than P codes is passed through whatever its window says (0..255; None: min(255, 3 T)).  search R: the
     reference of the blend is the previous filtered picture moved cell by cell by the vectors of a full search within +-R
@@ -151,6 +155,46 @@ class TNR:
     def rcp_table():
         """rtab of dcvc_tnr_fuse, 1021 float32: entry U is the float32 nearest the float64 quotient 1 / (256 + U)."""
         return (1.0 / (256.0 + np.arange(RCP, dtype=np.float64))).astype(np.float32)
+
+
+@dataclass(frozen=True)
+class AutoTNR:
+    """A TNR whose threshold is still to be measured: the keywords of TNR but `threshold`, checked by TNR itself, and
+    scale: the threshold is `scale` times the source's measured noise level, noise.auto_threshold (0.50 .. 16.00, snapped to
+    hundredths); min_cells: the counted cells noise.estimate needs for an estimate.  scale = 3.0 and min_cells = 1024 are
+    UNTUNED PLACEHOLDERS, as floor, pixel and penalty are.  pixel None: min(255, 3 T) of the resolved T."""
+    scale: float = 3.0
+    min_cells: int = 1024
+    floor: int = 64
+    pixel: int = None
+    search: int = None
+    penalty: int = PENALTY
+    intra: int = None
+    subpel: bool = False
+    split: bool = False
+    levels: int = None
+
+    def _settings(self):
+        return {name: getattr(self, name) for name in ("floor", "pixel", "search", "penalty", "intra", "subpel", "split", "levels")}
+
+    def __post_init__(self):
+        from . import noise
+
+        object.__setattr__(self, "scale", noise.scale100(self.scale) / 100.0)
+        object.__setattr__(self, "min_cells", whole("min_cells", self.min_cells, 1, 2 ** 31 - 1))
+        checked = TNR(1, **self._settings())  # (TNR's own refusals; no value of theirs depends on the threshold but pixel=None's)
+        for name, given in self._settings().items():
+            object.__setattr__(self, name, given if name == "pixel" and given is None else getattr(checked, name))
+
+    def resolve(self, estimate):
+        """The TNR of a noise.NoiseEstimate; one without a value is a ValueError that names the cause."""
+        from . import noise
+
+        if not isinstance(estimate, noise.NoiseEstimate):
+            raise ValueError(f"AutoTNR.resolve: expected a noise.NoiseEstimate, got {type(estimate).__name__}")
+        if estimate.mad32 is None:
+            raise ValueError(f"tnr-auto: no noise estimate for this source -- {estimate.why_none()}; pass --tnr T (tnr.TNR) instead")
+        return TNR(noise.auto_threshold(estimate.mad32, self.scale), **self._settings())
 
 
 class StreamFilter:
