@@ -1,5 +1,5 @@
 """The device boundary of the picture tools (metrics, yuv, roi, roilayer, bitmap, scenecut, picturehash, scale, aq, motionroi,
-tnr, redact, ratectl, deint, noise), written once: what a module checks about a picture before it hands its pointer and strides to a
+tnr, redact, ratectl, deint, noise, shake), written once: what a module checks about a picture before it hands its pointer and strides to a
 kernel, how it names its device, and how it launches.  A new picture tool takes its checks and its launches from here.
 
     MAX_SIDE                          the largest picture side any kernel takes

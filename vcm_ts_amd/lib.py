@@ -297,6 +297,11 @@ HEADERS = {
         "dcvc_noise_cells": [vp, i32, i64, i32, i32, vp, vp, i32, vp, vp],
         "dcvc_noise_hist": [vp, i64, vp, vp],
     },
+    "dcvc_hip_shake.h": {
+        "dcvc_shake_plane": [vp, i32, i64, i32, i32, vp, i32, vp],
+        "dcvc_shake_tiles": [vp, i32, i64, i32, i32, vp, i32, i32, vp, vp],
+        "dcvc_shake_vote": [vp, i32, i32, i32, i32, i32, vp, vp, vp],
+    },
 }
 
 
@@ -312,7 +317,7 @@ _CORE = ("dcvc_hip.h", "dcvc_hip_grad.h", "dcvc_hip_rans.h")
 HIP_SYMBOLS = sorted(name for h in _CORE for name in HEADERS[h])
 (METRICS_SYMBOLS, COLOR_SYMBOLS, ROI_SYMBOLS, ROIL_SYMBOLS, SCENE_SYMBOLS, BITS_SYMBOLS, HASH_SYMBOLS, SCALE_SYMBOLS, AQ_SYMBOLS,
  MOTION_SYMBOLS, TNR_SYMBOLS, REDACT_SYMBOLS, ME_SYMBOLS, PNG_SYMBOLS, GRAIN_SYMBOLS, TNR_FUSE_SYMBOLS, MESUB_SYMBOLS, MESPLIT_SYMBOLS,
- MEPYR_SYMBOLS, DEINT_SYMBOLS, NOISE_SYMBOLS) = (list(funcs) for h, funcs in HEADERS.items() if h not in _CORE)
+ MEPYR_SYMBOLS, DEINT_SYMBOLS, NOISE_SYMBOLS, SHAKE_SYMBOLS) = (list(funcs) for h, funcs in HEADERS.items() if h not in _CORE)
 HASH_CONSTANTS = ["dcvc_hash_chunk_bytes", "dcvc_hash_block_bytes", "dcvc_hash_scratch_bytes"]  # (int32 data symbols)
 RANS_SYMBOLS = [  # include/dcvc_rans.h (libdcvc_rans.so, bound in rans() above)
     "dcvc_rans_encoder_create", "dcvc_rans_encoder_destroy", "dcvc_rans_encoder_reset",

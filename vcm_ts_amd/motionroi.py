@@ -237,8 +237,8 @@ def read_info(root):
         return None
     path, info = found
     try:
-        if not isinstance(info, dict) or set(info) != {"version", "height", "width", "frames", "params"}:
-            raise ValueError("expected the keys version, height, width, frames and params")
+        if not isinstance(info, dict) or set(info) - {"shake"} != {"version", "height", "width", "frames", "params"}:
+            raise ValueError("expected the keys version, height, width, frames and params")  # ("shake": informational, run_codec boxes --shake)
         if info["version"] != VERSION:
             raise ValueError(f"format version {info['version']!r}, this code reads {VERSION}")
         size = tuple(whole(k, info[k], 1, MAX_SIDE) for k in ("height", "width"))
@@ -247,11 +247,13 @@ def read_info(root):
         raise ValueError(f"{path}: {ex}") from None
 
 
-def write_boxes(root, per_frame_boxes, params, height, width):
+def write_boxes(root, per_frame_boxes, params, height, width, shake=None):
     """`root`/motion_coords/%05d, numbered from 1: one pickled np.uint16 (n, 4) array of x1, y1, x2, y2 per frame, empty
     ones included (the reference's coordinate format: roi.PickleBoxes reads the folder as class "motion"), and
     `root`/motion.json with the parameters, the size, the frame count and a format version.  Refused: a motion_coords
-    that already holds the files of a run with another frame count or size (or of unknown origin) -- nothing is mixed."""
+    that already holds the files of a run with another frame count or size (or of unknown origin) -- nothing is mixed.
+    shake: what motion.json records under "shake" (the registration's setting and summary, vcm_ts_amd/shake.py); None: no
+    such key."""
     from .stream import write_sidecar
 
     p = _params(params)
@@ -282,4 +284,5 @@ def write_boxes(root, per_frame_boxes, params, height, width):
     for t, a in enumerate(arrays):
         with open(os.path.join(folder, "%05d" % (t + 1)), "wb") as f:
             pickle.dump(a, f)
-    write_sidecar(root, MOTION_JSON, {"version": VERSION, "height": H, "width": W, "frames": len(arrays), "params": p.to_json()})
+    write_sidecar(root, MOTION_JSON, dict({"version": VERSION, "height": H, "width": W, "frames": len(arrays), "params": p.to_json()},
+                                         **({} if shake is None else {"shake": shake})))

@@ -23,7 +23,8 @@ standard deviation of the luma noise OF ONE PICTURE in thousandths of a code if 
 pictures has sqrt(2) sigma and a mean absolute value of 2 sigma / sqrt(pi)); it is for information only.
 
 `min_cells` = 1024 and tnr.AutoTNR's `scale` = 3.0 are UNTUNED PLACEHOLDERS: no machine of the project holds a real video.
-LIMITS: fixed camera only -- a pan moves every cell, and what is measured is then motion, with no warning; one estimate
+LIMITS: fixed camera only -- a pan moves every cell, and what is measured is then motion, with no warning (a shake.Registrar in
+front of the scan, vcm_ts_amd/shake.py, takes out a shake of a few pixels and names a pan: its pictures are lost); one estimate
 per source, not per GOP; flicker and auto-gain inflate it; luma only.  The 8-bit rounding of R, G and B is counted as noise
 (4 % at one code of noise a channel), and on a monochrome source (R = G = B, where the luma of the codes has no fractional
 part of its own) so is the rounding of Y: 7 % high at one code, nothing from two codes on (tests/test_noise_host.py).

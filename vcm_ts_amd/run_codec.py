@@ -27,6 +27,7 @@
     python -m vcm_ts_amd.run_codec encode ... --tnr T --tnr-intra K
     python -m vcm_ts_amd.run_codec encode ... --tnr-auto [K] [--tnr-auto-min-cells N] [every --tnr-* option]
     python -m vcm_ts_amd.run_codec noise (--frames DIR | --video FILE) [--out FILE] [--max-frames N] [--min-cells N] [--scale K]
+    python -m vcm_ts_amd.run_codec shake (--frames DIR | --video FILE) --radius R [--min-votes N] [--out FILE] [--max-frames N]
     python -m vcm_ts_amd.run_codec encode ... --tnr T --grain [--grain-min-samples N]
     python -m vcm_ts_amd.run_codec decode ... --grain [PERCENT]
     python -m vcm_ts_amd.run_codec encode ... --roi-root ROOT --redact NAME [NAME ...] (--redact-tile N | --redact-fill K)
@@ -121,8 +122,18 @@ absolute luma difference of consecutive pictures (two kernels on the GPU), the l
 and T = ceil(K x that level) clamped to 1 .. 64 (K within 0.50 .. 16.00, default 3.0; K and --tnr-auto-min-cells, the counted
 cells an estimate needs, default 1024, are untuned placeholders).  Every --tnr-* option and --grain belong to either.  The
 .bin files are those of --tnr T; noise.json beside them and --report's `noise` hold the estimate and the chosen T.  Fixed
-camera only: a pan is measured as noise and nothing warns of it.  A source without an estimate is refused: pass --tnr T.
+camera only: a pan is measured as noise and nothing warns of it (but see --shake below).  A source without an estimate is refused: pass --tnr T.
 `run_codec noise` is the scan alone and prints the same JSON.
+
+With --shake R (boxes, noise, encode --tnr-auto; vcm_ts_amd/shake.py) a camera that is fixed but SHAKES by up to R
+whole pixels is steadied ahead of those scans: picture 0 is the anchor, every later picture is searched for in its luma (a
+2-D search on a sparse sample of every 64x64 tile, a median vote over the tiles: two kernels) and moved onto it by the one
+vector found (dcvc_me_compensate) before the scan sees it.  shake.json holds a record per picture; a picture with too few
+votes (--shake-min-votes, default 8, an untuned placeholder) or a vector at +-R is LOST and passed on unmoved, and a source
+with more than a quarter of its pictures lost is refused by the noise scan: the camera moves, pass --tnr T.  The coding pass
+is not touched (--tnr-search finds the shake cell by cell), the scene-cut scan keeps the unregistered pictures.  Whole pixels,
+translation only, no re-anchoring.  `run_codec shake` is the registration alone and prints the JSON.  Without the option
+nothing changes.
 With --tnr T --grain the encoder also measures what the filter took out of every P picture (vcm_ts_amd/grain.py: one more
 kernel per P picture, right behind the filter's) and leaves grain.json beside the .bin files: per GOP eight strengths by
 intensity, two taps and the sample counts.  Every other output is that of an encode without the option.  `decode --grain
@@ -644,7 +655,7 @@ class _EncodeRun:
 GOPS_JSON = "gops.json"
 
 
-def _scan_pass(source, gop, scenecut, min_gop, auto=None):
+def _scan_pass(source, gop, scenecut, min_gop, auto=None, steady=None):
     """(the GopPlan of an encode loop, the noise estimate of its source or None).  Without `scenecut` the fixed plan, and
     the source is not read.  With it the scan pass: every picture of the source once, in order, as the coding pass will see
     it (same reader, same conversion); each is summarised on the device (scenecut.SceneScan: one kernel per picture,
@@ -652,7 +663,14 @@ def _scan_pass(source, gop, scenecut, min_gop, auto=None):
 
     auto: a tnr.AutoTNR -- the pictures of the SAME pass also go through a noise.NoiseScan (one more kernel per picture,
     nothing synchronised) and the second value is the noise.NoiseEstimate of the whole source: with scenecut the source is
-    still read once before it is coded, and without scenecut this is the one pass that reads it."""
+    still read once before it is coded, and without scenecut this is the one pass that reads it.
+
+    steady: a shake.Registrar for the source (_registrar), with auto -- every picture goes through it first and the noise scan
+    is handed the picture registered onto picture 0 (three more launches per picture, nothing synchronised); the scene scan keeps the
+    UNREGISTERED picture, whose histograms do not care about a shift of a few pixels and whose plan must not change.  The
+    border is not masked here: dcvc_noise_hist reads the cells on the device, and the band a registered picture replicates
+    from its edge only ever inflates a border cell's difference, which the lower quartile does not see.  The caller reads the
+    registrar's log afterwards (_shake_document)."""
     from . import scenecut as SC
 
     n_frames = source.n_frames
@@ -670,12 +688,33 @@ def _scan_pass(source, gop, scenecut, min_gop, auto=None):
             if scan is not None:
                 scan.add(x)
             if auto is not None:
-                meter.add(x)
+                meter.add(x if steady is None else steady.add(x))
             seen += 1
     if seen != n_frames:
         raise ValueError(f"the scan pass saw {seen} pictures of {n_frames}")
     plan = GopPlan.fixed(n_frames, gop) if scan is None else GopPlan(n_frames, SC.plan(scan.distances(), gop, scenecut, min_gop))
     return plan, (None if auto is None else NS.estimate(meter.histogram(), auto.min_cells, meter.pairs))
+
+
+def _registrar(source, shake):
+    """The shake.Registrar of an opened source for the shake.ShakeParams `shake`; None without."""
+    if shake is None:
+        return None
+    from . import shake as SH
+
+    return SH.Registrar(source.dev, source.size[0], source.size[1], source.n_frames, shake)
+
+
+def _shake_document(steady, source):
+    """What shake.json says after the scan pass (None without a registrar).  A source with more than max_lost percent of its
+    pictures lost is a ValueError by name, before any estimate is made of it."""
+    if steady is None:
+        return None
+    from . import shake as SH
+
+    moved = SH.document(steady.log(), steady.params, *source.size)
+    SH.check_lost(moved["summary"], steady.params)
+    return moved
 
 
 def write_gop_plan(bin_dir, plan, gop, scenecut, min_gop):
@@ -1100,7 +1139,7 @@ class _VideoStage:
 def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None,
                      coder="host", io_workers=8, nets=None, gop_streams=1, report=None, roi=None, residuals=None, scenecut=None,
                      min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1,
-                     picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None, grain=None):
+                     picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None, grain=None, shake=None):
     """The one encode loop: the pictures of `source` (a _PngSource or a _VideoSource, opened here and closed on every exit)
     through tnr, redact and the base layer's scaling into an _EncodeRun, and every reconstruction through the base layer's
     up-scaling to the residual outputs, the report and `out` (a _PngStage or a _VideoStage).  The options are
@@ -1114,6 +1153,7 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
     _roiq_args(roi, roi_q)
     _aq_args(aq)
     _tnr_args(tnr)
+    _shake_args(shake, tnr)
     _grain_args(grain, tnr)
     _redact_args(redact, roi, residuals, residual_bins)
     bit_dir = _bitmap_args(bit_map, report)
@@ -1123,8 +1163,10 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
         rate = _rate_args(target_bpp, q_range, h, w, gop)
         dev = torch.device(device)
         base = _base_args(base_scale, roi, roi_q, bit_map, (h, w), dev)
-        plan, estimate = _scan_pass(source, gop, scenecut, min_gop, _tnr_auto(tnr))
-        tnr, measured = _resolve_tnr(tnr, estimate)  # (from here on a plain tnr.TNR: nothing below knows the difference)
+        steady = _registrar(source, shake)
+        plan, estimate = _scan_pass(source, gop, scenecut, min_gop, _tnr_auto(tnr), steady)
+        moved = _shake_document(steady, source)
+        tnr, measured = _resolve_tnr(tnr, estimate, moved)  # (from here on a plain tnr.TNR: nothing below knows the difference)
         layer = _RoiLayer(roi, plan, (h, w), dev) if roi is not None else None
         held = _redact_frames(redact, layer)
         run = _EncodeRun(bin_dir, plan, base.size if base else (h, w), gop, device, precision, i_ckpt, p_ckpt, coder, nets,
@@ -1135,6 +1177,7 @@ def _encode_sequence(source, out, bin_dir, gop=32, q=(1.0, 1.0, 1.0), device="cu
         SC.write_scale(bin_dir, base.scale if base else None)
         A.write_aq(bin_dir, aq)
         S.write_sidecar(bin_dir, NOISE_JSON, measured)
+        S.write_sidecar(bin_dir, SHAKE_JSON, moved)
         res_out = _ResidualOut(residuals, (h, w), run.K, io_workers) if residuals is not None else None
         rec_out = _RecordOut(residual_bins, residual_step, run.K) if residual_bins is not None else None
         filters = _tnr_filters(tnr, run, (h, w), report)
@@ -1210,7 +1253,7 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
                   i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8, nets=None, gop_streams=1,
                   report=None, roi=None, residuals=None, scenecut=None, min_gop=1, roi_q=None, bit_map=None, target_bpp=None,
                   q_range=None, residual_bins=None, residual_step=1, picture_hash=False, base_scale=None, aq=None, tnr=None,
-                  redact=None, png_device=False, grain=None):
+                  redact=None, png_device=False, grain=None, shake=None):
     """Returns (bits per frame list, (height, width)) -- and, with `report` (True, or the path of a JSON file to write),
     as a third value the rd_report() dictionary: PSNR and MS-SSIM of every picture measured on the device, one host read
     per GOP; without it no metric kernel is launched.  coder="device": payloads in the opt-in GPU
@@ -1331,7 +1374,14 @@ def encode_folder(frames_dir, bin_dir, recon_dir=None, gop=32, q=(1.0, 1.0, 1.0)
     grain.json beside the .bin files keeps, per GOP, eight strengths by intensity, two taps and the sample counts -- the
     same file with one or two GOP streams.  decode_folder(grain=) synthesises from it; nothing else reads it.  The .bin
     files, recon_dir, the report and hashes.json are those of an encode without it.  Without tnr= a ValueError.  None: no
-    launch, allocation, key or byte changes (a stale grain.json is removed)."""
+    launch, allocation, key or byte changes (a stale grain.json is removed).
+    shake: a shake.ShakeParams, with a tnr.AutoTNR -- the camera's shake is taken out ahead of the noise scan
+    (vcm_ts_amd/shake.py): every picture of the scan pass is registered onto picture 0 by one whole-pixel
+    vector before the noise scan sees it; the scene-cut scan and the coding pass keep the pictures as they are.  noise.json and
+    the report's `noise` gain a "shake" summary and shake.json beside the .bin files holds the per-picture records.  A
+    source with more than shake.max_lost percent of its pictures lost is a ValueError: the camera moves, pass a tnr.TNR.
+    Without a tnr.AutoTNR a ValueError.  None: no launch, allocation, file, key or byte changes (a stale shake.json is
+    removed)."""
     options = locals()
     frames_dir, recon_dir, max_frames, png_device = (options.pop(name) for name in ("frames_dir", "recon_dir", "max_frames", "png_device"))
     return _encode_sequence(_PngSource(frames_dir, device, io_workers, max_frames),
@@ -1892,7 +1942,18 @@ def _tnr_args(tnr):
             raise ValueError(f"tnr: expected a tnr.TNR or a tnr.AutoTNR, got {type(tnr).__name__}")
 
 
-NOISE_JSON = "noise.json"
+NOISE_JSON, SHAKE_JSON = "noise.json", "shake.json"
+
+
+def _shake_args(shake, tnr):
+    """shake= of an encode loop, refused by name before any GPU work."""
+    if shake is not None:
+        from .shake import ShakeParams
+
+        if not isinstance(shake, ShakeParams):
+            raise ValueError(f"shake: expected a shake.ShakeParams, got {type(shake).__name__}")
+        if _tnr_auto(tnr) is None:
+            raise ValueError("shake belongs to a tnr.AutoTNR (--tnr-auto): it steadies the noise scan, and the coding pass is not touched")
 
 
 def _tnr_auto(tnr):
@@ -1902,15 +1963,17 @@ def _tnr_auto(tnr):
     return tnr if isinstance(tnr, AutoTNR) else None
 
 
-def _resolve_tnr(tnr, estimate):
-    """(the tnr.TNR of an encode loop's tnr=, what noise.json and --report's `noise` say).  A TNR, or None, is itself and
+def _resolve_tnr(tnr, estimate, moved=None):
+    """(the tnr.TNR of an encode loop's tnr=, what noise.json and --report's `noise` say -- with `moved`, what shake.json
+    says, also its summary under "shake").  A TNR, or None, is itself and
     says nothing; a tnr.AutoTNR is resolved with the scan pass's estimate of the whole source -- one estimate for every GOP,
     GOP stream and shard -- or refuses by name where there is none."""
     auto = _tnr_auto(tnr)
     if auto is None:
         return tnr, None
     resolved = auto.resolve(estimate)
-    return resolved, dict(estimate.to_json(), scale=auto.scale, threshold=resolved.threshold, pixel=resolved.pixel)
+    return resolved, dict(estimate.to_json(), scale=auto.scale, threshold=resolved.threshold, pixel=resolved.pixel,
+                          **({} if moved is None else {"shake": moved["summary"]}))
 
 
 def _noise_report_keys(measured):
@@ -2102,7 +2165,7 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
                  device="cuda:0", precision=None, i_ckpt=None, p_ckpt=None, max_frames=None, coder="host", io_workers=8,
                  nets=None, gop_streams=1, report=None, bit_depth=8, fps=None, roi=None, residuals=None, scenecut=None,
                  min_gop=1, roi_q=None, bit_map=None, target_bpp=None, q_range=None, residual_bins=None, residual_step=1,
-                 picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None, grain=None, deinterlace=None):
+                 picture_hash=False, base_scale=None, aq=None, tnr=None, redact=None, grain=None, deinterlace=None, shake=None):
     """encode_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height) [bit_depth, fps]: same .bin
     files, same return values.  Per picture: file -> a ring of pinned buffers (the reader fills them in place) -> one
     asynchronous copy of 1.5 bytes per pixel on a copy stream -> yuv.yuv420_to_rgb on the GOP stream -> the encoder.
@@ -2130,6 +2193,8 @@ def encode_video(video, bin_dir, recon_video=None, size=None, spec=None, quantiz
     redact: as encode_folder -- after the colour conversion and tnr (RGB only); redact.json lies beside sequence.json, which
     is the same with or without.
     grain: as encode_folder (grain.json beside the .bin files; sequence.json is the same with or without).
+    shake: as encode_folder -- the pictures registered are the converted (and deinterlaced) ones; shake.json lies beside
+    sequence.json, which is the same with or without.
     deinterlace: None, a deint.Deinterlace, or "frame" / "field" with the field order of the file's header -- the file is
     interlaced material (a Y4M It / Ib, any file with an explicit order) and what is coded are progressive pictures made
     from its fields on the device (vcm_ts_amd/deint.py), one per frame or one per field, in front of the colour
@@ -2218,35 +2283,55 @@ def _deint_option(ap, a):
     return {"interlaced": True, "field_order": a.field_order}, setting
 
 
-def _motion_boxes(source, root, params):
-    """The motion scan of motion_boxes_folder / motion_boxes_video over a source, which is closed on every exit."""
+def _motion_boxes(source, root, params, shake=None):
+    """The motion scan of motion_boxes_folder / motion_boxes_video over a source, which is closed on every exit.  shake: a
+    shake.ShakeParams -- every picture goes through a shake.Registrar before the scan sees it, the counts of the cells that
+    the band replicated from a registered picture's edge touches are zeroed on the host before the boxes are made,
+    motion.json gains a "shake" entry and ROOT/shake.json holds the records."""
     from . import motionroi as M
 
+    moved = None
     try:
         source.open()
         n, (h, w) = source.n_frames, source.size
-        boxes = M.scan((x for x, _ in source.pictures(range(n))), n, (h, w), source.dev, params)
+        if shake is None:
+            boxes = M.scan((x for x, _ in source.pictures(range(n))), n, (h, w), source.dev, params)
+        else:
+            from . import shake as SH
+
+            if n < 1:
+                raise ValueError(f"no frames to scan, got {n}")
+            steady, run = SH.Registrar(source.dev, h, w, n, shake), M.MotionScan(source.dev, h, w, n, params)
+            with torch.no_grad():
+                for x, _ in source.pictures(range(n)):
+                    run.add(steady.add(x))
+            if run.n != n:
+                raise ValueError(f"the scan pass saw {run.n} pictures of {n}")
+            log = steady.log()
+            boxes = M.boxes_of_scan(SH.mask_border(run.counts(), log, h, w), h, w, params)
+            moved = SH.document(log, shake, h, w)
     finally:
         source.close()
-    M.write_boxes(root, boxes, params, h, w)
+    M.write_boxes(root, boxes, params, h, w, None if moved is None else dict(moved["params"], **moved["summary"]))
+    S.write_sidecar(root, SHAKE_JSON, moved)
     return boxes
 
 
-def motion_boxes_folder(frames_dir, root, params, device="cuda:0", io_workers=8, max_frames=None):
+def motion_boxes_folder(frames_dir, root, params, device="cuda:0", io_workers=8, max_frames=None, shake=None):
     """run_codec boxes --frames: the motion boxes (vcm_ts_amd/motionroi.py) of a PNG folder, written to `root` as
     motion_coords/%05d and motion.json -- then a roi.PickleBoxes root.  A pass of its own over the source, for the reason
     the scene-cut scan is one: the background model is a recursion over the whole sequence, while GOP streams and GOP
     sharding code GOPs independently.  The pictures come through the reader and conversion of encode_folder's coding
     pass.  Returns the list of (n, 4) box arrays."""
-    return _motion_boxes(_PngSource(frames_dir, device, io_workers, max_frames), root, params)
+    return _motion_boxes(_PngSource(frames_dir, device, io_workers, max_frames), root, params, shake)
 
 
 def motion_boxes_video(video, root, params, device="cuda:0", size=None, spec=None, quantize8=False, bit_depth=8, fps=None,
-                       max_frames=None, deinterlace=None):
+                       max_frames=None, deinterlace=None, shake=None):
     """motion_boxes_folder for a `.y4m` file, or a raw I420 `.yuv` file with size=(width, height): the pictures come
     through the ring, copy and colour conversion (spec, quantize8) of encode_video's coding pass -- with deinterlace
     (encode_video's) through its deinterlacer too, so the boxes are numbered as the pictures it codes."""
-    return _motion_boxes(_VideoSource(video, device, size, spec, quantize8, bit_depth, fps, max_frames, deinterlace), root, params)
+    return _motion_boxes(_VideoSource(video, device, size, spec, quantize8, bit_depth, fps, max_frames, deinterlace), root, params, shake)
 
 
 def _parser():
@@ -2261,7 +2346,11 @@ def _parser():
                        "pass (two small kernels on the GPU, vcm_ts_amd/noise.py) over consecutive pictures' luma difference "
                        "per 16x16 cell, the lower quartile of it, and the threshold encode --tnr-auto K would choose, as JSON on "
                        "stdout.  Fixed camera only: a pan is measured as noise and nothing warns of it")
-    for p in (e, b, n):
+    k = sub.add_parser("shake", description="The shake of a fixed camera, measured from the source alone: every picture is "
+                       "searched for in picture 0 (a 2-D whole-pixel search on a sparse sample of every 64x64 tile and a median "
+                       "vote over the tiles, vcm_ts_amd/shake.py) and the per-picture records and their summary are printed as "
+                       "JSON.  The registration of boxes / noise / encode --tnr-auto --shake R on its own")
+    for p in (e, b, n, k):
         p.add_argument("--frames", help="folder of im1.png / im00001.png ... (exactly one of --frames and --video)")
         p.add_argument("--video", metavar="FILE", help="a .y4m file, or a raw I420 .yuv file with --size")
         p.add_argument("--size", metavar="WxH", help="picture size of a raw .yuv file")
@@ -2303,6 +2392,24 @@ def _parser():
                    help="the K of encode --tnr-auto K whose threshold is reported, 0.50 .. 16.00 (default 3.0, an untuned placeholder)")
     n.add_argument("--device", default="cuda:0")
     n.add_argument("--io-workers", type=int, default=8, help="host threads for PNG decoding (0: inline)")
+    k.add_argument("--radius", type=int, required=True, metavar="R",
+                   help="the search range in whole pixels per axis, 1 .. 16 (no default exists -- the largest shake expected; a "
+                        "vector AT the radius is taken for a pan and the picture is lost)")
+    k.add_argument("--min-votes", type=int, default=None, metavar="N",
+                   help="a picture with fewer voting tiles is lost (default 8, an untuned placeholder)")
+    k.add_argument("--out", metavar="FILE", help="also write the JSON there")
+    k.add_argument("--max-frames", type=int, default=None, metavar="N", help="scan the first N pictures only")
+    k.add_argument("--device", default="cuda:0")
+    k.add_argument("--io-workers", type=int, default=8, help="host threads for PNG decoding (0: inline)")
+    for p, what in ((b, "the motion scan"), (n, "the noise scan"), (e, "with --tnr-auto: the noise scan")):
+        p.add_argument("--shake", type=int, default=None, metavar="R",
+                       help=f"the camera is fixed but shakes: register every picture onto picture 0 by one whole-pixel vector "
+                            f"within +-R (1 .. 16; vcm_ts_amd/shake.py: a tile search and a median vote on the GPU) before "
+                            f"{what} sees it.  shake.json holds the records.  Whole pixels, translation only, no "
+                            f"re-anchoring; the coding pass is not touched.  Untuned; no real video was seen")
+        p.add_argument("--shake-min-votes", type=int, default=None, metavar="N",
+                       help="with --shake: a picture with fewer voting tiles is lost and passed on unmoved (default 8, an "
+                            "untuned placeholder)")
     e.add_argument("--bins", required=True)
     e.add_argument("--recon")
     e.add_argument("--png-device", action="store_true",
@@ -2534,6 +2641,21 @@ def _verify_command(ap, a):
     print(f"{len(PH.read_hashes(a.bins)['pixels'])} pictures verified")
 
 
+def _shake_option(ap, radius, min_votes, names="--shake / --shake-min-votes"):
+    """The shake.ShakeParams of --shake R [--shake-min-votes N] (or of `run_codec shake`'s --radius R [--min-votes N]); None
+    without a radius."""
+    if radius is None:
+        if min_votes is not None:
+            ap.error("--shake-min-votes belongs to --shake")
+        return None
+    from . import shake as SH
+
+    try:
+        return SH.ShakeParams(radius, **({} if min_votes is None else {"min_votes": min_votes}))
+    except ValueError as ex:
+        ap.error(f"{names}: {ex}")
+
+
 def _boxes_command(ap, a):
     from . import motionroi as M
     from . import yuv as Y
@@ -2548,29 +2670,38 @@ def _boxes_command(ap, a):
         params = M.MotionParams(a.threshold, **given)
     except ValueError as ex:
         ap.error(f"boxes: {ex}")
+    shake = _shake_option(ap, a.shake, a.shake_min_votes)
     more, setting = _deint_option(ap, a)
     try:
         if a.video is not None:
             size, fps = _video_args(ap, a)
             with Y.open_video(a.video, size, a.bit_depth, fps, **more) as reader:
                 boxes = motion_boxes_video(reader, a.out, params, a.device, quantize8=a.quantize8, deinterlace=setting(reader),
-                                           spec=reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting))
+                                           spec=reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting),
+                                           shake=shake)
         else:
-            boxes = motion_boxes_folder(a.frames, a.out, params, a.device, io_workers=a.io_workers)
+            boxes = motion_boxes_folder(a.frames, a.out, params, a.device, io_workers=a.io_workers, shake=shake)
     except (ValueError, OSError) as ex:
         ap.error(f"boxes: {ex}")
     print(f"{len(boxes)} pictures, {sum(len(x) for x in boxes)} boxes -> {os.path.join(a.out, M.COORDS)}")
 
 
-def noise_estimate(source, auto):
-    """The noise.NoiseEstimate of a source (a _PngSource or a _VideoSource, opened here and closed on every exit) for the
-    tnr.AutoTNR `auto`: the scan pass of encode --tnr-auto on its own -- every picture once, through the reader and
-    conversion of the coding pass."""
+def noise_scan(source, auto, shake=None):
+    """(the noise.NoiseEstimate, what shake.json says or None) of a source (a _PngSource or a _VideoSource, opened here and
+    closed on every exit) for the tnr.AutoTNR `auto`: the scan pass of encode --tnr-auto on its own -- every picture once,
+    through the reader and conversion of the coding pass, with shake (a shake.ShakeParams) registered first."""
     try:
         source.open()
-        return _scan_pass(source, 1, None, 1, auto)[1]
+        steady = _registrar(source, shake)
+        est = _scan_pass(source, 1, None, 1, auto, steady)[1]
+        return est, _shake_document(steady, source)
     finally:
         source.close()
+
+
+def noise_estimate(source, auto):
+    """The noise.NoiseEstimate of noise_scan without a registration."""
+    return noise_scan(source, auto)[0]
 
 
 def _noise_command(ap, a):
@@ -2587,18 +2718,65 @@ def _noise_command(ap, a):
         auto = N.AutoTNR(**({} if a.scale is None else {"scale": a.scale}), **({} if a.min_cells is None else {"min_cells": a.min_cells}))
     except ValueError as ex:
         ap.error(f"noise: --scale / --min-cells: {ex}")
+    shake = _shake_option(ap, a.shake, a.shake_min_votes)
     more, setting = _deint_option(ap, a)
     try:
         if a.video is not None:
             size, fps = _video_args(ap, a)
             with Y.open_video(a.video, size, a.bit_depth, fps, **more) as reader:
                 spec = reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting)
-                est = noise_estimate(_VideoSource(reader, a.device, None, spec, a.quantize8, 8, None, a.max_frames, setting(reader)), auto)
+                est, moved = noise_scan(_VideoSource(reader, a.device, None, spec, a.quantize8, 8, None, a.max_frames, setting(reader)), auto, shake)
         else:
-            est = noise_estimate(_PngSource(a.frames, a.device, a.io_workers, a.max_frames), auto)
-        _, record = _resolve_tnr(auto, est)
+            est, moved = noise_scan(_PngSource(a.frames, a.device, a.io_workers, a.max_frames), auto, shake)
+        _, record = _resolve_tnr(auto, est, moved)
     except (ValueError, OSError) as ex:
         ap.error(f"noise: {ex}")
+    text = json.dumps(record, indent=2)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
+def shake_records(source, params):
+    """What `run_codec shake` prints for a source (a _PngSource or a _VideoSource, opened here and closed on every exit): every
+    picture once through a shake.Registrar, through the reader and conversion of the coding pass, and nothing else."""
+    from . import shake as SH
+
+    try:
+        source.open()
+        steady = _registrar(source, params)
+        with torch.no_grad():
+            for x, _ in source.pictures(range(source.n_frames)):
+                steady.add(x)
+        if steady.n != source.n_frames:
+            raise ValueError(f"the scan pass saw {steady.n} pictures of {source.n_frames}")
+        return SH.document(steady.log(), params, *source.size)
+    finally:
+        source.close()
+
+
+def _shake_command(ap, a):
+    import json
+
+    from . import yuv as Y
+
+    if (a.frames is None) == (a.video is None):
+        ap.error("give exactly one of --frames and --video")
+    if a.video is None and (a.size or a.quantize8 or a.matrix or a.range or a.siting):
+        ap.error("--size, --quantize8, --matrix, --range and --siting belong to --video")
+    params = _shake_option(ap, a.radius, a.min_votes, "--radius / --min-votes")
+    more, setting = _deint_option(ap, a)
+    try:
+        if a.video is not None:
+            size, fps = _video_args(ap, a)
+            with Y.open_video(a.video, size, a.bit_depth, fps, **more) as reader:
+                spec = reader.spec(a.matrix, None if a.range is None else a.range == "full", a.siting)
+                record = shake_records(_VideoSource(reader, a.device, None, spec, a.quantize8, 8, None, a.max_frames, setting(reader)), params)
+        else:
+            record = shake_records(_PngSource(a.frames, a.device, a.io_workers, a.max_frames), params)
+    except (ValueError, OSError) as ex:
+        ap.error(f"shake: {ex}")
     text = json.dumps(record, indent=2)
     if a.out:
         with open(a.out, "w") as f:
@@ -2653,6 +2831,10 @@ def _encode_command(ap, a):
         ap.error("give one of --tnr T and --tnr-auto [K]: the threshold is either given or measured")
     if a.tnr_auto is None and a.tnr_auto_min_cells is not None:
         ap.error("--tnr-auto-min-cells belongs to --tnr-auto")
+    if a.tnr_auto is None and (a.shake is not None or a.shake_min_votes is not None):
+        ap.error("--shake and --shake-min-votes belong to --tnr-auto: they steady the noise scan (the coding pass is not touched; "
+                 "--tnr-search finds the shake cell by cell)")
+    shake = _shake_option(ap, a.shake, a.shake_min_votes)
     filtered = a.tnr is not None or a.tnr_auto is not None  # (every --tnr-* option below belongs to either)
     if not filtered and (a.tnr_floor is not None or a.tnr_pixel is not None):
         ap.error("--tnr-floor and --tnr-pixel belong to --tnr")
@@ -2791,7 +2973,7 @@ def _encode_command(ap, a):
                    io_workers=a.io_workers, gop_streams=a.gop_streams, report=a.report, roi=roi, residuals=a.residuals,
                    scenecut=a.scenecut, min_gop=a.min_gop, roi_q=roi_q, bit_map=a.bit_map, target_bpp=a.target_bpp,
                    q_range=a.q_range, residual_bins=a.residual_bins, residual_step=a.residual_step, picture_hash=a.picture_hash,
-                   base_scale=a.base_scale, aq=aq, tnr=tnr, redact=redact, grain=grain)
+                   base_scale=a.base_scale, aq=aq, tnr=tnr, redact=redact, grain=grain, shake=shake)
     if a.video is not None:
         try:
             reader = Y.open_video(a.video, size, a.bit_depth, fps, **more)
@@ -2871,7 +3053,7 @@ def _decode_command(ap, a):
 def main(argv=None):
     ap = _parser()
     a = ap.parse_args(argv)
-    {"verify": _verify_command, "boxes": _boxes_command, "noise": _noise_command, "encode": _encode_command, "decode": _decode_command}[a.cmd](ap, a)
+    {"verify": _verify_command, "boxes": _boxes_command, "noise": _noise_command, "shake": _shake_command, "encode": _encode_command, "decode": _decode_command}[a.cmd](ap, a)
 
 
 if __name__ == "__main__":
